@@ -12,7 +12,7 @@ Workload: N = 1 runs BASELINE.json configs[1] (256 lattices on the GPU); N > 1 r
 configs[3]'s shape, 1024 lattices per GPU (8192 over 8 GPUs).  Every rank owns its own
 lattices (weak scaling, no data-path collective); the only exchange is the RCCL
 all-reduce of the scalar loss sum(log Z) at the end of each step.  The other per-GPU
-batch size is timed as well and reported under ``config.aux`` ("per_gpu_256" /
+batch size is timed as well with ``--full`` and reported under ``config.aux`` ("per_gpu_256" /
 "per_gpu_1024") at every N, so that scaling can be read at equal per-GPU work.
 
 ``python bench.py --gpus N`` without WORLD_SIZE in the environment starts its own N rank
@@ -24,19 +24,27 @@ batch moves ~131 MB per launch, less than the 256 MiB Infinity Cache, so replayi
 would measure the die-level cache, not HBM (MI355X_MICROARCH.md: a line stays resident only while
 everything touched between two of its uses fits in ~256 MiB).  With the rotation ~390 MB of other
 lattices and outputs pass between two uses of a line: every launch starts cold.  The replayed figure
-is reported beside it (``roofline.kernel_ms_replay``); ``value``, ``roofline.frac`` and the rocprofv3
+is reported beside it with ``--full`` (``roofline.kernel_ms_replay``); ``value``, ``roofline.frac`` and the rocprofv3
 summaries of the same command are the cold ones.
 
 Rank 0 prints one JSON line: value = lattice arcs processed by all ranks per
 second; ``roofline`` = algorithmic HBM bytes (32 B/arc +
 24 B/state) per launch / average kernel duration from HIP events, against the
 8 TB/s HBM3E peak (``frac``), and beside it ``frac_hw`` = the HBM bytes the PMC counters saw per
-launch (profiles/<tag>_pmc_traffic.json, taken on this same command) / the same duration / peak; ``cpu_baseline`` = the CPU oracle's float64 forward-backward
+launch (profiles/<tag>_pmc_traffic.json, taken on this same command) / the same duration / peak.
+
+A plain run sets up, warms up, times the K steps and prints that line, nothing else.  ``--full`` adds
+what takes runs or checks of its own: the replayed figure, a 1 GiB device copy (``roofline.hbm_copy_measured``),
+``cpu_baseline`` = the CPU oracle's float64 forward-backward
 (oracle/nfst_oracle.c, OpenMP over lattices) on the same batch on this box's
 host cores, rank 0 at N=1 only.  ``config.aux`` (N = 1): timed lines for the other
 BASELINE configs -- [2] 64 SNIPS-shaped lattices, [4] sampling K=16 + Viterbi with
 float32 / bfloat16-rounded scores --, for shallower / deeper lattices of the same size,
-and for the step with caller-supplied per-arc scores.
+and for the step with caller-supplied per-arc scores; at N > 1 the gathered log Z against the oracle.
+
+``--dump-outputs DIR`` writes what the last timed step returned (log Z in float32 and float64, log alpha,
+log beta, arc posteriors, and sum log Z over all ranks) as DIR/<name>.npy, at most 64 MiB in all (rows of
+larger arrays are sampled with a fixed seed).  The inputs depend on the arguments alone.
 """
 import argparse
 import collections
@@ -239,7 +247,8 @@ class Stepper:
         j, slot = self.slot_of(self.i)
         self.i += 1
         if self.mode == "bwd":
-            return ops.backward(self.lat, self.theta, arc_scores=self.arc_scores, want_logbeta=False)
+            self.out = ops.backward(self.lat, self.theta, arc_scores=self.arc_scores, want_logbeta=False)
+            return self.out
         # the steady state of a training loop: same batch, same score tensors, outputs overwritten -- one prepared launch per
         # slot triple (ops.ForwardBackwardLaunch: a ctypes call per step; the plain wrapper's ~40 us of host work per call is
         # longer than the kernel and left the GPU idle between launches)
@@ -352,6 +361,37 @@ def window_stats(windows):
     import numpy as np
     w = np.asarray(windows, dtype=np.float64)
     return {"n_windows": int(w.size), "min_ms": float(w.min()), "median_ms": float(np.median(w)), "max_ms": float(w.max())}
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def host_outputs(result, loss):
+    """The tensors of a step's result (a ForwardBackwardResult or BackwardResult) and its sum of log Z, copied to the host
+    as float64 (float64 tensors) or float32 (everything else)."""
+    import numpy as np
+    import torch
+    out = {}
+    for name, t in result._asdict().items():
+        if isinstance(t, torch.Tensor):
+            out[name] = t.detach().cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+    out["sum_logz"] = loss.detach().reshape(-1).cpu().numpy().astype(np.float64)
+    return out
+
+
+def dump_outputs(d, arrays, cap=DUMP_CAP_BYTES):
+    """arrays as d/<name>.npy; past `cap` bytes in all, every array keeps the same fraction of its rows, chosen with a
+    seed of its name (the same rows from run to run)."""
+    import zlib
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    budget = cap - 4096 * len(arrays)  # (room for the .npy headers)
+    frac = min(1.0, budget / max(1, sum(a.nbytes for a in arrays.values())))
+    for name, a in arrays.items():
+        if frac < 1.0 and a.shape[0] > 1:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a[np.sort(rng.choice(a.shape[0], max(1, int(a.shape[0] * frac)), replace=False))]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
 
 
 def global_shard(G, world, rank, width):
@@ -489,6 +529,11 @@ def main():
     ap.add_argument("--mode", default="fb", choices=["fb", "fb_sweeps_only", "bwd"],
                     help="fb = the benchmark; the others are diagnostics (not the BASELINE metric)")
     ap.add_argument("--arc-scores", action="store_true", help="tuning: caller-supplied per-arc scores (the autograd path) in every mode")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements and checks beyond the headline: replayed batch, HBM copy, config.aux, "
+                         "cpu_baseline, oracle check of the gathered log Z (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (at most 64 MiB in all)")
     ap.add_argument("--rehearse-cpu", action="store_true",
                     help="no GPU, no kernel, no number: ranks rendezvous over gloo, pack a few lattices, all-reduce a "
                          "scalar and rank 0 prints a line with value null (tests of the launcher on a CPU box)")
@@ -549,6 +594,7 @@ def main():
     alg_bytes = lat.algorithmic_bytes("forward_backward")
 
     fused = args.mode != "bwd" and not args.torch_sum and not args.graph  # a captured launch has one fixed slot
+    torch.manual_seed(1234 + rank)  # (--arc-scores: the same scores in every run)
     asc = torch.randn(lat.total_arcs, device=dev) * 0.1 if args.arc_scores else None
     st = Stepper(lat, theta, dev, world, mode=args.mode, fused=fused, arc_scores=asc)
     # cold launches: rotate over distinct resident batches (module docstring).  One launch touches ~0.51 MB per
@@ -586,30 +632,36 @@ def main():
             return st.out
 
     dt, windows, loss = timed_region(rotor, args.steps, args.warmup, world, dev, args.event_every, launch)
+    if args.dump_outputs:  # (before anything else launches: the replay below overwrites outputs of one of the batches)
+        arrays = host_outputs(rotor.cur.out, loss)
+        if world > 1:
+            arrays = {f"rank{rank}_{k}": v for k, v in arrays.items()}
+        dump_outputs(args.dump_outputs, arrays, DUMP_CAP_BYTES // world)
     arcs_timed = rotor.arcs_of_steps(args.warmup, args.steps) if launch is None else arcs * args.steps
     total_arcs_timed = sum_over_ranks(arcs_timed, world, dev)
     kern_ms = float(np.mean(windows))
     alg_bytes = float(np.mean([s_.lat.algorithmic_bytes("forward_backward") for s_ in steppers]))
     # the same step replaying ONE resident batch (what rounds 1-2 reported): its ~131 MB per launch fit the Infinity Cache
     replay_ms = None
-    if n_rot > 1 and not args.no_replay:
+    if args.full and n_rot > 1 and not args.no_replay:
         _, win_r, _ = timed_region(st, max(8, min(args.steps, 64)), 4, world, dev, args.event_every)
         replay_ms = float(np.mean(win_r))
     replay_frac = None if replay_ms is None else lat.algorithmic_bytes() / (replay_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
     # multi-rank: the per-lattice scores reassembled in job order on every rank (decode-style callers), checked against
-    # the oracle on a sample of this rank's own lattices; stragglers made visible (per-rank kernel time, arcs per rank)
+    # the oracle on a sample of this rank's own lattices (--full); stragglers made visible (per-rank kernel time, arcs per rank)
     sharding = None
     if world > 1:
         import torch.distributed as dist
         from nfst_amd.distributed import gather_logz
-        from oracle import oracle as O
         G = B * world
         full = gather_logz(st.out.logz64, shard, G)
         err = 0.0
-        for j in range(0, len(lats), max(1, len(lats) // 4)):
-            l = lats[j]
-            o = O.forward_backward(l.n_rows, l.src, l.dst, theta_np[l.label].astype(np.float64))
-            err = max(err, abs(float(full[shard[j]]) - o["logZ"]))
+        if args.full:
+            from oracle import oracle as O
+            for j in range(0, len(lats), max(1, len(lats) // 4)):
+                l = lats[j]
+                o = O.forward_backward(l.n_rows, l.src, l.dst, theta_np[l.label].astype(np.float64))
+                err = max(err, abs(float(full[shard[j]]) - o["logZ"]))
         stats = torch.tensor([kern_ms, float(arcs), float(lat.n_lattices), err], dtype=torch.float64, device=dev)
         allst = [torch.zeros_like(stats) for _ in range(world)]
         dist.all_gather(allst, stats)
@@ -618,15 +670,15 @@ def main():
                     "lattices_per_rank": [int(x) for x in allst[:, 2]], "arcs_per_rank": [int(x) for x in allst[:, 1]],
                     "lpt_imbalance_max_over_mean_arcs": float(allst[:, 1].max() / allst[:, 1].mean()),
                     "kernel_ms_per_rank_min": float(allst[:, 0].min()), "kernel_ms_per_rank_max": float(allst[:, 0].max()),
-                    "gathered_logz_max_abs_err_vs_oracle_sample": float(allst[:, 3].max()),
+                    "gathered_logz_max_abs_err_vs_oracle_sample": float(allst[:, 3].max()) if args.full else None,
                     "gathered_logz_finite": bool(torch.isfinite(full).all())}
-        assert sharding["gathered_logz_max_abs_err_vs_oracle_sample"] <= 1e-5, sharding
+        assert not args.full or sharding["gathered_logz_max_abs_err_vs_oracle_sample"] <= 1e-5, sharding
     del rotor, steppers[1:]
 
     # the other per-GPU batch size of the BASELINE configs, every rank, same protocol, fewer steps
     aux = {}
     default_shape = args.lattices_per_gpu == 0 and args.mode == "fb" and args.width == 16 and not args.graph and not args.arc_scores
-    if default_shape and not args.no_aux:
+    if args.full and default_shape and not args.no_aux:
         B2 = 1024 if B == 256 else 256
         key = {256: "per_gpu_256", 1024: "per_gpu_1024"}
         del st
@@ -677,7 +729,7 @@ def main():
                        "launch": "hip_graph_replay" if args.graph else "prepared launch (ops.ForwardBackwardLaunch: one ctypes call per step)",
                        "loss_reduction": "fused in the kernel (atomic adds)" if fused else "torch.sum",
                        "lds_reserve_kb": int(os.environ.get("NFST_LDS_RESERVE_KB", "0") or 0),
-                       "aux": aux},
+                       "aux": aux, "full": args.full},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS,
                          "frac_is": "algorithmic bytes (SURVEY 8d: 32 B/arc + 24 B/state) / kernel_ms_cold / peak",
@@ -691,9 +743,10 @@ def main():
                          "kernel_ms_windows": window_stats(windows),
                          "algorithmic_bytes": alg_bytes},
         }
-        out["roofline"]["hbm_copy_measured"] = measured_copy_gbs(dev)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(lats[:256], theta_np, args.cpu_budget)
+        if args.full:
+            out["roofline"]["hbm_copy_measured"] = measured_copy_gbs(dev)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(lats[:256], theta_np, args.cpu_budget)
         print(json.dumps(out), flush=True)
     if world > 1:
         import torch.distributed as dist

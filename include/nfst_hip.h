@@ -352,6 +352,39 @@ int nfst_pack_device_layout(int32_t *meta, const int32_t *status, const int32_t 
 int nfst_pack_device_emit(const nfst_arcs_device *arcs, const nfst_pack_opts *opts, void *ws, int64_t ws_bytes,
                           const int32_t *meta, int32_t *status, const nfst_batch *out, void *stream);
 
+/*
+ * The same programs cut on the device, for a batch the device packer has just emitted (nfst_pack_device_emit) while its
+ * workspace is still untouched: the cutter reads the depths, heights and arc lists the packer left there.  BIT-IDENTICAL to
+ * nfst_pack_chunks on the same batch (the decision, the header and every array).  opts as for nfst_pack_chunks (n_threads is
+ * ignored).  Two launches around one small read-back, on the packer's stream:
+ *   nfst_pack_chunks_device_plan    one workgroup per (lattice, direction): the cheapest plan of every program; summary
+ *                                   [B * 2 * NFST_CHK_SUM_WORDS] (device).  *launched = 0 (and nothing is written) for a batch
+ *                                   nfst_pack_chunks would decline without looking at it
+ *   nfst_pack_chunks_device_layout  (host) summary read back + the batch's meta (host) -> chunk_meta [B * 2 *
+ *                                   NFST_CHK_META_WORDS] and the sizes of *out (pointers untouched); *cut = 0: no programs.
+ *                                   Allocate the arrays (n_tab * 4, n_stream, n_pos, n_stream), store their device addresses
+ *                                   and a device copy of chunk_meta in *out
+ *   nfst_pack_chunks_device_emit    writes tab, stream (with its zero slack), pos and label
+ * pack_ws: the device packer's workspace of the same batch; ws: nfst_pack_chunks_device_ws_bytes() bytes, from the planning
+ * pass to the emitting one.  batch: device arrays (host struct), as nfst_pack_device_emit wrote them.
+ */
+#define NFST_CHK_SUM_WORDS 8
+#define NFST_CHK_SUM_OK 0      /* 1 = the program could be cut */
+#define NFST_CHK_SUM_C 1
+#define NFST_CHK_SUM_F 2
+#define NFST_CHK_SUM_R 3
+#define NFST_CHK_SUM_NPOS 4
+#define NFST_CHK_SUM_ENTRIES 5 /* stream entries, chunks padded to multiples of eight */
+#define NFST_CHK_SUM_CYCLES 6  /* two words: the bits of the plan's modelled cycles (a double) */
+int64_t nfst_pack_chunks_device_ws_bytes(int32_t n_lattices, int64_t total_rows, int64_t total_arcs);
+int nfst_pack_chunks_device_plan(const nfst_arcs_device *arcs, const void *pack_ws, int64_t pack_ws_bytes, const nfst_batch *batch,
+                                 const nfst_chunk_opts *opts, void *ws, int64_t ws_bytes, int32_t *summary, int32_t *launched,
+                                 void *stream);
+int nfst_pack_chunks_device_layout(const int32_t *summary, const int32_t *batch_meta, const nfst_batch *header,
+                                   const nfst_chunk_opts *opts, int32_t *chunk_meta, nfst_chunks *out, int32_t *cut);
+int nfst_pack_chunks_device_emit(const nfst_arcs_device *arcs, const void *pack_ws, int64_t pack_ws_bytes, const nfst_batch *batch,
+                                 const nfst_chunks *chunks, const void *ws, int64_t ws_bytes, void *stream);
+
 /* view of the arrays owned by a packed batch (host pointers, valid until free) */
 int nfst_packed_view(const nfst_packed *p, nfst_batch *view);
 void nfst_packed_free(nfst_packed *p);

@@ -21,6 +21,7 @@ if os.environ.get("NFST_TUNING") == "1" and os.environ.get("NFST_LIB"):
 META_WORDS = 16
 CHK_META_WORDS = 8
 CHK_C, CHK_F, CHK_R, CHK_NPOS, CHK_TAB_OFF, CHK_STREAM_OFF, CHK_POS_OFF, CHK_T_OFF = range(8)
+CHK_SUM_WORDS = 8  # summary of a program cut on the device (nfst_pack_chunks_device_plan)
 (META_ROW_OFF, META_N_ROWS, META_ARC_OFF, META_N_ARCS, META_FWD_OFF, META_FWD_TILES, META_BWD_OFF,
  META_BWD_TILES, META_SINK, META_N_REACH, META_DEPTH, META_N_DP, META_FWD_U, META_BWD_U, META_FWD_SLOT_OFF,
  META_BWD_SLOT_OFF) = range(16)
@@ -123,6 +124,11 @@ def _load():
         "nfst_chunks_view": (C.c_int, [vp, C.POINTER(Chunks)]),
         "nfst_chunks_free": (None, [vp]),
         "nfst_chunks_ws_bytes": (i64, [C.POINTER(Chunks)]),
+        "nfst_pack_chunks_device_ws_bytes": (i64, [i32, i64, i64]),
+        "nfst_pack_chunks_device_plan": (C.c_int, [C.POINTER(ArcsDevice), vp, i64, BP, C.POINTER(ChunkOpts), vp, i64, vp,
+                                                   C.POINTER(i32), vp]),
+        "nfst_pack_chunks_device_layout": (C.c_int, [vp, vp, BP, C.POINTER(ChunkOpts), vp, C.POINTER(Chunks), C.POINTER(i32)]),
+        "nfst_pack_chunks_device_emit": (C.c_int, [C.POINTER(ArcsDevice), vp, i64, BP, C.POINTER(Chunks), vp, i64, vp]),
         "nfst_lds_bytes": (i64, [BP]),
         "nfst_backward": (C.c_int, [BP, SP, vp, vp, vp, vp, vp]),
         "nfst_forward_backward": (C.c_int, [BP, SP, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp]),

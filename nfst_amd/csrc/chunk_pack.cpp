@@ -1,10 +1,12 @@
 // Host side of the chunked flavour for deep, narrow lattices (include/nfst_hip.h, "Chunked programs"): puts the states
 // of a lattice in topological order per direction, cuts the positions into chunks and writes one entry per arc in the
-// order a chunk's lanes walk them.  The kernels are in chunk_kernels.h.
+// order a chunk's lanes walk them.  The kernels are in chunk_kernels.h; the same cuts made on the device, from the device
+// packer's workspace, are in chunk_pack_kernels.h (the cost model and the plan search of both: chunk_cost.h).
 //
 // Reference shape this serves: the SNIPS tagging machines (/root/reference/src/main_snips.py, conf/train/lstm_snips.yaml:2
 // max_length 750; decode/decoder.py:77-79 walks them state by state): a few tag states per token position.
 #include "../../include/nfst_hip.h"
+#include "chunk_cost.h"
 
 #include <algorithm>
 #include <atomic>
@@ -24,15 +26,10 @@ struct nfst_chunks_host {
 
 namespace {
 
-constexpr int kCus = 256;        // MI355X
-constexpr int kMaxReach = 63;    // an entry's operand slot has 6 bits
-// cost model of the chunked sweep (cycles at 2.4 GHz, MI355X, measured with profiles/tune/chunk_stamps.py: DESIGN.md
-// section 4.4): pass 1 is the longest chunk at one entry per kEntry cycles (an LDS round trip per entry on a lane's chain:
-// 82 ns with one wave per SIMD, 88 ns with three), or -- a bound for workgroups full of lanes -- the whole program's entries
-// x F / 64 lanes x kIssue / 4 SIMDs; pass 2 is C steps of step_cycles(F); kFixed: weights, initialisation, the tail of pass 3,
-// the second kernel and the empty launch of the general one
-constexpr double kEntry = 205.0, kIssue = 60.0, kFixed = 25000.0;
-inline double step_cycles(int F) { return (F <= 2 ? 560.0 : F <= 4 ? 600.0 : 775.0) + 300.0 * ((F + 7) / 8 - 1); }  // (234 / 250 / 322 / 445 ns at F = 2 / 3 / 8 / 16)
+using nfst_chunk::kCus;
+using nfst_chunk::kMaxReach;
+using nfst_chunk::lds_need;
+using nfst_chunk::pow2_at_least;
 
 struct Prog {
   int C = 0, F = 0, R = 0, npos = 0;
@@ -40,8 +37,6 @@ struct Prog {
   std::vector<uint32_t> stream;
   double cycles = 0.0;           // cost model of the chunked sweep
 };
-
-inline int pow2_at_least(int x) { int r = 1; while (r < x) r <<= 1; return r; }
 
 template <class Fn>
 void parallel_for(int n, int n_threads, Fn f) {
@@ -53,12 +48,6 @@ void parallel_for(int n, int n_threads, Fn f) {
   for (int t = 0; t < n_threads; ++t)
     th.emplace_back([&] { for (int i; (i = next.fetch_add(1)) < n;) f(i); });
   for (auto &x : th) x.join();
-}
-
-// LDS of a workgroup that runs a program with C chunks of F right-hand sides and R ring slots: the rings (one padded
-// block per chunk), the frontier values of every chunk (mantissa + exponent) and the chunks' first positions
-inline int64_t lds_need(int C, int F, int R) {
-  return (int64_t)C * (R * F + F) * 8 + 64 + (int64_t)C * F * 12 + (int64_t)(2 * C + 2) * 4 + 64;
 }
 
 // One direction of one lattice.  level[s]: longest path from the start (alpha) / to the sink (beta); operands of a
@@ -92,61 +81,26 @@ bool cut(int n_rows, const std::vector<int32_t> &level, const std::vector<uint8_
   }
   pre[1] = 0;
   const int R = std::max(4, pow2_at_least(W + 1));
-  const int64_t total = pre[n];
   auto reach_of = [&](int a) { return a - low[a]; };  // frontier of a chunk that starts at a
   int Fb = 1;
   for (int a = 1; a < n; ++a) Fb = std::max(Fb, reach_of(a));
-  // Cuts for a frontier of at most Ft states: as many chunks as the lanes, the LDS and the balance of pass 1 against pass 2
-  // allow, about the same number of entries each; a cut whose frontier is wider than Ft moves to the nearest position
-  // where it is not (or is dropped).  The cheapest plan over all Ft by the cost model wins.
-  struct Plan { std::vector<int32_t> starts; int F = 0; double cycles = 0.0; };
-  auto plan_for = [&](int Ft, int lane_cap, Plan &pl) {
-    int C = std::min(std::min(threads, lane_cap) / Ft, n - 1);
-    C = std::min(C, std::max(1, (int)std::ceil(std::sqrt((double)total * kEntry / step_cycles(Ft)))));
-    while (C > 1 && lds_need(C, Ft, R) > lds_bytes) --C;
-    if (max_chunks > 0) C = std::min(C, max_chunks);
-    if (C < 1 || lds_need(C, Ft, R) > lds_bytes) return false;
-    pl.starts.assign(1, 1);
-    const int slack = std::max(1, (n / C) / 2);
-    for (int c = 1; c < C; ++c) {
-      const int64_t target = total * c / C;
-      int a = (int)(std::upper_bound(pre.begin() + 1, pre.begin() + n + 1, target) - pre.begin()) - 1;
-      a = std::max(a, pl.starts.back() + 1);
-      if (a >= n) break;
-      int best = -1;
-      for (int d = 0; d <= slack && best < 0; ++d)
-        for (int sgn = -1; sgn <= 1 && best < 0; sgn += 2) {
-          const int b = a + sgn * d;
-          if (b > pl.starts.back() && b < n && reach_of(b) <= Ft) best = b;
-        }
-      if (best > 0) pl.starts.push_back(best);
-    }
-    pl.F = 1;
-    for (int a : pl.starts) pl.F = std::max(pl.F, reach_of(a));
-    int64_t longest = 0;
-    for (size_t c = 0; c < pl.starts.size(); ++c) {
-      const int64_t cnt = pre[c + 1 < pl.starts.size() ? pl.starts[c + 1] : n] - pre[pl.starts[c]];
-      longest = std::max(longest, (cnt + 7) / 8 * 8);
-    }
-    // an entry of pass 1 is an LDS round trip on its lane's chain while a SIMD holds at most two of the workgroup's waves
-    // (82 .. 88 ns); with a third one the walks share its issue slots (88 .. 113 ns with nine waves, 112 .. 139 with twelve)
-    const int waves = ((int)pl.starts.size() * pl.F + 63) / 64, per_simd = (waves + 3) / 4;
-    const double entry = kEntry + 60.0 * std::max(0, per_simd - 2);
-    pl.cycles = std::max((double)longest * entry, (double)total * pl.F / 64.0 * kIssue / 4.0) +
-                (double)pl.starts.size() * step_cycles(pl.F) + kFixed;
-    return true;
-  };
-  Plan best;
-  for (int Ft = Fb; Ft >= 1; --Ft)
-    for (int lane_cap : {1024, 512}) {  // (fewer chunks can be faster: two waves per SIMD)
-      Plan pl;
-      if (!plan_for(Ft, lane_cap, pl)) continue;
-      if (best.F == 0 || pl.cycles < best.cycles) best = pl;
-    }
-  if (best.F == 0) return false;
-  const std::vector<int32_t> &starts = best.starts;
-  const int F = best.F;
-  const int C = (int)starts.size();
+  // the cheapest plan over all frontier limits by the cost model wins (nfst_chunk::plan_cut)
+  int best_k = -1;
+  double best_cycles = 0.0;
+  for (int k = 0; k < 2 * Fb; ++k) {
+    int pc, pf;
+    double cyc;
+    if (!nfst_chunk::plan_cut(nfst_chunk::plan_ft(Fb, k), nfst_chunk::plan_lane_cap(k), n, pre.data(), low.data(), R, threads,
+                              lds_bytes, max_chunks, [](int) {}, &pc, &pf, &cyc))
+      continue;
+    if (best_k < 0 || cyc < best_cycles) { best_k = k; best_cycles = cyc; }
+  }
+  if (best_k < 0) return false;
+  std::vector<int32_t> starts;
+  int C, F;
+  double cycles;
+  nfst_chunk::plan_cut(nfst_chunk::plan_ft(Fb, best_k), nfst_chunk::plan_lane_cap(best_k), n, pre.data(), low.data(), R, threads,
+                       lds_bytes, max_chunks, [&](int a) { starts.push_back(a); }, &C, &F, &cycles);
   if (C * F > threads || lds_need(C, F, R) > lds_bytes || F > R) return false;
   out.C = C; out.F = F; out.R = R; out.npos = n;
   out.pos.assign(order.begin(), order.end());
@@ -169,7 +123,48 @@ bool cut(int n_rows, const std::vector<int32_t> &level, const std::vector<uint8_
     const int64_t count = (int64_t)out.stream.size() - begin;
     out.tab.push_back(a); out.tab.push_back((int32_t)begin); out.tab.push_back((int32_t)count); out.tab.push_back(0);
   }
-  out.cycles = best.cycles;
+  out.cycles = cycles;
+  return true;
+}
+
+// what the layout of a batch's programs needs to know about one of them
+struct ProgSize {
+  int C = 0, F = 0, R = 0, npos = 0;
+  int64_t entries = 0;           // stream entries, chunks padded to multiples of eight
+  double cycles = 0.0;
+};
+
+// The programs of a batch one behind the other (direction 0 and 1 of lattice 0, then of lattice 1, ...) and the choice of the
+// flavour: cmeta [B * 2 * NFST_CHK_META_WORDS] and the sizes of v (pointers untouched).  False = no programs for this batch:
+// an offset beyond int32, or -- unless forced -- a chunked sweep the cost model does not find faster than the general one.
+bool lay_out(const int32_t *batch_meta, int B, const ProgSize *ps, int threads, bool force, int32_t *cmeta, nfst_chunks &v) {
+  const bool roomy = 2 * B <= kCus;
+  int64_t t_units = 0, n_tab = 0, n_stream = 0, n_pos = 0, lds_used = 0;
+  double cycles_chunked = 0.0, cycles_general = 0.0;
+  for (int b = 0; b < B; ++b) {
+    const int32_t *m = batch_meta + (size_t)b * NFST_META_WORDS;
+    for (int dir = 0; dir < 2; ++dir) {
+      const ProgSize &p = ps[2 * b + dir];
+      int32_t *cm = cmeta + ((size_t)b * 2 + dir) * NFST_CHK_META_WORDS;
+      cm[NFST_CHK_C] = p.C; cm[NFST_CHK_F] = p.F; cm[NFST_CHK_R] = p.R; cm[NFST_CHK_NPOS] = p.npos;
+      cm[NFST_CHK_TAB_OFF] = (int32_t)n_tab;
+      cm[NFST_CHK_STREAM_OFF] = (int32_t)n_stream;
+      cm[NFST_CHK_POS_OFF] = (int32_t)n_pos;
+      cm[NFST_CHK_T_OFF] = (int32_t)t_units;
+      t_units += ((int64_t)p.npos * p.F + 63) / 64;
+      if (t_units > INT32_MAX || n_stream + p.entries > (int64_t)INT32_MAX) return false;
+      n_tab += p.C; n_stream += p.entries; n_pos += p.npos;
+      lds_used = std::max(lds_used, lds_need(p.C, p.F, p.R));
+      cycles_chunked = std::max(cycles_chunked, p.cycles * (roomy ? 1.0 : 2.0 * B / kCus));
+    }
+    // the general flavour: a chain of tiles (precise flavour beyond 192 tiles), one lattice per CU
+    const int tiles = std::max(m[NFST_META_FWD_TILES], m[NFST_META_BWD_TILES]);
+    cycles_general = std::max(cycles_general, tiles * (tiles > 192 ? 500.0 : 400.0) * std::max(1.0, (double)B / kCus) + 12000.0);
+  }
+  if (!force && cycles_chunked > 0.9 * cycles_general) return false;  // (profiles/tune/chunk_auto.py: the choice against measurements)
+  v.n_lattices = B; v.threads = threads; v.lds_bytes = (int32_t)((lds_used + 255) & ~(int64_t)255); v.launches = 0;
+  v.n_tab = n_tab; v.n_stream = n_stream + 64;  // (slack: a lane of pass 1 reads up to 24 entries ahead)
+  v.n_pos = n_pos; v.t_units = t_units;
   return true;
 }
 
@@ -182,19 +177,15 @@ extern "C" int nfst_pack_chunks(const nfst_batch *hb, const nfst_chunk_opts *opt
   nfst_chunk_opts o{};
   if (opts) o = *opts;
   const int B = hb->n_lattices;
-  const bool roomy = 2 * B <= kCus;  // every (lattice, direction) workgroup has a CU to itself
-  const int threads = o.threads > 0 ? o.threads : (roomy ? 1024 : 512);
-  const int64_t lds_bytes = o.lds_bytes > 0 ? o.lds_bytes : (roomy ? 152 * 1024 : 64 * 1024);
-  if (threads < 64 || threads > 1024 || (threads & 63) || lds_bytes > 160 * 1024) return NFST_ERR_ARG;
+  int threads;
+  int64_t lds_bytes;
+  if (!nfst_chunk::resolve_opts(B, o.threads, o.lds_bytes, &threads, &lds_bytes)) return NFST_ERR_ARG;
   // a quick no: up to ~160 levels the general kernels are done before the fixed costs of this flavour are (the BASELINE shape:
   // 130 .. 150 tiles)
   if (!o.force && hb->max_tiles <= 160) return NFST_OK;
   nfst_chunks_host *h = new (std::nothrow) nfst_chunks_host();
   if (!h) return NFST_ERR_NOMEM;
   h->meta.assign((size_t)B * 2 * NFST_CHK_META_WORDS, 0);
-  int64_t t_units = 0;
-  double cycles_chunked = 0.0, cycles_general = 0.0;
-  int64_t lds_used = 0;
   // per lattice, on host threads: both programs (or "cannot be cut"), then the programs are laid out one behind the other
   struct One { int err = NFST_OK; bool ok = false; Prog p[2]; };
   std::vector<One> ones(B);
@@ -251,30 +242,22 @@ extern "C" int nfst_pack_chunks(const nfst_batch *hb, const nfst_chunk_opts *opt
     if (ones[b].err != NFST_OK) { const int err = ones[b].err; delete h; return err; }
     if (!ones[b].ok) { delete h; return NFST_OK; }
   }
-  for (int b = 0; b < B; ++b) {
-    const int32_t *m = hb->meta + (size_t)b * NFST_META_WORDS;
+  std::vector<ProgSize> ps((size_t)B * 2);
+  for (int b = 0; b < B; ++b)
     for (int dir = 0; dir < 2; ++dir) {
       const Prog &p = ones[b].p[dir];
-      int32_t *cm = h->meta.data() + ((size_t)b * 2 + dir) * NFST_CHK_META_WORDS;
-      cm[NFST_CHK_C] = p.C; cm[NFST_CHK_F] = p.F; cm[NFST_CHK_R] = p.R; cm[NFST_CHK_NPOS] = p.npos;
-      cm[NFST_CHK_TAB_OFF] = (int32_t)(h->tab.size() / 4);
-      cm[NFST_CHK_STREAM_OFF] = (int32_t)h->stream.size();
-      cm[NFST_CHK_POS_OFF] = (int32_t)h->pos.size();
-      cm[NFST_CHK_T_OFF] = (int32_t)t_units;
-      t_units += ((int64_t)p.npos * p.F + 63) / 64;
-      if (t_units > INT32_MAX || h->stream.size() + p.stream.size() > (size_t)INT32_MAX) { delete h; return NFST_OK; }
+      ps[2 * b + dir] = ProgSize{p.C, p.F, p.R, p.npos, (int64_t)p.stream.size(), p.cycles};
+    }
+  nfst_chunks &v = h->view;
+  if (!lay_out(hb->meta, B, ps.data(), threads, o.force != 0, h->meta.data(), v)) { delete h; return NFST_OK; }
+  for (int b = 0; b < B; ++b)
+    for (int dir = 0; dir < 2; ++dir) {
+      const Prog &p = ones[b].p[dir];
       h->tab.insert(h->tab.end(), p.tab.begin(), p.tab.end());
       h->stream.insert(h->stream.end(), p.stream.begin(), p.stream.end());
       h->pos.insert(h->pos.end(), p.pos.begin(), p.pos.end());
-      lds_used = std::max(lds_used, lds_need(p.C, p.F, p.R));
-      cycles_chunked = std::max(cycles_chunked, p.cycles * (roomy ? 1.0 : 2.0 * B / kCus));
     }
-    // the general flavour: a chain of tiles (precise flavour beyond 192 tiles), one lattice per CU
-    const int tiles = std::max(m[NFST_META_FWD_TILES], m[NFST_META_BWD_TILES]);
-    cycles_general = std::max(cycles_general, tiles * (tiles > 192 ? 500.0 : 400.0) * std::max(1.0, (double)B / kCus) + 12000.0);
-  }
-  if (!o.force && cycles_chunked > 0.9 * cycles_general) { delete h; return NFST_OK; }  // (profiles/tune/chunk_auto.py: the choice against measurements)
-  h->stream.resize(h->stream.size() + 64, 0);  // (slack: a lane of pass 1 reads up to 24 entries ahead)
+  h->stream.resize(v.n_stream, 0);
   // the label of every entry's arc, beside the entry
   h->label.assign(h->stream.size(), 0);
   for (int b = 0; b < B; ++b) {
@@ -289,10 +272,7 @@ extern "C" int nfst_pack_chunks(const nfst_batch *hb, const nfst_chunk_opts *opt
       }
     }
   }
-  nfst_chunks &v = h->view;
-  v.n_lattices = B; v.threads = threads; v.lds_bytes = (int32_t)((lds_used + 255) & ~(int64_t)255); v.launches = 0;
-  v.n_tab = (int64_t)h->tab.size() / 4; v.n_stream = (int64_t)h->stream.size(); v.n_pos = (int64_t)h->pos.size();
-  v.t_units = t_units; v.total_rows = hb->total_rows; v.total_arcs = hb->total_arcs;
+  v.total_rows = hb->total_rows; v.total_arcs = hb->total_arcs;
   v.meta = h->meta.data(); v.tab = h->tab.data(); v.stream = h->stream.data(); v.pos = h->pos.data(); v.label = h->label.data();
   v.ws = nullptr; v.ws_bytes = 0;
   *out = h;
@@ -312,4 +292,35 @@ extern "C" void nfst_chunks_free(nfst_chunks_host *c) { delete c; }
 extern "C" int64_t nfst_chunks_ws_bytes(const nfst_chunks *c) {
   if (!c) return NFST_ERR_ARG;
   return c->n_stream * 16 + c->t_units * 64 * 8 + c->total_rows * 2 * 16 + (int64_t)c->n_lattices * 16 + (int64_t)c->n_lattices * 4 + 1024;
+}
+
+// The layout step of the device cutter (chunk_pack_kernels.h): the same routine as nfst_pack_chunks', on the summaries the
+// planning pass read back.
+extern "C" int nfst_pack_chunks_device_layout(const int32_t *summary, const int32_t *batch_meta, const nfst_batch *header,
+                                              const nfst_chunk_opts *opts, int32_t *chunk_meta, nfst_chunks *out, int32_t *cut) {
+  if (!summary || !batch_meta || !header || !chunk_meta || !out || !cut || header->n_lattices <= 0) return NFST_ERR_ARG;
+  *cut = 0;
+  nfst_chunk_opts o{};
+  if (opts) o = *opts;
+  const int B = header->n_lattices;
+  int threads;
+  int64_t lds_bytes;
+  if (!nfst_chunk::resolve_opts(B, o.threads, o.lds_bytes, &threads, &lds_bytes)) return NFST_ERR_ARG;
+  if (!o.force && header->max_tiles <= 160) return NFST_OK;  // (the planning pass launched nothing: nfst_pack_chunks' quick no)
+  std::vector<ProgSize> ps((size_t)B * 2);
+  for (int i = 0; i < 2 * B; ++i) {
+    const int32_t *sm = summary + (size_t)i * NFST_CHK_SUM_WORDS;
+    if (sm[NFST_CHK_SUM_OK] != 1) return NFST_OK;  // a program that cannot be cut: no programs for the batch
+    ProgSize &p = ps[i];
+    p.C = sm[NFST_CHK_SUM_C]; p.F = sm[NFST_CHK_SUM_F]; p.R = sm[NFST_CHK_SUM_R]; p.npos = sm[NFST_CHK_SUM_NPOS];
+    p.entries = sm[NFST_CHK_SUM_ENTRIES];
+    std::memcpy(&p.cycles, sm + NFST_CHK_SUM_CYCLES, sizeof(double));
+  }
+  nfst_chunks v{};
+  std::memset(chunk_meta, 0, sizeof(int32_t) * (size_t)B * 2 * NFST_CHK_META_WORDS);
+  if (!lay_out(batch_meta, B, ps.data(), threads, o.force != 0, chunk_meta, v)) return NFST_OK;
+  v.total_rows = header->total_rows; v.total_arcs = header->total_arcs;
+  *out = v;
+  *cut = 1;
+  return NFST_OK;
 }

@@ -30,6 +30,7 @@ namespace {
 #include "path_kernels.h"
 #include "neural_kernels.h"
 #include "pack_kernels.h"
+#include "chunk_pack_kernels.h"
 #include "chunk_kernels.h"
 
 // ------------------------------------------------------------------ host helpers
@@ -284,6 +285,72 @@ int nfst_pack_device_emit(const nfst_arcs_device *arcs, const nfst_pack_opts *op
     return NFST_ERR_HIP;
   if ((rc = set_lds(k_pack_lattice<true>, kPkLdsBytes))) return rc;
   hipLaunchKernelGGL(k_pack_lattice<true>, dim3(arcs->n_lattices), dim3(kPkThreads), (size_t)kPkLdsBytes, (hipStream_t)stream, a);
+  return hip_status(hipGetLastError());
+}
+
+int64_t nfst_pack_chunks_device_ws_bytes(int32_t n_lattices, int64_t total_rows, int64_t total_arcs) {
+  if (n_lattices <= 0 || total_rows < 0 || total_arcs < 0) return NFST_ERR_ARG;
+  return 4 * cp_ws_words(n_lattices, total_rows);
+}
+
+static int chunk_device_args(const nfst_arcs_device *arcs, const void *pack_ws, int64_t pack_ws_bytes, const nfst_batch *batch,
+                             const void *ws, int64_t ws_bytes, CpArgs *a) {
+  if (!arcs || !pack_ws || !batch || !ws || arcs->n_lattices <= 0 || !arcs->row_off || !arcs->arc_off) return NFST_ERR_ARG;
+  if (batch->n_lattices != arcs->n_lattices || !batch->meta || !batch->arc_src || !batch->arc_dst || !batch->arc_label) return NFST_ERR_ARG;
+  if (batch->max_rows <= 0 || batch->max_rows > NFST_MAX_ROWS) return NFST_ERR_ARG;
+  if (pack_ws_bytes < 4 * pk_ws_words(arcs->n_lattices, arcs->total_rows, arcs->total_arcs) ||
+      ws_bytes < 4 * cp_ws_words(arcs->n_lattices, arcs->total_rows) || ((uintptr_t)ws & 3))
+    return NFST_ERR_ARG;
+  *a = CpArgs{};
+  a->pk_ws = (const int32_t *)pack_ws; a->row_off = arcs->row_off; a->arc_off = arcs->arc_off;
+  a->in_rows = arcs->total_rows; a->in_arcs = arcs->total_arcs; a->n_lattices = arcs->n_lattices;
+  a->meta = batch->meta; a->arc_src = batch->arc_src; a->arc_dst = batch->arc_dst; a->arc_label = batch->arc_label;
+  a->ws = (int32_t *)const_cast<void *>(ws);
+  return NFST_OK;
+}
+
+int nfst_pack_chunks_device_plan(const nfst_arcs_device *arcs, const void *pack_ws, int64_t pack_ws_bytes, const nfst_batch *batch,
+                                 const nfst_chunk_opts *opts, void *ws, int64_t ws_bytes, int32_t *summary, int32_t *launched,
+                                 void *stream) {
+  if (!summary || !launched) return NFST_ERR_ARG;
+  *launched = 0;
+  CpArgs a;
+  int rc = chunk_device_args(arcs, pack_ws, pack_ws_bytes, batch, ws, ws_bytes, &a);
+  if (rc) return rc;
+  nfst_chunk_opts o{};
+  if (opts) o = *opts;
+  int threads;
+  int64_t lds_bytes;
+  if (!nfst_chunk::resolve_opts(arcs->n_lattices, o.threads, o.lds_bytes, &threads, &lds_bytes)) return NFST_ERR_ARG;
+  // (nfst_pack_chunks' quick no: up to ~160 levels the general kernels are done before this flavour's fixed costs are)
+  if (!o.force && batch->max_tiles <= 160) return NFST_OK;
+  a.threads = threads; a.lds_bytes = lds_bytes; a.max_chunks = o.max_chunks; a.summary = summary;
+  const int64_t lds = cp_plan_lds(batch->max_rows);
+  if ((rc = set_lds(k_chunk_plan, lds))) return rc;
+  hipLaunchKernelGGL(k_chunk_plan, dim3(2 * arcs->n_lattices), dim3(kPkThreads), (size_t)lds, (hipStream_t)stream, a, (int)batch->max_rows);
+  if ((rc = hip_status(hipGetLastError()))) return rc;
+  *launched = 1;
+  return NFST_OK;
+}
+
+int nfst_pack_chunks_device_emit(const nfst_arcs_device *arcs, const void *pack_ws, int64_t pack_ws_bytes, const nfst_batch *batch,
+                                 const nfst_chunks *chunks, const void *ws, int64_t ws_bytes, void *stream) {
+  CpArgs a;
+  int rc = chunk_device_args(arcs, pack_ws, pack_ws_bytes, batch, ws, ws_bytes, &a);
+  if (rc) return rc;
+  if (!chunks || chunks->n_lattices != arcs->n_lattices || !chunks->meta || !chunks->tab || !chunks->stream || !chunks->pos ||
+      !chunks->label || chunks->n_stream < 64)
+    return NFST_ERR_ARG;
+  a.cmeta = chunks->meta; a.tab = const_cast<int32_t *>(chunks->tab); a.pos = const_cast<int32_t *>(chunks->pos);
+  a.stream = const_cast<uint32_t *>(chunks->stream); a.label = const_cast<uint16_t *>(chunks->label);
+  hipStream_t st = (hipStream_t)stream;
+  // the slack behind the last program's entries is part of the format: zero
+  if (hipMemsetAsync(a.stream + (chunks->n_stream - 64), 0, 64 * 4, st) != hipSuccess ||
+      hipMemsetAsync(a.label + (chunks->n_stream - 64), 0, 64 * 2, st) != hipSuccess)
+    return NFST_ERR_HIP;
+  const int64_t lds = 4 * (int64_t)batch->max_rows;
+  if ((rc = set_lds(k_chunk_emit, lds))) return rc;
+  hipLaunchKernelGGL(k_chunk_emit, dim3(2 * arcs->n_lattices), dim3(kPkThreads), (size_t)lds, st, a);
   return hip_status(hipGetLastError());
 }
 

@@ -470,7 +470,7 @@ __global__ __launch_bounds__(kPkThreads) void k_pack_lattice(PkArgs a) {
         if (hei[s] < hd + 1) { atomicMax(&hei[s], hd + 1); changed = 1; }
       }
       if (changed) sh[4 + it % 3] = 1;
-      if (tid == 0) sh[4 + (it + 2) % 3] = 0;  // the flag of the sweep after the next: nobody reads or sets it now
+      if (tid == 0) sh[4 + (it + 1) % 3] = 0;  // the flag of the next sweep: last read before the previous barrier, set after the next
       __syncthreads();
       const int any = sh[4 + it % 3];
       if (!any) break;

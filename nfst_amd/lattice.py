@@ -45,6 +45,11 @@ def _view(ptr, n, ctype, dtype) -> np.ndarray:
     return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,)).astype(dtype, copy=True)
 
 
+def _check_chunks_arg(chunks) -> None:
+    if not (chunks is False or chunks is True or chunks == "force"):
+        raise ValueError(f"chunks must be False, True or 'force', not {chunks!r}")
+
+
 class ChunkProgram:
     """The chunked programs of a batch of deep, narrow lattices (``nfst_chunks``, include/nfst_hip.h): per lattice and
     direction the states in topological order, cut into chunks that are swept at the same time.  Built on the host by
@@ -81,6 +86,47 @@ class ChunkProgram:
         finally:
             lib.nfst_chunks_free(handle)
         return cls(header, {k: torch.from_numpy(a) for k, a in arrs.items()})
+
+    @classmethod
+    def _cut_on_device(cls, lat: "LatticeBatch", batch: _lib.Batch, arcs: _lib.ArcsDevice, pack_ws: torch.Tensor, pack_ws_bytes: int,
+                       stream: int, force: bool = False, threads: int = 0, lds_bytes: int = 0, max_chunks: int = 0):
+        """The programs of a batch the device packer has just emitted, cut on the device from the packer's workspace
+        (``nfst_pack_chunks_device_plan / _layout / _emit``, on the packer's stream): bit-identical to ``build`` on a host
+        copy.  Returns ``(ChunkProgram or None, tensors the queued launches use)``; one read-back (the plan's summary)."""
+        dev = lat.device
+        B = lat.n_lattices
+        opts = _lib.ChunkOpts(int(threads), int(lds_bytes), 1 if force else 0, int(max_chunks), 0, 0)
+        ws_bytes = int(lib.nfst_pack_chunks_device_ws_bytes(B, arcs.total_rows, arcs.total_arcs))
+        check(min(ws_bytes, 0), "nfst_pack_chunks_device_ws_bytes")
+        ws = torch.empty(ws_bytes // 4 + 4, dtype=torch.int32, device=dev)
+        summary = torch.empty(B * 2 * _lib.CHK_SUM_WORDS, dtype=torch.int32, device=dev)
+        launched = C.c_int32(0)
+        check(lib.nfst_pack_chunks_device_plan(C.byref(arcs), pack_ws.data_ptr(), pack_ws_bytes, C.byref(batch), C.byref(opts), ws.data_ptr(),
+                                               ws_bytes, summary.data_ptr(), C.byref(launched), stream), "nfst_pack_chunks_device_plan")
+        if not launched.value:
+            return None, ()
+        summary_h = np.ascontiguousarray(summary.cpu().numpy())  # the one read-back: 8 words per program
+        meta = np.zeros(B * 2 * _lib.CHK_META_WORDS, dtype=np.int32)
+        v, cut = _lib.Chunks(), C.c_int32(0)
+        check(lib.nfst_pack_chunks_device_layout(summary_h.ctypes.data, lat.meta_host.ctypes.data, C.byref(batch), C.byref(opts),
+                                                 meta.ctypes.data, C.byref(v), C.byref(cut)), "nfst_pack_chunks_device_layout")
+        if not cut.value:
+            return None, (ws, summary)
+        out = cls.__new__(cls)
+        out._h = {k: int(getattr(v, k)) for k in cls._HEADER}
+        out._t = {"meta": torch.from_numpy(meta).to(dev),
+                  "tab": torch.empty(v.n_tab * 4, dtype=torch.int32, device=dev),
+                  "stream": torch.empty(v.n_stream, dtype=torch.int32, device=dev),
+                  "pos": torch.empty(v.n_pos, dtype=torch.int32, device=dev),
+                  "label": torch.empty(v.n_stream, dtype=torch.int16, device=dev)}
+        out.meta_host = meta.reshape(-1, 2, _lib.CHK_META_WORDS).copy()
+        out.ws, out._struct = None, None
+        # (zeroed once, as in ``to``)
+        out.ws = torch.zeros(int(lib.nfst_chunks_ws_bytes(C.byref(out.c_struct()))), dtype=torch.uint8, device=dev)
+        out._struct = None
+        check(lib.nfst_pack_chunks_device_emit(C.byref(arcs), pack_ws.data_ptr(), pack_ws_bytes, C.byref(batch), C.byref(out.c_struct()),
+                                               ws.data_ptr(), ws_bytes, stream), "nfst_pack_chunks_device_emit")
+        return out, (ws, summary)
 
     def to(self, device, non_blocking: bool = False) -> "ChunkProgram":
         device = torch.device(device)
@@ -170,17 +216,21 @@ class LatticeBatch:
         return out.to(device) if device is not None else out
 
     @classmethod
-    def from_dense(cls, emission, transition, device=None, **pack_opts) -> "LatticeBatch":
+    def from_dense(cls, emission, transition, device=None, chunks=False, chunk_opts: Optional[dict] = None,
+                   **pack_opts) -> "LatticeBatch":
         """emission ``[B, S+1, V]`` bool (or float log weights, -inf = no arc) and
         transition ``[B, S+1, V]`` int64, as ``set_masks`` receives them
-        (scorers.py:877-885; collated as in util/dataset_reader.py:175-186)."""
+        (scorers.py:877-885; collated as in util/dataset_reader.py:175-186).
+        ``chunks`` / ``chunk_opts``: the chunked programs of the batch, see ``from_arcs_device`` (tables on the host: cut
+        by ``build_chunks`` before the batch moves to ``device``)."""
+        _check_chunks_arg(chunks)
         if device is None and isinstance(transition, torch.Tensor) and transition.is_cuda:
             device = transition.device
         if isinstance(transition, torch.Tensor) and transition.is_cuda and isinstance(emission, torch.Tensor) and emission.is_cuda:
             # tables that already live on the GPU (the reference's trainer moves the collated batch there before
             # set_masks, lightning.py:417) are packed there; only what the device packer does not take goes back to the host
             try:
-                return cls.from_dense_device(emission, transition, **pack_opts).to(device)
+                return cls.from_dense_device(emission, transition, chunks=chunks, chunk_opts=chunk_opts, **pack_opts).to(device)
             except _lib.NfstError as e:
                 if e.code != -6:  # NFST_ERR_LIMIT: beyond the device packer (wide vocabulary, > 16384 states or pieces)
                     raise
@@ -197,7 +247,11 @@ class LatticeBatch:
         rc = lib.nfst_pack_dense(em.ctypes.data, 1 if is_float else 0, tr.ctypes.data, B, R, V, C.byref(opts),
                                  C.byref(handle), C.byref(bad))
         check(rc, "nfst_pack_dense", bad.value)
-        return cls._from_handle(handle, device)
+        if not chunks:
+            return cls._from_handle(handle, device)
+        out = cls._from_handle(handle, None)
+        out.build_chunks(force=chunks == "force", **(chunk_opts or {}))
+        return out.to(device) if device is not None else out
 
     @classmethod
     def from_arcs(cls, n_rows, arc_off, src, label, dst, vocab: int, arc_w=None, device=None,
@@ -221,13 +275,23 @@ class LatticeBatch:
 
     # ---------------------------------------------------------------- the packer on the device
     @classmethod
-    def from_arcs_device(cls, n_rows, arc_off, src, label, dst, vocab: int, arc_w=None, device=None, **pack_opts) -> "LatticeBatch":
+    def from_arcs_device(cls, n_rows, arc_off, src, label, dst, vocab: int, arc_w=None, device=None, chunks=False,
+                         chunk_opts: Optional[dict] = None, **pack_opts) -> "LatticeBatch":
         """``from_arcs`` with the packer running on the GPU (``nfst_pack_device_plan`` / ``_emit``): arc lists sorted by
         (src, label) -- 12 bytes per arc, what a loader uploads instead of 47-byte-per-arc packed batches or 5 MB dense
         tables.  ``n_rows`` and ``arc_off`` are small host arrays; ``src / label / dst (/ arc_w)`` may be host arrays
         (uploaded here) or tensors already on the device.  The result is bit-identical to ``from_arcs``.  Raises
         ``NfstError(NFST_ERR_LIMIT)`` for what only the host packer takes (vocab + 2 > 2048, > 16384 reachable states
-        or pieces of one sweep)."""
+        or pieces of one sweep).
+
+        ``chunks``: the chunked programs of the sweeps (deep, narrow lattices), cut on the device
+        right after the packer (``nfst_pack_chunks_device_*``; bit-identical to ``build_chunks`` on a host copy).  False
+        (the default): none, the general kernels; True: when the cost model says the chunked sweeps are faster, as
+        ``to`` decides for host batches; ``"force"``: whenever the batch can be cut (tests).  ``chunk_opts``: ``threads``,
+        ``lds_bytes``, ``max_chunks`` as ``build_chunks`` takes them.  The cut costs two launches and one small read-back
+        on every call (profiles/chunks_device.json): turn it on where a batch is swept more than once per packing, or
+        where its sweeps are long enough to pay for the cut."""
+        _check_chunks_arg(chunks)
         n_rows = np.ascontiguousarray(_host(n_rows, np.int32))
         arc_off = np.ascontiguousarray(_host(arc_off, np.int64))
         B = int(n_rows.shape[0])
@@ -285,15 +349,21 @@ class LatticeBatch:
                                         C.byref(header), stream), "nfst_pack_device_emit")
         out = cls.__new__(cls)
         out._h, out._t, out._struct = h, tensors, None
-        out.chunks, out._chunks_tried = None, True  # (packed on the device: the general kernels)
+        out.chunks, out._chunks_tried = None, True  # (packed on the device: the general kernels, unless cut here)
         out.meta_host = meta_h.reshape(-1, _lib.META_WORDS).copy()
-        out._keep = (ws, src_d, label_d, dst_d, w_d, small, n_rows_d, plan)  # alive until the emit launch has run
+        ck_keep = ()
+        if chunks:  # (while the packer's workspace is untouched: the cutter reads its depths, heights and arc lists)
+            out.chunks, ck_keep = ChunkProgram._cut_on_device(out, header, arcs, ws, ws_bytes, stream, force=chunks == "force",
+                                                              **(chunk_opts or {}))
+        out._keep = (ws, src_d, label_d, dst_d, w_d, small, n_rows_d, plan) + tuple(ck_keep)  # alive until the emit launches have run
         return out
 
     @classmethod
-    def from_dense_device(cls, emission: torch.Tensor, transition: torch.Tensor, **pack_opts) -> "LatticeBatch":
+    def from_dense_device(cls, emission: torch.Tensor, transition: torch.Tensor, chunks=False, chunk_opts: Optional[dict] = None,
+                          **pack_opts) -> "LatticeBatch":
         """``from_dense`` for tables that live on the GPU: reachable rows -> arc lists (``nfst_dense_to_arcs_count`` /
-        ``_write``), then the device packer.  Two small read-backs (arc counts, the plan), no table leaves the GPU."""
+        ``_write``), then the device packer.  Two small read-backs (arc counts, the plan), no table leaves the GPU.
+        ``chunks`` / ``chunk_opts``: see ``from_arcs_device`` (one more read-back when set)."""
         if not (emission.is_cuda and transition.is_cuda) or emission.dim() != 3 or transition.shape != emission.shape:
             raise ValueError("emission and transition must both be [B, S+1, V] tensors on the GPU")
         dev = transition.device
@@ -321,7 +391,8 @@ class LatticeBatch:
         check(lib.nfst_dense_to_arcs_write(em.data_ptr(), 1 if is_float else 0, tr.data_ptr(), B, R, V, reach.data_ptr(), row_cnt.data_ptr(),
                                            arc_off_d.data_ptr(), src.data_ptr(), label.data_ptr(), dst.data_ptr(),
                                            None if w is None else w.data_ptr(), stream), "nfst_dense_to_arcs_write")
-        return cls.from_arcs_device(np.full(B, R, dtype=np.int32), arc_off, src, label, dst, V, arc_w=w, device=dev, **pack_opts)
+        return cls.from_arcs_device(np.full(B, R, dtype=np.int32), arc_off, src, label, dst, V, arc_w=w, device=dev, chunks=chunks,
+                                    chunk_opts=chunk_opts, **pack_opts)
 
     @classmethod
     def from_synth(cls, lattices: Sequence, device=None, **pack_opts) -> "LatticeBatch":

@@ -21,7 +21,11 @@ from .lattice import LatticeBatch
 
 class LatticeScorer(torch.nn.Module):
     def __init__(self, vocab_size: int, pad: int = 0, bos: int = 1, eos: int = 2, max_length: int = 400,
-                 theta: Optional[torch.Tensor] = None, k: int = 1):
+                 theta: Optional[torch.Tensor] = None, k: int = 1, chunks=False):
+        """``chunks``: cut the chunked programs of the sweeps in ``set_masks`` (``LatticeBatch.from_dense``: False, True =
+        when the cost model says they are faster, ``"force"``).  On tables that live on the GPU the cut runs on the device
+        and adds a read-back to every ``set_masks``; worth it for deep, narrow machines (the SNIPS tagging shape) whose
+        batch is swept more than once per ``set_masks``, or swept for long."""
         super().__init__()
         assert vocab_size > 3  # scorers.py:223
         self.vocab_size = vocab_size
@@ -32,6 +36,7 @@ class LatticeScorer(torch.nn.Module):
         self.theta = torch.nn.Parameter(init)
         self.lattice: Optional[LatticeBatch] = None
         self.use_beta = True
+        self.chunks = chunks
 
     # ------------------------------------------------------------ tables
     def set_masks(self, emission: torch.Tensor, transition: torch.Tensor):
@@ -40,7 +45,7 @@ class LatticeScorer(torch.nn.Module):
         assert len(emission.shape) == 3
         assert len(transition.shape) == 3
         with torch.no_grad():
-            self.lattice = LatticeBatch.from_dense(emission, transition, device=self.theta.device)
+            self.lattice = LatticeBatch.from_dense(emission, transition, device=self.theta.device, chunks=self.chunks)
         return self
 
     def set_lattice(self, lattice: LatticeBatch):

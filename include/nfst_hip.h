@@ -37,6 +37,10 @@
  *                                      (lightning.py:511-516 trains through it),
  *                                      GPT2Wrapper.forward (transformer.py:45-52)
  *   nfst_iwae                          Estimators.iwae (estimatros.py:11-44)
+ *   nfst_expectation                   exact E_p[additive path value] and its covariance with
+ *                                      every arc: the entropy / KL terms that
+ *                                      Estimators.estimate_offset_kl_q_p estimates from
+ *                                      samples (estimatros.py:236-285), second derivatives of log Z
  *
  * Conventions
  *   - plain C: pointers and sizes only, no C++/torch types.
@@ -439,6 +443,35 @@ int nfst_backward(const nfst_batch *lat, const nfst_scores *scores, float *logbe
 int nfst_forward_backward(const nfst_batch *lat, const nfst_scores *scores, float *logalpha,
                           float *logbeta, double *logz64, float *logz32, float *posterior,
                           float *grad_theta, float *beta_me, double *logz_total, int32_t total_slot, void *stream);
+
+/*
+ * Expectations of an additive path function (the first-order expectation semiring; DESIGN.md sections 2 and 4.5).
+ * A path pi from state 0 to the sink has score S(pi) = sum of the log weights s_a of its arcs (nfst_scores) and
+ * probability exp(S(pi) - log Z).  Every arc carries a value
+ *     v_a = label_values[label_values_stride * b + label[a]]   (if label_values != NULL; stride 0: one [V] table)
+ *         + arc_values[a]                                      (if arc_values != NULL; [total_arcs], canonical order)
+ *         + score_coef * s_a
+ * (rounded to float32 per arc), and V(pi) = sum of v_a over the path.  Per lattice:
+ *     logz64[b] = log Z,  ev64[b] (and ev32[b], optional) = E[V]
+ * and, each optional, per canonical arc
+ *     posterior[a] = p_a (the arc posterior),  cov[a] = c_a = p_a (E[V | a on pi] - E[V]) = Cov(1_a, V)
+ * and per lattice and label ([B, V] float32)
+ *     label_cov[b, l] = sum of c_a over the arcs with label l (float64 atomic sums: their order is not fixed),
+ *     label_post[b, l] = sum of p_a over them (exact sums of p_a rounded to 2^-44: independent of the order).
+ * For values that do not depend on the scores c_a = dE[V]/ds_a = sum_b' d2 log Z / ds_a ds_b' v_b' (a Hessian-vector
+ * product of log Z); with score_coef = 1 and no other values, H(p) = log Z - E[V] and dH/ds_a = -c_a.
+ * Self loops (the sink's pad loop) and arcs of weight zero have p_a = c_a = 0.  Everything but label_cov is
+ * bit-identical from launch to launch.
+ * ws: device workspace of nfst_expectation_ws_bytes(lat) bytes (16-byte aligned), overwritten.  logz64 and ev64 are
+ * required.  The sweeps run the general tile programs (also when lat->chunks is set: this op has no chunked flavour)
+ * with the path mass as (float64 mantissa, int32 exponent) and E[value | row] in float64 for every program, 20 bytes
+ * of LDS per row: a batch whose max_rows exceeds 8191 (20 max_rows + 16 > 160 KiB) returns NFST_ERR_LIMIT.  Bad
+ * strides, null required pointers or a short workspace return NFST_ERR_ARG.
+ */
+int64_t nfst_expectation_ws_bytes(const nfst_batch *lat);
+int nfst_expectation(const nfst_batch *lat, const nfst_scores *scores, const float *label_values, int64_t label_values_stride,
+                     const float *arc_values, float score_coef, void *ws, int64_t ws_bytes, double *logz64, double *ev64,
+                     float *ev32, float *posterior, float *cov, float *label_cov, float *label_post, void *stream);
 
 /*
  * Viterbi: best[b] = max path score (float32), paths [B, max_len] int32 labels

@@ -32,6 +32,7 @@ namespace {
 #include "pack_kernels.h"
 #include "chunk_pack_kernels.h"
 #include "chunk_kernels.h"
+#include "expect_kernels.h"
 
 // ------------------------------------------------------------------ host helpers
 int check_batch(const nfst_batch *lat) {
@@ -838,6 +839,59 @@ int nfst_gather_label_scores(const nfst_batch *lat, const nfst_scores *scores, f
   if (!out) return NFST_ERR_ARG;
   hipLaunchKernelGGL(k_gather_label_scores, dim3(8, lat->n_lattices), dim3(256), 0, (hipStream_t)stream,
                      *lat, *scores, out);
+  return hip_status(hipGetLastError());
+}
+
+// ------------------------------------------------------------------ expectation semiring (expect_kernels.h)
+// workspace: slot-ordered weights (float64 mantissa, exponent) and values (float) of both programs, then (mantissa, R,
+// exponent) of every row in both directions, then the per-label sums of c (float64) and p (fixed point, 64-bit); every
+// part 256-byte aligned
+static int64_t exp_align(int64_t n) { return (n + 255) & ~(int64_t)255; }
+static int64_t exp_ws_layout(const nfst_batch *lat, char *base, ExpWs *w) {
+  const int64_t S = lat->fwd_slots + lat->bwd_slots, TR = lat->total_rows, BV = (int64_t)lat->n_lattices * lat->vocab;
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) { const int64_t o = off; off += exp_align(bytes); return base ? base + o : nullptr; };
+  char *wm = take(8 * S), *we = take(4 * S), *sv = take(4 * S), *rm = take(16 * TR), *rr = take(16 * TR), *re = take(8 * TR);
+  char *lc = take(8 * BV), *lp = take(8 * BV);
+  if (w) *w = {(double *)wm, (int *)we, (float *)sv, (double *)rm, (double *)rr, (int *)re, (double *)lc, (unsigned long long *)lp};
+  return off;
+}
+static int64_t exp_lds_bytes(const nfst_batch *lat) { return (int64_t)lat->max_rows * 20 + 16; }
+
+int64_t nfst_expectation_ws_bytes(const nfst_batch *lat) {
+  const int rc = check_batch(lat);
+  if (rc) return rc;
+  return exp_ws_layout(lat, nullptr, nullptr);
+}
+
+int nfst_expectation(const nfst_batch *lat, const nfst_scores *scores, const float *label_values, int64_t label_values_stride,
+                     const float *arc_values, float score_coef, void *ws, int64_t ws_bytes, double *logz64, double *ev64,
+                     float *ev32, float *posterior, float *cov, float *label_cov, float *label_post, void *stream) {
+  int rc = check_batch(lat);
+  if (rc) return rc;
+  if ((rc = check_scores(lat, scores))) return rc;
+  if (!logz64 || !ev64 || !ws || ((uintptr_t)ws & 15)) return NFST_ERR_ARG;
+  if (ws_bytes < exp_ws_layout(lat, nullptr, nullptr)) return NFST_ERR_ARG;
+  if (label_values && label_values_stride != 0 && label_values_stride < lat->vocab) return NFST_ERR_ARG;
+  if (label_values_stride < 0 || !(score_coef == score_coef)) return NFST_ERR_ARG;
+  if (!lat->arc_sd || !lat->arc_l16) return NFST_ERR_ARG;
+  // the general tile programs, also when the batch has chunked programs (there is no chunked flavour of this op)
+  const int64_t lds = exp_lds_bytes(lat);
+  if (lds > kMaxLds) return NFST_ERR_LIMIT;
+  if ((rc = set_lds(k_expect_sweep, lds))) return rc;
+  ExpWs w;
+  exp_ws_layout(lat, (char *)ws, &w);
+  const ExpVals x = {*scores, label_values, label_values ? label_values_stride : 0, arc_values, score_coef};
+  const hipStream_t st = (hipStream_t)stream;
+  const int64_t n_lab = (int64_t)lat->n_lattices * lat->vocab;
+  if (label_cov && (rc = hip_status(hipMemsetAsync(w.lc, 0, (size_t)n_lab * 8, st)))) return rc;
+  if (label_post && (rc = hip_status(hipMemsetAsync(w.lp, 0, (size_t)n_lab * 8, st)))) return rc;
+  hipLaunchKernelGGL(k_expect_prep, dim3(lat->n_lattices, 2, kExpParts), dim3(kExpPrepThreads), 0, st, *lat, x, w);
+  hipLaunchKernelGGL(k_expect_sweep, dim3(lat->n_lattices, 2), dim3(kExpThreads), (size_t)lds, st, *lat, w);
+  hipLaunchKernelGGL(k_expect_arcs, dim3(lat->n_lattices, kExpParts), dim3(kExpArcThreads), 0, st, *lat, x, w, logz64, ev64, ev32,
+                     posterior, cov, label_cov != nullptr, label_post != nullptr);
+  if (label_cov || label_post)
+    hipLaunchKernelGGL(k_expect_labels, dim3((unsigned)((n_lab + 255) / 256)), dim3(256), 0, st, w, n_lab, label_cov, label_post);
   return hip_status(hipGetLastError());
 }
 

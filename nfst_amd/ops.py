@@ -163,12 +163,18 @@ class _LogZ(torch.autograd.Function):
                              want_alpha_beta=False, want_posterior=need_a, want_grad_theta=need_t)
         ctx.lat = lat
         ctx.shared_theta = theta.dim() == 1
+        ctx.inputs = (theta, arc_scores)  # (read only by a backward that builds a graph, create_graph=True)
         ctx.save_for_backward(r.posterior if need_a else None, r.grad_theta if need_t else None)
         return r.logz
 
     @staticmethod
     def backward(ctx, g):
         post, gth = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            # create_graph=True: the posteriors depend on the scores; _LogZGrad carries that dependence (second order)
+            theta, arc_scores = ctx.inputs
+            g_theta, g_arc = _LogZGrad.apply(ctx.lat, ctx.shared_theta, theta, arc_scores, g, post, gth)
+            return None, g_theta, g_arc
         g_theta = g_arc = None
         if gth is not None:
             g_theta = gth * g[:, None]
@@ -182,6 +188,225 @@ class _LogZ(torch.autograd.Function):
 def log_z(lat: LatticeBatch, theta: torch.Tensor, arc_scores: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Differentiable exact log-marginal per lattice, float32 [B]."""
     return _LogZ.apply(lat, theta, arc_scores)
+
+
+# ----------------------------------------------------------------------------- expectation semiring
+class ExpectationResult(NamedTuple):
+    logz64: torch.Tensor  # [B] float64
+    ev64: torch.Tensor  # [B] float64 E[V]
+    ev: torch.Tensor  # [B] float32 E[V]
+    posterior: Optional[torch.Tensor]  # [total_arcs] p_a
+    cov: Optional[torch.Tensor]  # [total_arcs] c_a = Cov(1_a, V)
+    label_cov: Optional[torch.Tensor]  # [B, V] c_a summed per label
+    label_post: Optional[torch.Tensor]  # [B, V] p_a summed per label
+
+
+def _input(lat: LatticeBatch, t, name: str, per_lattice_ok: bool, per_arc: bool) -> Optional[torch.Tensor]:
+    """Checks a score or value tensor of the expectation ops: on the batch's device, floating point, [V] / [B, V]
+    (per-label) or [total_arcs] (per-arc).  Returns it as contiguous float32 (None stays None)."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a torch.Tensor, not {type(t).__name__}")
+    if t.device != lat.device:
+        raise ValueError(f"{name} is on {t.device}, the lattice batch on {lat.device}")
+    if not t.is_floating_point():
+        raise ValueError(f"{name} must be a floating-point tensor, not {t.dtype}")
+    if per_arc:
+        if t.shape != (lat.total_arcs,):
+            raise ValueError(f"{name} must be [{lat.total_arcs}] in canonical arc order, not {list(t.shape)}")
+    elif not (t.shape == (lat.vocab,) or (per_lattice_ok and t.shape == (lat.n_lattices, lat.vocab))):
+        raise ValueError(f"{name} must be [{lat.vocab}] or [{lat.n_lattices}, {lat.vocab}], not {list(t.shape)}")
+    return t.to(torch.float32).contiguous()
+
+
+def expectation_terms(lat: LatticeBatch, theta, arc_scores=None, label_values=None, arc_values=None, score_coef: float = 0.0,
+                      want_posterior=False, want_cov=False, want_label_cov=False, want_label_post=False) -> ExpectationResult:
+    """One launch of ``nfst_expectation`` (no autograd): for the per-arc values
+    v_a = label_values[b, label_a] + arc_values[a] + score_coef * s_a (each term optional; s_a the arc's log weight),
+    log Z, E[V] and, on request, the arc posteriors p_a, c_a = p_a (E[V | a] - E[V]) and both summed per label."""
+    _need_gpu(lat)
+    theta = _input(lat, theta, "theta", True, False)
+    arc_scores = _input(lat, arc_scores, "arc_scores", False, True)
+    label_values = _input(lat, label_values, "label_values", True, False)
+    arc_values = _input(lat, arc_values, "arc_values", False, True)
+    coef = float(score_coef)
+    if coef != coef or coef in (float("inf"), float("-inf")):
+        raise ValueError(f"score_coef must be finite, not {score_coef}")
+    sc, keep = _scores(lat, theta, arc_scores)
+    dev = lat.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    B, A = lat.n_lattices, lat.total_arcs
+    ws_bytes = int(lib.nfst_expectation_ws_bytes(C.byref(lat.c_struct())))
+    check(min(ws_bytes, 0), "nfst_expectation_ws_bytes")
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    z64 = torch.empty(B, dtype=torch.float64, device=dev)
+    ev64 = torch.empty(B, dtype=torch.float64, device=dev)
+    ev32 = torch.empty(B, **f32)
+    post = torch.empty(A, **f32) if want_posterior else None
+    cov = torch.empty(A, **f32) if want_cov else None
+    lc = torch.empty((B, lat.vocab), **f32) if want_label_cov else None
+    lp = torch.empty((B, lat.vocab), **f32) if want_label_post else None
+    lv_stride = 0 if label_values is None or label_values.dim() == 1 else lat.vocab
+    check(lib.nfst_expectation(C.byref(lat.c_struct()), C.byref(sc), _ptr(label_values), lv_stride, _ptr(arc_values), coef,
+                               ws.data_ptr(), ws_bytes, _ptr(z64), _ptr(ev64), _ptr(ev32), _ptr(post), _ptr(cov), _ptr(lc),
+                               _ptr(lp), _stream()), "nfst_expectation")
+    return ExpectationResult(z64, ev64, ev32, post, cov, lc, lp)
+
+
+def _per_label(x: torch.Tensor, g: torch.Tensor, shared: bool) -> torch.Tensor:
+    """[B, V] per-label sums times the incoming gradient [B]; summed over the batch for a shared [V] table."""
+    y = x * g[:, None]
+    return y.sum(dim=0) if shared else y
+
+
+class _Expectation(torch.autograd.Function):
+    """E[V] with dE/ds_a = c_a + coef p_a, dE/d(arc value) = p_a, dE/d(label value) = per-label sums of p_a."""
+
+    @staticmethod
+    def forward(ctx, lat, theta, arc_scores, label_values, arc_values, coef):
+        nt, na, nlv, nav = ctx.needs_input_grad[1:5]
+        r = expectation_terms(lat, theta.detach(), None if arc_scores is None else arc_scores.detach(),
+                              None if label_values is None else label_values.detach(),
+                              None if arc_values is None else arc_values.detach(), coef,
+                              want_posterior=nav or (na and coef != 0.0), want_cov=na, want_label_cov=nt,
+                              want_label_post=nlv or (nt and coef != 0.0))
+        ctx.lat, ctx.coef = lat, coef
+        ctx.shared = (theta.dim() == 1, label_values is not None and label_values.dim() == 1)
+        ctx.save_for_backward(r.posterior, r.cov, r.label_cov, r.label_post)
+        return r.ev
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        post, cov, lc, lp = ctx.saved_tensors
+        nt, na, nlv, nav = ctx.needs_input_grad[1:5]
+        k = ctx.coef
+        ga = g[ctx.lat.arc_lattice()] if (na or nav) else None
+        d_theta = _per_label(lc if k == 0.0 else lc + k * lp, g, ctx.shared[0]) if nt else None
+        d_arc = (cov if k == 0.0 else cov + k * post) * ga if na else None
+        d_lv = _per_label(lp, g, ctx.shared[1]) if nlv else None
+        d_av = post * ga if nav else None
+        return None, d_theta, d_arc, d_lv, d_av, None
+
+
+def expectation(lat: LatticeBatch, theta: torch.Tensor, arc_scores: Optional[torch.Tensor] = None,
+                label_values: Optional[torch.Tensor] = None, arc_values: Optional[torch.Tensor] = None,
+                score_coef: float = 0.0) -> torch.Tensor:
+    """Exact E_p[sum over the path of v_a] per lattice, float32 [B], where p is the lattice distribution of the scores
+    (``theta`` [V] or [B, V], ``arc_scores`` [total_arcs]) and v_a = label_values[(b,) label_a] + arc_values[a] +
+    score_coef * s_a: expected path length (label_values = ones), expected label counts, expected cost.  Differentiable
+    in theta, arc_scores, label_values and arc_values (one launch of the expectation semiring)."""
+    return _Expectation.apply(lat, theta, arc_scores, label_values, arc_values, float(score_coef))
+
+
+class _Entropy(torch.autograd.Function):
+    """H(p) = log Z - E_p[S] from one launch with score_coef = 1; dH/ds_a = -c_a."""
+
+    @staticmethod
+    def forward(ctx, lat, theta, arc_scores):
+        nt, na = ctx.needs_input_grad[1:3]
+        r = expectation_terms(lat, theta.detach(), None if arc_scores is None else arc_scores.detach(), score_coef=1.0,
+                              want_cov=na, want_label_cov=nt)
+        ctx.lat, ctx.shared = lat, theta.dim() == 1
+        ctx.save_for_backward(r.cov, r.label_cov)
+        return (r.logz64 - r.ev64).to(torch.float32)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        cov, lc = ctx.saved_tensors
+        nt, na = ctx.needs_input_grad[1:3]
+        d_theta = -_per_label(lc, g, ctx.shared) if nt else None
+        d_arc = -cov * g[ctx.lat.arc_lattice()] if na else None
+        return None, d_theta, d_arc
+
+
+def entropy(lat: LatticeBatch, theta: torch.Tensor, arc_scores: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Exact path entropy H(p) = log Z - E_p[S] per lattice, float32 [B] (in nats; the difference is taken in float64).
+    Differentiable in theta ([V] or [B, V]) and arc_scores: dH/ds_a = -Cov(1_a, S)."""
+    return _Entropy.apply(lat, theta, arc_scores)
+
+
+class _KL(torch.autograd.Function):
+    """KL(p||q) = log Z_q - log Z_p + E_p[S_p - S_q] (arc_w cancels in S_p - S_q); dKL/ds_p = c(v = S_p - S_q),
+    dKL/ds_q = p_q - p_p."""
+
+    @staticmethod
+    def forward(ctx, lat, theta_p, theta_q, arc_scores_p, arc_scores_q):
+        ntp, ntq, nap, naq = ctx.needs_input_grad[1:5]
+        tp, tq = theta_p.detach(), theta_q.detach()
+        asp = None if arc_scores_p is None else arc_scores_p.detach()
+        asq = None if arc_scores_q is None else arc_scores_q.detach()
+        for name, t in (("theta_p", tp), ("theta_q", tq)):
+            _input(lat, t, name, True, False)
+        for name, t in (("arc_scores_p", asp), ("arc_scores_q", asq)):
+            _input(lat, t, name, False, True)
+        lv = tp.to(torch.float32) - tq.to(torch.float32)  # ([V] - [B, V] broadcasts to [B, V])
+        av = None
+        if asp is not None or asq is not None:
+            av = (asp.to(torch.float32) if asp is not None else 0.0) - (asq.to(torch.float32) if asq is not None else 0.0)
+            if not isinstance(av, torch.Tensor):
+                av = None
+        rp = expectation_terms(lat, tp, asp, lv, av, 0.0, want_posterior=naq, want_cov=nap, want_label_cov=ntp,
+                               want_label_post=ntq)
+        rq = expectation_terms(lat, tq, asq, want_posterior=naq, want_label_post=ntq)
+        ctx.lat, ctx.shared = lat, (theta_p.dim() == 1, theta_q.dim() == 1)
+        ctx.save_for_backward(rp.cov, rp.label_cov, rp.posterior, rp.label_post, rq.posterior, rq.label_post)
+        return (rq.logz64 - rp.logz64 + rp.ev64).to(torch.float32)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        cov_p, lc_p, post_p, lp_p, post_q, lp_q = ctx.saved_tensors
+        ntp, ntq, nap, naq = ctx.needs_input_grad[1:5]
+        ga = g[ctx.lat.arc_lattice()] if (nap or naq) else None
+        return (None, _per_label(lc_p, g, ctx.shared[0]) if ntp else None,
+                _per_label(lp_q - lp_p, g, ctx.shared[1]) if ntq else None,
+                cov_p * ga if nap else None, (post_q - post_p) * ga if naq else None)
+
+
+def kl_divergence(lat: LatticeBatch, theta_p: torch.Tensor, theta_q: torch.Tensor, arc_scores_p: Optional[torch.Tensor] = None,
+                  arc_scores_q: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Exact KL(p || q) per lattice, float32 [B], of two weightings of the same batch (theta_p / theta_q [V] or [B, V],
+    optional per-arc scores); the float64 parts are combined in float64.  Differentiable in all four score inputs:
+    dKL/ds_p = Cov_p(1_a, S_p - S_q), dKL/ds_q = p_q - p_p.  The exact counterpart of the sampled KL terms of
+    Estimators.estimate_offset_kl_q_p (/root/reference/src/modules/estimatros.py:236-285) for a WFST proposal."""
+    return _KL.apply(lat, theta_p, theta_q, arc_scores_p, arc_scores_q)
+
+
+class _LogZGrad(torch.autograd.Function):
+    """The gradient of log Z as a differentiable function of the scores and of the incoming gradient g (the
+    create_graph=True backward of log_z): G_theta[b, l] = g_b sum_{a: label l} p_a, G_arc[a] = g_b p_a.  Its own backward
+    is one expectation launch with the incoming (u_theta, u_arc) as per-label and per-arc values:
+    dG.u/ds_a = g_b c_a(v = u) (a Hessian-vector product of log Z) and dG.u/dg_b = E_b[V]."""
+
+    @staticmethod
+    def forward(ctx, lat, shared, theta, arc_scores, g, post, gth):
+        ctx.lat, ctx.shared = lat, shared
+        ctx.save_for_backward(theta, arc_scores, g)
+        g_theta = g_arc = None
+        if gth is not None:
+            g_theta = _per_label(gth, g, shared)
+        if post is not None:
+            g_arc = post * g[lat.arc_lattice()]
+        return g_theta, g_arc
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, u_theta, u_arc):
+        theta, arc_scores, g = ctx.saved_tensors
+        nt, na, ng = ctx.needs_input_grad[2:5]
+        lat = ctx.lat
+        if u_theta is None and u_arc is None:
+            return None, None, None, None, None, None, None
+        f32 = dict(device=lat.device, dtype=torch.float32)  # (log_z takes scores anywhere and moves them; so does this)
+        r = expectation_terms(lat, theta.detach().to(**f32), None if arc_scores is None else arc_scores.detach().to(**f32),
+                              u_theta, u_arc, want_cov=na, want_label_cov=nt)
+        d_theta = _per_label(r.label_cov, g, ctx.shared) if nt else None
+        d_arc = r.cov * g[lat.arc_lattice()] if na else None
+        d_g = r.ev.to(g.dtype) if ng else None
+        return None, None, d_theta, d_arc, d_g, None, None
 
 
 class ViterbiResult(NamedTuple):

@@ -77,6 +77,10 @@ class LatticeScorer(torch.nn.Module):
         """Differentiable exact log Z per lattice ``[B]``; d/d theta = expected mark counts."""
         return ops.log_z(self._lat(), self.theta)
 
+    def entropy(self) -> torch.Tensor:
+        """Differentiable exact path entropy per lattice ``[B]`` (nats); d/d theta = -Cov(mark counts, path score)."""
+        return ops.entropy(self._lat(), self.theta)
+
     # ------------------------------------------------------------ per-step gathers
     def update_fsa_state(self, updated: torch.Tensor, prev_states: torch.Tensor) -> torch.Tensor:
         """scorers.py:683-690."""

@@ -41,6 +41,10 @@
  *                                      every arc: the entropy / KL terms that
  *                                      Estimators.estimate_offset_kl_q_p estimates from
  *                                      samples (estimatros.py:236-285), second derivatives of log Z
+ *   nfst_kbest                         the k best paths of every lattice: the n-best list that
+ *                                      evaluate/rerank.py reranks (read from an outside system
+ *                                      there) and the exact form of JointProb.forward's "best of
+ *                                      K samples" (lightning.py:474-479)
  *
  * Conventions
  *   - plain C: pointers and sizes only, no C++/torch types.
@@ -472,6 +476,33 @@ int64_t nfst_expectation_ws_bytes(const nfst_batch *lat);
 int nfst_expectation(const nfst_batch *lat, const nfst_scores *scores, const float *label_values, int64_t label_values_stride,
                      const float *arc_values, float score_coef, void *ws, int64_t ws_bytes, double *logz64, double *ev64,
                      float *ev32, float *posterior, float *cov, float *label_cov, float *label_post, void *stream);
+
+/*
+ * The k best paths of every lattice.  A path runs from state 0 to the sink; self loops (the
+ * sink's pad loop) are on no path.  Lattices are deterministic: distinct paths are distinct label sequences.
+ * Score: a float32 sum built from the sink backwards with the adds of nfst_viterbi's general kernel: the sink holds
+ * the single entry 0.0f, and arc a from state s to d extends entry r of d's list to
+ *     c = e_a + (theta[label_a] + v(d, r)),   e_a = 0.0f (+ arc_w[a] if weighted) (+ arc_scores[a] if given).
+ * Order: a state's list is the top k of its candidates (a, r) with c > -inf (a over its out-arcs without self loops,
+ * r over the entries of d's list), by (c desc, canonical arc asc, r asc): on exactly tied scores the smaller first
+ * label wins (arcs of a state are in label order).  Entry 0 is therefore nfst_viterbi's path (score, labels, arcs,
+ * length) bit for bit whenever the general Viterbi kernel runs (its tile-wave flavour for all-compact batches adds
+ * per-arc extras in another order: v + (theta + e_a); without arc_w and arc_scores both are the same).
+ * Outputs (device): best [B, k] float32; paths [B, k, max_len] labels (bos .. eos) padded with `pad`; path_arcs
+ * (optional) [B, k, max_len] canonical arc ids padded with -1; lengths [B, k] arcs per path; n_paths [B] =
+ * min(k, paths of score > -inf).  Entries j >= n_paths[b] have score -inf, length 0, labels pad and arcs -1.  A path
+ * longer than max_len is cut there and sets *status = NFST_ERR_LENGTH (status: device, one word, zeroed by the
+ * caller).
+ * Reads the canonical arrays only (row_ptr, arc_src, arc_dst, arc_label, arc_w): any batch, compact or not, with or
+ * without chunked programs, with the same bits.  ws: device workspace of nfst_kbest_ws_bytes(lat, k) bytes (16-byte
+ * aligned, overwritten): total_rows * k * 8 bytes of lists plus 12 bytes per row.  Limits: 1 <= k <= 64 (k < 1:
+ * NFST_ERR_ARG, k > 64: NFST_ERR_LIMIT); a back pointer holds (arc in lattice, rank) in 32 bits, so a batch that may
+ * hold a lattice of 2^24 arcs or more returns NFST_ERR_LIMIT.  All checks run on the host before any launch.
+ */
+int64_t nfst_kbest_ws_bytes(const nfst_batch *lat, int32_t k);
+int nfst_kbest(const nfst_batch *lat, const nfst_scores *scores, int32_t k, void *ws, int64_t ws_bytes, float *best,
+               int32_t *paths, int32_t *path_arcs, int32_t *lengths, int32_t *n_paths, int32_t max_len, int32_t pad,
+               int32_t *status, void *stream);
 
 /*
  * Viterbi: best[b] = max path score (float32), paths [B, max_len] int32 labels

@@ -33,6 +33,7 @@ namespace {
 #include "chunk_pack_kernels.h"
 #include "chunk_kernels.h"
 #include "expect_kernels.h"
+#include "kbest_kernels.h"
 
 // ------------------------------------------------------------------ host helpers
 int check_batch(const nfst_batch *lat) {
@@ -892,6 +893,54 @@ int nfst_expectation(const nfst_batch *lat, const nfst_scores *scores, const flo
                      posterior, cov, label_cov != nullptr, label_post != nullptr);
   if (label_cov || label_post)
     hipLaunchKernelGGL(k_expect_labels, dim3((unsigned)((n_lab + 255) / 256)), dim3(256), 0, st, w, n_lab, label_cov, label_post);
+  return hip_status(hipGetLastError());
+}
+
+// ------------------------------------------------------------------ k best paths (kbest_kernels.h)
+// workspace: the k-best lists of every row, then the topological order, the level starts and the level counts; every
+// part 256-byte aligned
+static int64_t kb_ws_layout(const nfst_batch *lat, int k, char *base, KbWs *w) {
+  const int64_t TR = lat->total_rows, B = lat->n_lattices;
+  int64_t off = 0;
+  auto take = [&](int64_t bytes) { const int64_t o = off; off += exp_align(bytes); return base ? base + o : nullptr; };
+  char *li = take(8 * TR * k), *od = take(4 * TR), *lv = take(4 * (TR + B)), *nl = take(4 * B);
+  if (w) *w = {(uint2 *)li, (int *)od, (int *)lv, (int *)nl};
+  return off;
+}
+static int kb_check_k(int32_t k) { return k < 1 ? NFST_ERR_ARG : (k > kKbMaxK ? NFST_ERR_LIMIT : NFST_OK); }
+
+int64_t nfst_kbest_ws_bytes(const nfst_batch *lat, int32_t k) {
+  int rc = check_batch(lat);
+  if (rc) return rc;
+  if ((rc = kb_check_k(k))) return rc;
+  return kb_ws_layout(lat, k, nullptr, nullptr);
+}
+
+int nfst_kbest(const nfst_batch *lat, const nfst_scores *scores, int32_t k, void *ws, int64_t ws_bytes, float *best,
+               int32_t *paths, int32_t *path_arcs, int32_t *lengths, int32_t *n_paths, int32_t max_len, int32_t pad,
+               int32_t *status, void *stream) {
+  int rc = check_batch(lat);
+  if (rc) return rc;
+  if ((rc = check_scores(lat, scores))) return rc;
+  if ((rc = kb_check_k(k))) return rc;
+  if (!best || !paths || !lengths || !n_paths || !status || max_len <= 0) return NFST_ERR_ARG;
+  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < kb_ws_layout(lat, k, nullptr, nullptr)) return NFST_ERR_ARG;
+  // a payload holds (arc in lattice, rank) in 32 bits: 2^24 arcs per lattice at most (the batch records its largest
+  // lattice's arc count up to a cap; beyond the cap the batch's total decides)
+  const int64_t max_arcs = ((int64_t)lat->reserved0 >> NFST_BATCH_MAX_ARCS_SHIFT) & NFST_BATCH_MAX_ARCS_CAP;
+  if (max_arcs >= NFST_BATCH_MAX_ARCS_CAP && lat->total_arcs >= ((int64_t)1 << 24)) return NFST_ERR_LIMIT;
+  const int64_t lds_lev = (int64_t)lat->max_rows * 12 + 16;
+  const int64_t lds_sweep = (int64_t)kKbSweepWaves * 2 * 64 * 8 + ((int64_t)lat->max_rows * 2 + 1) * 4;
+  if ((rc = set_lds(k_kbest_levels, lds_lev))) return rc;
+  if ((rc = set_lds(k_kbest_sweep, lds_sweep))) return rc;
+  KbWs w;
+  kb_ws_layout(lat, k, (char *)ws, &w);
+  const hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_kbest_levels, dim3(lat->n_lattices), dim3(kKbLevelThreads), (size_t)lds_lev, st, *lat, w);
+  hipLaunchKernelGGL(k_kbest_sweep, dim3(lat->n_lattices), dim3(kKbSweepThreads), (size_t)lds_sweep, st, *lat, *scores,
+                     (int)k, w);
+  hipLaunchKernelGGL(k_kbest_walk, dim3(lat->n_lattices), dim3(64), 0, st, *lat, (int)k, w, best, paths, path_arcs,
+                     lengths, n_paths, (int)max_len, (int)pad, status);
   return hip_status(hipGetLastError());
 }
 

@@ -62,6 +62,24 @@ class JointProb(torch.nn.Module):
             return num_prob, denom_prob, best_sample
         return num_prob, denom_prob
 
+    def nbest_from_npz(self, npz_path, k: int):
+        """The k best mark sequences of the record's numerator machine under ``tilde_p.theta`` (whatever ``exact``)
+        with their log-probabilities ``log p = score - log Z``: the n-best list a reranker consumes (evaluate/rerank.py
+        reads one from an outside system).  Returns a list of ``(log_p: float, mark: LongTensor[T])``, best first, at
+        most k entries (fewer when the machine has fewer paths); marks are cut after the implicit bos as
+        ``forward``'s ``best_sample`` is."""
+        em, tr = tuple(torch.from_numpy(_).unsqueeze(0) for _ in io.load_fsa_from_npz(npz_path))[:2]
+        self.tilde_p.set_masks(emission=em, transition=tr)
+        lat = self.tilde_p._lat()
+        theta = self.tilde_p.theta.detach()
+        with torch.no_grad():
+            r = ops.k_best(lat, theta, k, pad=self.tilde_p.__pad__)
+            logz = ops.forward_backward(lat, theta, want_alpha_beta=False, want_posterior=False).logz64
+        n = int(r.n_paths[0])
+        best = r.best[0, :n].to(torch.float64) - logz[0]
+        lens = r.lengths[0, :n].tolist()
+        return [(float(best[j]), r.paths[0, j, 1:max(lens[j], 2)].to(torch.int64)) for j in range(n)]
+
     def decode_from_npz(self, npz_path, vocab_size, pad):
         """lightning.py:647-658: ``(prob: float, mark: LongTensor[T])``."""
         single_batch = tuple(torch.from_numpy(_).unsqueeze(0) for _ in io.load_fsa_from_npz(npz_path))

@@ -432,6 +432,103 @@ def viterbi(lat: LatticeBatch, theta, arc_scores=None, max_len: Optional[int] = 
     return ViterbiResult(best, paths, arcs, lens)
 
 
+class KBestResult(NamedTuple):
+    best: torch.Tensor  # [B, k] float32, non-increasing; -inf beyond n_paths
+    paths: torch.Tensor  # [B, k, max_len] int32 labels (bos .. eos), pad-terminated
+    arcs: torch.Tensor  # [B, k, max_len] int32 canonical arc ids, -1 padded
+    lengths: torch.Tensor  # [B, k] int32 arcs per path (0 beyond n_paths)
+    n_paths: torch.Tensor  # [B] int32 min(k, paths of score > -inf)
+
+
+MAX_K = 64  # (nfst_kbest: a back pointer keeps the rank in 6 bits)
+
+
+def k_best_terms(lat: LatticeBatch, theta, k: int, arc_scores=None, max_len: Optional[int] = None, pad: int = 0) -> KBestResult:
+    """One launch of ``nfst_kbest`` (no autograd); see ``k_best``."""
+    _need_gpu(lat)
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
+        raise ValueError(f"k must be an int in [1, {MAX_K}], not {k!r}")
+    sc, keep = _scores(lat, theta, arc_scores)
+    if max_len is None:
+        max_len = int(lat.depth.max()) + 1
+    dev = lat.device
+    B = lat.n_lattices
+    ws_bytes = int(lib.nfst_kbest_ws_bytes(C.byref(lat.c_struct()), int(k)))
+    check(min(ws_bytes, 0), "nfst_kbest_ws_bytes")
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    best = torch.empty((B, k), dtype=torch.float32, device=dev)
+    paths = torch.empty((B, k, max_len), dtype=torch.int32, device=dev)
+    arcs = torch.empty((B, k, max_len), dtype=torch.int32, device=dev)
+    lens = torch.empty((B, k), dtype=torch.int32, device=dev)
+    n_paths = torch.empty(B, dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib.nfst_kbest(C.byref(lat.c_struct()), C.byref(sc), int(k), ws.data_ptr(), ws_bytes, _ptr(best), _ptr(paths),
+                         _ptr(arcs), _ptr(lens), _ptr(n_paths), int(max_len), int(pad), _ptr(status), _stream()),
+          "nfst_kbest")
+    st = int(status.item())
+    if st != 0:
+        raise _lib.NfstError(st, "nfst_kbest")  # a path longer than max_len
+    return KBestResult(best, paths, arcs, lens, n_paths)
+
+
+class _KBest(torch.autograd.Function):
+    """best[b, j] = the sum of the scores of path j's arcs: d/d arc_scores[a] = 1 on the path's arcs, d/d theta counts
+    its labels (per lattice for a [B, V] theta); -inf entries (no path) get no gradient."""
+
+    @staticmethod
+    def forward(ctx, lat, theta, arc_scores, k, max_len, pad):
+        r = k_best_terms(lat, theta.detach(), k, None if arc_scores is None else arc_scores.detach(), max_len, pad)
+        ctx.lat, ctx.theta_like = lat, theta
+        ctx.asc_like = arc_scores
+        ctx.save_for_backward(r.arcs)
+        ctx.mark_non_differentiable(r.paths, r.arcs, r.lengths, r.n_paths)
+        return r.best, r.paths, r.arcs, r.lengths, r.n_paths
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, *_):
+        (arcs,) = ctx.saved_tensors
+        nt, na = ctx.needs_input_grad[1:3]
+        lat = ctx.lat
+        B, K, T = arcs.shape
+        a = arcs.reshape(B, K * T).to(torch.int64)
+        on = a >= 0
+        gg = torch.where(torch.isfinite(g), g, torch.zeros_like(g)).to(torch.float32)
+        w = gg[:, :, None].expand(B, K, T).reshape(B, K * T)[on]  # (-inf entries have no arcs)
+        idx = a[on]
+        f32 = dict(dtype=torch.float32, device=arcs.device)
+        d_arc = d_theta = None
+        if na:
+            d_arc = torch.zeros(lat.total_arcs, **f32).index_add_(0, idx, w)
+            d_arc = d_arc.to(dtype=ctx.asc_like.dtype, device=ctx.asc_like.device)
+        if nt:
+            lab = lat.arc_label.to(torch.int64)[idx]
+            V = lat.vocab
+            if ctx.theta_like.dim() == 1:
+                d_theta = torch.zeros(V, **f32).index_add_(0, lab, w)
+            else:
+                row = torch.arange(B, device=arcs.device)[:, None].expand(B, K * T)[on]
+                d_theta = torch.zeros(B * V, **f32).index_add_(0, row * V + lab, w).view(B, V)
+            d_theta = d_theta.to(dtype=ctx.theta_like.dtype, device=ctx.theta_like.device)
+        return None, d_theta, d_arc, None, None, None
+
+
+def k_best(lat: LatticeBatch, theta, k: int, arc_scores=None, max_len: Optional[int] = None, pad: int = 0) -> KBestResult:
+    """The k best paths of every lattice, exact (``nfst_kbest``): the n-best list that
+    evaluate/rerank.py reranks and the exact, deterministic form of JointProb.forward's "best of K samples"
+    (modules/lightning.py:474-479).  ``theta`` [V] or [B, V], ``arc_scores`` [total_arcs] (optional); 1 <= k <= 64.
+    Entry 0 is ``viterbi``'s path (bit for bit with its general kernel); ties on exactly equal scores go to the smaller
+    first differing label.  Lattices with fewer than k paths of score > -inf fill the rest with score -inf, length 0,
+    ``pad`` labels and arc -1 (``n_paths`` counts the real ones).  ``max_len`` defaults to the longest path + 1; a
+    longer path raises ``NfstError`` (NFST_ERR_LENGTH).  ``best`` is differentiable in theta and arc_scores: the
+    gradient of a path's score counts its labels / marks its arcs."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
+        raise ValueError(f"k must be an int in [1, {MAX_K}], not {k!r}")
+    if not isinstance(theta, torch.Tensor):
+        theta = torch.as_tensor(theta, dtype=torch.float32)
+    return KBestResult(*_KBest.apply(lat, theta, arc_scores, k, max_len, pad))
+
+
 class SampleResult(NamedTuple):
     paths: torch.Tensor  # [B, K, max_len] int32 labels, pad-terminated
     arcs: torch.Tensor  # [B, K, max_len] int32 canonical arc ids

@@ -81,6 +81,11 @@ class LatticeScorer(torch.nn.Module):
         """Differentiable exact path entropy per lattice ``[B]`` (nats); d/d theta = -Cov(mark counts, path score)."""
         return ops.entropy(self._lat(), self.theta)
 
+    def k_best(self, k: int, max_len: Optional[int] = None) -> "ops.KBestResult":
+        """The k best paths of every lattice with their scores under ``theta`` (``ops.k_best``; ``best`` is
+        differentiable in theta)."""
+        return ops.k_best(self._lat(), self.theta, k, max_len=max_len, pad=self.__pad__)
+
     # ------------------------------------------------------------ per-step gathers
     def update_fsa_state(self, updated: torch.Tensor, prev_states: torch.Tensor) -> torch.Tensor:
         """scorers.py:683-690."""

@@ -16,15 +16,12 @@ struct LdsPlan {
   }
   __host__ __device__ int64_t bwd_fixed_precise() const { return ((int64_t)rows2 + v2) * 16 + kSweepFlags * 4 + 1024; }
   // words of one sweep's rings
-  static __host__ __device__ int64_t sweep_words(int R, int RS, bool extra) {
-    (void)extra;
-    return (int64_t)R * kSlotWords + (int64_t)RS * kRawWords;
+  static __host__ __device__ int64_t sweep_words(int R, int RS) { return (int64_t)R * kSlotWords + (int64_t)RS * kRawWords; }
+  __host__ __device__ int64_t fb_bytes(int R, int RS) const {
+    return ((int64_t)2 * rows2 + v2) * 8 + (int64_t)v4 * 4 + 2 * sweep_words(R, RS) * 4 + 2 * kSweepFlags * 4 + 1024;  // + flag words + 64 x 8 bytes of trash per fused sweep
   }
-  __host__ __device__ int64_t fb_bytes(int R, int RS, bool extra) const {
-    return ((int64_t)2 * rows2 + v2) * 8 + (int64_t)v4 * 4 + 2 * sweep_words(R, RS, extra) * 4 + 2 * kSweepFlags * 4 + 1024;  // + flag words + 64 x 8 bytes of trash per fused sweep
-  }
-  __host__ __device__ int64_t bwd_bytes(int R, int RS, bool extra) const {
-    return ((int64_t)rows2 + v2) * 8 + sweep_words(R, RS, extra) * 4 + kSweepFlags * 4;
+  __host__ __device__ int64_t bwd_bytes(int R, int RS) const {
+    return ((int64_t)rows2 + v2) * 8 + sweep_words(R, RS) * 4 + kSweepFlags * 4;
   }
 };
 
@@ -81,7 +78,7 @@ __global__ __launch_bounds__(NT) void k_backward(nfst_batch lat, nfst_scores sc,
   load_theta(th, sc.theta, sc.theta_stride, b, lat.vocab, tid, NT, theta_first);
   if (x_wave && m.bwd_u == 8) xw8.start_gathers(lane);
   __syncthreads();
-  int *flags = (int *)(ring + (TW ? (int64_t)R * kTwSlot : LdsPlan::sweep_words(R, RS, EXTRA)));
+  int *flags = (int *)(ring + (TW ? (int64_t)R * kTwSlot : LdsPlan::sweep_words(R, RS)));
   if (tid == 0) {
     val_set(beta[m.sink], 0.5f, 1);
     for (int i = 0; i < kSweepFlags; ++i) flags[i] = 0;
@@ -191,7 +188,7 @@ __global__ __launch_bounds__(NT) void k_forward_backward(
   const int my_tiles = bwd_side ? m.bwd_tiles : m.fwd_tiles;
   const int my_u = bwd_side ? m.bwd_u : m.fwd_u;
   const bool my_wide = (bwd_side ? m.bwd_wide : m.fwd_wide) != 0;
-  uint32_t *my_ring = bwd_side ? ring : ring + (TW ? (int64_t)R * kTwSlot : LdsPlan::sweep_words(R, RS, EXTRA));
+  uint32_t *my_ring = bwd_side ? ring : ring + (TW ? (int64_t)R * kTwSlot : LdsPlan::sweep_words(R, RS));
   const bool tw_v2 = TW && !my_wide;  // (the decoded-tile format of tile_sweep2: programs with narrow groups)
   uint32_t *my_raw = my_ring + (size_t)R * kSlotWords;
   // NT = 1024: the workgroup has the CU to itself: waves 4 / 5 load for the decoders (deep
@@ -200,20 +197,12 @@ __global__ __launch_bounds__(NT) void k_forward_backward(
   constexpr int kAhead = kSelf ? kDmaAheadShared : kDmaAheadDeep;
   static_assert(!(FUSED && EXTRA), "the fused sweep takes no per-arc extras");
   static_assert(!(EXTRA && NT < 512), "the extras waves need idle waves: 512 threads at least");
-#ifndef NFST_XW_MODE
-#define NFST_XW_MODE 0
-#endif
-  // extras waves per sweep, the first of them (tuning: NFST_XW_MODE 1 = only the waves on the decoders' SIMDs, 2 = only
-  // those on the sweep waves' SIMDs)
-  constexpr int kNE = (TW || (NT == 1024 && NFST_XW_MODE == 0)) ? 4 : 2, kFirstX = NT == 1024 ? 8 : 4;
-#ifndef NFST_TW_PLACE
-#define NFST_TW_PLACE 1
-#endif
-  // tile waves: 1 = waves 2 .. 9 (two per SIMD: one SIMD cannot issue a whole sweep's decoding -- ~100 slots per
-  // tile -- at the sweep's pace); 0 = the eight waves of SIMDs 2 and 3
-  const bool x_wave = TW ? (NFST_TW_PLACE == 1 ? (wv >= 2 && wv < 10) : (wv & 2) != 0)
-                         : EXTRA != 0 && wv >= kFirstX && (NT != 1024 || NFST_XW_MODE == 0 || ((wv >> 1) & 1) == (NFST_XW_MODE == 1 ? 1 : 0));
-  const int x_index = TW ? (NFST_TW_PLACE == 1 ? (wv - 2) >> 1 : wv >> 2) : (NT == 1024 && NFST_XW_MODE != 0) ? (wv - kFirstX) >> 2 : (wv - kFirstX) >> 1;
+  // extras waves per sweep, the first of them
+  constexpr int kNE = (TW || NT == 1024) ? 4 : 2, kFirstX = NT == 1024 ? 8 : 4;
+  // tile waves: waves 2 .. 9 (two per SIMD: one SIMD cannot issue a whole sweep's decoding -- ~100 slots per tile -- at
+  // the sweep's pace)
+  const bool x_wave = TW ? (wv >= 2 && wv < 10) : EXTRA != 0 && wv >= kFirstX;
+  const int x_index = TW ? (wv - 2) >> 1 : (wv - kFirstX) >> 1;
   if (FUSED) {
     if (wv < 2) FusedSweep<false>::start(my_prog, my_tiles, lane);  // (start() does not depend on WIDE)
   } else if (TW) {  // (the tile waves start below)
@@ -233,7 +222,7 @@ __global__ __launch_bounds__(NT) void k_forward_backward(
   if (grad_theta) for (int l = tid; l < lat.vocab; l += NT) gth[l] = 0.0f;
   if (x_wave && my_u == 8) xw8.start_gathers(lane);
   __syncthreads();
-  int *flags = (int *)(ring + 2 * (TW ? (int64_t)R * kTwSlot : LdsPlan::sweep_words(R, RS, EXTRA)));
+  int *flags = (int *)(ring + 2 * (TW ? (int64_t)R * kTwSlot : LdsPlan::sweep_words(R, RS)));
   float *xc = (float *)(flags + 2 * kSweepFlags + 256);  // (behind the flags and the 1 KiB of trash)
   constexpr int kTrash = PREC ? 16 : 8;  // bytes of trash per lane and sweep (the non-leader lanes' stores)
   const int xc_first = m.arc_off & ~3;

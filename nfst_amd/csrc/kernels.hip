@@ -83,6 +83,14 @@ int set_lds(K kernel, int64_t bytes) {
   return rc;
 }
 
+// Every kernel of the library is launched here: the LDS opt-in, the launch, the launch's status.
+template <class K, class... A>
+int launch(K kernel, dim3 grid, dim3 block, int64_t lds, hipStream_t st, A... args) {
+  if (int rc = set_lds(kernel, lds)) return rc;
+  hipLaunchKernelGGL(kernel, grid, block, (size_t)lds, st, args...);
+  return hip_status(hipGetLastError());
+}
+
 // number of CUs of the current device (cached per device; 256 on MI355X)
 int cu_count() {
   static std::mutex mu;
@@ -104,12 +112,7 @@ int cu_count() {
 struct Tuning {
   int64_t lds_reserve = 0;  // NFST_LDS_RESERVE_KB: LDS the one-lattice-per-CU flavours leave free on every CU
   int tw = 1;               // NFST_TW=0: loader + decoder + sweep instead of tile waves
-  int fused = 1;            // NFST_NO_FUSED=1: never the fused sweeps
-  int xcache = 1;           // NFST_XCACHE=0: per-arc extras gathered from HBM / L2, never staged in LDS
   int precise = -1;         // NFST_PRECISE: 0 never, 1 whenever it fits, unset: programs deeper than kPreciseTiles tiles
-  int neu_pack = 1;         // NFST_NEU_PACK=0: phase B reads Wh from the matrix itself
-  int neu_bf16 = 1;         // NFST_NEU_BF16=0: phase B on float32 MFMAs instead of three bfloat16 parts (hid a multiple of 64)
-  int neu_small = 1;        // NFST_NEU_NO_SMALL=1: two-phase neural kernels for every hidden size
   int chunked = 1;          // NFST_CHUNKED=0: never the chunked flavour (a batch with chunked programs runs the general kernels)
 };
 Tuning &tuning() {
@@ -119,12 +122,7 @@ Tuning &tuning() {
     const long kb = num("NFST_LDS_RESERVE_KB", 0);
     r.lds_reserve = (kb > 0 && kb <= 96) ? kb * 1024 : 0;
     r.tw = num("NFST_TW", 1) != 0;
-    r.fused = num("NFST_NO_FUSED", 0) != 1;
-    r.xcache = num("NFST_XCACHE", 1) != 0;
     r.precise = (int)num("NFST_PRECISE", -1);
-    r.neu_pack = num("NFST_NEU_PACK", 1) != 0;
-    r.neu_bf16 = num("NFST_NEU_BF16", 1) != 0;
-    r.neu_small = getenv("NFST_NEU_NO_SMALL") ? 0 : 1;
     r.chunked = num("NFST_CHUNKED", 1) != 0;
     return r;
   }();
@@ -132,44 +130,282 @@ Tuning &tuning() {
 }
 int64_t lds_reserve() { return tuning().lds_reserve; }
 
+// ------------------------------------------------------------------ choosing the kernel of a sweep op
+template <int N>
+using ic = std::integral_constant<int, N>;
+
+// arrays of per-arc extras: 0 none, 1 one (table weights or caller scores), 2 both; 3 (forward-backward tile waves only):
+// their sum staged in LDS
+int extras_case(const nfst_batch *lat, const nfst_scores *sc) {
+  const bool w = lat->weighted && lat->arc_w;
+  return w && sc->arc_scores ? 2 : (w || sc->arc_scores) ? 1 : 0;
+}
+template <bool Staged = false, class F>
+int with_extras(int ex, F f) {
+  if constexpr (Staged) {
+    if (ex == 3) return f(ic<3>());
+  }
+  return ex == 2 ? f(ic<2>()) : ex == 1 ? f(ic<1>()) : f(ic<0>());
+}
+// threads of the pipeline flavours: 256 or 512, and 1024 where Deep
+template <bool Deep, class F>
+int with_threads(int nt, F f) {
+  if constexpr (Deep) {
+    if (nt == 1024) return f(ic<1024>());
+  }
+  return nt == 512 ? f(ic<512>()) : f(ic<256>());
+}
+
+// the largest lattice's arc count; NFST_BATCH_MAX_ARCS_CAP: that many or more
+int64_t max_lattice_arcs(const nfst_batch *lat) { return ((int64_t)lat->reserved0 >> NFST_BATCH_MAX_ARCS_SHIFT) & NFST_BATCH_MAX_ARCS_CAP; }
+
+// ring slots per sweep beside `fixed` bytes when `reserve` bytes of the CU's LDS stay free: at most kMaxRing, a multiple
+// of four (tile_sweep2 takes four tiles per trip)
+int ring_slots(int64_t fixed, int64_t slot_bytes, int64_t reserve) {
+  const int64_t r = (kMaxLds - reserve - fixed) / slot_bytes;
+  return (int)(r > kMaxRing ? kMaxRing : r) & ~3;
+}
+
 // the precise flavour (float64 mantissas, semiring.h) runs all-compact batches whose deepest program has more than
 // kPreciseTiles tiles, when at least four ring slots per sweep fit beside the 16-byte values
 int precise_ring(const nfst_batch *lat, int64_t fixed, int n_rings) {
   const Tuning &tu = tuning();
   if (!(lat->reserved0 & NFST_BATCH_ALL_COMPACT) || tu.precise == 0) return 0;
   if (tu.precise != 1 && lat->max_tiles <= kPreciseTiles) return 0;
-  const int64_t r = (kMaxLds - lds_reserve() - fixed) / ((int64_t)kSlotWordsP * 4 * n_rings);
-  const int R = (int)(r > kMaxRing ? kMaxRing : r) & ~3;
+  const int R = ring_slots(fixed, (int64_t)kSlotWordsP * 4 * n_rings, lds_reserve());
   return R >= 4 ? R : 0;
 }
 
+// Ring sizes per sweep from the LDS budget of one workgroup, and which pipeline runs.
+//   deep   (at most one lattice per CU): loader + decoder + sweep waves, deep staging ring;
+//   shared (more lattices than CUs): the decoder loads for itself, shallow staging ring, and
+//          two workgroups share a CU's 160 KiB when the lattices are small enough.
+// A lattice too large for the deep rings runs the shared pipeline with the whole CU.
+// NFST_LDS_RESERVE_KB (environment, read once): LDS the one-lattice-per-CU flavour leaves free on
+// every CU, so that a small kernel of another stream -- RCCL's all-reduce of the loss -- finds a CU
+// to run on beside a sweep workgroup instead of waiting for one to retire.  Costs ring depth only.
+struct RingCfg { int R, RS; bool self; };
+bool ring_config(const LdsPlan &plan, bool fb, bool deep, RingCfg *c) {
+  const int n_rings = fb ? 2 : 1;
+  const int64_t slot = (int64_t)kSlotWords * 4 * n_rings;
+  auto fixed = [&](int RS) { return fb ? plan.fb_bytes(0, RS) : plan.bwd_bytes(0, RS); };
+  auto clampr = [](int64_t r) { return (int)(r > kMaxRing ? kMaxRing : r); };
+  if (deep) {
+    const int64_t r = (kMaxLds - lds_reserve() - fixed(kRawSlotsDeep)) / slot;
+    if (r >= kMinRing) { *c = {clampr(r), kRawSlotsDeep, false}; return true; }
+  } else {
+    const int64_t r = (kMaxLds / 2 - fixed(kRawSlotsShared)) / slot;
+    if (r >= kMinRing + 1) { *c = {clampr(r), kRawSlotsShared, true}; return true; }
+  }
+  const int64_t r = (kMaxLds - fixed(kRawSlotsShared)) / slot;
+  if (r < kMinRing) return false;
+  *c = {clampr(r), kRawSlotsShared, true};
+  return true;
+}
 
-// The chunked flavour (chunk_kernels.h): sweeps (one workgroup per lattice and direction), then posteriors / totals.  Returns
-// the device flags of the lattices that have to be run again by the general kernels (tagged *tag).
-int chunked_launch(const nfst_batch *lat, const nfst_scores *scores, int n_dirs, float *logalpha, float *logbeta, double *logz64,
-                   float *logz32, float *posterior, float *grad_theta, float *beta_me, double *logz_total, int total_slot, hipStream_t st,
-                   const int32_t **flags, int *tag) {
+// The kernel of a sweep op for a batch: flavour, threads, extras case, ring slots per sweep (R), staging slots or, for
+// staged extras, their room in floats (RS), dynamic LDS.
+//   precise:    tile waves with float64 mantissas (programs deeper than kPreciseTiles tiles);
+//   tile waves: one lattice per CU, all-compact (NFST_TW=0: the pipeline instead);
+//   pipeline:   loader + decoder + sweep waves (deep) or self-loading decoders + sweeps (shared; ring_config);
+//   fused:      forward-backward of all-compact batches without extras, more lattices than CUs (no rings at all);
+//   general:    Viterbi from global memory.
+enum class Flavour { precise, tile_waves, pipeline, fused, general };
+struct SweepPlan { Flavour flavour; int nt, ex, R, RS; int64_t lds; };
+
+int plan_backward(const nfst_batch *lat, const nfst_scores *sc, SweepPlan *p) {
+  const int ex = extras_case(lat, sc);
+  const LdsPlan plan(lat->max_rows, lat->vocab);
+  RingCfg cfg;
+  if (!ring_config(plan, false, lat->n_lattices <= cu_count(), &cfg)) return NFST_ERR_LIMIT;
+  if (ex && ((uintptr_t)lat->bwd_perm & 15)) return NFST_ERR_ARG;  // the extras waves read the slot -> arc map 16 bytes at a time
+  if (const int Rp = precise_ring(lat, plan.bwd_fixed_precise(), 1)) {
+    *p = {Flavour::precise, 512, ex, Rp, 0, plan.bwd_fixed_precise() + (int64_t)Rp * kSlotWordsP * 4};
+  } else if (!cfg.self && (lat->reserved0 & NFST_BATCH_ALL_COMPACT) && tuning().tw) {
+    const int64_t fixed = plan.bwd_bytes(0, 0) + 512;  // + 64 x 8 bytes of trash for the non-leader lanes' stores
+    const int R = ring_slots(fixed, (int64_t)kSlotWords2 * 4, lds_reserve());
+    if (R < 4) return NFST_ERR_LIMIT;
+    *p = {Flavour::tile_waves, 512, ex, R, 0, fixed + (int64_t)R * kSlotWords2 * 4};
+  } else {  // 512 threads: loader + decoder + sweep (deep); 256 threads: self-loading decoder + sweep
+    *p = {Flavour::pipeline, cfg.self ? 256 : 512, ex, cfg.R, cfg.RS, plan.bwd_bytes(cfg.R, cfg.RS)};
+  }
+  return NFST_OK;
+}
+
+int plan_forward_backward(const nfst_batch *lat, const nfst_scores *sc, SweepPlan *p) {
+  const int ex = extras_case(lat, sc);
+  if (ex && (((uintptr_t)lat->fwd_perm | (uintptr_t)lat->bwd_perm | (uintptr_t)lat->arc_w | (uintptr_t)sc->arc_scores) & 15))
+    return NFST_ERR_ARG;  // (maps and extras are read 16 bytes at a time)
+  const LdsPlan plan(lat->max_rows, lat->vocab);
+  const int cus = cu_count();
+  const bool compact = lat->reserved0 & NFST_BATCH_ALL_COMPACT;
+  // deep programs: the precise flavour, whatever the number of lattices
+  if (const int Rp = precise_ring(lat, plan.fb_fixed_precise(), 2)) {
+    *p = {Flavour::precise, 1024, ex, Rp, 0, plan.fb_fixed_precise() + (int64_t)Rp * kSlotWordsP * 4 * 2};
+    return NFST_OK;
+  }
+  // Measured (profiles/r02_ab_fused.txt): 227 against 164 G arcs/s at 1024 lattices, 210 against 160 at 2048,
+  // equal at 512; with one lattice per CU the three-wave pipeline is 10 % faster (46.8 against 51.8 us).
+  // (512 threads at most: with 1024 the 128 registers a lane may have leave hipcc 64 VGPRs beside the
+  // fused sweep's 32 AGPRs, and it then spills into AGPRs -- into the ones the sweep stages tiles in)
+  if (!ex && compact && lat->n_lattices > cus) {
+    *p = {Flavour::fused, lat->n_lattices <= 2 * cus ? 512 : 256, 0, 0, 0, plan.fb_bytes(0, 0)};
+    return NFST_OK;
+  }
+  RingCfg cfg;
+  if (!ring_config(plan, true, lat->n_lattices <= cus, &cfg)) return NFST_ERR_LIMIT;
+  if (!cfg.self && compact && tuning().tw) {  // no staging ring; ring slots of kSlotWords2 words
+    const int64_t slot = (int64_t)kSlotWords2 * 4 * 2, fixed = plan.fb_bytes(0, 0);
+    const int R = ring_slots(fixed, slot, lds_reserve());
+    if (R < 4) return NFST_ERR_LIMIT;
+    *p = {Flavour::tile_waves, 1024, ex, R, 0, fixed + (int64_t)R * slot};
+    // per-arc extras staged in LDS (the sum of both arrays, 4 bytes per arc of the largest lattice) when a ring of at least
+    // eight slots per sweep still fits beside them (lattices up to ~14k arcs at 2k states); RS carries the room in floats
+    const int64_t max_arcs = max_lattice_arcs(lat);
+    if (ex && max_arcs > 0 && max_arcs < NFST_BATCH_MAX_ARCS_CAP) {
+      const int64_t words = (max_arcs + 8 + 3) & ~(int64_t)3;
+      const int Rc = ring_slots(fixed + words * 4, slot, lds_reserve());
+      // (with four slots per sweep the tile waves cannot run ahead: 69 us against 50 from HBM / L2 at 256 x 20k arcs)
+      if (Rc >= 8) *p = {Flavour::tile_waves, 1024, 3, Rc, (int)words, fixed + (int64_t)Rc * slot + words * 4};
+    }
+    return NFST_OK;
+  }
+  // 1024 threads: loaders + decoders + sweeps and 10 more waves for the posterior pass (deep);
+  // 512 / 256 threads: self-loading decoders + sweeps, two workgroups per CU when they fit (extras waves: 512 threads)
+  const int nt = !cfg.self ? 1024 : (ex || lat->n_lattices <= 2 * cus) ? 512 : 256;
+  *p = {Flavour::pipeline, nt, ex, cfg.R, cfg.RS, plan.fb_bytes(cfg.R, cfg.RS)};
+  return NFST_OK;
+}
+
+int plan_viterbi(const nfst_batch *lat, const nfst_scores *sc, SweepPlan *p) {
+  // all-compact batches: the tile-wave kernel (NFST_TW=0: one wave reading the program from global memory)
+  const int ex = extras_case(lat, sc);
+  const int64_t fixed = VitLds(lat->max_rows, lat->vocab).fixed();
+  const int R = ring_slots(fixed, (int64_t)kSlotWords2 * 4, 0);
+  if ((lat->reserved0 & NFST_BATCH_ALL_COMPACT) && R >= 8 && tuning().tw &&  // (its trips check four tiles ahead: eight slots)
+      (!ex || (((uintptr_t)lat->arc_w | (uintptr_t)sc->arc_scores) & 3) == 0) && ((uintptr_t)lat->bwd_perm & 15) == 0)
+    *p = {Flavour::tile_waves, kVitTwThreads, ex, R, 0, fixed + (int64_t)R * kSlotWords2 * 4};
+  else
+    *p = {Flavour::general, kVitThreads, ex, 0, 0, (int64_t)lat->max_rows * 12 + (int64_t)lat->vocab * 4 + 16};
+  return NFST_OK;
+}
+
+// the outputs of nfst_backward (n_dirs 1) and nfst_forward_backward (n_dirs 2)
+struct SweepOut {
+  int n_dirs;
+  float *logalpha, *logbeta;
+  double *logz64;
+  float *logz32, *posterior, *grad_theta, *beta_me;
+  double *logz_total;
+  int total_slot;
+};
+
+int launch_backward(const nfst_batch *lat, const nfst_scores *sc, const SweepOut &o, hipStream_t st) {
+  SweepPlan p;
+  if (int rc = plan_backward(lat, sc, &p)) return rc;
+  auto go = [&](auto kernel) {
+    return launch(kernel, dim3(lat->n_lattices), dim3(p.nt), p.lds, st, *lat, *sc, p.R, p.RS, o.logbeta, o.logz64, o.logz32,
+                  (float2 *)o.beta_me);
+  };
+  switch (p.flavour) {
+    case Flavour::precise: return with_extras(p.ex, [&](auto EX) { return go(k_backward<512, EX, true, true>); });
+    case Flavour::tile_waves: return with_extras(p.ex, [&](auto EX) { return go(k_backward<512, EX, true>); });
+    default:
+      return with_threads<false>(p.nt, [&](auto NT) { return with_extras(p.ex, [&](auto EX) { return go(k_backward<NT, EX>); }); });
+  }
+}
+
+int launch_forward_backward(const nfst_batch *lat, const nfst_scores *sc, const SweepOut &o, hipStream_t st) {
+  SweepPlan p;
+  if (int rc = plan_forward_backward(lat, sc, &p)) return rc;
+  auto go = [&](auto kernel) {
+    return launch(kernel, dim3(lat->n_lattices), dim3(p.nt), p.lds, st, *lat, *sc, p.R, p.RS, o.logalpha, o.logbeta, o.logz64,
+                  o.logz32, o.logz_total, o.total_slot, o.posterior, o.grad_theta, (float2 *)o.beta_me);
+  };
+  switch (p.flavour) {
+    case Flavour::precise: return with_extras(p.ex, [&](auto EX) { return go(k_forward_backward<1024, EX, false, true, true>); });
+    case Flavour::tile_waves: return with_extras<true>(p.ex, [&](auto EX) { return go(k_forward_backward<1024, EX, false, true>); });
+    case Flavour::fused: return with_threads<false>(p.nt, [&](auto NT) { return go(k_forward_backward<NT, 0, true>); });
+    default:
+      return with_threads<true>(p.nt, [&](auto NT) {
+        if constexpr (NT == 256) return go(k_forward_backward<256, 0>);  // (the plan gives extras 512 threads)
+        else return with_extras(p.ex, [&](auto EX) { return go(k_forward_backward<NT, EX>); });
+      });
+  }
+}
+
+// The sweeps of nfst_backward and nfst_forward_backward.  Deep, narrow lattices run the chunked flavour (chunk_kernels.h):
+// sweeps (one workgroup per lattice and direction), then posteriors / totals; lattices whose numbers leave its range are
+// flagged on the device and run by the general kernels after it (a launch that finds no flag set returns at once).
+int sweeps(const nfst_batch *lat, const nfst_scores *sc, const SweepOut &o, hipStream_t st) {
+  if (!lat->chunks || !tuning().chunked)
+    return o.n_dirs == 2 ? launch_forward_backward(lat, sc, o, st) : launch_backward(lat, sc, o, st);
   nfst_chunks *ck = const_cast<nfst_chunks *>(lat->chunks);
   if (ck->n_lattices != lat->n_lattices || ck->total_rows != lat->total_rows || ck->total_arcs != lat->total_arcs || !ck->meta ||
       !ck->tab || !ck->stream || !ck->pos || !ck->label || !ck->ws || ck->ws_bytes < nfst_chunks_ws_bytes(ck) || ck->threads < 64 ||
       ck->threads > 1024 || (ck->threads & 63) || ck->lds_bytes <= 0 || ck->lds_bytes > kMaxLds || ((uintptr_t)ck->ws & 15))
     return NFST_ERR_ARG;
   ck->launches = ck->launches >= INT_MAX - 1 ? 1 : ck->launches + 1;
-  *tag = ck->launches;
-  *flags = chk_ws(*ck).flags;
-  int rc;
-  if ((rc = set_lds(k_chunk_sweep, ck->lds_bytes))) return rc;
-  hipLaunchKernelGGL(k_chunk_sweep, dim3(lat->n_lattices * n_dirs), dim3(ck->threads), (size_t)ck->lds_bytes, st, *lat, *scores, *ck,
-                     *tag, n_dirs, logalpha, logbeta, logz64, logz32, grad_theta, (float2 *)beta_me);
-  if (n_dirs == 2 && (posterior || grad_theta || logz_total)) {
-    const size_t lds = grad_theta ? (size_t)lat->vocab * 4 : 0;
+  nfst_batch rest = *lat;
+  rest.chunks = nullptr;
+  rest.only = chk_ws(*ck).flags;
+  rest.only_tag = ck->launches;
+  int rc = launch(k_chunk_sweep, dim3(lat->n_lattices * o.n_dirs), dim3(ck->threads), ck->lds_bytes, st, *lat, *sc, *ck, rest.only_tag,
+                  o.n_dirs, o.logalpha, o.logbeta, o.logz64, o.logz32, o.grad_theta, (float2 *)o.beta_me);
+  if (rc) return rc;
+  if (o.n_dirs == 2 && (o.posterior || o.grad_theta || o.logz_total)) {
     // workgroups of 256 threads, about four arcs per thread of the largest lattice: a slice of a lattice's arcs each
-    const int64_t max_arcs = ((int64_t)lat->reserved0 >> NFST_BATCH_MAX_ARCS_SHIFT) & NFST_BATCH_MAX_ARCS_CAP;
-    const int parts = (posterior || grad_theta) ? (int)std::max<int64_t>(1, std::min<int64_t>(64, (max_arcs + 1023) / 1024)) : 1;
-    hipLaunchKernelGGL(k_chunk_post, dim3(lat->n_lattices * parts), dim3(256), lds, st, *lat, *scores, *ck, *tag, parts, posterior,
-                       grad_theta, logz_total, total_slot);
+    const int parts = (o.posterior || o.grad_theta) ? (int)std::max<int64_t>(1, std::min<int64_t>(64, (max_lattice_arcs(lat) + 1023) / 1024)) : 1;
+    if ((rc = launch(k_chunk_post, dim3(lat->n_lattices * parts), dim3(256), o.grad_theta ? (int64_t)lat->vocab * 4 : 0, st, *lat, *sc,
+                     *ck, rest.only_tag, parts, o.posterior, o.grad_theta, o.logz_total, o.total_slot)))
+      return rc;
   }
-  return hip_status(hipGetLastError());
+  return sweeps(&rest, sc, o, st);
+}
+
+// ------------------------------------------------------------------ neural kernels and path_logprob
+// Phase B of the two-phase neural kernels runs on three bfloat16 parts of Wh when hid is a multiple of 64 from 256 on
+// (below 256 the split's two barriers per pass cost more than the matrix pipe gains: H = 128 1.41 against 1.39 ms); the
+// parts are packed in MFMA fragment order into the workspace behind its first `ws_floats` floats.
+int pack_wh(const float *wh, int hid, float *ws, int64_t ws_floats, hipStream_t st, int *packed) {
+  *packed = hid % 64 == 0 && hid >= 256;
+  if (!*packed) return NFST_OK;
+  return launch(k_pack_mfma_b3, dim3(((hid >> 4) * (hid >> 5) * 64 + 255) / 256), dim3(256), 0, st, wh, hid,
+                reinterpret_cast<uint4 *>(ws + neu_pack_off(ws_floats)));
+}
+// the hidden size as a template argument: the packed kernels <8 / 16 / 32> up to 32, then the two-phase kernels
+// <1 / 2 / 4 / 8>.  BASELINE batch, whole op: H = 8 0.52 against 1.19 ms, 16 0.58 / 1.18, 32 1.07 / 1.19; with a whole
+// wave per record (H = 64) the packed kernel has nothing to pack and loses to the two-phase one: 1.97 / 1.24
+template <class S, class T>
+int with_hid(int hid, S small, T two_phase) {
+  if (hid <= 8) return small(ic<8>());
+  if (hid <= 16) return small(ic<16>());
+  if (hid <= 32) return small(ic<32>());
+  if (hid <= 64) return two_phase(ic<1>());
+  if (hid <= 128) return two_phase(ic<2>());
+  if (hid <= 256) return two_phase(ic<4>());
+  return two_phase(ic<8>());
+}
+
+// the variant of the 16-byte streaming path_logprob kernels (plp_variant) as template arguments <NV, RB, L>; 0: the
+// general kernel
+template <class V, class G>
+int with_plp_variant(int u, V v4, G general) {
+  switch (u) {
+    case 0: return general();
+    case 1: return v4(ic<1>(), ic<8>(), ic<16>());
+    case 2: return v4(ic<2>(), ic<4>(), ic<16>());
+    case 3: return v4(ic<3>(), ic<4>(), ic<16>());
+    case 4: return v4(ic<4>(), ic<2>(), ic<16>());
+    case 5: return v4(ic<5>(), ic<2>(), ic<16>());
+    case 6: return v4(ic<6>(), ic<2>(), ic<16>());
+    case 7: return v4(ic<7>(), ic<1>(), ic<16>());
+    case 8: return v4(ic<8>(), ic<1>(), ic<16>());
+    case 13: return v4(ic<5>(), ic<2>(), ic<32>());  // 129 .. 160 slots
+    case 14: return v4(ic<6>(), ic<2>(), ic<32>());
+    case 15: return v4(ic<7>(), ic<1>(), ic<32>());
+    default: return v4(ic<8>(), ic<1>(), ic<32>());  // 16: up to 256 slots
+  }
 }
 
 }  // namespace
@@ -187,12 +423,7 @@ int nfst_tuning_set(const char *name, int value) {
   Tuning &t = tuning();
   const std::string n(name);
   if (n == "tw") t.tw = value != 0;
-  else if (n == "fused") t.fused = value != 0;
-  else if (n == "xcache") t.xcache = value != 0;
   else if (n == "precise") t.precise = value < 0 ? -1 : (value != 0);
-  else if (n == "neu_pack") t.neu_pack = value != 0;
-  else if (n == "neu_bf16") t.neu_bf16 = value != 0;
-  else if (n == "neu_small") t.neu_small = value != 0;
   else if (n == "chunked") t.chunked = value != 0;
   else if (n == "lds_reserve_kb") t.lds_reserve = (value > 0 && value <= 96) ? (int64_t)value * 1024 : 0;
   else return NFST_ERR_ARG;
@@ -205,18 +436,8 @@ int nfst_dense_to_arcs_count(const void *emission, int emission_is_float, const 
                              int32_t *status, void *stream) {
   if (!emission || !transition || !reach || !row_cnt || !counts || !status || n_lattices <= 0 || n_rows <= 0 || vocab <= 0) return NFST_ERR_ARG;
   if (n_rows > NFST_MAX_ROWS || vocab > NFST_MAX_VOCAB) return NFST_ERR_LIMIT;
-  const int64_t lds = (int64_t)n_rows * 12;
-  int rc;
-  if (emission_is_float) {
-    if ((rc = set_lds(k_dense_reach<true>, lds))) return rc;
-    hipLaunchKernelGGL(k_dense_reach<true>, dim3(n_lattices), dim3(kPkThreads), (size_t)lds, (hipStream_t)stream, emission, transition,
-                       (int)n_rows, (int)vocab, reach, row_cnt, counts, status);
-  } else {
-    if ((rc = set_lds(k_dense_reach<false>, lds))) return rc;
-    hipLaunchKernelGGL(k_dense_reach<false>, dim3(n_lattices), dim3(kPkThreads), (size_t)lds, (hipStream_t)stream, emission, transition,
-                       (int)n_rows, (int)vocab, reach, row_cnt, counts, status);
-  }
-  return hip_status(hipGetLastError());
+  return launch(emission_is_float ? k_dense_reach<true> : k_dense_reach<false>, dim3(n_lattices), dim3(kPkThreads), (int64_t)n_rows * 12,
+                (hipStream_t)stream, emission, transition, (int)n_rows, (int)vocab, reach, row_cnt, counts, status);
 }
 
 int nfst_dense_to_arcs_write(const void *emission, int emission_is_float, const int64_t *transition, int32_t n_lattices,
@@ -226,14 +447,8 @@ int nfst_dense_to_arcs_write(const void *emission, int emission_is_float, const 
     return NFST_ERR_ARG;
   if (emission_is_float && !arc_w) return NFST_ERR_ARG;
   if (n_rows > NFST_MAX_ROWS || vocab > NFST_MAX_VOCAB) return NFST_ERR_LIMIT;
-  const int64_t lds = (int64_t)n_rows * 4;
-  if (emission_is_float)
-    hipLaunchKernelGGL(k_dense_write<true>, dim3(n_lattices), dim3(kPkThreads), (size_t)lds, (hipStream_t)stream, emission, transition,
-                       (int)n_rows, (int)vocab, reach, row_cnt, arc_off, src, label, dst, arc_w);
-  else
-    hipLaunchKernelGGL(k_dense_write<false>, dim3(n_lattices), dim3(kPkThreads), (size_t)lds, (hipStream_t)stream, emission, transition,
-                       (int)n_rows, (int)vocab, reach, row_cnt, arc_off, src, label, dst, arc_w);
-  return hip_status(hipGetLastError());
+  return launch(emission_is_float ? k_dense_write<true> : k_dense_write<false>, dim3(n_lattices), dim3(kPkThreads), (int64_t)n_rows * 4,
+                (hipStream_t)stream, emission, transition, (int)n_rows, (int)vocab, reach, row_cnt, arc_off, src, label, dst, arc_w);
 }
 
 int64_t nfst_pack_device_ws_bytes(int32_t n_lattices, int64_t total_rows, int64_t total_arcs) {
@@ -262,9 +477,7 @@ int nfst_pack_device_plan(const nfst_arcs_device *arcs, const nfst_pack_opts *op
   if (rc) return rc;
   if (!meta || !status || !scratch_rows) return NFST_ERR_ARG;
   a.meta = meta; a.status = status; a.scratch = scratch_rows;
-  if ((rc = set_lds(k_pack_lattice<false>, kPkLdsBytes))) return rc;
-  hipLaunchKernelGGL(k_pack_lattice<false>, dim3(arcs->n_lattices), dim3(kPkThreads), (size_t)kPkLdsBytes, (hipStream_t)stream, a);
-  return hip_status(hipGetLastError());
+  return launch(k_pack_lattice<false>, dim3(arcs->n_lattices), dim3(kPkThreads), kPkLdsBytes, (hipStream_t)stream, a);
 }
 
 int nfst_pack_device_emit(const nfst_arcs_device *arcs, const nfst_pack_opts *opts, void *ws, int64_t ws_bytes,
@@ -285,9 +498,7 @@ int nfst_pack_device_emit(const nfst_arcs_device *arcs, const nfst_pack_opts *op
       hipMemsetAsync(const_cast<uint32_t *>(out->arc_sd) + out->total_arcs, 0, 8 * 4, st) != hipSuccess ||
       hipMemsetAsync(const_cast<uint16_t *>(out->arc_l16) + out->total_arcs, 0, 8 * 2, st) != hipSuccess)
     return NFST_ERR_HIP;
-  if ((rc = set_lds(k_pack_lattice<true>, kPkLdsBytes))) return rc;
-  hipLaunchKernelGGL(k_pack_lattice<true>, dim3(arcs->n_lattices), dim3(kPkThreads), (size_t)kPkLdsBytes, (hipStream_t)stream, a);
-  return hip_status(hipGetLastError());
+  return launch(k_pack_lattice<true>, dim3(arcs->n_lattices), dim3(kPkThreads), kPkLdsBytes, st, a);
 }
 
 int64_t nfst_pack_chunks_device_ws_bytes(int32_t n_lattices, int64_t total_rows, int64_t total_arcs) {
@@ -327,10 +538,9 @@ int nfst_pack_chunks_device_plan(const nfst_arcs_device *arcs, const void *pack_
   // (nfst_pack_chunks' quick no: up to ~160 levels the general kernels are done before this flavour's fixed costs are)
   if (!o.force && batch->max_tiles <= 160) return NFST_OK;
   a.threads = threads; a.lds_bytes = lds_bytes; a.max_chunks = o.max_chunks; a.summary = summary;
-  const int64_t lds = cp_plan_lds(batch->max_rows);
-  if ((rc = set_lds(k_chunk_plan, lds))) return rc;
-  hipLaunchKernelGGL(k_chunk_plan, dim3(2 * arcs->n_lattices), dim3(kPkThreads), (size_t)lds, (hipStream_t)stream, a, (int)batch->max_rows);
-  if ((rc = hip_status(hipGetLastError()))) return rc;
+  if ((rc = launch(k_chunk_plan, dim3(2 * arcs->n_lattices), dim3(kPkThreads), cp_plan_lds(batch->max_rows), (hipStream_t)stream, a,
+                   (int)batch->max_rows)))
+    return rc;
   *launched = 1;
   return NFST_OK;
 }
@@ -350,42 +560,12 @@ int nfst_pack_chunks_device_emit(const nfst_arcs_device *arcs, const void *pack_
   if (hipMemsetAsync(a.stream + (chunks->n_stream - 64), 0, 64 * 4, st) != hipSuccess ||
       hipMemsetAsync(a.label + (chunks->n_stream - 64), 0, 64 * 2, st) != hipSuccess)
     return NFST_ERR_HIP;
-  const int64_t lds = 4 * (int64_t)batch->max_rows;
-  if ((rc = set_lds(k_chunk_emit, lds))) return rc;
-  hipLaunchKernelGGL(k_chunk_emit, dim3(2 * arcs->n_lattices), dim3(kPkThreads), (size_t)lds, st, a);
-  return hip_status(hipGetLastError());
+  return launch(k_chunk_emit, dim3(2 * arcs->n_lattices), dim3(kPkThreads), 4 * (int64_t)batch->max_rows, st, a);
 }
 
 int64_t nfst_lds_bytes(const nfst_batch *lat) {
   if (!lat) return NFST_ERR_ARG;
-  return LdsPlan(lat->max_rows, lat->vocab).fb_bytes(kMinRing, kRawSlotsShared, lat->weighted != 0);
-}
-
-// Ring sizes per sweep from the LDS budget of one workgroup, and which kernel flavour runs.
-//   deep   (at most one lattice per CU): loader + decoder + sweep waves, deep staging ring;
-//   shared (more lattices than CUs): the decoder loads for itself, shallow staging ring, and
-//          two workgroups share a CU's 160 KiB when the lattices are small enough.
-// A lattice too large for the deep rings runs the shared flavour with the whole CU.
-// NFST_LDS_RESERVE_KB (environment, read once): LDS the one-lattice-per-CU flavour leaves free on
-// every CU, so that a small kernel of another stream -- RCCL's all-reduce of the loss -- finds a CU
-// to run on beside a sweep workgroup instead of waiting for one to retire.  Costs ring depth only.
-struct RingCfg { int R, RS; bool self; };
-static bool ring_config(const LdsPlan &plan, bool fb, bool extra, bool deep, RingCfg *c) {
-  const int n_rings = fb ? 2 : 1;
-  const int64_t slot = (int64_t)kSlotWords * 4 * n_rings;
-  auto fixed = [&](int RS) { return fb ? plan.fb_bytes(0, RS, extra) : plan.bwd_bytes(0, RS, extra); };
-  auto clampr = [](int64_t r) { return (int)(r > kMaxRing ? kMaxRing : r); };
-  if (deep) {
-    const int64_t r = (kMaxLds - lds_reserve() - fixed(kRawSlotsDeep)) / slot;
-    if (r >= kMinRing) { *c = {clampr(r), kRawSlotsDeep, false}; return true; }
-  } else {
-    const int64_t r = (kMaxLds / 2 - fixed(kRawSlotsShared)) / slot;
-    if (r >= kMinRing + 1) { *c = {clampr(r), kRawSlotsShared, true}; return true; }
-  }
-  const int64_t r = (kMaxLds - fixed(kRawSlotsShared)) / slot;
-  if (r < kMinRing) return false;
-  *c = {clampr(r), kRawSlotsShared, true};
-  return true;
+  return LdsPlan(lat->max_rows, lat->vocab).fb_bytes(kMinRing, kRawSlotsShared);
 }
 
 int nfst_backward(const nfst_batch *lat, const nfst_scores *scores, float *logbeta, double *logz64,
@@ -393,63 +573,7 @@ int nfst_backward(const nfst_batch *lat, const nfst_scores *scores, float *logbe
   int rc = check_batch(lat);
   if (rc) return rc;
   if ((rc = check_scores(lat, scores))) return rc;
-  if (lat->chunks && tuning().chunked) {
-    // deep, narrow lattices: the chunked sweeps; lattices whose numbers leave their range are flagged on the device and
-    // run by the general kernels below (a launch that finds no flag set returns at once)
-    nfst_batch rest = *lat;
-    rest.chunks = nullptr;
-    if ((rc = chunked_launch(lat, scores, 1, nullptr, logbeta, logz64, logz32, nullptr, nullptr, beta_me, nullptr, 0, (hipStream_t)stream,
-                             &rest.only, &rest.only_tag)))
-      return rc;
-    return nfst_backward(&rest, scores, logbeta, logz64, logz32, beta_me, stream);
-  }
-  const bool extra = (lat->weighted && lat->arc_w) || scores->arc_scores;
-  const LdsPlan plan(lat->max_rows, lat->vocab);
-  RingCfg cfg;
-  if (!ring_config(plan, false, extra, lat->n_lattices <= cu_count(), &cfg)) return NFST_ERR_LIMIT;
-  if (extra && ((uintptr_t)lat->bwd_perm & 15)) return NFST_ERR_ARG;  // the extras waves read the slot -> arc map 16 bytes at a time
-  const bool both = lat->weighted && lat->arc_w && scores->arc_scores;
-  if (const int Rp = precise_ring(lat, plan.bwd_fixed_precise(), 1)) {
-    const int64_t ldsp = plan.bwd_fixed_precise() + (int64_t)Rp * kSlotWordsP * 4;
-#define NFST_LAUNCH_BWD_P(EX)                                                                            \
-    {                                                                                                  \
-      if ((rc = set_lds(k_backward<512, EX, true, true>, ldsp))) return rc;                            \
-      hipLaunchKernelGGL((k_backward<512, EX, true, true>), dim3(lat->n_lattices), dim3(512), (size_t)ldsp, \
-                         (hipStream_t)stream, *lat, *scores, Rp, 0, logbeta, logz64, logz32, (float2 *)beta_me); \
-    }
-    if (both) NFST_LAUNCH_BWD_P(2) else if (extra) NFST_LAUNCH_BWD_P(1) else NFST_LAUNCH_BWD_P(0)
-#undef NFST_LAUNCH_BWD_P
-    return hip_status(hipGetLastError());
-  }
-  // one lattice per CU, all-compact: tile waves (NFST_TW=0: loader + decoder + sweep, for A/B runs)
-  const bool tw = !cfg.self && (lat->reserved0 & NFST_BATCH_ALL_COMPACT) && tuning().tw;
-  const int64_t tw_fixed = plan.bwd_bytes(0, 0, extra) + 512;  // + 64 x 8 bytes of trash for the non-leader lanes' stores
-  if (tw) {
-    const int64_t r = (kMaxLds - lds_reserve() - tw_fixed) / ((int64_t)kSlotWords2 * 4);
-    cfg = {(int)(r > kMaxRing ? kMaxRing : r) & ~3, 0, false};
-    if (cfg.R < 4) return NFST_ERR_LIMIT;
-  }
-  const int R = cfg.R, RS = cfg.RS;
-  const int64_t lds = tw ? tw_fixed + (int64_t)R * kSlotWords2 * 4 : plan.bwd_bytes(R, RS, extra);
-#define NFST_LAUNCH_BWD_TW(EX)                                                                           \
-  {                                                                                                    \
-    if ((rc = set_lds(k_backward<512, EX, true>, lds))) return rc;                                     \
-    hipLaunchKernelGGL((k_backward<512, EX, true>), dim3(lat->n_lattices), dim3(512), (size_t)lds,     \
-                       (hipStream_t)stream, *lat, *scores, R, RS, logbeta, logz64, logz32, (float2 *)beta_me); \
-  }
-#define NFST_LAUNCH_BWD(NT, EX)                                                                          \
-  {                                                                                                    \
-    if ((rc = set_lds(k_backward<NT, EX>, lds))) return rc;                                            \
-    hipLaunchKernelGGL((k_backward<NT, EX>), dim3(lat->n_lattices), dim3(NT), (size_t)lds,             \
-                       (hipStream_t)stream, *lat, *scores, R, RS, logbeta, logz64, logz32, (float2 *)beta_me); \
-  }
-  // 512 threads: loader + decoder + sweep (deep); 256 threads: self-loading decoder + sweep
-  if (tw) { if (both) NFST_LAUNCH_BWD_TW(2) else if (extra) NFST_LAUNCH_BWD_TW(1) else NFST_LAUNCH_BWD_TW(0) }
-  else if (!cfg.self) { if (both) NFST_LAUNCH_BWD(512, 2) else if (extra) NFST_LAUNCH_BWD(512, 1) else NFST_LAUNCH_BWD(512, 0) }
-  else { if (both) NFST_LAUNCH_BWD(256, 2) else if (extra) NFST_LAUNCH_BWD(256, 1) else NFST_LAUNCH_BWD(256, 0) }
-#undef NFST_LAUNCH_BWD
-#undef NFST_LAUNCH_BWD_TW
-  return hip_status(hipGetLastError());
+  return sweeps(lat, scores, {1, nullptr, logbeta, logz64, logz32, nullptr, nullptr, beta_me, nullptr, 0}, (hipStream_t)stream);
 }
 
 int nfst_forward_backward(const nfst_batch *lat, const nfst_scores *scores, float *logalpha,
@@ -461,107 +585,8 @@ int nfst_forward_backward(const nfst_batch *lat, const nfst_scores *scores, floa
   if (posterior && ((uintptr_t)posterior & 15)) return NFST_ERR_ARG;
   if (logz_total && (total_slot < 0 || total_slot > 2)) return NFST_ERR_ARG;
   if (!lat->arc_sd || !lat->arc_l16 || ((uintptr_t)lat->arc_sd & 15) || ((uintptr_t)lat->arc_l16 & 7)) return NFST_ERR_ARG;
-  if (lat->chunks && tuning().chunked) {  // (as in nfst_backward)
-    nfst_batch rest = *lat;
-    rest.chunks = nullptr;
-    if ((rc = chunked_launch(lat, scores, 2, logalpha, logbeta, logz64, logz32, posterior, grad_theta, beta_me, logz_total, (int)total_slot,
-                             (hipStream_t)stream, &rest.only, &rest.only_tag)))
-      return rc;
-    return nfst_forward_backward(&rest, scores, logalpha, logbeta, logz64, logz32, posterior, grad_theta, beta_me, logz_total, total_slot,
-                                 stream);
-  }
-  const bool extra = (lat->weighted && lat->arc_w) || scores->arc_scores;
-  const bool both = lat->weighted && lat->arc_w && scores->arc_scores;
-  const LdsPlan plan(lat->max_rows, lat->vocab);
-  const int cus = cu_count();
-  RingCfg cfg;
-  if (extra && (((uintptr_t)lat->fwd_perm | (uintptr_t)lat->bwd_perm | (uintptr_t)lat->arc_w | (uintptr_t)scores->arc_scores) & 15))
-    return NFST_ERR_ARG;  // (maps and extras are read 16 bytes at a time)
-  // deep programs: the precise flavour (tile waves with float64 mantissas), whatever the number of lattices
-  if (const int Rp = precise_ring(lat, plan.fb_fixed_precise(), 2)) {
-    const int64_t ldsp = plan.fb_fixed_precise() + (int64_t)Rp * kSlotWordsP * 4 * 2;
-#define NFST_LAUNCH_TWP(EX)                                                                               \
-    {                                                                                                   \
-      if ((rc = set_lds(k_forward_backward<1024, EX, false, true, true>, ldsp))) return rc;             \
-      hipLaunchKernelGGL((k_forward_backward<1024, EX, false, true, true>), dim3(lat->n_lattices), dim3(1024), (size_t)ldsp, \
-                         (hipStream_t)stream, *lat, *scores, Rp, 0, logalpha, logbeta, logz64, logz32, logz_total,        \
-                         (int)total_slot, posterior, grad_theta, (float2 *)beta_me);                    \
-    }
-    if (both) NFST_LAUNCH_TWP(2) else if (extra) NFST_LAUNCH_TWP(1) else NFST_LAUNCH_TWP(0)
-#undef NFST_LAUNCH_TWP
-    return hip_status(hipGetLastError());
-  }
-  // every program compact and no per-arc extras: the fused sweeps (no rings at all)
-  // Measured (profiles/r02_ab_fused.txt): 227 against 164 G arcs/s at 1024 lattices, 210 against 160 at 2048,
-  // equal at 512; with one lattice per CU the three-wave pipeline is 10 % faster (46.8 against 51.8 us).
-  const bool fused = !extra && (lat->reserved0 & NFST_BATCH_ALL_COMPACT) && lat->n_lattices > cus && tuning().fused;
-  // one lattice per CU: tile waves instead of loader + decoder (NFST_TW=0: the three-wave pipeline, for A/B runs)
-  bool tw = false, cached = false;
-  if (fused) cfg = {0, 0, lat->n_lattices > cus};
-  else if (!ring_config(plan, true, extra, lat->n_lattices <= cus, &cfg)) return NFST_ERR_LIMIT;
-  else if (!cfg.self && (lat->reserved0 & NFST_BATCH_ALL_COMPACT) && tuning().tw) {
-    tw = true;  // no staging ring; ring slots of kSlotWords2 words
-    const int64_t slot = (int64_t)kSlotWords2 * 4 * 2;
-    const int64_t r = (kMaxLds - lds_reserve() - plan.fb_bytes(0, 0, extra)) / slot;
-    cfg = {(int)(r > kMaxRing ? kMaxRing : r) & ~3, 0, false};  // (tile_sweep2 takes four tiles per trip: a multiple of four slots)
-    if (cfg.R < 4) return NFST_ERR_LIMIT;
-    // per-arc extras staged in LDS (the sum of both arrays, 4 bytes per arc of the largest lattice) when a ring of at least
-    // eight slots per sweep still fits beside them (lattices up to ~14k arcs at 2k states); RS carries the room in floats
-    const int64_t max_arcs = ((int64_t)lat->reserved0 >> NFST_BATCH_MAX_ARCS_SHIFT) & NFST_BATCH_MAX_ARCS_CAP;
-    if (extra && max_arcs > 0 && max_arcs < NFST_BATCH_MAX_ARCS_CAP && tuning().xcache) {  // (NFST_XCACHE=0: gather from HBM / L2 instead, for A/B runs)
-      const int64_t words = (max_arcs + 8 + 3) & ~(int64_t)3;
-      const int64_t rc2 = ((kMaxLds - lds_reserve() - plan.fb_bytes(0, 0, extra) - words * 4) / slot) & ~(int64_t)3;
-      if (rc2 >= 8) {  // (with four slots per sweep the tile waves cannot run ahead: 69 us against 50 from HBM / L2 at 256 x 20k arcs)
-        cached = true;
-        cfg = {(int)(rc2 > kMaxRing ? kMaxRing : rc2), (int)words, false};
-      }
-    }
-  }
-  const int R = cfg.R, RS = cfg.RS;
-  const int64_t lds = tw ? plan.fb_bytes(0, 0, extra) + (int64_t)R * kSlotWords2 * 4 * 2 + (cached ? (int64_t)RS * 4 : 0) : plan.fb_bytes(R, RS, extra);
-#define NFST_LAUNCH_FB(NT, EX)                                                                            \
-  {                                                                                                     \
-    if ((rc = set_lds(k_forward_backward<NT, EX>, lds))) return rc;                                     \
-    hipLaunchKernelGGL((k_forward_backward<NT, EX>), dim3(lat->n_lattices), dim3(NT), (size_t)lds,      \
-                       (hipStream_t)stream, *lat, *scores, R, RS, logalpha, logbeta, logz64, logz32, logz_total,    \
-                       (int)total_slot, posterior,                                                      \
-                       grad_theta, (float2 *)beta_me);                                                  \
-  }
-#define NFST_LAUNCH_TW(EX)                                                                                 \
-  {                                                                                                     \
-    if ((rc = set_lds(k_forward_backward<1024, EX, false, true>, lds))) return rc;                      \
-    hipLaunchKernelGGL((k_forward_backward<1024, EX, false, true>), dim3(lat->n_lattices), dim3(1024), (size_t)lds, \
-                       (hipStream_t)stream, *lat, *scores, R, RS, logalpha, logbeta, logz64, logz32, logz_total,    \
-                       (int)total_slot, posterior, grad_theta, (float2 *)beta_me);                      \
-  }
-#define NFST_LAUNCH_FUSED(NT)                                                                            \
-  {                                                                                                     \
-    if ((rc = set_lds(k_forward_backward<NT, 0, true>, lds))) return rc;                                \
-    hipLaunchKernelGGL((k_forward_backward<NT, 0, true>), dim3(lat->n_lattices), dim3(NT), (size_t)lds,     \
-                       (hipStream_t)stream, *lat, *scores, R, RS, logalpha, logbeta, logz64, logz32, logz_total,    \
-                       (int)total_slot, posterior, grad_theta, (float2 *)beta_me);                      \
-  }
-  // 1024 threads: loaders + decoders + sweeps and 10 more waves for the posterior pass (deep);
-  // 512 / 256 threads: self-loading decoders + sweeps, two workgroups per CU when they fit
-  if (fused) {
-    if (lds > kMaxLds) return NFST_ERR_LIMIT;
-    // (512 threads at most: with 1024 the 128 registers a lane may have leave hipcc 64 VGPRs beside the
-    // fused sweep's 32 AGPRs, and it then spills into AGPRs -- into the ones the sweep stages tiles in)
-    if (lat->n_lattices <= 2 * cus) NFST_LAUNCH_FUSED(512)
-    else NFST_LAUNCH_FUSED(256)
-  } else if (!cfg.self && tw) {
-    if (cached) NFST_LAUNCH_TW(3) else if (both) NFST_LAUNCH_TW(2) else if (extra) NFST_LAUNCH_TW(1) else NFST_LAUNCH_TW(0)
-  } else if (!cfg.self) {
-    if (both) NFST_LAUNCH_FB(1024, 2) else if (extra) NFST_LAUNCH_FB(1024, 1) else NFST_LAUNCH_FB(1024, 0)
-  }
-  else if (both) NFST_LAUNCH_FB(512, 2)  // (the weight waves are waves 4 .. 7)
-  else if (extra) NFST_LAUNCH_FB(512, 1)
-  else if (lat->n_lattices <= 2 * cus) NFST_LAUNCH_FB(512, 0)
-  else NFST_LAUNCH_FB(256, 0)
-#undef NFST_LAUNCH_FB
-#undef NFST_LAUNCH_TW
-#undef NFST_LAUNCH_FUSED
-  return hip_status(hipGetLastError());
+  return sweeps(lat, scores, {2, logalpha, logbeta, logz64, logz32, posterior, grad_theta, beta_me, logz_total, (int)total_slot},
+                (hipStream_t)stream);
 }
 
 int nfst_viterbi(const nfst_batch *lat, const nfst_scores *scores, float *best, int32_t *paths,
@@ -570,30 +595,16 @@ int nfst_viterbi(const nfst_batch *lat, const nfst_scores *scores, float *best, 
   if (rc) return rc;
   if ((rc = check_scores(lat, scores))) return rc;
   if (!best || !paths || !lengths || max_len <= 0) return NFST_ERR_ARG;
-  // all-compact batches: the tile-wave kernel (NFST_TW=0: one wave reading the program from global memory, for A/B runs)
-  const bool extra = (lat->weighted && lat->arc_w) || scores->arc_scores;
-  const bool both = lat->weighted && lat->arc_w && scores->arc_scores;
-  const int64_t tw_fixed = VitLds(lat->max_rows, lat->vocab).fixed();
-  int64_t tw_r = (kMaxLds - tw_fixed) / ((int64_t)kSlotWords2 * 4);
-  tw_r = (tw_r > kMaxRing ? kMaxRing : tw_r) & ~(int64_t)3;
-  if ((lat->reserved0 & NFST_BATCH_ALL_COMPACT) && tw_r >= 8 && tuning().tw &&  // (its trips check four tiles ahead: eight slots)
-      (!extra || (((uintptr_t)lat->arc_w | (uintptr_t)scores->arc_scores) & 3) == 0) && ((uintptr_t)lat->bwd_perm & 15) == 0) {
-    const int64_t lds = tw_fixed + tw_r * kSlotWords2 * 4;
-#define NFST_LAUNCH_VIT(XM)                                                                                          \
-    {                                                                                                                \
-      if ((rc = set_lds(k_viterbi_tw<XM>, lds))) return rc;                                                          \
-      hipLaunchKernelGGL(k_viterbi_tw<XM>, dim3(lat->n_lattices), dim3(kVitTwThreads), (size_t)lds, (hipStream_t)stream, \
-                         *lat, *scores, (int)tw_r, best, paths, path_arcs, lengths, (int)max_len, (int)pad);        \
-    }
-    if (both) NFST_LAUNCH_VIT(2) else if (extra) NFST_LAUNCH_VIT(1) else NFST_LAUNCH_VIT(0)
-#undef NFST_LAUNCH_VIT
-    return hip_status(hipGetLastError());
-  }
-  const int64_t lds = (int64_t)lat->max_rows * 12 + (int64_t)lat->vocab * 4 + 16;
-  if ((rc = set_lds(k_viterbi, lds))) return rc;
-  hipLaunchKernelGGL(k_viterbi, dim3(lat->n_lattices), dim3(kVitThreads), (size_t)lds, (hipStream_t)stream, *lat,
-                     *scores, best, paths, path_arcs, lengths, (int)max_len, (int)pad);
-  return hip_status(hipGetLastError());
+  SweepPlan p;
+  if ((rc = plan_viterbi(lat, scores, &p))) return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  if (p.flavour == Flavour::tile_waves)
+    return with_extras(p.ex, [&](auto EX) {
+      return launch(k_viterbi_tw<EX>, dim3(lat->n_lattices), dim3(p.nt), p.lds, st, *lat, *scores, p.R, best, paths, path_arcs, lengths,
+                    (int)max_len, (int)pad);
+    });
+  return launch(k_viterbi, dim3(lat->n_lattices), dim3(p.nt), p.lds, st, *lat, *scores, best, paths, path_arcs, lengths, (int)max_len,
+                (int)pad);
 }
 
 int nfst_sample_paths(const nfst_batch *lat, const nfst_scores *scores, const float *beta_me,
@@ -612,17 +623,14 @@ int nfst_sample_paths(const nfst_batch *lat, const nfst_scores *scores, const fl
   // when it fits what it was given
   const int64_t csr = ((int64_t)lat->max_rows + 8) * 4 + ((int64_t)lat->max_tiles * 256 + 8) * 6;
   const int64_t lds = lds_min + csr <= kMaxLds ? lds_min + csr : (lds_min + 64 * 1024 <= kMaxLds ? kMaxLds : lds_min);
-  if ((rc = set_lds(k_sample, lds))) return rc;
   // 16 walks per 256 threads; up to 64 walks (1024 threads) of a lattice in one block share its staged data
   // (with the arcs' probabilities precomputed per block -- path_arcs given and the CSR fits -- every block has 1024
   // threads for that pass, whatever k)
   const bool precdf = path_arcs && lds > lds_min;  // (the kernel decides per lattice, from its own arc count)
   const int walks = (k >= 64 || precdf) ? 64 : ((k + 15) / 16) * 16;
-  hipLaunchKernelGGL(k_sample, dim3(lat->n_lattices, (k + walks - 1) / walks), dim3(walks * 16),
-                     (size_t)lds, (hipStream_t)stream,
-                     *lat, *scores, (const float2 *)beta_me, logz64, (int)k, (int)max_len, uniforms,
-                     seed, (int)pad, stage_theta, (int)lds, paths, path_arcs, lengths, logq, status);
-  return hip_status(hipGetLastError());
+  return launch(k_sample, dim3(lat->n_lattices, (k + walks - 1) / walks), dim3(walks * 16), lds, (hipStream_t)stream, *lat, *scores,
+                (const float2 *)beta_me, logz64, (int)k, (int)max_len, uniforms, seed, (int)pad, stage_theta, (int)lds, paths, path_arcs,
+                lengths, logq, status);
 }
 
 int nfst_score_paths(const nfst_batch *lat, const nfst_scores *scores, const int32_t *marks, int32_t k,
@@ -631,10 +639,8 @@ int nfst_score_paths(const nfst_batch *lat, const nfst_scores *scores, const int
   if (rc) return rc;
   if ((rc = check_scores(lat, scores))) return rc;
   if (!marks || !path_score || !end_state || k <= 0 || max_len <= 0) return NFST_ERR_ARG;
-  hipLaunchKernelGGL(k_score_paths, dim3(lat->n_lattices, (k + 63) / 64), dim3(64), 0,
-                     (hipStream_t)stream, *lat, *scores, marks, (int)k, (int)max_len, path_score,
-                     end_state);
-  return hip_status(hipGetLastError());
+  return launch(k_score_paths, dim3(lat->n_lattices, (k + 63) / 64), dim3(64), 0, (hipStream_t)stream, *lat, *scores, marks, (int)k,
+                (int)max_len, path_score, end_state);
 }
 
 int nfst_step(const nfst_batch *lat, const int64_t *state, const int64_t *label, int64_t *next,
@@ -643,9 +649,7 @@ int nfst_step(const nfst_batch *lat, const int64_t *state, const int64_t *label,
   if (rc) return rc;
   if (!state || !label || !next || k <= 0) return NFST_ERR_ARG;
   const int64_t n = (int64_t)lat->n_lattices * k;
-  hipLaunchKernelGGL(k_step, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *lat,
-                     state, label, next, (int)k, n);
-  return hip_status(hipGetLastError());
+  return launch(k_step, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *lat, state, label, next, (int)k, n);
 }
 
 int nfst_emission_mask(const nfst_batch *lat, const int64_t *state, const int64_t *inp, int32_t pad,
@@ -655,11 +659,8 @@ int nfst_emission_mask(const nfst_batch *lat, const int64_t *state, const int64_
   if (rc) return rc;
   if (!state || !out || k <= 0) return NFST_ERR_ARG;
   const int64_t n = (int64_t)lat->n_lattices * k;
-  if ((rc = set_lds(k_row_gather<0>, (int64_t)lat->vocab * 4))) return rc;
-  hipLaunchKernelGGL(k_row_gather<0>, dim3((unsigned)n), dim3(64), (size_t)lat->vocab * 4, (hipStream_t)stream, *lat, state,
-                     (const float *)nullptr, inp, (int)pad, (int)bos, (int)eos, (int)has_to_end, out,
-                     (int)k);
-  return hip_status(hipGetLastError());
+  return launch(k_row_gather<0>, dim3((unsigned)n), dim3(64), (int64_t)lat->vocab * 4, (hipStream_t)stream, *lat, state,
+                (const float *)nullptr, inp, (int)pad, (int)bos, (int)eos, (int)has_to_end, out, (int)k);
 }
 
 int nfst_beta_logits(const nfst_batch *lat, const float *values, const int64_t *state, float *out,
@@ -668,10 +669,8 @@ int nfst_beta_logits(const nfst_batch *lat, const float *values, const int64_t *
   if (rc) return rc;
   if (!values || !state || !out || k <= 0) return NFST_ERR_ARG;
   const int64_t n = (int64_t)lat->n_lattices * k;
-  if ((rc = set_lds(k_row_gather<1>, (int64_t)lat->vocab * 4))) return rc;
-  hipLaunchKernelGGL(k_row_gather<1>, dim3((unsigned)n), dim3(64), (size_t)lat->vocab * 4, (hipStream_t)stream, *lat, state,
-                     values, (const int64_t *)nullptr, 0, 0, 0, 0, out, (int)k);
-  return hip_status(hipGetLastError());
+  return launch(k_row_gather<1>, dim3((unsigned)n), dim3(64), (int64_t)lat->vocab * 4, (hipStream_t)stream, *lat, state, values,
+                (const int64_t *)nullptr, 0, 0, 0, 0, out, (int)k);
 }
 
 int nfst_proposal_step(const nfst_batch *lat, const int64_t *state, const int64_t *inp, const float *scores,
@@ -692,11 +691,9 @@ int nfst_proposal_step(const nfst_batch *lat, const int64_t *state, const int64_
   }
   const int64_t n = (int64_t)lat->n_lattices * k;
   const int64_t lds = (int64_t)kStepWaves * ((values && ex.value_state) ? 3 : 2) * lat->vocab * 4;
-  if ((rc = set_lds(k_proposal_step, lds))) return rc;
-  hipLaunchKernelGGL(k_proposal_step, dim3((unsigned)((n + kStepWaves - 1) / kStepWaves)), dim3(64 * kStepWaves), (size_t)lds,
-                     (hipStream_t)stream, *lat, state, inp, scores, values, (int)pad, (int)bos, (int)eos, (int)has_to_end,
-                     temperature, uniforms, forced, ex, symbol, logq, logz, next_state, logits_out, (int)k, n);
-  return hip_status(hipGetLastError());
+  return launch(k_proposal_step, dim3((unsigned)((n + kStepWaves - 1) / kStepWaves)), dim3(64 * kStepWaves), lds, (hipStream_t)stream,
+                *lat, state, inp, scores, values, (int)pad, (int)bos, (int)eos, (int)has_to_end, temperature, uniforms, forced, ex, symbol,
+                logq, logz, next_state, logits_out, (int)k, n);
 }
 
 int nfst_proposal_step_backward(const nfst_batch *lat, const int64_t *value_state, const float *logits,
@@ -709,10 +706,8 @@ int nfst_proposal_step_backward(const nfst_batch *lat, const int64_t *value_stat
   if (grad_values && !value_state) return NFST_ERR_ARG;
   if (!g_logq && !g_logz) return NFST_ERR_ARG;
   const int64_t n = (int64_t)lat->n_lattices * k;
-  hipLaunchKernelGGL(k_proposal_step_bwd, dim3((unsigned)((n + kStepWaves - 1) / kStepWaves)), dim3(64 * kStepWaves), 0,
-                     (hipStream_t)stream, *lat, value_state, logits, symbol, logz, g_logq, g_logz, (int)pad, temperature,
-                     grad_scores, grad_values, (int)k, n);
-  return hip_status(hipGetLastError());
+  return launch(k_proposal_step_bwd, dim3((unsigned)((n + kStepWaves - 1) / kStepWaves)), dim3(64 * kStepWaves), 0, (hipStream_t)stream,
+                *lat, value_state, logits, symbol, logz, g_logq, g_logz, (int)pad, temperature, grad_scores, grad_values, (int)k, n);
 }
 
 int64_t nfst_neural_ws_floats(const nfst_batch *lat, int32_t hid) {
@@ -728,37 +723,18 @@ int nfst_backward_neural(const nfst_batch *lat, const float *label_x, const floa
   if (!label_x || !wh || !w || !log_beta || !beta_hat || !ws || hid <= 0) return NFST_ERR_ARG;
   if (hid > kNeuMaxHid) return NFST_ERR_LIMIT;
   const int64_t lds = NeuLds(lat->max_rows, hid).bytes();
-    // phase B on three bfloat16 parts when hid is a multiple of 64 from 256 on (neu_pack = 0 or neu_bf16 = 0: float32 MFMAs from the matrix itself)
-  const int wh_packed = tuning().neu_pack && tuning().neu_bf16 && hid % 64 == 0 && hid >= 256;  // (below 256 the split's two barriers per pass cost more than the matrix pipe gains: H = 128 1.41 against 1.39 ms)
-  float *wh_ws = ws + neu_pack_off(2 * (int64_t)lat->n_lattices * lat->max_rows * (hid + 1));
-  if (wh_packed)
-    hipLaunchKernelGGL(k_pack_mfma_b3, dim3(((hid >> 4) * (hid >> 5) * 64 + 255) / 256), dim3(256), 0, (hipStream_t)stream, wh, (int)hid,
-                       reinterpret_cast<uint4 *>(wh_ws));
-#define NFST_LAUNCH_NEU(HC)                                                                                   \
-  do {                                                                                                        \
-    if ((rc = set_lds(k_backward_neural<HC>, lds))) return rc;                                                \
-    hipLaunchKernelGGL(k_backward_neural<HC>, dim3(lat->n_lattices), dim3(kNeuThreads), (size_t)lds,          \
-                       (hipStream_t)stream, *lat, label_x, wh, w, (int)hid, log_beta, beta_hat, ws, wh_packed); \
-  } while (0)
-#define NFST_LAUNCH_NEU_SMALL(LPR)                                                                             \
-  do {                                                                                                        \
-    if ((rc = set_lds(k_backward_neural_small<LPR>, lds))) return rc;                                         \
-    hipLaunchKernelGGL(k_backward_neural_small<LPR>, dim3(lat->n_lattices), dim3(kNeuThreads), (size_t)lds,   \
-                       (hipStream_t)stream, *lat, label_x, wh, w, (int)hid, log_beta, beta_hat, ws);        \
-  } while (0)
-  const int no_small = !tuning().neu_small;  // (A/B against the two-phase kernel)
-  // BASELINE batch, whole op: H = 8 0.52 against 1.19 ms, 16 0.58 / 1.18, 32 1.07 / 1.19; with a whole wave per
-  // record (H = 64) the packed kernel has nothing to pack and loses to the two-phase one: 1.97 / 1.24
-  if (hid <= 8 && !no_small) NFST_LAUNCH_NEU_SMALL(8);
-  else if (hid <= 16 && !no_small) NFST_LAUNCH_NEU_SMALL(16);
-  else if (hid <= 32 && !no_small) NFST_LAUNCH_NEU_SMALL(32);
-  else if (hid <= 64) NFST_LAUNCH_NEU(1);
-  else if (hid <= 128) NFST_LAUNCH_NEU(2);
-  else if (hid <= 256) NFST_LAUNCH_NEU(4);
-  else NFST_LAUNCH_NEU(8);
-#undef NFST_LAUNCH_NEU
-#undef NFST_LAUNCH_NEU_SMALL
-  return hip_status(hipGetLastError());
+  const hipStream_t st = (hipStream_t)stream;
+  int wh_packed;
+  if ((rc = pack_wh(wh, hid, ws, 2 * (int64_t)lat->n_lattices * lat->max_rows * (hid + 1), st, &wh_packed))) return rc;
+  const dim3 grid(lat->n_lattices), block(kNeuThreads);
+  return with_hid(
+      hid,
+      [&](auto LPR) {
+        return launch(k_backward_neural_small<LPR>, grid, block, lds, st, *lat, label_x, wh, w, (int)hid, log_beta, beta_hat, ws);
+      },
+      [&](auto HC) {
+        return launch(k_backward_neural<HC>, grid, block, lds, st, *lat, label_x, wh, w, (int)hid, log_beta, beta_hat, ws, wh_packed);
+      });
 }
 
 #ifdef NFST_PROF
@@ -794,43 +770,26 @@ int nfst_backward_neural_grad(const nfst_batch *lat, const float *label_x, const
   if (hid > kNeuMaxHid) return NFST_ERR_LIMIT;
   if (lat->fwd_slots > 0 && !lat->fwd_perm) return NFST_ERR_ARG;
   const int64_t lds = NeuGradLds(lat->max_rows, hid).bytes();
-  // phase B on three bfloat16 parts when hid is a multiple of 64 from 256 on (neu_pack = 0 or neu_bf16 = 0: float32 MFMAs from the matrix itself)
-  const int wh_packed = tuning().neu_pack && tuning().neu_bf16 && hid % 64 == 0 && hid >= 256;  // (below 256 the split's two barriers per pass cost more than the matrix pipe gains: H = 128 1.41 against 1.39 ms)
-  float *wh_ws = ws + neu_pack_off(2 * (int64_t)lat->n_lattices * lat->max_rows * hid);
-  if (wh_packed)
-    hipLaunchKernelGGL(k_pack_mfma_b3, dim3(((hid >> 4) * (hid >> 5) * 64 + 255) / 256), dim3(256), 0, (hipStream_t)stream, wh_t, (int)hid,
-                       reinterpret_cast<uint4 *>(wh_ws));
-#define NFST_LAUNCH_NEUG(HC)                                                                                       \
-  do {                                                                                                             \
-    if ((rc = set_lds(k_backward_neural_grad<HC>, lds))) return rc;                                                \
-    hipLaunchKernelGGL(k_backward_neural_grad<HC>, dim3(lat->n_lattices), dim3(kNeuThreads), (size_t)lds,          \
-                       (hipStream_t)stream, *lat, label_x, wh_t, w, (int)hid, beta_hat, ws_fwd, g_log_beta,         \
-                       g_beta_hat, gamma, grad_label_x, grad_w, ws, wh_packed);                                    \
-  } while (0)
+  const hipStream_t st = (hipStream_t)stream;
+  int wh_packed;
+  if ((rc = pack_wh(wh_t, hid, ws, 2 * (int64_t)lat->n_lattices * lat->max_rows * hid, st, &wh_packed))) return rc;
   // (the packed kernel sums dL/dx per lattice in LDS when [V, hid] floats fit beside its rows and staged tiles)
   const int64_t lds_small0 = (int64_t)neu_rows_al(lat->max_rows) * 8 + (int64_t)((lat->max_rows + 3) & ~3) * 4 + 2 * kNeuGradStageWords * 4 + 16;
   // (BASELINE batch, whole gradient op: H = 8 1.34 ms with the LDS table against 1.72 with global atomics; H = 16 1.80
   // against 1.56, H = 32 3.13 against 2.56 -- the table is contended only when its rows are a few lanes wide)
   const int gx_in_lds = hid <= 8 && lds_small0 + (int64_t)lat->vocab * hid * 4 <= kMaxLds;
   const int64_t lds_small = lds_small0 + (gx_in_lds ? (int64_t)lat->vocab * hid * 4 : 0);
-#define NFST_LAUNCH_NEUG_SMALL(LPR)                                                                               \
-  do {                                                                                                             \
-    if ((rc = set_lds(k_backward_neural_grad_small<LPR>, lds_small))) return rc;                                   \
-    hipLaunchKernelGGL(k_backward_neural_grad_small<LPR>, dim3(lat->n_lattices), dim3(kNeuThreads), (size_t)lds_small, \
-                       (hipStream_t)stream, *lat, label_x, wh_t, w, (int)hid, beta_hat, ws_fwd, g_log_beta,         \
-                       g_beta_hat, gamma, grad_label_x, grad_w, ws, gx_in_lds);                                    \
-  } while (0)
-  const int no_small = !tuning().neu_small;  // (A/B against the two-phase kernel)
-  if (hid <= 8 && !no_small) NFST_LAUNCH_NEUG_SMALL(8);
-  else if (hid <= 16 && !no_small) NFST_LAUNCH_NEUG_SMALL(16);
-  else if (hid <= 32 && !no_small) NFST_LAUNCH_NEUG_SMALL(32);
-  else if (hid <= 64) NFST_LAUNCH_NEUG(1);
-  else if (hid <= 128) NFST_LAUNCH_NEUG(2);
-  else if (hid <= 256) NFST_LAUNCH_NEUG(4);
-  else NFST_LAUNCH_NEUG(8);
-#undef NFST_LAUNCH_NEUG
-#undef NFST_LAUNCH_NEUG_SMALL
-  return hip_status(hipGetLastError());
+  const dim3 grid(lat->n_lattices), block(kNeuThreads);
+  return with_hid(
+      hid,
+      [&](auto LPR) {
+        return launch(k_backward_neural_grad_small<LPR>, grid, block, lds_small, st, *lat, label_x, wh_t, w, (int)hid, beta_hat, ws_fwd,
+                      g_log_beta, g_beta_hat, gamma, grad_label_x, grad_w, ws, gx_in_lds);
+      },
+      [&](auto HC) {
+        return launch(k_backward_neural_grad<HC>, grid, block, lds, st, *lat, label_x, wh_t, w, (int)hid, beta_hat, ws_fwd, g_log_beta,
+                      g_beta_hat, gamma, grad_label_x, grad_w, ws, wh_packed);
+      });
 }
 
 int nfst_gather_label_scores(const nfst_batch *lat, const nfst_scores *scores, float *out, void *stream) {
@@ -838,24 +797,30 @@ int nfst_gather_label_scores(const nfst_batch *lat, const nfst_scores *scores, f
   if (rc) return rc;
   if ((rc = check_scores(lat, scores))) return rc;
   if (!out) return NFST_ERR_ARG;
-  hipLaunchKernelGGL(k_gather_label_scores, dim3(8, lat->n_lattices), dim3(256), 0, (hipStream_t)stream,
-                     *lat, *scores, out);
-  return hip_status(hipGetLastError());
+  return launch(k_gather_label_scores, dim3(8, lat->n_lattices), dim3(256), 0, (hipStream_t)stream, *lat, *scores, out);
 }
+
+// consecutive parts of a caller's workspace, each 256-byte aligned; with a null base only the size adds up
+struct WsCarve {
+  char *base;
+  int64_t size = 0;
+  char *take(int64_t bytes) {
+    char *p = base ? base + size : nullptr;
+    size += (bytes + 255) & ~(int64_t)255;
+    return p;
+  }
+};
 
 // ------------------------------------------------------------------ expectation semiring (expect_kernels.h)
 // workspace: slot-ordered weights (float64 mantissa, exponent) and values (float) of both programs, then (mantissa, R,
-// exponent) of every row in both directions, then the per-label sums of c (float64) and p (fixed point, 64-bit); every
-// part 256-byte aligned
-static int64_t exp_align(int64_t n) { return (n + 255) & ~(int64_t)255; }
+// exponent) of every row in both directions, then the per-label sums of c (float64) and p (fixed point, 64-bit)
 static int64_t exp_ws_layout(const nfst_batch *lat, char *base, ExpWs *w) {
   const int64_t S = lat->fwd_slots + lat->bwd_slots, TR = lat->total_rows, BV = (int64_t)lat->n_lattices * lat->vocab;
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { const int64_t o = off; off += exp_align(bytes); return base ? base + o : nullptr; };
-  char *wm = take(8 * S), *we = take(4 * S), *sv = take(4 * S), *rm = take(16 * TR), *rr = take(16 * TR), *re = take(8 * TR);
-  char *lc = take(8 * BV), *lp = take(8 * BV);
+  WsCarve c{base};
+  char *wm = c.take(8 * S), *we = c.take(4 * S), *sv = c.take(4 * S), *rm = c.take(16 * TR), *rr = c.take(16 * TR), *re = c.take(8 * TR);
+  char *lc = c.take(8 * BV), *lp = c.take(8 * BV);
   if (w) *w = {(double *)wm, (int *)we, (float *)sv, (double *)rm, (double *)rr, (int *)re, (double *)lc, (unsigned long long *)lp};
-  return off;
+  return c.size;
 }
 static int64_t exp_lds_bytes(const nfst_batch *lat) { return (int64_t)lat->max_rows * 20 + 16; }
 
@@ -879,7 +844,6 @@ int nfst_expectation(const nfst_batch *lat, const nfst_scores *scores, const flo
   // the general tile programs, also when the batch has chunked programs (there is no chunked flavour of this op)
   const int64_t lds = exp_lds_bytes(lat);
   if (lds > kMaxLds) return NFST_ERR_LIMIT;
-  if ((rc = set_lds(k_expect_sweep, lds))) return rc;
   ExpWs w;
   exp_ws_layout(lat, (char *)ws, &w);
   const ExpVals x = {*scores, label_values, label_values ? label_values_stride : 0, arc_values, score_coef};
@@ -887,25 +851,24 @@ int nfst_expectation(const nfst_batch *lat, const nfst_scores *scores, const flo
   const int64_t n_lab = (int64_t)lat->n_lattices * lat->vocab;
   if (label_cov && (rc = hip_status(hipMemsetAsync(w.lc, 0, (size_t)n_lab * 8, st)))) return rc;
   if (label_post && (rc = hip_status(hipMemsetAsync(w.lp, 0, (size_t)n_lab * 8, st)))) return rc;
-  hipLaunchKernelGGL(k_expect_prep, dim3(lat->n_lattices, 2, kExpParts), dim3(kExpPrepThreads), 0, st, *lat, x, w);
-  hipLaunchKernelGGL(k_expect_sweep, dim3(lat->n_lattices, 2), dim3(kExpThreads), (size_t)lds, st, *lat, w);
-  hipLaunchKernelGGL(k_expect_arcs, dim3(lat->n_lattices, kExpParts), dim3(kExpArcThreads), 0, st, *lat, x, w, logz64, ev64, ev32,
-                     posterior, cov, label_cov != nullptr, label_post != nullptr);
+  if ((rc = launch(k_expect_prep, dim3(lat->n_lattices, 2, kExpParts), dim3(kExpPrepThreads), 0, st, *lat, x, w)) ||
+      (rc = launch(k_expect_sweep, dim3(lat->n_lattices, 2), dim3(kExpThreads), lds, st, *lat, w)) ||
+      (rc = launch(k_expect_arcs, dim3(lat->n_lattices, kExpParts), dim3(kExpArcThreads), 0, st, *lat, x, w, logz64, ev64, ev32, posterior,
+                   cov, label_cov != nullptr, label_post != nullptr)))
+    return rc;
   if (label_cov || label_post)
-    hipLaunchKernelGGL(k_expect_labels, dim3((unsigned)((n_lab + 255) / 256)), dim3(256), 0, st, w, n_lab, label_cov, label_post);
-  return hip_status(hipGetLastError());
+    return launch(k_expect_labels, dim3((unsigned)((n_lab + 255) / 256)), dim3(256), 0, st, w, n_lab, label_cov, label_post);
+  return NFST_OK;
 }
 
 // ------------------------------------------------------------------ k best paths (kbest_kernels.h)
-// workspace: the k-best lists of every row, then the topological order, the level starts and the level counts; every
-// part 256-byte aligned
+// workspace: the k-best lists of every row, then the topological order, the level starts and the level counts
 static int64_t kb_ws_layout(const nfst_batch *lat, int k, char *base, KbWs *w) {
   const int64_t TR = lat->total_rows, B = lat->n_lattices;
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) { const int64_t o = off; off += exp_align(bytes); return base ? base + o : nullptr; };
-  char *li = take(8 * TR * k), *od = take(4 * TR), *lv = take(4 * (TR + B)), *nl = take(4 * B);
+  WsCarve c{base};
+  char *li = c.take(8 * TR * k), *od = c.take(4 * TR), *lv = c.take(4 * (TR + B)), *nl = c.take(4 * B);
   if (w) *w = {(uint2 *)li, (int *)od, (int *)lv, (int *)nl};
-  return off;
+  return c.size;
 }
 static int kb_check_k(int32_t k) { return k < 1 ? NFST_ERR_ARG : (k > kKbMaxK ? NFST_ERR_LIMIT : NFST_OK); }
 
@@ -927,21 +890,17 @@ int nfst_kbest(const nfst_batch *lat, const nfst_scores *scores, int32_t k, void
   if (!ws || ((uintptr_t)ws & 15) || ws_bytes < kb_ws_layout(lat, k, nullptr, nullptr)) return NFST_ERR_ARG;
   // a payload holds (arc in lattice, rank) in 32 bits: 2^24 arcs per lattice at most (the batch records its largest
   // lattice's arc count up to a cap; beyond the cap the batch's total decides)
-  const int64_t max_arcs = ((int64_t)lat->reserved0 >> NFST_BATCH_MAX_ARCS_SHIFT) & NFST_BATCH_MAX_ARCS_CAP;
-  if (max_arcs >= NFST_BATCH_MAX_ARCS_CAP && lat->total_arcs >= ((int64_t)1 << 24)) return NFST_ERR_LIMIT;
+  if (max_lattice_arcs(lat) >= NFST_BATCH_MAX_ARCS_CAP && lat->total_arcs >= ((int64_t)1 << 24)) return NFST_ERR_LIMIT;
   const int64_t lds_lev = (int64_t)lat->max_rows * 12 + 16;
   const int64_t lds_sweep = (int64_t)kKbSweepWaves * 2 * 64 * 8 + ((int64_t)lat->max_rows * 2 + 1) * 4;
-  if ((rc = set_lds(k_kbest_levels, lds_lev))) return rc;
-  if ((rc = set_lds(k_kbest_sweep, lds_sweep))) return rc;
   KbWs w;
   kb_ws_layout(lat, k, (char *)ws, &w);
   const hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_kbest_levels, dim3(lat->n_lattices), dim3(kKbLevelThreads), (size_t)lds_lev, st, *lat, w);
-  hipLaunchKernelGGL(k_kbest_sweep, dim3(lat->n_lattices), dim3(kKbSweepThreads), (size_t)lds_sweep, st, *lat, *scores,
-                     (int)k, w);
-  hipLaunchKernelGGL(k_kbest_walk, dim3(lat->n_lattices), dim3(64), 0, st, *lat, (int)k, w, best, paths, path_arcs,
-                     lengths, n_paths, (int)max_len, (int)pad, status);
-  return hip_status(hipGetLastError());
+  if ((rc = launch(k_kbest_levels, dim3(lat->n_lattices), dim3(kKbLevelThreads), lds_lev, st, *lat, w)) ||
+      (rc = launch(k_kbest_sweep, dim3(lat->n_lattices), dim3(kKbSweepThreads), lds_sweep, st, *lat, *scores, (int)k, w)))
+    return rc;
+  return launch(k_kbest_walk, dim3(lat->n_lattices), dim3(64), 0, st, *lat, (int)k, w, best, paths, path_arcs, lengths, n_paths,
+                (int)max_len, (int)pad, status);
 }
 
 // shared argument checks and the variant table of the 16-byte streaming kernels: a row lies on a
@@ -962,39 +921,18 @@ static int plp_variant(const void *p0, const void *p1, int32_t vocab) {
   const int f4 = vocab / 4;
   return f4 <= 128 ? (f4 + 15) / 16 : 8 + (f4 + 31) / 32;
 }
-#define NFST_PLP_SWITCH(u, LAUNCH, FALLBACK) \
-  switch (u) {                               \
-    case 0: FALLBACK; break;                 \
-    case 1: LAUNCH(1, 8, 16); break;         \
-    case 2: LAUNCH(2, 4, 16); break;         \
-    case 3: LAUNCH(3, 4, 16); break;         \
-    case 4: LAUNCH(4, 2, 16); break;         \
-    case 5: LAUNCH(5, 2, 16); break;         \
-    case 6: LAUNCH(6, 2, 16); break;         \
-    case 7: LAUNCH(7, 1, 16); break;         \
-    case 8: LAUNCH(8, 1, 16); break;         \
-    case 13: LAUNCH(5, 2, 32); break; /* 129 .. 160 slots */ \
-    case 14: LAUNCH(6, 2, 32); break;        \
-    case 15: LAUNCH(7, 1, 32); break;        \
-    default: LAUNCH(8, 1, 32); break; /* 16: up to 256 slots */ \
-  }
-
 int nfst_path_logprob(const float *scores, const int64_t *marks, int64_t n, int32_t t, int32_t vocab,
                       int32_t pad, int32_t bos, int32_t eos, int32_t max_length, float temp,
                       int32_t normalize, float smoothing, int32_t mask_mode, float *out, void *stream) {
   int rc = plp_check(scores, marks, n, t, vocab, temp, smoothing, mask_mode);
   if (rc) return rc;
   if (!out) return NFST_ERR_ARG;
-#define NFST_LAUNCH_PLP(NV, RB, L)                                                                         \
-  hipLaunchKernelGGL((k_path_logprob_v4<NV, RB, L>), dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream,  \
-                     scores, marks, (int)t, (int)vocab, (int)pad, (int)bos, (int)eos, (int)max_length,      \
-                     temp, (int)normalize, smoothing, (int)mask_mode, out)
-  NFST_PLP_SWITCH(plp_variant(scores, nullptr, vocab), NFST_LAUNCH_PLP,
-                  hipLaunchKernelGGL(k_path_logprob, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, scores, marks,
-                                     (int)t, (int)vocab, (int)pad, (int)bos, (int)eos, (int)max_length, temp,
-                                     (int)normalize, smoothing, (int)mask_mode, out))
-#undef NFST_LAUNCH_PLP
-  return hip_status(hipGetLastError());
+  auto go = [&](auto kernel) {
+    return launch(kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, scores, marks, (int)t, (int)vocab, (int)pad, (int)bos,
+                  (int)eos, (int)max_length, temp, (int)normalize, smoothing, (int)mask_mode, out);
+  };
+  return with_plp_variant(plp_variant(scores, nullptr, vocab), [&](auto NV, auto RB, auto L) { return go(k_path_logprob_v4<NV, RB, L>); },
+                          [&] { return go(k_path_logprob); });
 }
 
 int nfst_path_logprob_backward(const float *scores, const int64_t *marks, const float *grad_out, int64_t n, int32_t t,
@@ -1003,24 +941,19 @@ int nfst_path_logprob_backward(const float *scores, const int64_t *marks, const 
   int rc = plp_check(scores, marks, n, t, vocab, temp, smoothing, mask_mode);
   if (rc) return rc;
   if (!grad_out || !grad_scores) return NFST_ERR_ARG;
-#define NFST_LAUNCH_PLPB(NV, RB, L)                                                                            \
-  hipLaunchKernelGGL((k_path_logprob_bwd_v4<NV, RB, L>), dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream,  \
-                     scores, marks, grad_out, (int)t, (int)vocab, (int)pad, (int)bos, (int)eos, (int)max_length, \
-                     temp, (int)normalize, smoothing, (int)mask_mode, grad_scores)
-  NFST_PLP_SWITCH(plp_variant(scores, grad_scores, vocab), NFST_LAUNCH_PLPB,
-                  hipLaunchKernelGGL(k_path_logprob_bwd, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, scores, marks,
-                                     grad_out, (int)t, (int)vocab, (int)pad, (int)bos, (int)eos, (int)max_length, temp,
-                                     (int)normalize, smoothing, (int)mask_mode, grad_scores))
-#undef NFST_LAUNCH_PLPB
-  return hip_status(hipGetLastError());
+  auto go = [&](auto kernel) {
+    return launch(kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, scores, marks, grad_out, (int)t, (int)vocab, (int)pad,
+                  (int)bos, (int)eos, (int)max_length, temp, (int)normalize, smoothing, (int)mask_mode, grad_scores);
+  };
+  return with_plp_variant(plp_variant(scores, grad_scores, vocab),
+                          [&](auto NV, auto RB, auto L) { return go(k_path_logprob_bwd_v4<NV, RB, L>); },
+                          [&] { return go(k_path_logprob_bwd); });
 }
 
 int nfst_iwae(const float *log_p, const float *log_q, int32_t b, int32_t k, float *log_w,
               float *log_marginal, void *stream) {
   if (!log_p || !log_q || !log_w || !log_marginal || b <= 0 || k <= 0) return NFST_ERR_ARG;
-  hipLaunchKernelGGL(k_iwae, dim3((b + 127) / 128), dim3(128), 0, (hipStream_t)stream, log_p, log_q,
-                     (int)b, (int)k, log_w, log_marginal);
-  return hip_status(hipGetLastError());
+  return launch(k_iwae, dim3((b + 127) / 128), dim3(128), 0, (hipStream_t)stream, log_p, log_q, (int)b, (int)k, log_w, log_marginal);
 }
 
 }  // extern "C"

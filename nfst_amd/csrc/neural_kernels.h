@@ -224,8 +224,8 @@ __device__ __forceinline__ void neu_phase_b(float *rows_s, int hs, int n_lead, c
       if ((hid & 15) == 0) {
         const float *bp = wh + (size_t)col * hid + 4 * kq;
         const float *ap = rows + li * hs + 4 * kq;
-        // B fragments from the matrix itself (16 rows x 64 bytes per load instruction: hidden sizes that are not a multiple of
-        // 64, and the float32 reference path of the A/B switch `neu_bf16`; multiples of 64 take the split path above)
+        // B fragments from the matrix itself (16 rows x 64 bytes per load instruction: hidden sizes below 256 or not a
+        // multiple of 64; the others take the split path above)
         const float4 *b4 = reinterpret_cast<const float4 *>(bp);
         constexpr int sd = 4, sh = 16;  // float4 strides per d and per 64 of K
         int h = 0;

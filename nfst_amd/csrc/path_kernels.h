@@ -294,7 +294,7 @@ struct VitWave {
       const bool any_unit = __builtin_amdgcn_ballot_w64(unit != 0) != 0;
       while (__builtin_expect(prog_seen < t - R + 1, 0)) {  // the slot's previous tile is consumed
         prog_seen = __builtin_amdgcn_readfirstlane(*(const volatile lds_u32 *)(uintptr_t)prog_a);
-        if (prog_seen < t - R + 1) __builtin_amdgcn_s_sleep(NFST_X_NAP);
+        if (prog_seen < t - R + 1) __builtin_amdgcn_s_sleep(kXNap);
       }
       asm volatile("" ::: "memory");
       const uint32_t sb = ring_base + (uint32_t)(t % R) * SB;

@@ -701,9 +701,7 @@ __device__ __forceinline__ void tile_decoder(int n_tiles, const uint32_t *raw, i
 // and caller scores): hipcc keeps counted s_waitcnt only where no branch lies between a load and its use.
 // Measured at 256 lattices: gathering both arrays when only one exists doubled the vector-L1 lookups
 // (64 per gather instruction) and slowed the tile stream of the loaders by a third.
-#ifndef NFST_X_NAP
-#define NFST_X_NAP 12
-#endif
+constexpr int kXNap = 12;  // s_sleep of a tile wave waiting for a free ring slot (R >= 8)
 template <int F, int NE, int XM, bool FULL, bool PREC = false>  // XM: arrays of per-arc extras (0: none -- label weights only --, 1, 2; 3: their sum is staged in LDS)
 struct WeightWave {
   static_assert(!PREC || (F == 8 && FULL && XM != 3), "precise flavour: compact tiles, tile waves, extras from HBM / L2");
@@ -849,7 +847,7 @@ struct WeightWave {
         }
         while (__builtin_expect(prog_seen < t - R + 1, 0)) {  // the slot's previous tile is consumed
           prog_seen = __builtin_amdgcn_readfirstlane(*(const volatile lds_u32 *)(uintptr_t)prog_a);
-          if (prog_seen < t - R + 1) { if (R >= 8) __builtin_amdgcn_s_sleep(NFST_X_NAP); else __builtin_amdgcn_s_sleep(1); }
+          if (prog_seen < t - R + 1) { if (R >= 8) __builtin_amdgcn_s_sleep(kXNap); else __builtin_amdgcn_s_sleep(1); }
         }
         asm volatile("" ::: "memory");
         const uint32_t sb = ring_base + (uint32_t)(t % R) * (kSlotWordsP * 4);
@@ -883,7 +881,7 @@ struct WeightWave {
       while (__builtin_expect(prog_seen < t - R + 1, 0)) {  // the slot's previous tile is consumed
         prog_seen = __builtin_amdgcn_readfirstlane(*(const volatile lds_u32 *)(uintptr_t)prog_a);
         // (a blocked wave has its tile ready and the sweep is R - NE tiles behind: long naps, few issue slots)
-        if (prog_seen < t - R + 1) { if (R >= 8) __builtin_amdgcn_s_sleep(NFST_X_NAP); else __builtin_amdgcn_s_sleep(1); }
+        if (prog_seen < t - R + 1) { if (R >= 8) __builtin_amdgcn_s_sleep(kXNap); else __builtin_amdgcn_s_sleep(1); }
       }
       asm volatile("" ::: "memory");
       const uint32_t sb = ring_base + (uint32_t)(t % R) * SB;
@@ -1407,22 +1405,11 @@ __device__ __forceinline__ int tile_math3p(const Dec2P &c, const Rec64 (&vv)[4],
   const uint32_t wide = (c.dst >> 25) & 1u;  // the tile's largest group exceeds 8 lanes (same in every lane)
   const uint64_t bad = __builtin_amdgcn_ballot_w64((((uint32_t)(dmax + 900) > 1800u) & (dmax > kZeroish)) | (wide != 0));
   // (v_ldexp_f64 takes any int32 exponent: an exact zero's exponent, about -2^28, gives zero)
-#ifdef NFST_P_CLAMP
-  double M = ldexp_clamped(mt[0], d[0]);
-#pragma unroll
-  for (int j = 1; j < 4; ++j) M += ldexp_clamped(mt[j], d[j]);
-#else
   double M = ldexp(mt[0], d[0]);
 #pragma unroll
   for (int j = 1; j < 4; ++j) M += ldexp(mt[j], d[j]);
-#endif
   // the three stages: partner's value by two v_mov_b32_dpp (every lane has a partner: the destination needs no initial
   // value), times the 0 / 1 multiplier whose high word the tile wave left in the slot
-#ifdef NFST_P_BUILTINDPP
-  M = fma(dpp_d<0xB1>(M), __hiloint2double((int)c.k0, 0), M);
-  M = fma(dpp_d<0x4E>(M), __hiloint2double((int)c.k1, 0), M);
-  M = fma(dpp_d<0x141>(M), __hiloint2double((int)c.k2, 0), M);
-#else
   {
     int plo, phi;
 #define NFST_DPP_PAIR(CTRL)                                                                                              \
@@ -1436,7 +1423,6 @@ __device__ __forceinline__ int tile_math3p(const Dec2P &c, const Rec64 (&vv)[4],
     M = fma(__hiloint2double(phi, plo), __hiloint2double((int)c.k2, 0), M);
 #undef NFST_DPP_PAIR
   }
-#endif
   int E = ref;
   if (__builtin_expect(bad != 0, 0)) {
     const int g = (int)((c.dst >> 20) & 7u);
@@ -1455,11 +1441,7 @@ __device__ __forceinline__ int tile_math3p(const Dec2P &c, const Rec64 (&vv)[4],
 __device__ __forceinline__ Rec64 rec64_load(uint32_t a) {
   const v4u x = *(const lds_v4u *)(uintptr_t)a;
   // (the pad word is dead, so hipcc reads 8 + 4 bytes in two instructions -- and that is the fast form: kept alive as one
-  // ds_read_b128 per operand these random gathers cost 70 ns more per tile, 209 against 156 us on the SNIPS-shaped batch;
-  // profiles/tune/ab_precise.sh)
-#ifdef NFST_P_B128
-  asm volatile("" ::"v"(x));
-#endif
+  // ds_read_b128 per operand these random gathers cost 70 ns more per tile, 209 against 156 us on the SNIPS-shaped batch)
   Rec64 r;
   r.m = __hiloint2double((int)x.y, (int)x.x);
   r.e = (int)x.z;

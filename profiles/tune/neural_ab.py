@@ -1,5 +1,6 @@
 """Neuralised beta sweep on the BASELINE batch for several hidden sizes (kernel time by HIP events around the op).
-NFST_NEU_NO_SMALL=1 selects the two-phase kernel for H <= 64 (A/B)."""
+The two-phase kernel's timings for H <= 32 were taken through a launcher switch that has since been removed:
+the library always picks the packed kernels there."""
 import json, os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

@@ -388,12 +388,18 @@ def test_device_pack_layout_matches_host_packer():
     assert rc == -3 and bad.value == 1
 
 
-def test_tuning_switches_are_checked():
+def test_remaining_tuning_switches_are_checked():
     assert _lib.lib.nfst_tuning_set(b"no such switch", 1) == -1
-    with _lib.tuning(tw=0, precise=1, neu_bf16=0):
+    with _lib.tuning(tw=0, precise=1, chunked=0):
         pass
+    assert _lib.lib.nfst_tuning_set(b"lds_reserve_kb", 0) == 0
     with pytest.raises(ValueError):
         _lib.tuning(nonsense=1)
+    # switches that only A/B runs used are gone: every flavour they picked is the one the batch picks
+    for name in ("fused", "xcache", "neu_pack", "neu_bf16", "neu_small"):
+        assert _lib.lib.nfst_tuning_set(name.encode(), 1) == -1, name
+        with pytest.raises(ValueError):
+            _lib.tuning(**{name: 1})
 
 
 def test_build_guard_on_register_reports():

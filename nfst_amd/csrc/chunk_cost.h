@@ -5,11 +5,7 @@
 
 #include <stdint.h>
 
-#if defined(__HIP__)
-#define NFST_HD __attribute__((host)) __attribute__((device))
-#else
-#define NFST_HD
-#endif
+#include "tile_format.h"  // (NFST_HD)
 
 namespace nfst_chunk {
 

@@ -186,9 +186,10 @@ __global__ __launch_bounds__(kExpThreads) void k_expect_sweep(nfst_batch lat, Ex
         uint32_t rcs[4];
         if (kCompact) {
           const uint4 x = cur.x;
-          const uint32_t r[4] = {x.y, __builtin_amdgcn_alignbit(x.z, x.y, 24), __builtin_amdgcn_alignbit(x.w, x.z, 16), x.w >> 8};
+          uint32_t r[4];
+          unpack24(x.y, x.z, x.w, r);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) rcs[j] = ((r[j] & 0x1fffu) << 3) | (((r[j] >> 13) & 0x7ffu) << 16);
+          for (int j = 0; j < 4; ++j) rcs[j] = rec24_to_32(r[j]);
         } else {
 #pragma unroll
           for (int j = 0; j < 4; ++j) rcs[j] = cur.w[j];
@@ -197,7 +198,7 @@ __global__ __launch_bounds__(kExpThreads) void k_expect_sweep(nfst_batch lat, Ex
         int te[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const int other = (int)((rcs[j] & 0xffffu) >> 3), l = (int)(rcs[j] >> 16);
+          const int other = (int)rec32_state(rcs[j]), l = (int)rec32_label(rcs[j]);
           ME64 wt = {cur.m[j], cur.e[j]};  // (empty slot: weight zero)
           double v = (double)cur.v[j];
           if (l == V + 1) { wt.m = 1.0; wt.e = 0; v = 0.0; }  // carry / combine record
@@ -208,8 +209,8 @@ __global__ __launch_bounds__(kExpThreads) void k_expect_sweep(nfst_batch lat, Ex
           tr[j] = (tm[j] != 0.0) ? tm[j] * (o.y + v) : 0.0;
         }
         const int E = max(max(te[0], te[1]), max(te[2], te[3]));
-        const int gl = (int)((ctl >> 20) & 7u);
-        const int gmax = (int)((__builtin_amdgcn_readfirstlane(ctl) >> 23) & 7u);
+        const int gl = (int)ctl_g(ctl);
+        const int gmax = (int)ctl_gmax(__builtin_amdgcn_readfirstlane(ctl));
         const int Eg = exp_seg_max(E, gl, gmax);
         double M = 0.0, N = 0.0;
 #pragma unroll
@@ -218,8 +219,8 @@ __global__ __launch_bounds__(kExpThreads) void k_expect_sweep(nfst_batch lat, Ex
           N += __builtin_amdgcn_ldexp(tr[j], te[j] - Eg);
         }
         exp_seg_sum2(M, N, gl, gmax);
-        if (ctl & (1u << 31)) {
-          const uint32_t sid = (ctl & 0xffffu) >> 3;
+        if (ctl_leader(ctl)) {
+          const uint32_t sid = ctl_state(ctl);
           const Rec64 a = me_pack64(M, Eg);
           mr[sid] = make_double2(a.m, (M != 0.0) ? N / M : 0.0);
           ex[sid] = a.e;

@@ -21,8 +21,11 @@
 #include <vector>
 
 #include "nfst_hip.h"
+#include "tile_format.h"
 
 namespace {
+
+using namespace nfst_tile;
 
 #include "semiring.h"
 #include "tile_pipeline.h"
@@ -491,12 +494,11 @@ int nfst_pack_device_emit(const nfst_arcs_device *arcs, const nfst_pack_opts *op
   if ((((uintptr_t)out->fwd_perm | (uintptr_t)out->bwd_perm) & 15)) return NFST_ERR_ARG;
   a.meta = const_cast<int32_t *>(meta); a.status = status; a.scratch = nullptr; a.out = *out;
   // the slack behind the streams and the 8 spare entries of the 6-byte arc arrays are part of the format: zero
-  const int64_t slack = 512;
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(const_cast<uint32_t *>(out->fwd_stream) + (out->fwd_words - slack), 0, slack * 4, st) != hipSuccess ||
-      hipMemsetAsync(const_cast<uint32_t *>(out->bwd_stream) + (out->bwd_words - slack), 0, slack * 4, st) != hipSuccess ||
-      hipMemsetAsync(const_cast<uint32_t *>(out->arc_sd) + out->total_arcs, 0, 8 * 4, st) != hipSuccess ||
-      hipMemsetAsync(const_cast<uint16_t *>(out->arc_l16) + out->total_arcs, 0, 8 * 2, st) != hipSuccess)
+  if (hipMemsetAsync(const_cast<uint32_t *>(out->fwd_stream) + (out->fwd_words - kStreamSlack), 0, kStreamSlack * 4, st) != hipSuccess ||
+      hipMemsetAsync(const_cast<uint32_t *>(out->bwd_stream) + (out->bwd_words - kStreamSlack), 0, kStreamSlack * 4, st) != hipSuccess ||
+      hipMemsetAsync(const_cast<uint32_t *>(out->arc_sd) + out->total_arcs, 0, kArcSpare * 4, st) != hipSuccess ||
+      hipMemsetAsync(const_cast<uint16_t *>(out->arc_l16) + out->total_arcs, 0, kArcSpare * 2, st) != hipSuccess)
     return NFST_ERR_HIP;
   return launch(k_pack_lattice<true>, dim3(arcs->n_lattices), dim3(kPkThreads), kPkLdsBytes, st, a);
 }

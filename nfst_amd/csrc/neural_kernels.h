@@ -108,9 +108,10 @@ __device__ __forceinline__ void neu_stage_tile(const uint32_t *prog, const int32
   if (F == 8) {
     const uint4 x = *reinterpret_cast<const uint4 *>(prog + (size_t)T * ST + lane * 4);
     c = x.x;
-    const uint32_t r[4] = {x.y, __builtin_amdgcn_alignbit(x.z, x.y, 24), __builtin_amdgcn_alignbit(x.w, x.z, 16), x.w >> 8};
+    uint32_t r[4];
+    unpack24(x.y, x.z, x.w, r);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) rec[lane * 4 + j] = ((r[j] & 0x1fffu) << 3) | (((r[j] >> 13) & 0x7ffu) << 16);
+    for (int j = 0; j < 4; ++j) rec[lane * 4 + j] = rec24_to_32(r[j]);
   } else {
     c = prog[(size_t)T * ST + lane];
     for (int j = 0; j < U; ++j) rec[lane + 64 * j] = prog[(size_t)T * ST + 64 + lane + 64 * j];
@@ -121,8 +122,8 @@ __device__ __forceinline__ void neu_stage_tile(const uint32_t *prog, const int32
     if (arc_dst) ((int *)(st + kNeuStageWords))[lane + 64 * j] = ca >= 0 ? arc_dst[ca] : -1;
   }
   ctl[lane] = c;
-  const uint64_t leaders = __builtin_amdgcn_ballot_w64((c >> 31) != 0);
-  if (c >> 31) lead[__builtin_popcountll(leaders & ((1ull << lane) - 1))] = lane;
+  const uint64_t leaders = __builtin_amdgcn_ballot_w64(ctl_leader(c));
+  if (ctl_leader(c)) lead[__builtin_popcountll(leaders & ((1ull << lane) - 1))] = lane;
   if (lane == 0) nlead[0] = __builtin_popcountll(leaders);
 }
 
@@ -164,7 +165,7 @@ __device__ __forceinline__ void neu_phase_b(float *rows_s, int hs, int n_lead, c
       __syncthreads();
       for (int i = tid; i < n * hid; i += kNeuThreads) {
         const int g = i / hid, h = i - g * hid;
-        const int sid = (int)((ctl_s[lead_s[g0 + g]] & 0xffffu) >> 3);
+        const int sid = (int)ctl_state(ctl_s[lead_s[g0 + g]]);
         rows_s[g * hs + h] = neu_load_fresh(row_of(sid) + h);
       }
       __syncthreads();
@@ -210,7 +211,7 @@ __device__ __forceinline__ void neu_phase_b(float *rows_s, int hs, int n_lead, c
         for (int r = 0; r < 4; ++r) {  // lane holds D[4 kq + r][li]
           const int g = 4 * kq + r;
           if (g < n && col < hid) {
-            const int sid = (int)((ctl_s[lead_s[g0 + g]] & 0xffffu) >> 3);
+            const int sid = (int)ctl_state(ctl_s[lead_s[g0 + g]]);
             put(sid, col, acc[r]);
           }
         }
@@ -261,7 +262,7 @@ __device__ __forceinline__ void neu_phase_b(float *rows_s, int hs, int n_lead, c
       for (int r = 0; r < 4; ++r) {  // lane holds D[4 kq + r][li]
         const int g = 4 * kq + r;
         if (g < n && col < hid) {
-          const int sid = (int)((ctl_s[lead_s[g0 + g]] & 0xffffu) >> 3);
+          const int sid = (int)ctl_state(ctl_s[lead_s[g0 + g]]);
           put(sid, col, acc[r]);
         }
       }
@@ -359,7 +360,7 @@ __global__ __launch_bounds__(kNeuThreads) void k_backward_neural(nfst_batch lat,
     for (int rnd = (wv == kNeuWaves - 1), i = neu_group_of(wv, rnd); i < n_lead; ++rnd, i = neu_group_of(wv, rnd)) {
       const int l0 = __builtin_amdgcn_readfirstlane(lead_s[i]);
       const uint32_t c0 = __builtin_amdgcn_readfirstlane(ctl_s[l0]);
-      const int sid = (int)((c0 & 0xffffu) >> 3), n_rec = (1 << ((c0 >> 20) & 7u)) * U;
+      const int sid = (int)ctl_state(c0), n_rec = (1 << ctl_g(c0)) * U;
       float macc = 0.0f, tacc[HC];
       int eacc = kEZero;
 #pragma unroll
@@ -371,7 +372,7 @@ __global__ __launch_bounds__(kNeuThreads) void k_backward_neural(nfst_batch lat,
         if (q0 + lane < n_rec) { rc_l = rec_s[l0 * U + q0 + lane]; ca_l = cas_s[l0 * U + q0 + lane]; }
         uint64_t todo = __builtin_amdgcn_ballot_w64(ca_l >= 0 || (int)(rc_l >> 16) == V + 1);
         const float x_l = arc_w ? arc_w[max(ca_l, 0)] : 0.0f;  // table weight of this lane's record
-        const int other_l = (int)((rc_l & 0xffffu) >> 3);
+        const int other_l = (int)rec32_state(rc_l);
         // Records are taken D at a time.  Their operands (L2 hits: label table, u and beta_hat
         // rows) are all requested before the first is used -- one after the other each would cost
         // a round trip.  The H-wide part (tanh, W . t) runs per record on all lanes; everything
@@ -387,7 +388,7 @@ __global__ __launch_bounds__(kNeuThreads) void k_backward_neural(nfst_batch lat,
           o.p = p;
           const uint32_t rc = (uint32_t)__builtin_amdgcn_readlane((int)rc_l, p);
           o.ca = __builtin_amdgcn_readlane(ca_l, p);
-          const int other = (int)((rc & 0xffffu) >> 3), lab = (int)(rc >> 16);
+          const int other = (int)rec32_state(rc), lab = (int)rec32_label(rc);
           const float *pa = o.ca >= 0 ? label_x + (size_t)lab * hid : bh_row(other);
           const float *pb = u_w + (size_t)other * hid;
 #pragma unroll
@@ -578,7 +579,7 @@ __global__ __launch_bounds__(kNeuThreads) void k_backward_neural_small(nfst_batc
     for (int rnd = (wv == kNeuWaves - 1), i = neu_group_of(wv, rnd); i < n_lead; ++rnd, i = neu_group_of(wv, rnd)) {
       const int l0 = __builtin_amdgcn_readfirstlane(lead_s[i]);
       const uint32_t c0 = __builtin_amdgcn_readfirstlane(ctl_s[l0]);
-      const int sid = (int)((c0 & 0xffffu) >> 3), n_rec = (1 << ((c0 >> 20) & 7u)) * U;
+      const int sid = (int)ctl_state(c0), n_rec = (1 << ctl_g(c0)) * U;
       float macc = 0.0f, tacc = 0.0f;
       int eacc = kEZero;
       for (int q0 = 0; q0 < n_rec; q0 += D * RPB) {
@@ -591,7 +592,7 @@ __global__ __launch_bounds__(kNeuThreads) void k_backward_neural_small(nfst_batc
           const bool in = q < n_rec;
           const uint32_t rc = in ? rec_s[l0 * U + q] : 0u;
           const int ca = in ? cas_s[l0 * U + q] : -1;
-          const int other = (int)((rc & 0xffffu) >> 3), lab = (int)(rc >> 16);
+          const int other = (int)rec32_state(rc), lab = (int)rec32_label(rc);
           real[k] = ca >= 0;
           act[k] = real[k] || lab == V + 1;
           const float *pa = real[k] ? label_x + (size_t)lab * hid : bh_row(other);
@@ -741,6 +742,7 @@ __global__ __launch_bounds__(kNeuThreads) void k_backward_neural_grad(
     for (int rnd = (wv == kNeuWaves - 1), i = neu_group_of(wv, rnd); i < n_lead; ++rnd, i = neu_group_of(wv, rnd)) {
       const int l0 = __builtin_amdgcn_readfirstlane(lead_s[i]);
       const uint32_t c0 = __builtin_amdgcn_readfirstlane(ctl_s[l0]);
+      // (these two lines through the accessors of tile_format.h: the compiler emits other instructions)
       const int sid = (int)((c0 & 0xffffu) >> 3), n_rec = (1 << ((c0 >> 20) & 7u)) * U;
       const bool continuation = (c0 >> 30) & 1u;
       float lacc = 0.0f, gacc[HC], ud[HC];
@@ -763,7 +765,7 @@ __global__ __launch_bounds__(kNeuThreads) void k_backward_neural_grad(
           have_d = true;
         }
         // one record per lane: source row, its beta and lambda, the table weight
-        const int src_l = (int)((rc_l & 0xffffu) >> 3);
+        const int src_l = (int)rec32_state(rc_l);
         const float x_l = (arc_w && ca_l >= 0) ? arc_w[ca_l] : 0.0f;
         const float2 bs_l = bme[src_l];
         const float lam_l = lam[src_l];
@@ -779,7 +781,7 @@ __global__ __launch_bounds__(kNeuThreads) void k_backward_neural_grad(
           o.p = p;
           const uint32_t rc = (uint32_t)__builtin_amdgcn_readlane((int)rc_l, p);
           o.ca = __builtin_amdgcn_readlane(ca_l, p);
-          const int src = (int)((rc & 0xffffu) >> 3);
+          const int src = (int)rec32_state(rc);
           o.lab = (int)(rc >> 16);
           const bool is_arc = o.ca >= 0;
           const int srow = is_arc ? src : 0;
@@ -943,6 +945,7 @@ __global__ __launch_bounds__(kNeuThreads) void k_backward_neural_grad_small(
     for (int rnd = (wv == kNeuWaves - 1), i = neu_group_of(wv, rnd); i < n_lead; ++rnd, i = neu_group_of(wv, rnd)) {
       const int l0 = __builtin_amdgcn_readfirstlane(lead_s[i]);
       const uint32_t c0 = __builtin_amdgcn_readfirstlane(ctl_s[l0]);
+      // (these two lines through the accessors of tile_format.h: the compiler emits other instructions)
       const int sid = (int)((c0 & 0xffffu) >> 3), n_rec = (1 << ((c0 >> 20) & 7u)) * U;
       const bool continuation = (c0 >> 30) & 1u;
       // the state the group's arcs enter (all the same): its u row and beta
@@ -966,7 +969,7 @@ __global__ __launch_bounds__(kNeuThreads) void k_backward_neural_grad_small(
           const bool in = q < n_rec;
           const uint32_t rc = in ? rec_s[l0 * U + q] : 0u;
           const int ca = in ? cas_s[l0 * U + q] : -1;
-          const int src = (int)((rc & 0xffffu) >> 3);
+          const int src = (int)rec32_state(rc);
           lab[k] = (int)(rc >> 16);
           isarc[k] = ca >= 0;
           act[k] = isarc[k] || lab[k] == V + 1;

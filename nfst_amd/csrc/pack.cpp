@@ -18,8 +18,11 @@
 #include <vector>
 
 #include "nfst_hip.h"
+#include "tile_format.h"
 
 namespace {
+
+using namespace nfst_tile;
 
 struct Opts {
   int n_threads = 0;
@@ -42,141 +45,90 @@ struct Lat {
   int err = NFST_OK;
 };
 
-inline int ceil_log2(int x) { int g = 0; while ((1 << g) < x) ++g; return g; }
-
-// One sweep direction as a "tile program" (DESIGN.md section 3).  A tile is one
-// wave-wide unit of work: 64 control words + 64*U arc records (U = slots per lane).
-// A state with d arcs takes 2^g lanes, g = ceil(log2(ceil(d/U))), at a lane offset
-// that is a multiple of 2^g; lane r of the group owns arcs [r*U, r*U+U).  Tiles
-// never mix levels, so every record's operand was produced by an earlier tile.
-//
-// A state whose arcs do not fit the largest group (2^max_g lanes) is cut into pieces
-// that go into successive tiles: every continuation piece starts with a CARRY record
-// (operand = the state itself, label = vocab + 1, weight one), so its sum includes what
-// the earlier pieces stored and the piece simply overwrites the state's value.  Its
-// leader lane also carries the "accumulate" flag (the max-plus kernel keeps the earlier
-// back pointer when the carry wins).  max_g = 3 ("narrow": groups of up to 8 lanes, the
-// sweep needs no cross-row reduction stage) or 6 ("wide": up to the whole wave).
-// A state with many more arcs than a group holds (three or more groups' worth) is summed as
-// a tree instead of a chain: its arcs are spread over PARTIAL groups that write scratch rows
-// (ids from n_rows up, reused from level to level) -- up to eight of them side by side in one
-// tile -- and a COMBINE piece in a later tile adds the scratch rows up with unit-label records.
-struct Piece {
-  int32_t state;       // row that receives the sum (a scratch row for a partial group)
-  int32_t begin, end;  // arcs [begin,end) of the state's list, or scratch rows [begin,end) for a combine piece
-  bool accum;          // continuation piece: starts with the carry record
-  bool units;          // combine piece: its records are unit-label records of scratch rows
-};
-
-struct TileCount { int tiles = 0, wide = 0, scratch = 0; };  // wide: tiles whose largest group exceeds 8 lanes
-
-template <class ArcsOf, class Other>
-void emit_level(const std::vector<int32_t> &states, int U, int max_g, bool compact, uint32_t null_label, int n_rows,
-                ArcsOf arcs_of, Other other, const std::vector<int32_t> &list, const std::vector<int32_t> &label,
-                std::vector<uint32_t> *stream, std::vector<int32_t> *perm, TileCount &count) {
-  const int cap = (1 << max_g) * U;
-  const uint32_t null_rec = null_label << 16, unit_label = null_label + 1;
-  // pass k holds the k-th piece of every state of the level
-  std::vector<std::vector<Piece>> passes(1);
-  auto add = [&](size_t k, const Piece &p) {
-    if (passes.size() <= k) passes.emplace_back();
-    passes[k].push_back(p);
-  };
-  // a chain of pieces over the index range [b, e): the first takes `cap` slots, every
-  // continuation piece one less (its carry), starting in pass k0
-  auto chain = [&](int32_t state, int b, int e, bool units, size_t k0) {
-    for (size_t k = k0;; ++k) {
-      const int room = (k == k0) ? cap : cap - 1;
-      const int stop = std::min(e, b + room);
-      add(k, {state, b, stop, k > k0, units});
-      b = stop;
-      if (b >= e) break;
-    }
-  };
-  int scratch = n_rows;  // next free scratch row of this level
+// One sweep direction as a tile program (tile_format.h).  The states of a level, in level order, as
+// shapes: a narrow program sums a state with many arcs as a tree unless its scratch rows would push the lattice past
+// NFST_MAX_ROWS (then as a chain; the device packer refuses such a lattice instead).  Returns the scratch rows used.
+int level_shapes(const std::vector<int32_t> &states, const std::vector<int32_t> &ptr, int max_g, int cap, int n_rows,
+                 std::vector<Shape> &shapes) {
+  shapes.clear();
+  int scratch = 0;
   for (int32_t s : states) {
-    auto r = arcs_of(s);
-    const int d = r.second - r.first;
-    if (max_g == 3 && d > 2 * cap && n_rows + (d + cap - 1) / cap + (scratch - n_rows) <= NFST_MAX_ROWS) {
-      const int first = scratch;
-      for (int b = r.first; b < r.second; b += cap) add(0, {scratch++, b, std::min(r.second, b + cap), false, false});
-      chain(s, first, scratch, true, 1);
-    } else {
-      chain(s, r.first, r.second, false, 0);
-    }
+    Shape st{s, ptr[s], ptr[s + 1], tree_parts(ptr[s + 1] - ptr[s], max_g, cap), n_rows + scratch};
+    if (n_rows + scratch + st.n_part > NFST_MAX_ROWS) st.n_part = 0;
+    scratch += st.n_part;
+    shapes.push_back(st);
   }
-  count.scratch = std::max(count.scratch, scratch - n_rows);
-  auto lanes_of = [&](const Piece &p) { return std::max(1, (p.end - p.begin + (p.accum ? 1 : 0) + U - 1) / U); };
-  for (auto &pieces : passes) {
-    std::stable_sort(pieces.begin(), pieces.end(), [&](const Piece &a, const Piece &b) {
-      return ceil_log2(lanes_of(a)) > ceil_log2(lanes_of(b));
-    });
-    size_t i = 0;
-    while (i < pieces.size()) {
-      uint32_t ctl[64];
-      std::vector<uint32_t> rec;
-      std::vector<int32_t> pm;
-      if (stream) { rec.assign((size_t)64 * U, null_rec); pm.assign((size_t)64 * U, -1); }
-      for (int l = 0; l < 64; ++l) ctl[l] = 0;
-      int lane = 0, gmax = 0;
-      bool any_accum = false;
-      while (i < pieces.size()) {
-        const Piece &p = pieces[i];
-        const int g = ceil_log2(lanes_of(p));
-        const int size = 1 << g;
-        if (lane + size > 64) break;
-        gmax = std::max(gmax, g);
-        any_accum = any_accum || p.accum;
-        if (stream) {
-          int slot = 0;  // position among the piece's slots: the carry first, then the arcs
-          const int n_slots = (p.end - p.begin) + (p.accum ? 1 : 0);
-          for (int r = 0; r < size; ++r) {
-            uint32_t c = ((uint32_t)p.state << 3) | ((uint32_t)g << 20);
-            if (r == 0) c |= (1u << 31) | (p.accum ? (1u << 30) : 0u);
-            ctl[lane + r] = c;
-            for (int j = 0; j < U; ++j, ++slot) {
-              if (slot >= n_slots) continue;
-              const size_t at = (size_t)(lane + r) * U + j;
-              if (p.accum && slot == 0) {
-                rec[at] = ((uint32_t)p.state << 3) | (unit_label << 16);
-              } else if (p.units) {
-                rec[at] = ((uint32_t)(p.begin + slot - (p.accum ? 1 : 0)) << 3) | (unit_label << 16);
-              } else {
-                const int32_t arc = list[p.begin + slot - (p.accum ? 1 : 0)];
-                rec[at] = ((uint32_t)other(arc) << 3) | ((uint32_t)label[arc] << 16);
-                pm[at] = arc;
-              }
-            }
-          }
-        }
-        lane += size;
-        ++i;
+  return scratch;
+}
+
+struct TileCount { int64_t tiles = 0, wide = 0; int scratch = 0; };  // wide: tiles whose largest group exceeds 8 lanes
+
+// tiles of one level by segment sums (tile_format.h: program order), without laying them out
+void count_level(const std::vector<Shape> &shapes, int cap, int U, std::vector<int> &lanes, std::vector<int> &wide_lanes,
+                 TileCount &count) {
+  lanes.clear(); wide_lanes.clear();
+  for (const Shape &st : shapes) {
+    const int passes = state_passes(st, cap);
+    if ((int)lanes.size() < passes) { lanes.resize(passes, 0); wide_lanes.resize(passes, 0); }
+    for (int k = 0; k < passes; ++k)
+      for (int j = 0; j < pass_pieces(st, k); ++j) {
+        const int g = piece(st, k, j, cap, U).g;
+        lanes[k] += 1 << g;
+        if (g > kNarrowG) wide_lanes[k] += 1 << g;
       }
-      if (stream) {
-        for (int l = 0; l < 64; ++l) ctl[l] |= ((uint32_t)gmax << 23) | (any_accum ? (1u << 26) : 0u);
-        if (!compact) {
-          stream->insert(stream->end(), ctl, ctl + 64);
-          stream->insert(stream->end(), rec.begin(), rec.end());
-        } else {
-          // compact tile (U = 4, labels < 2048): 16 bytes per lane = control word + four 24-bit
-          // records (state id 13 bits | label 11 bits) -- one 16-byte LDS-DMA per tile
-          for (int l = 0; l < 64; ++l) {
-            uint32_t r24[4];
-            for (int j = 0; j < 4; ++j) {
-              const uint32_t x = rec[(size_t)l * 4 + j];
-              r24[j] = ((x & 0xffffu) >> 3) | ((x >> 16) << 13);
-            }
-            stream->push_back(ctl[l]);
-            stream->push_back(r24[0] | (r24[1] << 24));
-            stream->push_back((r24[1] >> 8) | (r24[2] << 16));
-            stream->push_back((r24[2] >> 16) | (r24[3] << 8));
-          }
+  }
+  for (size_t k = 0; k < lanes.size(); ++k) { count.tiles += seg_tiles(lanes[k]); count.wide += seg_tiles(wide_lanes[k]); }
+}
+
+// lays out the tiles of one level: pieces in program order (pass, group size falling; a stable sort keeps the order of
+// enumeration, position then partial index), every lane encoded by the shared record formulas
+void emit_level(const std::vector<Shape> &shapes, int cap, int U, bool compact, uint32_t vocab, const std::vector<int32_t> &list,
+                const int32_t *other, const int32_t *label, std::vector<std::pair<int, Piece>> &pieces,
+                std::vector<uint32_t> &stream, std::vector<int32_t> &perm, TileCount &count) {
+  pieces.clear();
+  for (const Shape &st : shapes)
+    for (int k = 0, passes = state_passes(st, cap); k < passes; ++k)
+      for (int j = 0; j < pass_pieces(st, k); ++j) pieces.emplace_back(k, piece(st, k, j, cap, U));
+  std::stable_sort(pieces.begin(), pieces.end(), [](const std::pair<int, Piece> &a, const std::pair<int, Piece> &b) {
+    return a.first != b.first ? a.first < b.first : a.second.g > b.second.g;
+  });
+  uint32_t ctl[64];
+  std::vector<uint32_t> rec((size_t)64 * U);
+  std::vector<int32_t> pm((size_t)64 * U);
+  for (size_t i = 0; i < pieces.size();) {
+    std::fill(ctl, ctl + 64, 0u);
+    std::fill(rec.begin(), rec.end(), compact ? rec24(0, vocab) : rec32(0, vocab));
+    std::fill(pm.begin(), pm.end(), -1);
+    const int pass = pieces[i].first, gmax = pieces[i].second.g;
+    bool any_accum = false;
+    for (int lane = 0; i < pieces.size() && pieces[i].first == pass && lane < 64; ++i) {
+      const Piece &p = pieces[i].second;
+      any_accum = any_accum || p.accum;
+      for (int r = 0; r < (1 << p.g); ++r, ++lane) {
+        ctl[lane] = ctl_word((uint32_t)p.row, (uint32_t)p.g, r == 0, p.accum);
+        for (int j = 0; j < U; ++j) {
+          uint32_t s, l;
+          const int at = piece_slot(p, r * U + j, vocab, &s, &l);
+          if (at >= 0) { const int32_t arc = list[at]; s = (uint32_t)other[arc]; l = (uint32_t)label[arc]; pm[(size_t)lane * U + j] = arc; }
+          rec[(size_t)lane * U + j] = compact ? rec24(s, l) : rec32(s, l);
         }
-        perm->insert(perm->end(), pm.begin(), pm.end());
       }
-      ++count.tiles;
-      if (gmax > 3) ++count.wide;
     }
+    for (int l = 0; l < 64; ++l) ctl[l] |= ctl_tile_bits((uint32_t)gmax, any_accum);
+    if (!compact) {
+      stream.insert(stream.end(), ctl, ctl + 64);
+      stream.insert(stream.end(), rec.begin(), rec.end());
+    } else {
+      for (int l = 0; l < 64; ++l) {
+        const uint32_t r[4] = {rec[(size_t)l * 4], rec[(size_t)l * 4 + 1], rec[(size_t)l * 4 + 2], rec[(size_t)l * 4 + 3]};
+        uint32_t w[4] = {ctl[l]};
+        pack24(r, w[1], w[2], w[3]);
+        stream.insert(stream.end(), w, w + 4);
+      }
+    }
+    perm.insert(perm.end(), pm.begin(), pm.end());
+    ++count.tiles;
+    if (gmax > kNarrowG) ++count.wide;
   }
 }
 
@@ -241,53 +193,54 @@ void schedule(Lat &L, int vocab, const Opts &o) {
     std::stable_sort(by_height[t].begin(), by_height[t].end(), [&](int a, int b) { return outdeg[a] > outdeg[b]; });
     std::stable_sort(by_depth[t].begin(), by_depth[t].end(), [&](int a, int b) { return indeg[a] > indeg[b]; });
   }
-  auto out_of = [&](int s) { return std::make_pair(out_ptr[s], out_ptr[s + 1]); };
-  auto in_of = [&](int s) { return std::make_pair(in_ptr[s], in_ptr[s + 1]); };
-  auto dst_of = [&](int a) { return L.dst[a]; };
-  auto src_of = [&](int a) { return L.src[a]; };
-  const uint32_t null_label = (uint32_t)vocab;
-  // Slots per lane U and the largest group (narrow / wide) per direction: the cheapest
-  // program by a cost model of the sweep kernel -- cycles per tile as measured on MI355X
-  // (one wave): ~330 + 55 U, and ~450 more for a tile on the general
-  // path; a program without wide tiles also saves the per-tile test for them.
-  // Round 2: where the labels fit the compact tile, four slots per lane always -- all-compact batches run
-  // the tile-wave / fused kernels, whose tile costs ~370 cycles whatever its fill (measured, 256 lattices
-  // of 2k states: 551 levels 131 -> 106 us, 277 levels 77 -> 59 us against the cost model's choice of U = 1, 2).
-  const bool compact_ok = vocab + 2 <= 2048 && !o.no_compact;
-  auto pick = [&](bool backward, int &u_out, int &wide_out) {
-    const int us[3] = {1, 2, 4};
-    double best = 0.0;
+  // Slots per lane U and the largest group (narrow / wide) per direction: the cheapest program by the cost model
+  // (tile_format.h).  Where the labels fit the compact tile, four slots per lane always (round 2): all-compact batches run
+  // the tile-wave / fused kernels, whose tile costs ~370 cycles whatever its fill (measured, 256 lattices of 2k states:
+  // 551 levels 131 -> 106 us, 277 levels 77 -> 59 us against the cost model's choice of U = 1, 2).
+  const bool compact_ok = vocab + 2 <= kCompactLabels && !o.no_compact;
+  std::vector<Shape> shapes;
+  std::vector<int> lanes, wide_lanes;
+  auto pick = [&](const std::vector<std::vector<int32_t>> &levels, const std::vector<int32_t> &ptr, int &u_out, int &wide_out) {
+    int64_t best = 0;
     bool have = false;
-    for (int q = 0; q < 3; ++q) {
-      if ((o.slots_per_lane == 1 || o.slots_per_lane == 2 || o.slots_per_lane == 4) && us[q] != o.slots_per_lane) continue;
-      if (o.slots_per_lane == 0 && compact_ok && us[q] != 4) continue;
+    for (int U = 1; U <= 4; U *= 2) {
+      if ((o.slots_per_lane == 1 || o.slots_per_lane == 2 || o.slots_per_lane == 4) && U != o.slots_per_lane) continue;
+      if (o.slots_per_lane == 0 && compact_ok && U != 4) continue;
       for (int wide = 0; wide < 2; ++wide) {
         if ((o.group_mode == 1 && wide) || (o.group_mode == 2 && !wide)) continue;
+        const int max_g = wide ? kWideG : kNarrowG, cap = group_cap(max_g, U);
         TileCount c;
         for (int t = 1; t <= D; ++t) {
-          if (backward) emit_level(by_height[t], us[q], wide ? 6 : 3, false, null_label, n, out_of, dst_of, out_list, L.label, nullptr, nullptr, c);
-          else emit_level(by_depth[t], us[q], wide ? 6 : 3, false, null_label, n, in_of, src_of, in_list, L.label, nullptr, nullptr, c);
+          level_shapes(levels[t], ptr, max_g, cap, n, shapes);
+          count_level(shapes, cap, U, lanes, wide_lanes, c);
         }
         if (wide && c.wide == 0 && o.group_mode != 2) continue;  // same program as the narrow one
-        const double cost = (double)c.tiles * (330.0 + 55.0 * us[q] + (wide ? 60.0 : 0.0)) + 450.0 * c.wide;
-        if (!have || cost < best) { have = true; best = cost; u_out = us[q]; wide_out = wide; }
+        const int64_t cost = program_cycles(c.tiles, c.wide, U, wide);
+        if (!have || cost < best) { have = true; best = cost; u_out = U; wide_out = wide; }
       }
     }
   };
-  pick(true, L.bwd_u, L.bwd_wide);
-  pick(false, L.fwd_u, L.fwd_wide);
+  pick(by_height, out_ptr, L.bwd_u, L.bwd_wide);
+  pick(by_depth, in_ptr, L.fwd_u, L.fwd_wide);
   L.fwd.clear(); L.bwd.clear(); L.fwd_perm.clear(); L.bwd_perm.clear();
   // programs with four slots per lane use the compact tile when the labels fit 11 bits
   L.bwd_compact = compact_ok && L.bwd_u == 4;
   L.fwd_compact = compact_ok && L.fwd_u == 4;
-  TileCount cb, cf;
-  for (int t = 1; t <= D; ++t) {
-    emit_level(by_height[t], L.bwd_u, L.bwd_wide ? 6 : 3, L.bwd_compact, null_label, n, out_of, dst_of, out_list, L.label, &L.bwd, &L.bwd_perm, cb);
-    emit_level(by_depth[t], L.fwd_u, L.fwd_wide ? 6 : 3, L.fwd_compact, null_label, n, in_of, src_of, in_list, L.label, &L.fwd, &L.fwd_perm, cf);
-  }
-  L.bwd_tiles = cb.tiles;
-  L.fwd_tiles = cf.tiles;
-  L.scratch_rows = std::max(cb.scratch, cf.scratch);
+  std::vector<std::pair<int, Piece>> pieces;
+  auto emit = [&](const std::vector<std::vector<int32_t>> &levels, const std::vector<int32_t> &ptr, const std::vector<int32_t> &list,
+                  const int32_t *other, int U, int wide, bool compact, std::vector<uint32_t> &stream, std::vector<int32_t> &perm) {
+    const int max_g = wide ? kWideG : kNarrowG, cap = group_cap(max_g, U);
+    TileCount c;
+    for (int t = 1; t <= D; ++t) {
+      c.scratch = std::max(c.scratch, level_shapes(levels[t], ptr, max_g, cap, n, shapes));
+      emit_level(shapes, cap, U, compact, (uint32_t)vocab, list, other, L.label.data(), pieces, stream, perm, c);
+    }
+    L.scratch_rows = std::max(L.scratch_rows, c.scratch);
+    return (int)c.tiles;
+  };
+  L.scratch_rows = 0;
+  L.bwd_tiles = emit(by_height, out_ptr, out_list, L.dst.data(), L.bwd_u, L.bwd_wide, L.bwd_compact, L.bwd, L.bwd_perm);
+  L.fwd_tiles = emit(by_depth, in_ptr, in_list, L.src.data(), L.fwd_u, L.fwd_wide, L.fwd_compact, L.fwd, L.fwd_perm);
 }
 
 template <class F>
@@ -313,6 +266,48 @@ Opts read_opts(const nfst_pack_opts *o) {
   return r;
 }
 
+// The scalar fields of a batch from its lattices, or from the batches it concatenates, in order: running totals (the
+// offsets of the next lattice), maxima, flags, the limits and the streams' slack.  The host packer (finish), the device
+// packer (nfst_pack_device_layout) and concatenation (nfst_concat_sizes, nfst_concat_packed) lay batches out with it.
+struct BatchSizes {
+  int64_t lattices = 0, rows = 0, arcs = 0, dp = 0, fw = 0, bw = 0, fs = 0, bs = 0;  // fw, bw: stream words without slack
+  int64_t max_rows = 0, max_tiles = 0, max_arcs = 0;
+  bool all_compact = true;
+
+  void add(const BatchSizes &x) {
+    lattices += x.lattices; rows += x.rows; arcs += x.arcs; dp += x.dp; fw += x.fw; bw += x.bw; fs += x.fs; bs += x.bs;
+    max_rows = std::max(max_rows, x.max_rows); max_tiles = std::max(max_tiles, x.max_tiles);
+    max_arcs = std::max(max_arcs, x.max_arcs); all_compact = all_compact && x.all_compact;
+  }
+  void write_offsets(int32_t *m) const {
+    m[NFST_META_ROW_OFF] = (int32_t)rows; m[NFST_META_ARC_OFF] = (int32_t)arcs;
+    m[NFST_META_FWD_OFF] = (int32_t)fw; m[NFST_META_BWD_OFF] = (int32_t)bw;
+    m[NFST_META_FWD_SLOT_OFF] = (int32_t)fs; m[NFST_META_BWD_SLOT_OFF] = (int32_t)bs;
+  }
+  bool fits() const { return std::max({rows, arcs, fw, bw, fs, bs}) <= kMaxOffset; }
+  nfst_batch header(int32_t vocab, int32_t weighted) const {
+    nfst_batch h{};
+    h.n_lattices = (int32_t)lattices; h.vocab = vocab; h.max_rows = (int32_t)max_rows; h.max_tiles = (int32_t)max_tiles;
+    h.weighted = weighted;
+    h.reserved0 = (all_compact ? NFST_BATCH_ALL_COMPACT : 0) |
+                  (int32_t)(std::min<int64_t>(max_arcs, NFST_BATCH_MAX_ARCS_CAP) << NFST_BATCH_MAX_ARCS_SHIFT);
+    h.total_rows = rows; h.total_arcs = arcs; h.total_dp_arcs = dp;
+    h.fwd_words = fw + kStreamSlack; h.bwd_words = bw + kStreamSlack; h.fwd_slots = fs; h.bwd_slots = bs;
+    return h;
+  }
+};
+
+// a packed batch as a part of a concatenation
+BatchSizes sizes_of(const nfst_batch &p) {
+  BatchSizes x;
+  x.lattices = p.n_lattices; x.rows = p.total_rows; x.arcs = p.total_arcs; x.dp = p.total_dp_arcs;
+  x.fw = p.fwd_words - kStreamSlack; x.bw = p.bwd_words - kStreamSlack; x.fs = p.fwd_slots; x.bs = p.bwd_slots;
+  x.max_rows = p.max_rows; x.max_tiles = p.max_tiles;
+  x.max_arcs = ((int64_t)p.reserved0 >> NFST_BATCH_MAX_ARCS_SHIFT) & NFST_BATCH_MAX_ARCS_CAP;
+  x.all_compact = (p.reserved0 & NFST_BATCH_ALL_COMPACT) != 0;
+  return x;
+}
+
 }  // namespace
 
 struct nfst_packed {
@@ -332,38 +327,31 @@ static int finish(std::vector<Lat> &lats, int vocab, bool weighted, const Opts &
     if (lats[b].err != NFST_OK) { if (err_lattice) *err_lattice = b; return lats[b].err; }
   nfst_packed *p = new (std::nothrow) nfst_packed();
   if (!p) return NFST_ERR_NOMEM;
-  int64_t rows = 0, arcs = 0, dp = 0, fw = 0, bw = 0, fs = 0, bs = 0;
-  int max_rows = 0, max_tiles = 0;
+  BatchSizes t;
   p->meta.assign((size_t)B * NFST_META_WORDS, 0);
   for (int b = 0; b < B; ++b) {
     Lat &L = lats[b];
     int32_t *m = &p->meta[(size_t)b * NFST_META_WORDS];
-    m[NFST_META_ROW_OFF] = (int32_t)rows; m[NFST_META_N_ROWS] = L.n_rows;
-    m[NFST_META_ARC_OFF] = (int32_t)arcs; m[NFST_META_N_ARCS] = (int32_t)L.src.size();
-    m[NFST_META_FWD_OFF] = (int32_t)fw; m[NFST_META_FWD_TILES] = L.fwd_tiles;
-    m[NFST_META_BWD_OFF] = (int32_t)bw; m[NFST_META_BWD_TILES] = L.bwd_tiles;
-    m[NFST_META_SINK] = L.sink; m[NFST_META_N_REACH] = L.n_reach; m[NFST_META_DEPTH] = L.depth;
-    m[NFST_META_N_DP] = L.n_dp; m[NFST_META_FWD_U] = (L.fwd_compact ? 8 : L.fwd_u) | (L.fwd_wide << 8);
-    m[NFST_META_BWD_U] = (L.bwd_compact ? 8 : L.bwd_u) | (L.bwd_wide << 8);
-    m[NFST_META_FWD_SLOT_OFF] = (int32_t)fs; m[NFST_META_BWD_SLOT_OFF] = (int32_t)bs;
-    rows += L.n_rows; arcs += (int64_t)L.src.size(); dp += L.n_dp;
-    // tile sizes are multiples of 64 words, so every lattice's stream starts on a
-    // 256-byte boundary (LDS-DMA chunks are 16 B per lane)
-    fw += (int64_t)L.fwd.size(); bw += (int64_t)L.bwd.size();
-    fs += (int64_t)L.fwd_perm.size(); bs += (int64_t)L.bwd_perm.size();
-    max_rows = std::max(max_rows, L.n_rows + L.scratch_rows);
-    max_tiles = std::max(max_tiles, std::max(L.fwd_tiles, L.bwd_tiles));
-    if (arcs > 0x7fffff00ll || fw > 0x7ffff000ll || bw > 0x7ffff000ll || rows > 0x7fffff00ll ||
-        fs > 0x7fffff00ll || bs > 0x7fffff00ll) {
-      delete p; if (err_lattice) *err_lattice = b; return NFST_ERR_LIMIT;
-    }
+    t.write_offsets(m);
+    m[NFST_META_N_ROWS] = L.n_rows; m[NFST_META_N_ARCS] = (int32_t)L.src.size();
+    m[NFST_META_FWD_TILES] = L.fwd_tiles; m[NFST_META_BWD_TILES] = L.bwd_tiles;
+    m[NFST_META_SINK] = L.sink; m[NFST_META_N_REACH] = L.n_reach; m[NFST_META_DEPTH] = L.depth; m[NFST_META_N_DP] = L.n_dp;
+    m[NFST_META_FWD_U] = meta_fmt(L.fwd_compact, L.fwd_u, L.fwd_wide); m[NFST_META_BWD_U] = meta_fmt(L.bwd_compact, L.bwd_u, L.bwd_wide);
+    // tile sizes are multiples of 64 words, so every lattice's stream starts on a 256-byte boundary (LDS-DMA chunks are
+    // 16 B per lane)
+    BatchSizes x;
+    x.lattices = 1; x.rows = L.n_rows; x.arcs = (int64_t)L.src.size(); x.dp = L.n_dp;
+    x.fw = (int64_t)L.fwd.size(); x.bw = (int64_t)L.bwd.size(); x.fs = (int64_t)L.fwd_perm.size(); x.bs = (int64_t)L.bwd_perm.size();
+    x.max_rows = L.n_rows + L.scratch_rows; x.max_tiles = std::max(L.fwd_tiles, L.bwd_tiles); x.max_arcs = x.arcs;
+    x.all_compact = L.fwd_compact && L.bwd_compact;
+    t.add(x);
+    if (!t.fits()) { delete p; if (err_lattice) *err_lattice = b; return NFST_ERR_LIMIT; }
   }
-  // slack at the end of each stream: an empty last lattice still owns valid memory
-  const int64_t slack = 512;
+  const int64_t rows = t.rows, arcs = t.arcs;
   p->row_ptr.resize(rows + B); p->arc_src.resize(arcs); p->arc_dst.resize(arcs); p->arc_label.resize(arcs);
   if (weighted) p->arc_w.resize(arcs);
-  p->arc_sd.assign(arcs + 8, 0); p->arc_l16.assign(arcs + 8, 0);
-  p->fwd.assign(fw + slack, 0); p->bwd.assign(bw + slack, 0); p->fwd_perm.resize(fs); p->bwd_perm.resize(bs);
+  p->arc_sd.assign(arcs + kArcSpare, 0); p->arc_l16.assign(arcs + kArcSpare, 0);
+  p->fwd.assign(t.fw + kStreamSlack, 0); p->bwd.assign(t.bw + kStreamSlack, 0); p->fwd_perm.resize(t.fs); p->bwd_perm.resize(t.bs);
   parallel_for(B, o.n_threads, [&](int b) {
     Lat &L = lats[b];
     const int32_t *m = &p->meta[(size_t)b * NFST_META_WORDS];
@@ -390,15 +378,7 @@ static int finish(std::vector<Lat> &lats, int vocab, bool weighted, const Opts &
     std::vector<int32_t>().swap(L.src); std::vector<uint32_t>().swap(L.fwd); std::vector<uint32_t>().swap(L.bwd);
   });
   nfst_batch &v = p->view;
-  v.n_lattices = B; v.vocab = vocab; v.max_rows = max_rows; v.max_tiles = max_tiles;
-  bool all_compact = true;
-  for (const Lat &L : lats) all_compact = all_compact && L.fwd_compact && L.bwd_compact;
-  int64_t max_arcs = 0;
-  for (const Lat &L : lats) max_arcs = std::max<int64_t>(max_arcs, (int64_t)L.label.size());
-  v.weighted = weighted ? 1 : 0;
-  v.reserved0 = (all_compact ? NFST_BATCH_ALL_COMPACT : 0) | (int32_t)(std::min<int64_t>(max_arcs, NFST_BATCH_MAX_ARCS_CAP) << NFST_BATCH_MAX_ARCS_SHIFT);
-  v.total_rows = rows; v.total_arcs = arcs; v.total_dp_arcs = dp;
-  v.fwd_words = fw + slack; v.bwd_words = bw + slack; v.fwd_slots = fs; v.bwd_slots = bs;
+  v = t.header(vocab, weighted ? 1 : 0);
   v.meta = p->meta.data(); v.row_ptr = p->row_ptr.data(); v.arc_src = p->arc_src.data();
   v.arc_dst = p->arc_dst.data(); v.arc_label = p->arc_label.data();
   v.arc_w = weighted ? p->arc_w.data() : nullptr;
@@ -459,7 +439,9 @@ extern "C" int nfst_validate_batch(const nfst_batch *lat, int32_t *err_lattice) 
   if (!lat->meta || !lat->row_ptr || !lat->fwd_stream || !lat->bwd_stream || !lat->arc_sd || !lat->arc_l16) return NFST_ERR_ARG;
   if (lat->total_arcs > 0 && (!lat->arc_src || !lat->arc_dst || !lat->arc_label)) return NFST_ERR_ARG;
   if ((lat->fwd_slots > 0 && !lat->fwd_perm) || (lat->bwd_slots > 0 && !lat->bwd_perm) || (lat->weighted && !lat->arc_w)) return NFST_ERR_ARG;
-  if (lat->total_rows < 0 || lat->total_arcs < 0 || lat->fwd_words < 512 || lat->bwd_words < 512 || lat->fwd_slots < 0 || lat->bwd_slots < 0) return NFST_ERR_ARG;
+  if (lat->total_rows < 0 || lat->total_arcs < 0 || lat->fwd_words < kStreamSlack || lat->bwd_words < kStreamSlack || lat->fwd_slots < 0 ||
+      lat->bwd_slots < 0)
+    return NFST_ERR_ARG;
   const int B = lat->n_lattices, V = lat->vocab;
   bool all_compact = true;
   int64_t max_arcs = 0, dp_total = 0;
@@ -487,32 +469,33 @@ extern "C" int nfst_validate_batch(const nfst_batch *lat, int32_t *err_lattice) 
     // tile programs and slot -> arc maps
     for (int dir = 0; dir < 2; ++dir) {
       const int64_t off = m[dir ? NFST_META_BWD_OFF : NFST_META_FWD_OFF], tiles = m[dir ? NFST_META_BWD_TILES : NFST_META_FWD_TILES];
-      const int code = m[dir ? NFST_META_BWD_U : NFST_META_FWD_U] & 0xff;
+      const int code = meta_code(m[dir ? NFST_META_BWD_U : NFST_META_FWD_U]);
       const int64_t slot_off = m[dir ? NFST_META_BWD_SLOT_OFF : NFST_META_FWD_SLOT_OFF];
       const int64_t words = dir ? lat->bwd_words : lat->fwd_words, slots = dir ? lat->bwd_slots : lat->fwd_slots;
       const uint32_t *stream = dir ? lat->bwd_stream : lat->fwd_stream;
       const int32_t *perm = dir ? lat->bwd_perm : lat->fwd_perm;
-      if (code != 1 && code != 2 && code != 4 && code != 8) return fail(NFST_ERR_ARG);
-      all_compact = all_compact && code == 8;
-      const int U = code == 8 ? 4 : code, tw = code == 8 ? 256 : 64 * (1 + code);
-      if (tiles < 0 || tiles > lat->max_tiles || off < 0 || (off & 63) || off + tiles * tw > words - 512) return fail(NFST_ERR_INDEX);
+      if (code != 1 && code != 2 && code != 4 && code != kFmtCompact) return fail(NFST_ERR_ARG);
+      all_compact = all_compact && code == kFmtCompact;
+      const int U = fmt_u(code), tw = fmt_words(code);
+      if (tiles < 0 || tiles > lat->max_tiles || off < 0 || (off & 63) || off + tiles * tw > words - kStreamSlack) return fail(NFST_ERR_INDEX);
       if (slot_off < 0 || slot_off + tiles * 64 * U > slots) return fail(NFST_ERR_INDEX);
       const uint32_t max_state = (uint32_t)lat->max_rows, max_label = (uint32_t)V + 1;
       for (int64_t t = 0; t < tiles; ++t) {
         const uint32_t *w = stream + off + t * tw;
         for (int l = 0; l < 64; ++l) {
           uint32_t ctl, rec_state[4], rec_label[4];
-          if (code == 8) {
+          if (code == kFmtCompact) {
             const uint32_t *x = w + 4 * l;
+            uint32_t r[4];
             ctl = x[0];
-            const uint32_t r[4] = {x[1] & 0xffffffu, ((x[1] >> 24) | (x[2] << 8)) & 0xffffffu, ((x[2] >> 16) | (x[3] << 16)) & 0xffffffu, x[3] >> 8};
-            for (int j = 0; j < 4; ++j) { rec_state[j] = r[j] & 0x1fffu; rec_label[j] = r[j] >> 13; }
+            unpack24(x[1], x[2], x[3], r);
+            for (int j = 0; j < 4; ++j) { rec_state[j] = rec24_state(r[j]); rec_label[j] = rec24_label(r[j]); }
           } else {
             ctl = w[l];
-            for (int j = 0; j < U; ++j) { const uint32_t r = w[64 + l * U + j]; rec_state[j] = (r & 0xffffu) >> 3; rec_label[j] = r >> 16; }
+            for (int j = 0; j < U; ++j) { rec_state[j] = rec32_state(w[64 + l * U + j]); rec_label[j] = rec32_label(w[64 + l * U + j]); }
           }
-          const uint32_t g = (ctl >> 20) & 7u, gmax = (ctl >> 23) & 7u;
-          if (((ctl & 0xffffu) >> 3) >= max_state || (ctl & 7u) || g > 6 || gmax > 6 || g > gmax) return fail(NFST_ERR_INDEX);
+          const uint32_t g = ctl_g(ctl), gmax = ctl_gmax(ctl);
+          if (ctl_state(ctl) >= max_state || (ctl & 7u) || g > kWideG || gmax > kWideG || g > gmax) return fail(NFST_ERR_INDEX);
           for (int j = 0; j < U; ++j)
             if (rec_state[j] >= max_state || rec_label[j] > max_label) return fail(NFST_ERR_INDEX);
         }
@@ -535,24 +518,16 @@ extern "C" int nfst_validate_batch(const nfst_batch *lat, int32_t *err_lattice) 
 // calls nfst_concat_packed, which writes through them.
 extern "C" int nfst_concat_sizes(const nfst_batch *parts, int32_t n_parts, nfst_batch *total) {
   if (!parts || n_parts <= 0 || !total) return NFST_ERR_ARG;
-  nfst_batch t{};
-  t.vocab = parts[0].vocab; t.weighted = parts[0].weighted;
-  int all_compact = 1;
-  int64_t max_arcs = 0;
-  const int64_t slack = 512;
+  BatchSizes t;
   for (int i = 0; i < n_parts; ++i) {
     const nfst_batch &p = parts[i];
-    if (p.vocab != t.vocab || p.weighted != t.weighted || p.n_lattices <= 0 || p.fwd_words < slack || p.bwd_words < slack) return NFST_ERR_ARG;
-    t.n_lattices += p.n_lattices; t.max_rows = std::max(t.max_rows, p.max_rows); t.max_tiles = std::max(t.max_tiles, p.max_tiles);
-    t.total_rows += p.total_rows; t.total_arcs += p.total_arcs; t.total_dp_arcs += p.total_dp_arcs;
-    t.fwd_words += p.fwd_words - slack; t.bwd_words += p.bwd_words - slack; t.fwd_slots += p.fwd_slots; t.bwd_slots += p.bwd_slots;
-    all_compact &= (p.reserved0 & NFST_BATCH_ALL_COMPACT) ? 1 : 0;
-    max_arcs = std::max<int64_t>(max_arcs, ((int64_t)p.reserved0 >> NFST_BATCH_MAX_ARCS_SHIFT) & NFST_BATCH_MAX_ARCS_CAP);
+    if (p.vocab != parts[0].vocab || p.weighted != parts[0].weighted || p.n_lattices <= 0 || p.fwd_words < kStreamSlack ||
+        p.bwd_words < kStreamSlack)
+      return NFST_ERR_ARG;
+    t.add(sizes_of(p));
   }
-  if (std::max({t.total_arcs, t.fwd_words, t.bwd_words, t.fwd_slots, t.bwd_slots, t.total_rows}) > 0x7ffff000ll) return NFST_ERR_LIMIT;
-  t.fwd_words += slack; t.bwd_words += slack;
-  t.reserved0 = (all_compact ? NFST_BATCH_ALL_COMPACT : 0) | (int32_t)(max_arcs << NFST_BATCH_MAX_ARCS_SHIFT);
-  *total = t;
+  if (!t.fits()) return NFST_ERR_LIMIT;
+  *total = t.header(parts[0].vocab, parts[0].weighted);
   return NFST_OK;
 }
 
@@ -568,21 +543,13 @@ extern "C" int nfst_concat_packed(const nfst_batch *parts, int32_t n_parts, cons
   if (!out->meta || !out->row_ptr || !out->fwd_stream || !out->bwd_stream || !out->arc_sd || !out->arc_l16) return NFST_ERR_ARG;
   if (out->total_arcs > 0 && (!out->arc_src || !out->arc_dst || !out->arc_label || (out->weighted && !out->arc_w))) return NFST_ERR_ARG;
   if ((out->fwd_slots > 0 && !out->fwd_perm) || (out->bwd_slots > 0 && !out->bwd_perm)) return NFST_ERR_ARG;
-  struct Off { int64_t lat, rows, arcs, fw, bw, fs, bs; };
-  std::vector<Off> off((size_t)n_parts);
-  Off o{0, 0, 0, 0, 0, 0, 0};
-  const int64_t slack = 512;
-  for (int i = 0; i < n_parts; ++i) {
-    off[i] = o;
-    const nfst_batch &p = parts[i];
-    o.lat += p.n_lattices; o.rows += p.total_rows; o.arcs += p.total_arcs; o.fw += p.fwd_words - slack; o.bw += p.bwd_words - slack;
-    o.fs += p.fwd_slots; o.bs += p.bwd_slots;
-  }
+  std::vector<BatchSizes> off((size_t)n_parts);  // offsets of every part
+  for (int i = 1; i < n_parts; ++i) { off[i] = off[i - 1]; off[i].add(sizes_of(parts[i - 1])); }
   auto W32 = [](const int32_t *p) { return const_cast<int32_t *>(p); };
   parallel_for(n_parts, n_threads, [&](int i) {
     const nfst_batch &p = parts[i];
-    const Off &f = off[i];
-    int32_t *meta = W32(out->meta) + (size_t)f.lat * NFST_META_WORDS;
+    const BatchSizes &f = off[i];
+    int32_t *meta = W32(out->meta) + (size_t)f.lattices * NFST_META_WORDS;
     std::memcpy(meta, p.meta, (size_t)p.n_lattices * NFST_META_WORDS * 4);
     for (int b = 0; b < p.n_lattices; ++b) {
       int32_t *m = meta + (size_t)b * NFST_META_WORDS;
@@ -590,7 +557,7 @@ extern "C" int nfst_concat_packed(const nfst_batch *parts, int32_t n_parts, cons
       m[NFST_META_FWD_OFF] += (int32_t)f.fw; m[NFST_META_BWD_OFF] += (int32_t)f.bw;
       m[NFST_META_FWD_SLOT_OFF] += (int32_t)f.fs; m[NFST_META_BWD_SLOT_OFF] += (int32_t)f.bs;
     }
-    int32_t *rp = W32(out->row_ptr) + f.rows + f.lat;
+    int32_t *rp = W32(out->row_ptr) + f.rows + f.lattices;
     const int64_t nrp = p.total_rows + p.n_lattices;
     for (int64_t k = 0; k < nrp; ++k) rp[k] = p.row_ptr[k] + (int32_t)f.arcs;
     const size_t A = (size_t)p.total_arcs;
@@ -602,16 +569,16 @@ extern "C" int nfst_concat_packed(const nfst_batch *parts, int32_t n_parts, cons
       std::memcpy(const_cast<uint32_t *>(out->arc_sd) + f.arcs, p.arc_sd, A * 4);
       std::memcpy(const_cast<uint16_t *>(out->arc_l16) + f.arcs, p.arc_l16, A * 2);
     }
-    std::memcpy(const_cast<uint32_t *>(out->fwd_stream) + f.fw, p.fwd_stream, (size_t)(p.fwd_words - slack) * 4);
-    std::memcpy(const_cast<uint32_t *>(out->bwd_stream) + f.bw, p.bwd_stream, (size_t)(p.bwd_words - slack) * 4);
+    std::memcpy(const_cast<uint32_t *>(out->fwd_stream) + f.fw, p.fwd_stream, (size_t)(p.fwd_words - kStreamSlack) * 4);
+    std::memcpy(const_cast<uint32_t *>(out->bwd_stream) + f.bw, p.bwd_stream, (size_t)(p.bwd_words - kStreamSlack) * 4);
     int32_t *fp = W32(out->fwd_perm) + f.fs, *bp = W32(out->bwd_perm) + f.bs;
     for (int64_t k = 0; k < p.fwd_slots; ++k) fp[k] = p.fwd_perm[k] < 0 ? -1 : p.fwd_perm[k] + (int32_t)f.arcs;
     for (int64_t k = 0; k < p.bwd_slots; ++k) bp[k] = p.bwd_perm[k] < 0 ? -1 : p.bwd_perm[k] + (int32_t)f.arcs;
   });
-  std::memset(const_cast<uint32_t *>(out->fwd_stream) + (out->fwd_words - slack), 0, slack * 4);
-  std::memset(const_cast<uint32_t *>(out->bwd_stream) + (out->bwd_words - slack), 0, slack * 4);
-  std::memset(const_cast<uint32_t *>(out->arc_sd) + out->total_arcs, 0, 8 * 4);
-  std::memset(const_cast<uint16_t *>(out->arc_l16) + out->total_arcs, 0, 8 * 2);
+  std::memset(const_cast<uint32_t *>(out->fwd_stream) + (out->fwd_words - kStreamSlack), 0, kStreamSlack * 4);
+  std::memset(const_cast<uint32_t *>(out->bwd_stream) + (out->bwd_words - kStreamSlack), 0, kStreamSlack * 4);
+  std::memset(const_cast<uint32_t *>(out->arc_sd) + out->total_arcs, 0, kArcSpare * 4);
+  std::memset(const_cast<uint16_t *>(out->arc_l16) + out->total_arcs, 0, kArcSpare * 2);
   return NFST_OK;
 }
 
@@ -622,28 +589,19 @@ extern "C" int nfst_pack_device_layout(int32_t *meta, const int32_t *status, con
   if (!meta || !status || !scratch_rows || !header || n_lattices <= 0 || vocab <= 0) return NFST_ERR_ARG;
   for (int b = 0; b < n_lattices; ++b)
     if (status[b] != NFST_OK) { if (err_lattice) *err_lattice = b; return status[b]; }
-  nfst_batch h{};
-  int64_t rows = 0, arcs = 0, dp = 0, fw = 0, bw = 0, fs = 0, bs = 0, max_arcs = 0;
-  int max_rows = 0, max_tiles = 0;
+  BatchSizes t;
   for (int b = 0; b < n_lattices; ++b) {
     int32_t *m = meta + (size_t)b * NFST_META_WORDS;
-    const int64_t ft = m[NFST_META_FWD_TILES], bt = m[NFST_META_BWD_TILES];
-    m[NFST_META_ROW_OFF] = (int32_t)rows; m[NFST_META_ARC_OFF] = (int32_t)arcs;
-    m[NFST_META_FWD_OFF] = (int32_t)fw; m[NFST_META_BWD_OFF] = (int32_t)bw;
-    m[NFST_META_FWD_SLOT_OFF] = (int32_t)fs; m[NFST_META_BWD_SLOT_OFF] = (int32_t)bs;
-    rows += m[NFST_META_N_ROWS]; arcs += m[NFST_META_N_ARCS]; dp += m[NFST_META_N_DP];
-    fw += ft * 256; bw += bt * 256; fs += ft * 256; bs += bt * 256;  // compact tiles: 256 words, 256 slots each
-    max_rows = std::max(max_rows, m[NFST_META_N_ROWS] + scratch_rows[b]);
-    max_tiles = std::max<int64_t>(max_tiles, std::max(ft, bt));
-    max_arcs = std::max<int64_t>(max_arcs, m[NFST_META_N_ARCS]);
-    if (arcs > 0x7fffff00ll || fw > 0x7ffff000ll || bw > 0x7ffff000ll || rows > 0x7fffff00ll) { if (err_lattice) *err_lattice = b; return NFST_ERR_LIMIT; }
+    t.write_offsets(m);
+    BatchSizes x;  // compact tiles: fmt_words(kFmtCompact) words and as many slots each
+    const int64_t ft = m[NFST_META_FWD_TILES], bt = m[NFST_META_BWD_TILES], tw = fmt_words(kFmtCompact);
+    x.lattices = 1; x.rows = m[NFST_META_N_ROWS]; x.arcs = m[NFST_META_N_ARCS]; x.dp = m[NFST_META_N_DP];
+    x.fw = x.fs = ft * tw; x.bw = x.bs = bt * tw;
+    x.max_rows = m[NFST_META_N_ROWS] + scratch_rows[b]; x.max_tiles = std::max(ft, bt); x.max_arcs = x.arcs;
+    t.add(x);
+    if (!t.fits()) { if (err_lattice) *err_lattice = b; return NFST_ERR_LIMIT; }
   }
-  const int64_t slack = 512;
-  h.n_lattices = n_lattices; h.vocab = vocab; h.max_rows = max_rows; h.max_tiles = max_tiles; h.weighted = weighted ? 1 : 0;
-  h.reserved0 = NFST_BATCH_ALL_COMPACT | (int32_t)(std::min<int64_t>(max_arcs, NFST_BATCH_MAX_ARCS_CAP) << NFST_BATCH_MAX_ARCS_SHIFT);
-  h.total_rows = rows; h.total_arcs = arcs; h.total_dp_arcs = dp;
-  h.fwd_words = fw + slack; h.bwd_words = bw + slack; h.fwd_slots = fs; h.bwd_slots = bs;
-  *header = h;
+  *header = t.header(vocab, weighted ? 1 : 0);
   return NFST_OK;
 }
 

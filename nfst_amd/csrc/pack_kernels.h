@@ -126,45 +126,6 @@ __device__ void pk_sort(unsigned long long *key, int n) {
     }
 }
 
-__device__ __forceinline__ int pk_ceil_log2(int x) { return x <= 1 ? 0 : 32 - __builtin_clz(x - 1); }
-
-// ---- pieces of a state (pack.cpp: emit_level), as closed formulas of (state, pass, partial index) -------------------
-struct PkPiece {
-  int row, begin, end, accum, units, g;
-};
-struct PkState {  // what the formulas need about one state of the level being laid out
-  int s, b0, e0, tree, n_part, first;  // arcs [b0, e0) of its list; tree: partial groups write scratch rows first ..
-};
-__device__ __forceinline__ int pk_chain_pieces(int len, int cap) { return len <= cap ? 1 : 1 + (len - cap + cap - 2) / (cap - 1); }
-__device__ __forceinline__ int pk_state_pieces(const PkState &st, int cap) {
-  return st.tree ? st.n_part + pk_chain_pieces(st.n_part, cap) : pk_chain_pieces(st.e0 - st.b0, cap);
-}
-// the c-th piece of a chain over [b, e): the first takes `cap` slots, every continuation piece one less (its carry)
-__device__ __forceinline__ void pk_chain_piece(int b, int e, int c, int cap, int &pb, int &pe) {
-  pb = c == 0 ? b : b + cap + (c - 1) * (cap - 1);
-  pe = min(e, pb + (c == 0 ? cap : cap - 1));
-}
-__device__ __forceinline__ PkPiece pk_piece(const PkState &st, int pass, int sub, int cap) {
-  PkPiece p;
-  if (st.tree && pass == 0) {
-    p.row = st.first + sub; p.begin = st.b0 + sub * cap; p.end = min(st.e0, p.begin + cap); p.accum = 0; p.units = 0;
-  } else if (st.tree) {
-    pk_chain_piece(st.first, st.first + st.n_part, pass - 1, cap, p.begin, p.end);
-    p.row = st.s; p.accum = pass > 1; p.units = 1;
-  } else {
-    pk_chain_piece(st.b0, st.e0, pass, cap, p.begin, p.end);
-    p.row = st.s; p.accum = pass > 0; p.units = 0;
-  }
-  p.g = pk_ceil_log2(max(1, (p.end - p.begin + p.accum + 3) / 4));
-  return p;
-}
-// sort key of a piece: tiles are laid out by level, then pass, then group size (largest first), then the order in
-// which pack.cpp's emit_level met the pieces (position of the state in its level, partial index)
-__device__ __forceinline__ unsigned long long pk_key(int level, int pass, int g, int pos, int sub) {
-  return ((unsigned long long)level << 50) | ((unsigned long long)pass << 36) | ((unsigned long long)(7 - g) << 33) |
-         ((unsigned long long)pos << 13) | (unsigned long long)sub;  // level 13 | pass 14 | 3 | pos 20 | sub 13 bits
-}
-
 // ---- one direction, one group mode: tile layout (count or emit) -------------------------------------------------------
 struct PkDir {
   const int32_t *ord, *lvlp, *lev, *ptr, *list;  // level order, level starts, level of a state, list pointers, arc list (canonical ids)
@@ -182,26 +143,20 @@ __device__ PkLayout pk_layout(const PkDir &d, int max_g, int vocab, unsigned lon
                               int32_t *pa, int32_t *pb, int32_t *pc, int32_t *tile_bits, int aux_cap, int *red, uint32_t *stream,
                               int32_t *perm, int32_t perm_base) {
   PkLayout out{0, 0, 0, 0};
-  const int cap = (1 << max_g) * 4;
+  const int cap = group_cap(max_g, 4);
   const int first_pos = d.lvlp[1], n_st = d.n_reach - first_pos;  // states of the levels 1 .. D (level 0 holds one state and emits nothing)
   if (n_st <= 0) return out;
   auto state_at = [&](int pos) {  // pos: position in the level order
-    PkState st;
-    st.s = d.ord[pos];
-    st.b0 = d.ptr[st.s]; st.e0 = d.ptr[st.s + 1];
-    const int deg = st.e0 - st.b0;
-    st.tree = max_g == 3 && deg > 2 * cap;
-    st.n_part = st.tree ? (deg + cap - 1) / cap : 0;
-    st.first = 0;
-    return st;
+    const int s = d.ord[pos];
+    return Shape{s, d.ptr[s], d.ptr[s + 1], tree_parts(d.ptr[s + 1] - d.ptr[s], max_g, cap), 0};
   };
   // scratch rows: tmp_a[i] = partial groups of the states before i (position first_pos + i) in the level order
   pk_scan<false>(n_st, [&](int i) { return state_at(first_pos + i).n_part; }, tmp_a, red);
   // pieces per state -> offsets of their keys
-  const int n_pieces = pk_scan<false>(n_st, [&](int i) { return pk_state_pieces(state_at(first_pos + i), cap); }, tmp_b, red);
+  const int n_pieces = pk_scan<false>(n_st, [&](int i) { return state_pieces(state_at(first_pos + i), cap); }, tmp_b, red);
   if (n_pieces > kPkMaxKeys || n_pieces + 1 > aux_cap) { out.err = NFST_ERR_LIMIT; return out; }
   auto full_state = [&](int pos, int level) {
-    PkState st = state_at(pos);
+    Shape st = state_at(pos);
     const int i = pos - first_pos;
     st.first = d.n_rows + tmp_a[i] - tmp_a[d.lvlp[level] - first_pos];
     return st;
@@ -223,25 +178,19 @@ __device__ PkLayout pk_layout(const PkDir &d, int max_g, int vocab, unsigned lon
   // keys
   for (int i = threadIdx.x; i < n_st; i += kPkThreads) {
     const int pos = first_pos + i, level = d.lev[d.ord[pos]];
-    const PkState st = full_state(pos, level);
+    const Shape st = full_state(pos, level);
     int k = tmp_b[i];
     const int lp = pos - d.lvlp[level];
-    if (st.tree) {
-      for (int j = 0; j < st.n_part; ++j) keys[k++] = pk_key(level, 0, pk_piece(st, 0, j, cap).g, lp, j);
-      const int nc = pk_chain_pieces(st.n_part, cap);
-      for (int c = 0; c < nc; ++c) keys[k++] = pk_key(level, 1 + c, pk_piece(st, 1 + c, 0, cap).g, lp, 0);
-    } else {
-      const int nc = pk_chain_pieces(st.e0 - st.b0, cap);
-      for (int c = 0; c < nc; ++c) keys[k++] = pk_key(level, c, pk_piece(st, c, 0, cap).g, lp, 0);
-    }
+    for (int c = 0, passes = state_passes(st, cap); c < passes; ++c)
+      for (int j = 0; j < pass_pieces(st, c); ++j) keys[k++] = piece_key(level, c, piece(st, c, j, cap, 4).g, lp, j);
   }
   __syncthreads();
   pk_sort(keys, n_pieces);
   // lane offsets: sizes are powers of two in falling order inside a (level, pass) segment, so a piece never straddles
   // a tile and "next fit" is the running sum.  pa = sum of sizes before i, pb = head index of i's segment,
   // pc = tiles of the segments that end before i
-  auto size_of = [&](int i) { return 1 << (7 - (int)((keys[i] >> 33) & 7ull)); };
-  auto seg_of = [&](int i) { return keys[i] >> 36; };
+  auto size_of = [&](int i) { return 1 << key_g(keys[i]); };
+  auto seg_of = [&](int i) { return key_segment(keys[i]); };
   pk_scan<false>(n_pieces, size_of, pa, red);
   pk_scan<true>(n_pieces + 1, [&](int i) { return (i < n_pieces && (i == 0 || seg_of(i) != seg_of(i - 1))) ? i : -1; }, pb, red);
   // pb[i + 1] = head of i's segment (an exclusive max scan shifted by one)
@@ -249,18 +198,19 @@ __device__ PkLayout pk_layout(const PkDir &d, int max_g, int vocab, unsigned lon
   auto seg_tiles_at_end = [&](int i) {  // for the last piece of a segment: the segment's tiles
     if (i + 1 < n_pieces && seg_of(i + 1) == seg_of(i)) return 0;
     const int h = head_of(i);
-    return (pa[i] + size_of(i) - pa[h] + 63) >> 6;
+    return seg_tiles(pa[i] + size_of(i) - pa[h]);
   };
   out.tiles = pk_scan<false>(n_pieces, seg_tiles_at_end, pc, red);
   // tiles whose first piece is a wide group
   out.wide = pk_count(n_pieces, [&](int i) {
     const int h = head_of(i);
-    return (((pa[i] - pa[h]) & 63) == 0 && (7 - (int)((keys[i] >> 33) & 7ull)) > 3) ? 1 : 0;
+    return (((pa[i] - pa[h]) & 63) == 0 && key_g(keys[i]) > kNarrowG) ? 1 : 0;
   }, red);
   if (!EMIT) return out;
   // ---- emission.  (a) every tile gets its default words: control 0, null records, no arcs
-  const uint32_t null24 = (uint32_t)vocab << 13;
-  const uint32_t n1 = null24 | (null24 << 24), n2 = (null24 >> 8) | (null24 << 16), n3 = (null24 >> 16) | (null24 << 8);
+  const uint32_t null24[4] = {rec24(0, vocab), rec24(0, vocab), rec24(0, vocab), rec24(0, vocab)};
+  uint32_t n1, n2, n3;
+  pack24(null24, n1, n2, n3);
   for (int i = threadIdx.x; i < out.tiles * 64; i += kPkThreads) {
     reinterpret_cast<uint4 *>(stream)[i] = make_uint4(0u, n1, n2, n3);
     reinterpret_cast<int4 *>(perm)[i] = make_int4(-1, -1, -1, -1);
@@ -268,38 +218,28 @@ __device__ PkLayout pk_layout(const PkDir &d, int max_g, int vocab, unsigned lon
   for (int i = threadIdx.x; i < out.tiles; i += kPkThreads) tile_bits[i] = 0;
   __syncthreads();
   // (b) the pieces
-  const uint32_t unit_label = (uint32_t)vocab + 1;
   for (int i = threadIdx.x; i < n_pieces; i += kPkThreads) {
     const unsigned long long key = keys[i];
-    const int level = (int)(key >> 50), pass = (int)((key >> 36) & 0x3fffull), lp = (int)((key >> 13) & 0xfffffull), sub = (int)(key & 0x1fffull);
-    const PkState st = full_state(d.lvlp[level] + lp, level);
-    const PkPiece p = pk_piece(st, pass, sub, cap);
+    const int level = key_level(key), pass = key_pass(key);
+    const Shape st = full_state(d.lvlp[level] + key_pos(key), level);
+    const Piece p = piece(st, pass, key_sub(key), cap, 4);
     const int h = head_of(i), off = pa[i] - pa[h], tile = pc[h] + (off >> 6), lane0 = off & 63;
-    if (lane0 == 0) atomicOr(&tile_bits[tile], p.g << 23);  // (falling sizes: the tile's first piece has its largest group)
-    if (p.accum) atomicOr(&tile_bits[tile], 1 << 26);
-    const int n_slots = p.end - p.begin + p.accum;
-    int slot = 0;
+    if (lane0 == 0) atomicOr(&tile_bits[tile], (int)ctl_tile_bits(p.g, false));  // (falling sizes: the tile's first piece has its largest group)
+    if (p.accum) atomicOr(&tile_bits[tile], (int)ctl_tile_bits(0, true));
     for (int r = 0; r < (1 << p.g); ++r) {
-      uint32_t r24[4];
+      uint32_t r24[4], w1, w2, w3;
       int pm[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j, ++slot) {
-        r24[j] = null24; pm[j] = -1;
-        if (slot >= n_slots) continue;
-        if (p.accum && slot == 0) {
-          r24[j] = (uint32_t)p.row | (unit_label << 13);
-        } else if (p.units) {
-          r24[j] = (uint32_t)(p.begin + slot - p.accum) | (unit_label << 13);
-        } else {
-          const int arc = d.list[p.begin + slot - p.accum];
-          r24[j] = (uint32_t)d.other[arc] | ((uint32_t)d.lab[arc] << 13);
-          pm[j] = perm_base + arc;
-        }
+      for (int j = 0; j < 4; ++j) {
+        uint32_t s, l;
+        const int at = piece_slot(p, r * 4 + j, (uint32_t)vocab, &s, &l);
+        pm[j] = -1;
+        if (at >= 0) { const int arc = d.list[at]; s = (uint32_t)d.other[arc]; l = (uint32_t)d.lab[arc]; pm[j] = perm_base + arc; }
+        r24[j] = rec24(s, l);
       }
-      uint32_t c = ((uint32_t)p.row << 3) | ((uint32_t)p.g << 20);
-      if (r == 0) c |= (1u << 31) | (p.accum ? (1u << 30) : 0u);
+      pack24(r24, w1, w2, w3);
       const size_t at = (size_t)tile * 64 + lane0 + r;
-      reinterpret_cast<uint4 *>(stream)[at] = make_uint4(c, r24[0] | (r24[1] << 24), (r24[1] >> 8) | (r24[2] << 16), (r24[2] >> 16) | (r24[3] << 8));
+      reinterpret_cast<uint4 *>(stream)[at] = make_uint4(ctl_word((uint32_t)p.row, (uint32_t)p.g, r == 0, p.accum), w1, w2, w3);
       reinterpret_cast<int4 *>(perm)[at] = make_int4(pm[0], pm[1], pm[2], pm[3]);
     }
   }
@@ -318,27 +258,21 @@ __device__ PkLayout pk_layout(const PkDir &d, int max_g, int vocab, unsigned lon
 // NFST_ERR_ARG when the tables do not fit (the caller then counts with pk_layout<false>).
 __device__ PkLayout pk_count_layout(const PkDir &d, int max_g, int32_t *table, int words, int aux_cap, int *red) {
   PkLayout out{0, 0, 0, 0};
-  const int cap = (1 << max_g) * 4;
+  const int cap = group_cap(max_g, 4);
   const int first_pos = d.lvlp[1], n_st = d.n_reach - first_pos;
   if (n_st <= 0) return out;
   auto state_at = [&](int pos) {
-    PkState st;
-    st.s = d.ord[pos];
-    st.b0 = d.ptr[st.s]; st.e0 = d.ptr[st.s + 1];
-    const int deg = st.e0 - st.b0;
-    st.tree = max_g == 3 && deg > 2 * cap;
-    st.n_part = st.tree ? (deg + cap - 1) / cap : 0;
-    st.first = 0;
-    return st;
+    const int s = d.ord[pos];
+    return Shape{s, d.ptr[s], d.ptr[s + 1], tree_parts(d.ptr[s + 1] - d.ptr[s], max_g, cap), 0};
   };
   // (the emitting pass sorts the pieces in LDS: what it cannot take is refused here, where the host still can fall back)
-  const int n_pieces = pk_count(n_st, [&](int i) { return pk_state_pieces(state_at(first_pos + i), cap); }, red);
+  const int n_pieces = pk_count(n_st, [&](int i) { return state_pieces(state_at(first_pos + i), cap); }, red);
   if (n_pieces > kPkMaxKeys || n_pieces + 1 > aux_cap) { out.err = NFST_ERR_LIMIT; return out; }
   // passes of the longest chain
   int pmax_t = 1, P = 1;
   for (int i = threadIdx.x; i < n_st; i += kPkThreads) {
-    const PkState st = state_at(first_pos + i);
-    pmax_t = max(pmax_t, st.tree ? 1 + pk_chain_pieces(st.n_part, cap) : pk_chain_pieces(st.e0 - st.b0, cap));
+    const Shape st = state_at(first_pos + i);
+    pmax_t = max(pmax_t, state_passes(st, cap));
   }
   pk_block_excl<true>(pmax_t, red, &P);
   __syncthreads();
@@ -348,25 +282,19 @@ __device__ PkLayout pk_count_layout(const PkDir &d, int max_g, int32_t *table, i
   for (int i = threadIdx.x; i < L * (2 * P + 1); i += kPkThreads) table[i] = 0;
   __syncthreads();
   for (int i = threadIdx.x; i < n_st; i += kPkThreads) {
-    const PkState st = state_at(first_pos + i);
-    const int level = d.lev[st.s];
-    auto add = [&](int pass, const PkPiece &p) {
-      atomicAdd(&t_size[level * P + pass], 1 << p.g);
-      if (p.g > 3) atomicAdd(&t_wide[level * P + pass], 1 << p.g);
-    };
-    if (st.tree) {
-      atomicAdd(&t_scr[level], st.n_part);
-      for (int j = 0; j < st.n_part; ++j) add(0, pk_piece(st, 0, j, cap));
-      const int nc = pk_chain_pieces(st.n_part, cap);
-      for (int c = 0; c < nc; ++c) add(1 + c, pk_piece(st, 1 + c, 0, cap));
-    } else {
-      const int nc = pk_chain_pieces(st.e0 - st.b0, cap);
-      for (int c = 0; c < nc; ++c) add(c, pk_piece(st, c, 0, cap));
-    }
+    const Shape st = state_at(first_pos + i);
+    const int level = d.lev[st.row];
+    if (st.n_part) atomicAdd(&t_scr[level], st.n_part);
+    for (int c = 0, passes = state_passes(st, cap); c < passes; ++c)
+      for (int j = 0; j < pass_pieces(st, c); ++j) {
+        const int g = piece(st, c, j, cap, 4).g;
+        atomicAdd(&t_size[level * P + c], 1 << g);
+        if (g > kNarrowG) atomicAdd(&t_wide[level * P + c], 1 << g);
+      }
   }
   __syncthreads();
-  out.tiles = pk_count(L * P, [&](int i) { return (t_size[i] + 63) >> 6; }, red);
-  out.wide = pk_count(L * P, [&](int i) { return (t_wide[i] + 63) >> 6; }, red);
+  out.tiles = pk_count(L * P, [&](int i) { return seg_tiles(t_size[i]); }, red);
+  out.wide = pk_count(L * P, [&](int i) { return seg_tiles(t_wide[i]); }, red);
   int scr_t = 0;
   for (int i = threadIdx.x; i < L; i += kPkThreads) scr_t = max(scr_t, t_scr[i]);
   pk_block_excl<true>(scr_t, red, &out.scratch);
@@ -591,7 +519,7 @@ __global__ __launch_bounds__(kPkThreads) void k_pack_lattice(PkArgs a) {
       // the cheapest of narrow (8-lane groups) and wide (64-lane) programs by pack.cpp's cost model
       PkLayout best{0, 0, 0, 0};
       int best_wide = 0;
-      double best_cost = 0.0;
+      int64_t best_cost = 0;
       bool have = false;
       // (a wide program differs from the narrow one only if some state has more arcs than a narrow group holds)
       int dmax_t = 0, dmax = 0;
@@ -600,22 +528,23 @@ __global__ __launch_bounds__(kPkThreads) void k_pack_lattice(PkArgs a) {
       __syncthreads();
       for (int w = 0; w < 2; ++w) {
         if ((a.group_mode == 1 && w) || (a.group_mode == 2 && !w)) continue;
-        if (w && dmax <= 32 && a.group_mode != 2) continue;  // no group beyond 8 lanes: the same program as the narrow one
-        PkLayout l = pk_count_layout(dirs[dir], w ? 6 : 3, reinterpret_cast<int32_t *>(pk_lds), (int)(kPkLdsBytes / 4), aux_cap, red);
+        if (w && dmax <= group_cap(kNarrowG, 4) && a.group_mode != 2) continue;  // no group beyond 8 lanes: the same program as the narrow one
+        const int max_g = w ? kWideG : kNarrowG;
+        PkLayout l = pk_count_layout(dirs[dir], max_g, reinterpret_cast<int32_t *>(pk_lds), (int)(kPkLdsBytes / 4), aux_cap, red);
         if (l.err == NFST_ERR_ARG)  // (tables of levels x passes beyond LDS: count by laying the tiles out)
-          l = pk_layout<false>(dirs[dir], w ? 6 : 3, a.vocab, pk_lds, tmp_a, tmp_b, pa_, pb_, pc_, tile_bits, aux_cap, red, nullptr, nullptr, 0);
+          l = pk_layout<false>(dirs[dir], max_g, a.vocab, pk_lds, tmp_a, tmp_b, pa_, pb_, pc_, tile_bits, aux_cap, red, nullptr, nullptr, 0);
         if (l.err) { fail(l.err); return; }
         if (w && l.wide == 0 && a.group_mode != 2) continue;  // the same program as the narrow one
-        const double cost = (double)l.tiles * (330.0 + 55.0 * 4 + (w ? 60.0 : 0.0)) + 450.0 * l.wide;
+        const int64_t cost = program_cycles(l.tiles, l.wide, 4, w);
         if (!have || cost < best_cost) { have = true; best_cost = cost; best = l; best_wide = w; }
       }
       tiles[dir] = best.tiles; wide[dir] = best_wide;
       scratch_rows = max(scratch_rows, best.scratch);
     } else {
-      const int w = (meta[dir ? NFST_META_BWD_U : NFST_META_FWD_U] >> 8) & 1;
+      const int w = meta_wide(meta[dir ? NFST_META_BWD_U : NFST_META_FWD_U]);
       uint32_t *stream = const_cast<uint32_t *>(dir ? a.out.bwd_stream : a.out.fwd_stream) + meta[dir ? NFST_META_BWD_OFF : NFST_META_FWD_OFF];
       int32_t *perm = const_cast<int32_t *>(dir ? a.out.bwd_perm : a.out.fwd_perm) + meta[dir ? NFST_META_BWD_SLOT_OFF : NFST_META_FWD_SLOT_OFF];
-      const PkLayout l = pk_layout<true>(dirs[dir], w ? 6 : 3, a.vocab, pk_lds, tmp_a, tmp_b, pa_, pb_, pc_, tile_bits, aux_cap, red, stream, perm, arc_base);
+      const PkLayout l = pk_layout<true>(dirs[dir], w ? kWideG : kNarrowG, a.vocab, pk_lds, tmp_a, tmp_b, pa_, pb_, pc_, tile_bits, aux_cap, red, stream, perm, arc_base);
       if (l.err || l.tiles != meta[dir ? NFST_META_BWD_TILES : NFST_META_FWD_TILES]) { fail(l.err ? l.err : NFST_ERR_ARG); return; }
     }
   }
@@ -623,7 +552,7 @@ __global__ __launch_bounds__(kPkThreads) void k_pack_lattice(PkArgs a) {
   if (!EMIT && tid == 0) {
     meta[NFST_META_N_ROWS] = n; meta[NFST_META_N_ARCS] = n_arcs; meta[NFST_META_FWD_TILES] = tiles[0]; meta[NFST_META_BWD_TILES] = tiles[1];
     meta[NFST_META_SINK] = sink; meta[NFST_META_N_REACH] = n_reach; meta[NFST_META_DEPTH] = D; meta[NFST_META_N_DP] = n_dp;
-    meta[NFST_META_FWD_U] = 8 | (wide[0] << 8); meta[NFST_META_BWD_U] = 8 | (wide[1] << 8);
+    meta[NFST_META_FWD_U] = meta_fmt(true, 4, wide[0]); meta[NFST_META_BWD_U] = meta_fmt(true, 4, wide[1]);
     a.scratch[b] = scratch_rows;
     a.status[b] = 0;
   }

@@ -95,9 +95,10 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(nfst_batch lat, nfst_sc
     float xs[4];
     if (kCompact) {
       const uint4 x = cur.x;
-      const uint32_t r[4] = {x.y, __builtin_amdgcn_alignbit(x.z, x.y, 24), __builtin_amdgcn_alignbit(x.w, x.z, 16), x.w >> 8};
+      uint32_t r[4];
+      unpack24(x.y, x.z, x.w, r);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) rcs[j] = ((r[j] & 0x1fffu) << 3) | (((r[j] >> 13) & 0x7ffu) << 16);  // as a 32-bit record
+      for (int j = 0; j < 4; ++j) rcs[j] = rec24_to_32(r[j]);  // as a 32-bit record
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j) rcs[j] = cur.w[j];
@@ -118,25 +119,25 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(nfst_batch lat, nfst_sc
     for (int j = 0; j < 4; ++j) {
       // straight-line: every slot reads its label score and operand value (an empty slot has
       // operand 0 and the null label, whose "score" is the word behind the table -- never used)
-      const int other = (int)((rcs[j] & 0xffffu) >> 3);
-      xs[j] += tl[rcs[j] >> 16] + v[other];
+      const int other = (int)rec32_state(rcs[j]);
+      xs[j] += tl[rec32_label(rcs[j])] + v[other];
     }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) vit_take(bv, ba, bn, xs[j], cas[j], (int)((rcs[j] & 0xffffu) >> 3), cas[j] >= 0);
+    for (int j = 0; j < 4; ++j) vit_take(bv, ba, bn, xs[j], cas[j], (int)rec32_state(rcs[j]), cas[j] >= 0);
     // a unit-label record stands for what row `other` holds -- the state's own earlier pieces
     // (carry) or a scratch row of a partial group: its best arc competes as such.  Rare.
     bool unit[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) unit[j] = (j < U) & (cas[j] < 0) & ((int)(rcs[j] >> 16) == lat.vocab + 1);
+    for (int j = 0; j < 4; ++j) unit[j] = (j < U) & (cas[j] < 0) & ((int)rec32_label(rcs[j]) == lat.vocab + 1);
     if (__builtin_amdgcn_ballot_w64(unit[0] | unit[1] | unit[2] | unit[3])) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int other = (int)((rcs[j] & 0xffffu) >> 3);
+        const int other = (int)rec32_state(rcs[j]);
         if (unit[j] && bp[other] >= 0) vit_take(bv, ba, bn, v[other], bp[other], ns[other]);
       }
     }
-    const int gl = (int)((ctl >> 20) & 7u);
-    const int gmax = (int)((__builtin_amdgcn_readfirstlane(ctl) >> 23) & 7u);
+    const int gl = (int)ctl_g(ctl);
+    const int gmax = (int)ctl_gmax(__builtin_amdgcn_readfirstlane(ctl));
     // segmented max over the state's lanes: quad permutes and row mirrors (DPP), then the
     // two cross-row stages; every lane of a state ends with the same (value, arc, next state)
 #define NFST_VIT_STAGE(ST, FV, FI)                                          \
@@ -156,8 +157,8 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(nfst_batch lat, nfst_sc
 #undef NFST_VIT_STAGE
 #undef NFST_SHFL16
 #undef NFST_SHFL32
-    if (ctl & (1u << 31)) {
-      const uint32_t sid = (ctl & 0xffffu) >> 3;
+    if (ctl_leader(ctl)) {
+      const uint32_t sid = ctl_state(ctl);
       v[sid] = bv;
       bp[sid] = (ba == kNone) ? -1 : ba;
       ns[sid] = bn;
@@ -279,14 +280,14 @@ struct VitWave {
     auto process = [&](int i, const G &g) {
       const int t = ei + min(i, n_mine - 1) * kVitNE;
       const uint32_t ctl = g.raw[0];
-      const uint32_t r[4] = {g.raw[1], __builtin_amdgcn_alignbit(g.raw[2], g.raw[1], 24), __builtin_amdgcn_alignbit(g.raw[3], g.raw[2], 16),
-                             g.raw[3] >> 8};
+      uint32_t r[4];
+      unpack24(g.raw[1], g.raw[2], g.raw[3], r);
       uint32_t opa[4], unit = 0;
       float sc[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const uint32_t lab = (r[j] >> 13) & 0x7ffu;
-        opa[j] = ((r[j] & 0x1fffu) << 4) + rec_base;  // the operand state's record
+        const uint32_t lab = rec24_label(r[j]);
+        opa[j] = (rec24_state(r[j]) << 4) + rec_base;  // the operand state's record
         sc[j] = *(const __attribute__((address_space(3))) float *)(uintptr_t)(tl_base + lab * 4);  // (null and unit label: -inf)
         if (XM != 0 && g.a[j] >= 0) sc[j] += XM == 2 ? g.w[j] + g.s[XM == 2 ? j : 0] : g.w[j];
         unit |= (((g.a[j] < 0) & ((int)lab == vocab + 1)) ? 1u : 0u) << j;
@@ -298,11 +299,11 @@ struct VitWave {
       }
       asm volatile("" ::: "memory");
       const uint32_t sb = ring_base + (uint32_t)(t % R) * SB;
-      const uint32_t dst = ((int)ctl < 0) ? ((ctl & 0xffffu) << 1) + rec_base : trash;  // 8 x state -> 16 x state
+      const uint32_t dst = ctl_leader(ctl) ? (ctl_off8(ctl) << 1) + rec_base : trash;  // 8 x state -> 16 x state
       // word 0: store address (18 bits) | group size g (3) | largest g of the tile (3) | unit slots (4) | the tile has unit records (1);
       // words 1 .. 3: all-ones where the state owns more than 2^s lanes (stage s of the segmented maximum)
-      const uint32_t gl = (ctl >> 20) & 7u;
-      const uint32_t w0 = dst | (gl << 18) | (((ctl >> 23) & 7u) << 21) | (unit << 24) | ((any_unit ? 1u : 0u) << 28);
+      const uint32_t gl = ctl_g(ctl);
+      const uint32_t w0 = dst | (gl << 18) | (ctl_gmax(ctl) << 21) | (unit << 24) | ((any_unit ? 1u : 0u) << 28);
       *(lds_v4u *)(uintptr_t)(sb + lane * 16) = v4u{w0, gl > 0 ? ~0u : 0u, gl > 1 ? ~0u : 0u, gl > 2 ? ~0u : 0u};
       *(lds_v4u *)(uintptr_t)(sb + 1024 + lane * 16) = v4u{opa[0], opa[1], opa[2], opa[3]};
       *(lds_v4f *)(uintptr_t)(sb + 2048 + lane * 16) = v4f{sc[0], sc[1], sc[2], sc[3]};

@@ -157,8 +157,8 @@ __device__ __forceinline__ Meta load_meta(const int32_t *meta, int b) {
   r.n_dp = m[NFST_META_N_DP];
   // program format code (1, 2, 4: slots per lane; 8: compact tiles), and bit 8: the program has
   // tiles with groups wider than 8 lanes
-  r.fwd_u = m[NFST_META_FWD_U] & 0xff; r.bwd_u = m[NFST_META_BWD_U] & 0xff;
-  r.fwd_wide = (m[NFST_META_FWD_U] >> 8) & 1; r.bwd_wide = (m[NFST_META_BWD_U] >> 8) & 1;
+  r.fwd_u = meta_code(m[NFST_META_FWD_U]); r.bwd_u = meta_code(m[NFST_META_BWD_U]);
+  r.fwd_wide = meta_wide(m[NFST_META_FWD_U]); r.bwd_wide = meta_wide(m[NFST_META_BWD_U]);
   r.fwd_slot_off = m[NFST_META_FWD_SLOT_OFF]; r.bwd_slot_off = m[NFST_META_BWD_SLOT_OFF];
   return r;
 }

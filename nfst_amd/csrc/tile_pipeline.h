@@ -3,21 +3,10 @@
 #pragma once
 
 // ---------------------------------------------------------------- tile programs
-// A sweep is a "tile program" laid out by the host packer (pack.cpp, DESIGN.md
-// section 3): a sequence of fixed-size tiles, each one wave-wide unit of work --
-// 64 control words and 64*U arc records (U = 1, 2 or 4 slots per lane).  ONE wave
+// A sweep runs a "tile program" (format: tile_format.h).  ONE wave
 // runs one sweep: its LDS accesses are ordered, a tile only reads states that an
 // earlier tile wrote, so a sweep needs no barrier at all, and the alpha and beta
 // sweeps of a lattice run as two independent waves of the workgroup.
-//
-// control word: [0:16) 8 x state id (the byte offset of its value in the alpha / beta array)
-//               [20:23) g: the state's lanes are the 2^g-aligned group of 2^g lanes
-//               [23:26) largest g in this tile (same in every lane)
-//               [26] the tile holds a continuation piece (same in every lane)
-//               [30] continuation piece (its first record is the carry)  [31] leader lane
-//               (stores the state's sum)
-// record:       [0:16) 8 x operand state | [16:32) label (vocab = the null label: weight 0,
-//               vocab + 1 = the unit label of a carry record: weight 1)
 //
 // The program does not depend on DP values, so two helper waves of the workgroup run far
 // ahead of the sweep.  The LOADER copies tiles from HBM into a small staging ring in LDS
@@ -42,11 +31,6 @@ constexpr int kSlotWords = 64 * (1 + 3 * 4);    // decoded tile for U = 4: 3328 
 constexpr int kSlotWords2 = 1024;               // ring slot of the tile-wave pipeline: 64 lanes x 64 bytes
 constexpr int kSlotWordsP = 1280;               // ... of its precise flavour (float64 mantissas): 64 lanes x 80 bytes
 constexpr int kPreciseTiles = 192;              // programs with more tiles than this run the precise flavour (semiring.h)
-// program format code (meta word, bits 0..7): 1, 2, 4 = slots per lane with 32-bit records and a
-// separate control block; 8 = the compact tile: four slots per lane, 16 bytes per lane = control
-// word + four 24-bit records (state 13 bits | label 11 bits)
-__host__ __device__ constexpr int fmt_u(int F) { return F == 8 ? 4 : F; }
-__host__ __device__ constexpr int fmt_words(int F) { return F == 8 ? 256 : 64 * (1 + F); }
 constexpr int kMaxRing = 12, kMinRing = 3;       // ring slots per sweep (chosen at launch from the LDS budget)
 
 template <int CTRL>
@@ -260,8 +244,8 @@ __device__ __forceinline__ float seg_sum_fmac3(float M, float gf) {
 template <int U, bool WIDE>
 __device__ __forceinline__ void tile_math(const v2f (&tw)[U], const v2f (&vv)[U], uint32_t ctl, uint32_t dst_addr,
                                           uint32_t trash, bool wide_tile, int &ref) {
-  const int gl = (int)((ctl >> 20) & 7u);
-  const bool leader = (int)ctl < 0;
+  const int gl = (int)ctl_g(ctl);
+  const bool leader = ctl_leader(ctl);
   const int nref = -ref;
   float mt[U];
   int d[U];
@@ -319,11 +303,12 @@ struct FusedSweep {
   }
   __device__ __forceinline__ static void unpack(const v4u x, uint32_t val_base, Dec &w) {
     w.ctl = x.x;
-    const uint32_t r[4] = {x.y, __builtin_amdgcn_alignbit(x.z, x.y, 24), __builtin_amdgcn_alignbit(x.w, x.z, 16), x.w >> 8};
+    uint32_t r[4];
+    unpack24(x.y, x.z, x.w, r);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      w.opa[j] = ((r[j] << 3) & 0xfff8u) + val_base;  // state (13 bits) x 8 + the array's base
-      w.lab8[j] = (r[j] >> 10) & 0x3ff8u;             // label (11 bits) x 8
+      w.opa[j] = rec24_off8(r[j]) + val_base;
+      w.lab8[j] = rec24_label8(r[j]);
     }
   }
   // the oldest tile in flight (set J) -> w; set J then loads tile `tile + K` (past the end: the last
@@ -354,7 +339,7 @@ struct FusedSweep {
       __builtin_amdgcn_sched_barrier(0);  /* nothing is scheduled in front of the operand gathers */      \
       take<JN>(g, t + 1, last, lane, val_base, NXT);                                                      \
       asm volatile("" ::: "memory");                                                                      \
-      tile_math<4, WIDE>(TW, vv, CUR.ctl, (CUR.ctl & 0xffffu) + val_base, trash,                           \
+      tile_math<4, WIDE>(TW, vv, CUR.ctl, ctl_off8(CUR.ctl) + val_base, trash,                           \
                          WIDE && ((__builtin_amdgcn_readfirstlane(CUR.ctl) >> 25) & 1u), ref);            \
       asm volatile("" ::: "memory");                                                                      \
       __builtin_amdgcn_sched_barrier(0);                                                                  \
@@ -524,13 +509,12 @@ __device__ __forceinline__ void raw_fetch(uint32_t rb, int lane, RawRegs<fmt_u(F
   if (F == 8) {
     const v4u x = *(const lds_v4u *)(uintptr_t)(rb + lane * 16);
     w.ctl = x.x;
-    const uint32_t r0 = x.y, r1 = __builtin_amdgcn_alignbit(x.z, x.y, 24), r2 = __builtin_amdgcn_alignbit(x.w, x.z, 16),
-                   r3 = x.w >> 8;
-    const uint32_t r[4] = {r0, r1, r2, r3};
+    uint32_t r[4];
+    unpack24(x.y, x.z, x.w, r);
 #pragma unroll
     for (int j = 0; j < U; ++j) {
-      w.opoff[j] = (r[j % 4] << 3) & 0xfff8u;   // state (13 bits) x 8
-      w.lab8[j] = (r[j % 4] >> 10) & 0x3ff8u;   // label (11 bits) x 8
+      w.opoff[j] = rec24_off8(r[j % 4]);
+      w.lab8[j] = rec24_label8(r[j % 4]);
     }
     return;
   }
@@ -546,8 +530,8 @@ __device__ __forceinline__ void raw_fetch(uint32_t rb, int lane, RawRegs<fmt_u(F
   }
 #pragma unroll
   for (int j = 0; j < U; ++j) {
-    w.opoff[j] = rc[j] & 0xffffu;
-    w.lab8[j] = (rc[j] >> 16) << 3;
+    w.opoff[j] = rec32_off8(rc[j]);
+    w.lab8[j] = rec32_label8(rc[j]);
   }
 }
 
@@ -754,20 +738,20 @@ struct WeightWave {
   __device__ __forceinline__ static void unpack(const uint32_t (&raw)[RW], uint32_t &ctl, uint32_t (&opoff)[U], uint32_t (&lab8)[U]) {
     if (F == 8) {
       ctl = raw[0];
-      const uint32_t r[4] = {raw[1], __builtin_amdgcn_alignbit(raw[2], raw[1], 24), __builtin_amdgcn_alignbit(raw[3], raw[2], 16),
-                             raw[3] >> 8};
+      uint32_t r[4];
+      unpack24(raw[1], raw[2], raw[3], r);
 #pragma unroll
       for (int j = 0; j < U; ++j) {
-        opoff[j] = (r[j % 4] << 3) & 0xfff8u;
-        lab8[j] = (r[j % 4] >> 10) & 0x3ff8u;
+        opoff[j] = rec24_off8(r[j % 4]);
+        lab8[j] = rec24_label8(r[j % 4]);
       }
     } else {
       ctl = FULL ? raw[0] : 0u;
 #pragma unroll
       for (int j = 0; j < U; ++j) {
         const uint32_t rc = raw[(FULL ? 1 : 0) + j];
-        opoff[j] = rc & 0xffffu;
-        lab8[j] = (rc >> 16) << 3;
+        opoff[j] = rec32_off8(rc);
+        lab8[j] = rec32_label8(rc);
       }
     }
   }
@@ -851,7 +835,7 @@ struct WeightWave {
         }
         asm volatile("" ::: "memory");
         const uint32_t sb = ring_base + (uint32_t)(t % R) * (kSlotWordsP * 4);
-        const int gl = (int)((ctl >> 20) & 7u);
+        const int gl = (int)((ctl >> 20) & 7u);  // (through the accessors of tile_format.h the compiler schedules this differently)
         const uint32_t dst = (((int)ctl < 0) ? 2 * (ctl & 0xffffu) + val_base : trash) | (ctl & 0x03f00000u);
         *(lds_v4u *)(uintptr_t)(sb + lane * 16) = v4u{dst, gl > 0 ? 0x3ff00000u : 0u, gl > 1 ? 0x3ff00000u : 0u, gl > 2 ? 0x3ff00000u : 0u};
         *(lds_v4u *)(uintptr_t)(sb + 1024 + lane * 16) = v4u{2 * opoff[0] + val_base, 2 * opoff[1 % U] + val_base, 2 * opoff[2 % U] + val_base, 2 * opoff[3 % U] + val_base};
@@ -886,8 +870,8 @@ struct WeightWave {
       asm volatile("" ::: "memory");
       const uint32_t sb = ring_base + (uint32_t)(t % R) * SB;
       if (FULL && v2) {
-        const int gl = (int)((ctl >> 20) & 7u);
-        const uint32_t dst = ((int)ctl < 0) ? (ctl & 0xffffu) + val_base : trash;
+        const int gl = (int)ctl_g(ctl);
+        const uint32_t dst = ctl_leader(ctl) ? ctl_off8(ctl) + val_base : trash;
         *(lds_v4u *)(uintptr_t)(sb + lane * 16) = v4u{dst, gl > 0 ? 0x3f800000u : 0u, gl > 1 ? 0x3f800000u : 0u, gl > 2 ? 0x3f800000u : 0u};
         if (U == 4) {
           *(lds_v4u *)(uintptr_t)(sb + 1024 + lane * 16) = v4u{opoff[0] + val_base, opoff[1 % U] + val_base, opoff[2 % U] + val_base, opoff[3 % U] + val_base};
@@ -1026,9 +1010,9 @@ __device__ __forceinline__ void tile_sweep(int n_tiles, const uint32_t *ring, in
     // --- what only needs the tile's control word: stage masks (lanes whose state owns
     // more than 2^s lanes), leader lanes, store address
     const uint32_t w0 = cur.w0;
-    const int gl = (int)((w0 >> 20) & 7u);
+    const int gl = (int)ctl_g(w0);  // (word 0 of a decoded tile keeps the control word's fields from bit 20 on)
     lds_v2f *dst = (lds_v2f *)(uintptr_t)(w0 & 0xfffffu);
-    const bool leader = (int)w0 < 0;
+    const bool leader = ctl_leader(w0);
     const uint64_t m0 = __builtin_amdgcn_ballot_w64(gl > 0), m1 = __builtin_amdgcn_ballot_w64(gl > 1),
                    m2 = __builtin_amdgcn_ballot_w64(gl > 2);
     asm volatile("" ::: "memory");
@@ -1425,7 +1409,7 @@ __device__ __forceinline__ int tile_math3p(const Dec2P &c, const Rec64 (&vv)[4],
   }
   int E = ref;
   if (__builtin_expect(bad != 0, 0)) {
-    const int g = (int)((c.dst >> 20) & 7u);
+    const int g = (int)ctl_g(c.dst);
     M = ldexp_clamped(mt[0], d[0] - dmax);
 #pragma unroll
     for (int j = 1; j < 4; ++j) M += ldexp_clamped(mt[j], d[j] - dmax);

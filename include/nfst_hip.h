@@ -508,6 +508,15 @@ int nfst_kbest(const nfst_batch *lat, const nfst_scores *scores, int32_t k, void
  * Viterbi: best[b] = max path score (float32), paths [B, max_len] int32 labels
  * of the best path (bos .. eos) padded with `pad`, lengths [B]; path_arcs
  * (optional) canonical arc ids, -1 padded.  Ties keep the smallest label.
+ * The score is a float32 sum built from the sink (0.0f) backwards; arc a from s to d gives the candidate
+ *     general kernel:    c = e_a + (theta[label_a] + v(d)),  e_a = 0.0f (+ arc_w[a] if weighted) (+ arc_scores[a] if given)
+ *     tile-wave kernel:  c = v(d) + (theta[label_a] + e_a),  e_a = arc_w[a] + arc_scores[a], arc_w[a] or arc_scores[a]
+ * (all-compact batches run the tile-wave kernel; without arc_w and arc_scores both are theta[label_a] + v(d)), and
+ * v(s) is the largest candidate of s, the smaller canonical arc on exactly tied candidates.  Self loops are on no path.
+ * A lattice without a path of finite score (labels at -inf on every path) gets best = -inf, length 0, labels all
+ * `pad` and arcs all -1: entry 0 of nfst_kbest for such a lattice.  A path longer than max_len gets length -1.
+ * The general kernel keeps 12 bytes per row and 4 per label in LDS: a batch it has to run (not all-compact, or too
+ * large for the tile-wave ring) with 12 max_rows + 4 vocab + 16 > 160 KiB returns NFST_ERR_LIMIT before any launch.
  */
 int nfst_viterbi(const nfst_batch *lat, const nfst_scores *scores, float *best, int32_t *paths,
                  int32_t *path_arcs, int32_t *lengths, int32_t max_len, int32_t pad,
@@ -601,8 +610,9 @@ typedef struct nfst_step_extras {
  * `state` is the state after the previous symbol `inp` was consumed.  inp may be NULL: no bos / pad /
  * eos legality masks and no counters then.  values is row-indexed [total_rows] (e.g. beta in the domain
  * the caller's scorer expects) or NULL.  extras may be NULL.  logits_out (optional, [N, V]) receives the
- * masked, scaled logits: what nfst_proposal_step_backward needs.  vocab <= 4096 (<= 3400 with
- * extras->value_state).
+ * masked, scaled logits: what nfst_proposal_step_backward needs.  vocab <= 4096 (<= 3413 with
+ * values and extras->value_state: four walkers x three rows of vocab words must fit 160 KiB of LDS); a larger
+ * vocabulary returns NFST_ERR_LIMIT before any launch.
  */
 int nfst_proposal_step(const nfst_batch *lat, const int64_t *state, const int64_t *inp, const float *scores,
                        const float *values, int32_t pad, int32_t bos, int32_t eos, int32_t has_to_end, float temperature,
@@ -697,7 +707,7 @@ int nfst_path_logprob_backward(const float *scores, const int64_t *marks, const 
                                int32_t max_length, float temp, int32_t normalize, float smoothing,
                                int32_t mask_mode, float *grad_scores, void *stream);
 
-/* log_w [B,K] = log_p - log_q ; log_marginal [B] = logsumexp_k(log_w) - log K */
+/* log_w [B,K] = log_p - log_q ; log_marginal [B] = logsumexp_k(log_w) - log K (-inf for a row whose log_w are all -inf) */
 int nfst_iwae(const float *log_p, const float *log_q, int32_t b, int32_t k, float *log_w,
               float *log_marginal, void *stream);
 

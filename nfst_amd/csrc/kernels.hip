@@ -290,7 +290,9 @@ int plan_viterbi(const nfst_batch *lat, const nfst_scores *sc, SweepPlan *p) {
     *p = {Flavour::tile_waves, kVitTwThreads, ex, R, 0, fixed + (int64_t)R * kSlotWords2 * 4};
   else
     *p = {Flavour::general, kVitThreads, ex, 0, 0, (int64_t)lat->max_rows * 12 + (int64_t)lat->vocab * 4 + 16};
-  return NFST_OK;
+  // (the general kernel keeps 12 bytes per row and the label scores in LDS: a large lattice over a large vocabulary
+  // does not fit)
+  return p->lds > kMaxLds ? NFST_ERR_LIMIT : NFST_OK;
 }
 
 // the outputs of nfst_backward (n_dirs 1) and nfst_forward_backward (n_dirs 2)
@@ -693,6 +695,7 @@ int nfst_proposal_step(const nfst_batch *lat, const int64_t *state, const int64_
   }
   const int64_t n = (int64_t)lat->n_lattices * k;
   const int64_t lds = (int64_t)kStepWaves * ((values && ex.value_state) ? 3 : 2) * lat->vocab * 4;
+  if (lds > kMaxLds) return NFST_ERR_LIMIT;  // (three rows per walker with a value state: vocab <= 3413)
   return launch(k_proposal_step, dim3((unsigned)((n + kStepWaves - 1) / kStepWaves)), dim3(64 * kStepWaves), lds, (hipStream_t)stream,
                 *lat, state, inp, scores, values, (int)pad, (int)bos, (int)eos, (int)has_to_end, temperature, uniforms, forced, ex, symbol,
                 logq, logz, next_state, logits_out, (int)k, n);

@@ -186,10 +186,14 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(nfst_batch lat, nfst_sc
   int *pa = (int *)v;
   int *res = progress;  // [0] length, [1] reached the sink
   if (tid == 0) {
-    best[b] = v[0];
+    const float top = v[0];
+    best[b] = top;
     int s0 = 0, len = 0;
     const int cap = min(max_len, m.n_rows);
-    while (s0 != m.sink && len < cap) {
+    // no path of finite score: the back pointers hold arcs of value -inf (vit_take keeps the smaller arc on a tie);
+    // they are not walked -- best = -inf, length 0, an empty path
+    const bool none = !(top > kNegInf);
+    while (!none && s0 != m.sink && len < cap) {
       const int a = bp[s0];
       if (a < 0) break;
       const int nx = ns[s0];
@@ -197,7 +201,7 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(nfst_batch lat, nfst_sc
       s0 = nx;
     }
     res[0] = len;
-    res[1] = (s0 == m.sink) ? 1 : 0;
+    res[1] = (none || s0 == m.sink) ? 1 : 0;
   }
   __syncthreads();
   const int len = res[0];
@@ -477,19 +481,21 @@ __global__ __launch_bounds__(kVitTwThreads) void k_viterbi_tw(nfst_batch lat, nf
   int *pa = (int *)ring;
   int *res = flags;  // [0] length, [1] reached the sink
   if (tid == 0) {
-    best[b] = __uint_as_float(rec[0].x);
+    const float top = __uint_as_float(rec[0].x);
+    best[b] = top;
     uint32_t at = rec_base;
     const uint32_t sink_at = rec_base + (uint32_t)m.sink * 16;
     int len = 0;
     const int cap = min(min(max_len, m.n_rows), R * kSlotWords2);
-    while (at != sink_at && len < cap) {
+    const bool none = !(top > kNegInf);  // no path of finite score: best = -inf, length 0, an empty path (as k_viterbi)
+    while (!none && at != sink_at && len < cap) {
       const v4u o = *(const lds_v4u *)(uintptr_t)at;
       if ((int)o.y < 0) break;
       pa[len++] = (int)o.y;
       at = o.z;
     }
     res[0] = len;
-    res[1] = (at == sink_at) ? 1 : 0;
+    res[1] = (none || at == sink_at) ? 1 : 0;
   }
   __syncthreads();
   const int len = res[0];
@@ -1390,6 +1396,10 @@ __global__ void k_iwae(const float *log_p, const float *log_q, int B, int K, flo
     const float w = log_p[(size_t)b * K + k] - log_q[(size_t)b * K + k];
     log_w[(size_t)b * K + k] = w;
     mx = fmaxf(mx, w);
+  }
+  if (mx == kNegInf) {  // every weight is -inf (every sample off p's support): logsumexp = -inf, not exp(-inf - -inf)
+    log_marginal[b] = kNegInf;
+    return;
   }
   float sm = 0.0f;
   for (int k = 0; k < K; ++k) sm += expf(log_w[(size_t)b * K + k] - mx);

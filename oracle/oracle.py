@@ -341,7 +341,9 @@ def iwae(log_p: np.ndarray, log_q: np.ndarray):
     log_w = (log_p - log_q).astype(np.float32)
     k = log_w.shape[1]
     m = log_w.max(axis=1, keepdims=True)
-    lse = (m[:, 0] + np.log(np.exp(log_w - m).sum(axis=1))).astype(np.float32)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        lse = (m[:, 0] + np.log(np.exp(log_w - m).sum(axis=1))).astype(np.float32)
+    lse = np.where(np.isneginf(m[:, 0]), np.float32(-np.inf), lse)  # a row all -inf: -inf, as torch.logsumexp gives
     return (lse - np.float32(np.log(k))).astype(np.float32), log_w
 
 

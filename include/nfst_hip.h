@@ -505,6 +505,35 @@ int nfst_kbest(const nfst_batch *lat, const nfst_scores *scores, int32_t k, void
                int32_t *status, void *stream);
 
 /*
+ * Arc slack, the max-plus counterpart of the arc posteriors, and beam masks (DESIGN.md sections 2 and 4.7).  A path
+ * runs from state 0 to the sink; self loops (the sink's pad loop) are on no path.  All arithmetic is float32, in this order:
+ *     c_a = e_a + (theta[label_a] + vbeta(dst_a)),  e_a = 0.0f (+ arc_w[a] if weighted) (+ arc_scores[a] if given)
+ *     vbeta(sink) = 0,  vbeta(s) = max of c_a over the out-arcs of s without self loops (-inf without one)
+ *     best[b] = vbeta(0): the bits of nfst_kbest's entry 0 (and of nfst_viterbi's best without per-arc extras)
+ *     gap_a = vbeta(src_a) - c_a where c_a > -inf: >= 0, and exactly 0 on the arc that attains the maximum
+ *     delta(0) = 0 if best > -inf, else +inf;  slack_a = delta(src_a) + gap_a (+inf where c_a = -inf or delta = +inf)
+ *     delta(d) = min of slack_a over the in-arcs of d without self loops (+inf without one);  a self loop at s: delta(s)
+ * slack_a is how far the best path through arc a falls short of the best path: >= 0, exactly 0 on every arc of
+ * nfst_kbest's entry 0, +inf on arcs that lie on no path of finite score; best[b] - slack_a is the arc's max-marginal
+ * (one more rounding).  With beam ([B], device, each >= 0 or +inf): keep[a] = slack_a <= beam[b] and slack_a < +inf
+ * (uint8 0 / 1; an arc on no path of finite score is never kept, also under beam +inf) and n_kept[b] = the kept arcs.  The kept arcs are trim: every kept arc lies on a path of kept arcs from state
+ * 0 to the sink, and the sink's pad loop is kept whenever best > -inf.  The beam is not read on the host: the caller
+ * validates it (the Python wrapper raises for a negative or NaN beam); under such a beam a lattice keeps no arc.
+ * Outputs (device): best [B]; slack [total_arcs]; keep [total_arcs] and n_kept [B] (both required with beam, both
+ * NULL without); optional vbeta and state_slack [total_rows]: vbeta(s) and delta(s) of the rows that lie on a path of
+ * finite score, -inf and +inf for every other row.  A lattice without a path of finite score gets best = -inf, slack
+ * +inf everywhere and n_kept = 0.  Every output is written exactly once: bit-identical from launch to launch, and for
+ * every packing of the same lattices (max and min are exact, the programs only order them), with or without chunked
+ * programs (this op has no chunked flavour).
+ * ws: device workspace of nfst_arc_slack_ws_bytes(lat) bytes (16-byte aligned, overwritten): 4 bytes per arc and 8 per
+ * row.  LDS: 8 bytes per row and 4 per label: 8 max_rows + 4 vocab + 16 > 160 KiB returns NFST_ERR_LIMIT.  Null
+ * required pointers, keep / n_kept without beam (or beam without them) or a short workspace return NFST_ERR_ARG.
+ */
+int64_t nfst_arc_slack_ws_bytes(const nfst_batch *lat);
+int nfst_arc_slack(const nfst_batch *lat, const nfst_scores *scores, const float *beam, void *ws, int64_t ws_bytes, float *best,
+                   float *vbeta, float *state_slack, float *slack, uint8_t *keep, int32_t *n_kept, void *stream);
+
+/*
  * Viterbi: best[b] = max path score (float32), paths [B, max_len] int32 labels
  * of the best path (bos .. eos) padded with `pad`, lengths [B]; path_arcs
  * (optional) canonical arc ids, -1 padded.  Ties keep the smallest label.

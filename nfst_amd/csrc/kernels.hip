@@ -37,6 +37,7 @@ using namespace nfst_tile;
 #include "chunk_kernels.h"
 #include "expect_kernels.h"
 #include "kbest_kernels.h"
+#include "slack_kernels.h"
 
 // ------------------------------------------------------------------ host helpers
 int check_batch(const nfst_batch *lat) {
@@ -906,6 +907,45 @@ int nfst_kbest(const nfst_batch *lat, const nfst_scores *scores, int32_t k, void
     return rc;
   return launch(k_kbest_walk, dim3(lat->n_lattices), dim3(64), 0, st, *lat, (int)k, w, best, paths, path_arcs, lengths, n_paths,
                 (int)max_len, (int)pad, status);
+}
+
+// ------------------------------------------------------------------ arc slack and beam masks (slack_kernels.h)
+// workspace: the gap of every canonical arc, then beta* and delta of every row (the rows only carry the values from
+// launch to launch when the phases run as separate launches)
+static int64_t slk_ws_layout(const nfst_batch *lat, char *base, SlkWs *w) {
+  WsCarve c{base};
+  char *gap = c.take(4 * lat->total_arcs), *vb = c.take(4 * lat->total_rows), *dl = c.take(4 * lat->total_rows);
+  if (w) *w = {(float *)gap, (float *)vb, (float *)dl};
+  return c.size;
+}
+
+int64_t nfst_arc_slack_ws_bytes(const nfst_batch *lat) {
+  const int rc = check_batch(lat);
+  if (rc) return rc;
+  return slk_ws_layout(lat, nullptr, nullptr);
+}
+
+int nfst_arc_slack(const nfst_batch *lat, const nfst_scores *scores, const float *beam, void *ws, int64_t ws_bytes, float *best,
+                   float *vbeta, float *state_slack, float *slack, uint8_t *keep, int32_t *n_kept, void *stream) {
+  int rc = check_batch(lat);
+  if (rc) return rc;
+  if ((rc = check_scores(lat, scores))) return rc;
+  if (!best || !slack || (beam && (!keep || !n_kept)) || (!beam && (keep || n_kept))) return NFST_ERR_ARG;
+  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < slk_ws_layout(lat, nullptr, nullptr)) return NFST_ERR_ARG;
+  // the general tile programs, also when the batch has chunked programs (there is no chunked flavour of this op)
+  const int64_t lds = ((int64_t)lat->max_rows * 2 + lat->vocab + 2 + 2) * 4;
+  if (lds > kMaxLds) return NFST_ERR_LIMIT;
+  SlkWs w;
+  slk_ws_layout(lat, (char *)ws, &w);
+  const SlkOut o = {beam, best, vbeta, state_slack, slack, keep, n_kept};
+  const hipStream_t st = (hipStream_t)stream;
+#ifdef NFST_SLACK_LAUNCHES  // measurement build: one launch per phase instead of barriers inside one
+  for (int ph = kSlkBeta; ph <= kSlkArcs; ph <<= 1)
+    if ((rc = launch(k_arc_slack, dim3(lat->n_lattices), dim3(kSlkThreads), lds, st, *lat, *scores, w, ph, o))) return rc;
+  return NFST_OK;
+#else
+  return launch(k_arc_slack, dim3(lat->n_lattices), dim3(kSlkThreads), lds, st, *lat, *scores, w, (int)kSlkAll, o);
+#endif
 }
 
 // shared argument checks and the variant table of the 16-byte streaming kernels: a row lies on a

@@ -645,6 +645,64 @@ class LatticeBatch:
         reps = torch.from_numpy(self.n_arcs.astype(np.int64))
         return torch.repeat_interleave(torch.arange(self.n_lattices), reps).to(self.device)
 
+    # ---------------------------------------------------------------- sub-lattices
+    def restrict(self, keep, n_kept=None, chunks=False, chunk_opts: Optional[dict] = None, **pack_opts):
+        """``(LatticeBatch, arc_map)``: the canonical arcs with ``keep[a]`` set, packed again over the same rows, state
+        ids and vocabulary (``arc_w`` filtered).  ``arc_map`` (int64 ``[A']``, increasing) holds the positions of the new
+        canonical arcs among the old ones: ``arc_scores[arc_map]`` scores the new batch, and autograd flows through the
+        indexing.  ``keep`` must be trim -- every kept arc on a path of kept arcs from state 0 to the sink, as
+        ``ops.arc_slack`` masks are: a subset of the canonical arcs is then a sorted arc list of its own, and states
+        without kept arcs become unreachable rows, which the packers ignore.  Trimness is not checked here; the packer's
+        errors surface (an arc of a state that the kept arcs no longer reach would be dropped by the packer: that raises).
+        A batch on the GPU is packed there (``from_arcs_device``, with ``chunks`` / ``chunk_opts``; one small read-back of
+        ``n_kept`` -- pass the ``[B]`` counts if they are at hand); what only the host packer takes falls back to
+        ``from_arcs`` with a warning.  A host batch goes through ``from_arcs``.  Raises ``ValueError`` naming the lattice
+        if a lattice keeps no arc."""
+        dev = self.device
+        A, B = self.total_arcs, self.n_lattices
+        keep_t = keep if isinstance(keep, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(keep))
+        keep_t = keep_t.to(device=dev).reshape(-1)
+        if keep_t.dtype != torch.bool:
+            keep_t = keep_t != 0
+        if keep_t.numel() != A:
+            raise ValueError(f"keep must have {A} entries, one per canonical arc")
+        arc_map = torch.nonzero(keep_t).reshape(-1)
+        if n_kept is None:
+            cnt = torch.bincount(self.arc_lattice()[arc_map], minlength=B).cpu().numpy().astype(np.int64)
+        else:
+            cnt = (n_kept.detach().cpu().numpy() if isinstance(n_kept, torch.Tensor) else np.asarray(n_kept)).astype(np.int64).reshape(-1)
+            if cnt.shape[0] != B:
+                raise ValueError(f"n_kept must have {B} entries")
+        if (cnt <= 0).any():
+            raise ValueError(f"lattice {int(np.nonzero(cnt <= 0)[0][0])} keeps no arc")
+        if int(arc_map.numel()) != int(cnt.sum()):
+            raise ValueError("n_kept does not count the arcs that keep marks")
+        arc_off = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(cnt, out=arc_off[1:])
+        src, label, dst = self.arc_src[arc_map], self.arc_label[arc_map], self.arc_dst[arc_map]
+        w = self.arc_w[arc_map] if self.weighted else None
+        n_rows = self.n_rows.astype(np.int32)
+        out = None
+        if dev.type == "cuda":
+            try:
+                out = LatticeBatch.from_arcs_device(n_rows, arc_off, src, label, dst, self.vocab, arc_w=w, device=dev, chunks=chunks,
+                                                    chunk_opts=chunk_opts, **pack_opts)
+            except _lib.NfstError as e:
+                if e.code != -6:  # NFST_ERR_LIMIT: beyond the device packer
+                    raise
+                warnings.warn("nfst_amd: restrict packs this batch on the host (beyond the device packer's limits)", stacklevel=2)
+        if out is None:
+            _check_chunks_arg(chunks)
+            out = LatticeBatch.from_arcs(n_rows, arc_off, src.cpu(), label.cpu(), dst.cpu(), self.vocab,
+                                         arc_w=None if w is None else w.cpu(), **pack_opts)
+            if chunks:
+                out.build_chunks(force=chunks == "force", **(chunk_opts or {}))
+            if dev.type == "cuda":
+                out = out.to(dev)
+        if out.total_arcs != int(arc_map.numel()) or not np.array_equal(out.n_arcs.astype(np.int64), cnt):
+            raise ValueError("keep is not trim: the packer dropped kept arcs of states that the kept arcs do not reach")
+        return out, arc_map
+
     # ---------------------------------------------------------------- C view
     def c_struct(self) -> _lib.Batch:
         """nfst_batch whose pointers are this batch's tensors (device memory)."""

@@ -529,6 +529,80 @@ def k_best(lat: LatticeBatch, theta, k: int, arc_scores=None, max_len: Optional[
     return KBestResult(*_KBest.apply(lat, theta, arc_scores, k, max_len, pad))
 
 
+class ArcSlackResult(NamedTuple):
+    best: torch.Tensor  # [B] float32: the best path's score (the bits of k_best(k=1).best)
+    slack: torch.Tensor  # [total_arcs] float32 >= 0; +inf on arcs that lie on no path of finite score
+    keep: Optional[torch.Tensor]  # [total_arcs] bool: slack <= beam (with a beam)
+    n_kept: Optional[torch.Tensor]  # [B] int32 kept arcs per lattice (with a beam)
+    vbeta: Optional[torch.Tensor]  # [total_rows] float32 best score from the row to the sink (want_rows)
+    state_slack: Optional[torch.Tensor]  # [total_rows] float32 slack of the best path through the row (want_rows)
+
+
+def _beam(lat: LatticeBatch, beam) -> torch.Tensor:
+    """[B] float32 on the batch's device; every entry >= 0 (+inf allowed)."""
+    if isinstance(beam, torch.Tensor):
+        if beam.dim() == 0:
+            beam = beam.reshape(1).expand(lat.n_lattices)
+        if beam.shape != (lat.n_lattices,):
+            raise ValueError(f"beam must be a number or a [{lat.n_lattices}] tensor, not {tuple(beam.shape)}")
+        beam = beam.detach().to(device=lat.device, dtype=torch.float32).contiguous()
+        if not bool((beam >= 0).all()):  # (NaN fails the comparison too)
+            raise ValueError("every beam must be >= 0 (inf allowed), not negative or NaN")
+        return beam
+    if isinstance(beam, bool) or not isinstance(beam, (int, float)) or not beam >= 0:
+        raise ValueError(f"beam must be a number >= 0 (inf allowed) or a [{lat.n_lattices}] tensor, not {beam!r}")
+    return torch.full((lat.n_lattices,), float(beam), dtype=torch.float32, device=lat.device)
+
+
+def arc_slack(lat: LatticeBatch, theta, arc_scores=None, beam=None, want_rows: bool = False) -> ArcSlackResult:
+    """Exact arc slack (``nfst_arc_slack``, DESIGN.md sections 2 and 4.7): per canonical arc, how far the best path
+    through the arc falls short of the best path of its lattice -- the max-plus counterpart of ``forward_backward``'s
+    arc posteriors, next to ``viterbi`` and ``k_best``.  ``slack`` is >= 0, exactly 0 on the arcs of ``k_best``'s
+    entry 0 and +inf on arcs that lie on no path of finite score; ``best - slack`` is the arc's max-marginal (one more
+    rounding).  ``theta`` [V] or [B, V], ``arc_scores`` [total_arcs] (optional).  ``beam``: a number or a ``[B]`` tensor,
+    every entry >= 0 (``inf`` allowed; a negative or NaN beam raises ``ValueError``): ``keep = slack <= beam`` and
+    ``n_kept`` per lattice.  The kept arcs are trim -- every one lies on a path of kept arcs from state 0 to the sink
+    -- so ``LatticeBatch.restrict(keep)`` packs them as they are.  ``want_rows``: ``vbeta`` and ``state_slack`` per
+    row (-inf / +inf for rows on no path of finite score).  Results are bit-identical from call to call and for every
+    packing of the same lattices.  Not differentiable: the outputs carry no gradient."""
+    _need_gpu(lat)
+    sc, alive = _scores(lat, theta.detach() if isinstance(theta, torch.Tensor) else torch.as_tensor(theta, dtype=torch.float32),
+                        None if arc_scores is None else arc_scores.detach())
+    dev = lat.device
+    B, A, R = lat.n_lattices, lat.total_arcs, lat.total_rows
+    bm = None if beam is None else _beam(lat, beam)
+    ws_bytes = int(lib.nfst_arc_slack_ws_bytes(C.byref(lat.c_struct())))
+    check(min(ws_bytes, 0), "nfst_arc_slack_ws_bytes")
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    best = torch.empty(B, dtype=torch.float32, device=dev)
+    slack = torch.empty(A, dtype=torch.float32, device=dev)
+    keep = torch.empty(A, dtype=torch.uint8, device=dev) if bm is not None else None
+    n_kept = torch.empty(B, dtype=torch.int32, device=dev) if bm is not None else None
+    vbeta = torch.empty(R, dtype=torch.float32, device=dev) if want_rows else None
+    sslack = torch.empty(R, dtype=torch.float32, device=dev) if want_rows else None
+    check(lib.nfst_arc_slack(C.byref(lat.c_struct()), C.byref(sc), _ptr(bm), ws.data_ptr(), ws_bytes, _ptr(best), _ptr(vbeta),
+                             _ptr(sslack), _ptr(slack), _ptr(keep), _ptr(n_kept), _stream()), "nfst_arc_slack")
+    return ArcSlackResult(best, slack, None if keep is None else keep.view(torch.bool), n_kept, vbeta, sslack)
+
+
+class PruneResult(NamedTuple):
+    lat: LatticeBatch  # the kept arcs, packed: same rows, state ids and vocabulary
+    arc_map: torch.Tensor  # int64 [A']: positions of the new canonical arcs among the old ones (increasing)
+    n_kept: torch.Tensor  # [B] int32
+    best: torch.Tensor  # [B] float32
+
+
+def prune(lat: LatticeBatch, theta, beam, arc_scores=None, **pack_opts) -> PruneResult:
+    """Beam pruning: the arcs whose best path is within ``beam`` of the lattice's best path (``arc_slack``), packed
+    into a new batch (``LatticeBatch.restrict``; ``pack_opts`` go to the packer, ``chunks=`` / ``chunk_opts=``
+    included).  ``arc_scores[arc_map]`` scores the new batch.  The best path always survives (beam 0 keeps exactly the
+    arcs of the paths tied for best); a lattice without a path of finite score keeps nothing and raises ``ValueError``.
+    One small read-back (``n_kept``)."""
+    r = arc_slack(lat, theta, arc_scores=arc_scores, beam=beam)
+    new, arc_map = lat.restrict(r.keep, n_kept=r.n_kept, **pack_opts)
+    return PruneResult(new, arc_map, r.n_kept, r.best)
+
+
 class SampleResult(NamedTuple):
     paths: torch.Tensor  # [B, K, max_len] int32 labels, pad-terminated
     arcs: torch.Tensor  # [B, K, max_len] int32 canonical arc ids

@@ -86,6 +86,12 @@ class LatticeScorer(torch.nn.Module):
         differentiable in theta)."""
         return ops.k_best(self._lat(), self.theta, k, max_len=max_len, pad=self.__pad__)
 
+    def prune(self, beam, **pack_opts) -> "ops.PruneResult":
+        """The scorer's lattice cut down to the arcs within ``beam`` of each lattice's best path under ``theta``
+        (``ops.prune``): ``(lat, arc_map, n_kept, best)``.  The scorer keeps its own lattice; hand the result to
+        ``set_lattice`` to go on with the pruned one."""
+        return ops.prune(self._lat(), self.theta.detach(), beam, **pack_opts)
+
     # ------------------------------------------------------------ per-step gathers
     def update_fsa_state(self, updated: torch.Tensor, prev_states: torch.Tensor) -> torch.Tensor:
         """scorers.py:683-690."""

@@ -534,6 +534,53 @@ int nfst_arc_slack(const nfst_batch *lat, const nfst_scores *scores, const float
                    float *vbeta, float *state_slack, float *slack, uint8_t *keep, int32_t *n_kept, void *stream);
 
 /*
+ * The product of every lattice with a deterministic automaton over the labels (DESIGN.md sections 2 and 4.8): sorted
+ * arc lists that both packers take, whose paths are exactly the paths of the lattice that the automaton accepts.  A
+ * path runs from state 0 to the sink over canonical arcs; self loops (the sink's pad loop) are on no path.
+ * Automaton: n_q states, 1 <= n_q <= 64, start state 0; delta[q][l] in {-1, 0 .. n_q - 1} for every label l < vocab
+ * (-1: no transition); final states.  It reads the label of every arc of a path, bos and eos included, never the label
+ * of a self loop; a path is accepted when every step has a transition and the run ends in a final state.  On the device
+ * the table is label-major: delta_t [vocab, 64] int8, -1 padded (delta_t[l * 64 + q] = delta[q][l]) and final_mask is one
+ * 64-bit word (bit q = final[q]); delta_stride / final_stride = 0: one automaton for the batch, else the distance in
+ * elements between the automata of consecutive lattices (delta_stride >= vocab * 64, final_stride >= 1).
+ * Product, per lattice (fwd, bwd, live: sets of automaton states, 64-bit masks):
+ *     fwd(0) = {0};  fwd(d) = union over the in-arcs (s, l, d) without self loops of { delta[q][l] >= 0 : q in fwd(s) }
+ *     bwd(sink) = the final states;  bwd(s) = union over the out-arcs (s, l, d) without self loops of
+ *                 { q : delta[q][l] in bwd(d) }
+ *     live(s) = fwd(s) & bwd(s) for the states that state 0 reaches, empty for every other row; the product is empty
+ *               iff 0 is not in live(0)
+ * Rows: the pairs (s, q), q in live(s), in (s ascending, q ascending) order; all pairs of the sink are ONE row, at the
+ * position of the first of them.  A row's id is its rank in that order (row 0 = (0, 0)); row_state = s, row_q = q (the
+ * sink row: its smallest live q).
+ * Arcs: for every row (s, q) in row order, for every canonical arc a = (s, l, d) of s in canonical order: a self loop
+ * gives (row, l, row), once per row; any other arc with t = delta[q][l] >= 0 and t in live(d) gives
+ * (row(s, q), l, row(d, t)); nothing else.  arc_map = a's position among the batch's canonical arcs (int64), arc_q = q
+ * (0 on a self loop of the sink row).  The list is sorted by (src, label), deterministic, acyclic apart from self loops,
+ * trim, and has exactly one sink; row and state ids are relative to the lattice, as nfst_arcs_device takes them.
+ * Every output is an integer written once at a position fixed by prefix sums: bit-identical from launch to launch and
+ * for every packing of the input, with or without chunked programs (only the canonical arrays are read).
+ *   nfst_intersect_count  counts [B, 2] = (rows, arcs) of every product, status [B]: a product of more than
+ *                         NFST_MAX_ROWS rows gets NFST_ERR_LIMIT (counts = (rows, 0)); an empty product has counts (0, 0)
+ *                         and status 0.  Leaves the masks and the offsets in ws.
+ *   nfst_intersect_write  after one read-back of counts and status: out_row_off / out_arc_off [B] int64 (device) = the
+ *                         exclusive prefix sums of the rows / arcs of count (0 rows and arcs for a lattice over the
+ *                         limit); src, label, dst, arc_q [sum of arcs] int32, arc_map [sum of arcs] int64, row_state,
+ *                         row_q [sum of rows] int32.  Same lat, delta_t, n_q and ws as the count call.
+ * ws: device workspace of nfst_intersect_ws_bytes(lat, n_q) bytes (16-byte aligned, overwritten): 24 bytes per row of
+ * the batch and 8 * NFST_MAX_ROWS + 8 per lattice.  LDS: 16 bytes per row of the largest lattice.  Any lattice the
+ * engine packs is taken.  n_q > 64: NFST_ERR_LIMIT; n_q < 1, null required pointers, bad strides or a short workspace:
+ * NFST_ERR_ARG; all on the host before any launch.  The entries of delta_t are not read on the host: the caller
+ * validates them (the Python wrapper does).
+ */
+int64_t nfst_intersect_ws_bytes(const nfst_batch *lat, int32_t n_q);
+int nfst_intersect_count(const nfst_batch *lat, const int8_t *delta_t, int64_t delta_stride, const uint64_t *final_mask,
+                         int64_t final_stride, int32_t n_q, void *ws, int64_t ws_bytes, int32_t *counts, int32_t *status,
+                         void *stream);
+int nfst_intersect_write(const nfst_batch *lat, const int8_t *delta_t, int64_t delta_stride, int32_t n_q, void *ws,
+                         int64_t ws_bytes, const int64_t *out_row_off, const int64_t *out_arc_off, int32_t *src, int32_t *label,
+                         int32_t *dst, int64_t *arc_map, int32_t *arc_q, int32_t *row_state, int32_t *row_q, void *stream);
+
+/*
  * Viterbi: best[b] = max path score (float32), paths [B, max_len] int32 labels
  * of the best path (bos .. eos) padded with `pad`, lengths [B]; path_arcs
  * (optional) canonical arc ids, -1 padded.  Ties keep the smallest label.

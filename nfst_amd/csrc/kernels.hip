@@ -38,6 +38,7 @@ using namespace nfst_tile;
 #include "expect_kernels.h"
 #include "kbest_kernels.h"
 #include "slack_kernels.h"
+#include "intersect_kernels.h"
 
 // ------------------------------------------------------------------ host helpers
 int check_batch(const nfst_batch *lat) {
@@ -946,6 +947,64 @@ int nfst_arc_slack(const nfst_batch *lat, const nfst_scores *scores, const float
 #else
   return launch(k_arc_slack, dim3(lat->n_lattices), dim3(kSlkThreads), lds, st, *lat, *scores, w, (int)kSlkAll, o);
 #endif
+}
+
+// ------------------------------------------------------------------ product with a label automaton (intersect_kernels.h)
+// workspace: the level order of k_kbest_levels, then live and the first product row of every lattice state, then the
+// pair and the first arc of every product row (NFST_MAX_ROWS per lattice) and the product rows per lattice
+static int64_t is_ws_layout(const nfst_batch *lat, char *base, IsWs *w) {
+  const int64_t TR = lat->total_rows, B = lat->n_lattices;
+  WsCarve c{base};
+  char *od = c.take(4 * TR), *lv = c.take(4 * (TR + B)), *nl = c.take(4 * B), *li = c.take(8 * TR), *fi = c.take(4 * TR);
+  char *pa = c.take(4 * B * NFST_MAX_ROWS), *ao = c.take(4 * B * NFST_MAX_ROWS), *no = c.take(4 * B);
+  if (w) *w = {(int *)od, (int *)lv, (int *)nl, (is_mask *)li, (int *)fi, (int *)pa, (int *)ao, (int *)no};
+  return c.size;
+}
+static int is_check_q(int32_t n_q) { return n_q < 1 ? NFST_ERR_ARG : (n_q > 64 ? NFST_ERR_LIMIT : NFST_OK); }
+static int is_check(const nfst_batch *lat, const int8_t *delta, int64_t delta_stride, int32_t n_q, const void *ws, int64_t ws_bytes) {
+  int rc = check_batch(lat);
+  if (rc) return rc;
+  if ((rc = is_check_q(n_q))) return rc;
+  if (!delta || (delta_stride != 0 && delta_stride < (int64_t)lat->vocab * 64)) return NFST_ERR_ARG;
+  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < is_ws_layout(lat, nullptr, nullptr)) return NFST_ERR_ARG;
+  return NFST_OK;
+}
+
+int64_t nfst_intersect_ws_bytes(const nfst_batch *lat, int32_t n_q) {
+  int rc = check_batch(lat);
+  if (rc) return rc;
+  if ((rc = is_check_q(n_q))) return rc;
+  return is_ws_layout(lat, nullptr, nullptr);
+}
+
+int nfst_intersect_count(const nfst_batch *lat, const int8_t *delta, int64_t delta_stride, const uint64_t *final_mask,
+                         int64_t final_stride, int32_t n_q, void *ws, int64_t ws_bytes, int32_t *counts, int32_t *status,
+                         void *stream) {
+  int rc = is_check(lat, delta, delta_stride, n_q, ws, ws_bytes);
+  if (rc) return rc;
+  if (!final_mask || final_stride < 0 || !counts || !status) return NFST_ERR_ARG;
+  const int64_t lds_lev = (int64_t)lat->max_rows * 12 + 16, lds = (int64_t)lat->max_rows * 16 + 256;
+  if (lds > kMaxLds) return NFST_ERR_LIMIT;  // (never: max_rows <= NFST_MAX_ROWS)
+  IsWs w;
+  is_ws_layout(lat, (char *)ws, &w);
+  const KbWs kw = {nullptr, w.order, w.lev, w.n_lev};
+  const IsDfa d = {delta, delta_stride, (const is_mask *)final_mask, final_stride};
+  const hipStream_t st = (hipStream_t)stream;
+  if ((rc = launch(k_kbest_levels, dim3(lat->n_lattices), dim3(kKbLevelThreads), lds_lev, st, *lat, kw))) return rc;
+  return launch(k_intersect_count, dim3(lat->n_lattices), dim3(kIsThreads), lds, st, *lat, d, w, counts, status);
+}
+
+int nfst_intersect_write(const nfst_batch *lat, const int8_t *delta, int64_t delta_stride, int32_t n_q, void *ws,
+                         int64_t ws_bytes, const int64_t *out_row_off, const int64_t *out_arc_off, int32_t *src, int32_t *label,
+                         int32_t *dst, int64_t *arc_map, int32_t *arc_q, int32_t *row_state, int32_t *row_q, void *stream) {
+  const int rc = is_check(lat, delta, delta_stride, n_q, ws, ws_bytes);
+  if (rc) return rc;
+  if (!out_row_off || !out_arc_off || !src || !label || !dst || !arc_map || !arc_q || !row_state || !row_q) return NFST_ERR_ARG;
+  IsWs w;
+  is_ws_layout(lat, (char *)ws, &w);
+  const IsDfa d = {delta, delta_stride, nullptr, 0};
+  const IsOut o = {out_row_off, out_arc_off, src, label, dst, arc_map, arc_q, row_state, row_q};
+  return launch(k_intersect_write, dim3(lat->n_lattices), dim3(kIsThreads), 0, (hipStream_t)stream, *lat, d, w, o);
 }
 
 // shared argument checks and the variant table of the 16-byte streaming kernels: a row lies on a

@@ -166,6 +166,36 @@ class ChunkProgram:
         return self._struct
 
 
+class IntersectResult:
+    """What ``LatticeBatch.intersect`` returns; unpacks as ``(lattice, arc_map, arc_q, row_state, row_q)``."""
+    __slots__ = ("lattice", "arc_map", "arc_q", "row_state", "row_q", "dfa")
+
+    def __init__(self, lattice, arc_map, arc_q, row_state, row_q, dfa):
+        self.lattice = lattice      # LatticeBatch: the products, packed
+        self.arc_map = arc_map      # int64 [A']: position of every product arc's lattice arc among the input's canonical arcs
+        self.arc_q = arc_q          # int32 [A']: automaton state at the arc's source (0 on the sink row's self loop)
+        self.row_state = row_state  # int32 [R']: lattice state of every product row (relative to its lattice)
+        self.row_q = row_q          # int32 [R']: automaton state of every product row (the sink row: its smallest)
+        self.dfa = dfa
+
+    def __iter__(self):
+        return iter((self.lattice, self.arc_map, self.arc_q, self.row_state, self.row_q))
+
+    def scores(self, arc_scores: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``[A']`` float32 per-arc scores of the product: ``arc_scores[arc_map]`` (per-arc scores of the input batch, if
+        given) plus ``dfa.weight[(b,) arc_q, label]`` (if the automaton is weighted); autograd flows through both
+        gathers.  Self loops lie on no path: their value does not matter (it is the gathered one)."""
+        lat = self.lattice
+        out = torch.zeros(lat.total_arcs, dtype=torch.float32, device=lat.device)
+        if arc_scores is not None:
+            out = out + arc_scores.to(device=lat.device, dtype=torch.float32)[self.arc_map]
+        if self.dfa.weight is not None:
+            w = self.dfa.weight.to(device=lat.device, dtype=torch.float32)
+            q, l = self.arc_q.to(torch.int64), lat.arc_label.to(torch.int64)
+            out = out + (w[q, l] if w.dim() == 2 else w[lat.arc_lattice(), q, l])
+        return out
+
+
 class LatticeBatch:
     """Packed lattices.  Tensors live on ``self.device``; ``meta`` is also kept on
     the host (numpy) because shapes and offsets are needed to size outputs."""
@@ -702,6 +732,73 @@ class LatticeBatch:
         if out.total_arcs != int(arc_map.numel()) or not np.array_equal(out.n_arcs.astype(np.int64), cnt):
             raise ValueError("keep is not trim: the packer dropped kept arcs of states that the kept arcs do not reach")
         return out, arc_map
+
+    # ---------------------------------------------------------------- product with a constraint automaton
+    def intersect(self, dfa, chunks=False, chunk_opts: Optional[dict] = None, **pack_opts) -> "IntersectResult":
+        """The product of every lattice with a ``constraints.ConstraintDFA`` (one for the batch or one per lattice), packed
+        into a new batch: its paths are exactly the paths of this batch whose label sequences the automaton accepts
+        (``nfst_intersect_count`` / ``_write``, DESIGN.md sections 2 and 4.8).  Returns ``IntersectResult(lattice,
+        arc_map, arc_q, row_state, row_q)``; every op runs on ``lattice`` unchanged, ``arc_scores[arc_map]`` (or
+        ``result.scores(arc_scores)``) scores it, ``arc_w`` is carried over.  Two launches around one small read-back,
+        then the device packer (``from_arcs_device`` with ``chunks`` / ``chunk_opts`` / ``pack_opts``); what only the
+        host packer takes falls back to ``from_arcs`` with a warning.  Raises ``ValueError`` naming the lattice if a
+        product is empty, ``NfstError(NFST_ERR_LIMIT)`` naming it if a product has more than 8192 rows (before any
+        packer runs), ``RuntimeError`` for a host batch."""
+        from .ops import _need_gpu, _stream
+
+        _need_gpu(self)
+        _check_chunks_arg(chunks)
+        dfa.check(self.vocab, self.n_lattices)
+        dev, B = self.device, self.n_lattices
+        delta_t, fin = dfa.to(dev)
+        per = dfa.n_lattices is not None
+        d_stride, f_stride = (self.vocab * 64, 1) if per else (0, 0)
+        bs = C.byref(self.c_struct())
+        ws_bytes = int(lib.nfst_intersect_ws_bytes(bs, dfa.n_states))
+        check(min(ws_bytes, 0), "nfst_intersect_ws_bytes")
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        cs = torch.zeros(3 * B, dtype=torch.int32, device=dev)  # counts [B, 2] | status [B]
+        check(lib.nfst_intersect_count(bs, delta_t.data_ptr(), d_stride, fin.data_ptr(), f_stride, dfa.n_states, ws.data_ptr(),
+                                       ws_bytes, cs.data_ptr(), cs[2 * B:].data_ptr(), _stream()), "nfst_intersect_count")
+        cs_h = cs.cpu().numpy()  # the one read-back
+        cnt, status = cs_h[:2 * B].reshape(B, 2).astype(np.int64), cs_h[2 * B:]
+        if status.any():
+            bad = int(np.nonzero(status)[0][0])
+            raise _lib.NfstError(int(status[bad]), f"nfst_intersect_count (a product of {int(cnt[bad, 0])} rows)", bad)
+        if (cnt[:, 0] == 0).any():
+            raise ValueError(f"lattice {int(np.nonzero(cnt[:, 0] == 0)[0][0])}: the automaton accepts none of its paths (empty product)")
+        off = np.zeros((2, B + 1), dtype=np.int64)
+        np.cumsum(cnt[:, 0], out=off[0, 1:])
+        np.cumsum(cnt[:, 1], out=off[1, 1:])
+        R, A = int(off[0, -1]), int(off[1, -1])
+        off_d = torch.from_numpy(off).to(dev)
+        arcs = torch.empty(4 * A, dtype=torch.int32, device=dev)
+        src, label, dst, arc_q = arcs[:A], arcs[A:2 * A], arcs[2 * A:3 * A], arcs[3 * A:]
+        arc_map = torch.empty(A, dtype=torch.int64, device=dev)
+        rows = torch.empty(2 * R, dtype=torch.int32, device=dev)
+        row_state, row_q = rows[:R], rows[R:]
+        check(lib.nfst_intersect_write(bs, delta_t.data_ptr(), d_stride, dfa.n_states, ws.data_ptr(), ws_bytes, off_d[0].data_ptr(),
+                                       off_d[1].data_ptr(), src.data_ptr(), label.data_ptr(), dst.data_ptr(), arc_map.data_ptr(),
+                                       arc_q.data_ptr(), row_state.data_ptr(), row_q.data_ptr(), _stream()), "nfst_intersect_write")
+        n_rows, arc_off = cnt[:, 0].astype(np.int32), off[1]
+        w = self.arc_w[arc_map] if self.weighted else None
+        out = None
+        try:
+            out = LatticeBatch.from_arcs_device(n_rows, arc_off, src, label, dst, self.vocab, arc_w=w, device=dev, chunks=chunks,
+                                                chunk_opts=chunk_opts, **pack_opts)
+        except _lib.NfstError as e:
+            if e.code != -6:  # NFST_ERR_LIMIT: beyond the device packer
+                raise
+            warnings.warn("nfst_amd: intersect packs this batch on the host (beyond the device packer's limits)", stacklevel=2)
+        if out is None:
+            out = LatticeBatch.from_arcs(n_rows, arc_off, src.cpu(), label.cpu(), dst.cpu(), self.vocab,
+                                         arc_w=None if w is None else w.cpu(), **pack_opts)
+            if chunks:
+                out.build_chunks(force=chunks == "force", **(chunk_opts or {}))
+            out = out.to(dev)
+        if out.total_arcs != A or not np.array_equal(out.n_arcs.astype(np.int64), cnt[:, 1]):
+            raise RuntimeError("nfst_amd: the packer did not keep every arc of the product")
+        return IntersectResult(out, arc_map, arc_q, row_state, row_q, dfa)
 
     # ---------------------------------------------------------------- C view
     def c_struct(self) -> _lib.Batch:

@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import lib, check
-from .lattice import LatticeBatch
+from .lattice import IntersectResult, LatticeBatch
 
 
 def _stream() -> int:
@@ -601,6 +601,15 @@ def prune(lat: LatticeBatch, theta, beam, arc_scores=None, **pack_opts) -> Prune
     r = arc_slack(lat, theta, arc_scores=arc_scores, beam=beam)
     new, arc_map = lat.restrict(r.keep, n_kept=r.n_kept, **pack_opts)
     return PruneResult(new, arc_map, r.n_kept, r.best)
+
+
+def intersect(lat: LatticeBatch, dfa, **pack_opts) -> IntersectResult:
+    """The product of every lattice with a constraint automaton (``constraints.ConstraintDFA``), packed into a new
+    batch whose paths are exactly the accepted paths of ``lat``: ``LatticeBatch.intersect`` (``nfst_intersect_count`` /
+    ``_write``, DESIGN.md sections 2 and 4.8).  ``(lattice, arc_map, arc_q, row_state, row_q)``; ``pack_opts`` go to
+    the packer, ``chunks=`` / ``chunk_opts=`` included."""
+    _need_gpu(lat)
+    return lat.intersect(dfa, **pack_opts)
 
 
 class SampleResult(NamedTuple):

@@ -92,6 +92,12 @@ class LatticeScorer(torch.nn.Module):
         ``set_lattice`` to go on with the pruned one."""
         return ops.prune(self._lat(), self.theta.detach(), beam, **pack_opts)
 
+    def constrain(self, dfa, **pack_opts) -> "ops.IntersectResult":
+        """The scorer's lattice under a constraint automaton (``ops.intersect``): ``(lattice, arc_map, arc_q, row_state,
+        row_q)``.  The scorer keeps its own lattice; hand ``result.lattice`` to ``set_lattice`` to go on under the
+        constraint."""
+        return ops.intersect(self._lat(), dfa, **pack_opts)
+
     # ------------------------------------------------------------ per-step gathers
     def update_fsa_state(self, updated: torch.Tensor, prev_states: torch.Tensor) -> torch.Tensor:
         """scorers.py:683-690."""

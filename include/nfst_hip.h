@@ -464,8 +464,12 @@ int nfst_forward_backward(const nfst_batch *lat, const nfst_scores *scores, floa
  *     label_post[b, l] = sum of p_a over them (exact sums of p_a rounded to 2^-44: independent of the order).
  * For values that do not depend on the scores c_a = dE[V]/ds_a = sum_b' d2 log Z / ds_a ds_b' v_b' (a Hessian-vector
  * product of log Z); with score_coef = 1 and no other values, H(p) = log Z - E[V] and dH/ds_a = -c_a.
- * Self loops (the sink's pad loop) and arcs of weight zero have p_a = c_a = 0.  Everything but label_cov is
- * bit-identical from launch to launch.
+ * Self loops (the sink's pad loop) and arcs of weight zero have p_a = c_a = 0.  An arc of weight zero (a label or an
+ * arc score at -inf) has no value: its label_values / arc_values entries are not read into any output (they may be
+ * infinite or NaN) and score_coef * s_a is left out.  A lattice without a path of finite score gets
+ *     logz64[b] = -inf,  ev64[b] = ev32[b] = 0,  posterior = cov = 0 on its arcs,  label_cov[b, :] = label_post[b, :] = 0
+ * (never a NaN; H = log Z - E[V] is then -inf) and does not disturb the other lattices of the batch.  Everything but
+ * label_cov is bit-identical from launch to launch.
  * ws: device workspace of nfst_expectation_ws_bytes(lat) bytes (16-byte aligned), overwritten.  logz64 and ev64 are
  * required.  The sweeps run the general tile programs (also when lat->chunks is set: this op has no chunked flavour)
  * with the path mass as (float64 mantissa, int32 exponent) and E[value | row] in float64 for every program, 20 bytes

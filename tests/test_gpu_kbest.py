@@ -1,6 +1,10 @@
 """ops.k_best (nfst_kbest: the exact k best paths of every lattice) against the float32 NumPy reference of
 tests/kbest_ref.py, bit for bit; entry 0 against ops.viterbi; scores against ops.score_paths; gradients; the
-LatticeScorer and JointProb entry points."""
+LatticeScorer and JointProb entry points.
+
+The edge cases (exact ties across the carry lane, labels at -inf, lattices without a finite path, LDS above 64 KiB, more
+lattices than compute units) take their inputs from tests/edge_cases.py; tests/test_kbest_cpu.py proves on the reference
+alone that those inputs are what the cases need."""
 import os
 
 import numpy as np
@@ -12,6 +16,7 @@ from nfst_amd.joint import JointProb
 from nfst_amd.lattice import LatticeBatch
 from nfst_amd.scorers import LatticeScorer
 from oracle import oracle as O
+from tests import edge_cases as E
 from tests import kbest_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -20,27 +25,7 @@ V = 64
 KS = (1, 2, 7, 20, 64)
 
 
-def _mixed_batch():  # (the mixed batch of test_gpu_parity.py)
-    return [
-        synth.layered_lattice(3, n_states=30, avg_degree=3.0, vocab=V, width=4, span=2),
-        synth.layered_lattice(4, n_states=300, avg_degree=8.0, vocab=V, width=9, span=5),
-        synth.layered_lattice(5, n_states=90, avg_degree=5.0, vocab=V, width=1, span=6),
-        synth.edit_lattice([10, 11, 12, 13, 14], [20, 21, 22, 23], vocab=V, seed=2),
-        synth.layered_lattice(6, n_states=700, avg_degree=10.0, vocab=V, width=16, span=8),
-        synth._finish(2, V, [0], [synth.EOS], [1]),
-    ]
-
-
-def _weighted_batch(n=4, vocab=48):
-    return [synth.layered_lattice(s, n_states=150 + 20 * s, avg_degree=6.0, vocab=vocab, width=7, span=3, weighted=True)
-            for s in range(n)]
-
-
-def _star():  # a state with 200 out-arcs (test_gpu_parity.py): its arcs take four chunks of the sweep
-    src = [0] + [1] * 200 + list(range(2, 202)) + [202]
-    lab = [BOS] + list(range(3, 203)) + [5] * 200 + [EOS]
-    dst = [1] + list(range(2, 202)) + [202] * 200 + [203]
-    return synth._finish(204, 256, src, lab, dst)
+_mixed_batch, _weighted_batch, _star = E.mixed_batch, E.weighted_batch, E.star  # (one definition: tests/edge_cases.py)
 
 
 def _refs(lat, lats, theta, asc=None):
@@ -298,3 +283,115 @@ def test_joint_prob_nbest_from_npz(dev, tmp_path):
     jp = JointProb(V2, pad=PAD, bos=BOS, eos=EOS, k=8, theta=torch.from_numpy(theta)).to(dev)
     _, mark = jp.decode_from_npz(path, V2, PAD)
     assert torch.equal(jp.nbest_from_npz(path, 3)[0][1].cpu(), mark.cpu())
+
+
+# ============================================================================= the edges (inputs: tests/edge_cases.py)
+def _t(x, dev):
+    return None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+
+
+def _run_all_k_general(tag, lat, lats, theta_np, dev, asc_np=None, ks=KS):
+    """Every k of ``ks`` against the reference, bit for bit, with entry 0 held to Viterbi's general kernel (``tw=0``: the
+    adds of nfst_kbest) bit for bit and the scores to ops.score_paths at k = 7 and 64.  Returns (references, results
+    by k)."""
+    with np.errstate(invalid="ignore"):  # (+inf + -inf in the reference: no candidate)
+        refs = _refs(lat, lats, theta_np, asc_np)
+    theta, asc = _t(theta_np, dev), _t(asc_np, dev)
+    with _lib.tuning(tw=0):
+        v = ops.viterbi(lat, theta, arc_scores=asc, pad=PAD)
+    out = {}
+    for k in ks:
+        r = ops.k_best(lat, theta, k, arc_scores=asc, pad=PAD)
+        _check(tag, lat, lats, r, refs, k)
+        _check_viterbi(lat, r, v)
+        if k in (7, 64):
+            _check_scores(lat, theta, r, asc)
+        out[k] = r
+    return refs, out
+
+
+# ----------------------------------------------------------------------------- B1: exact ties
+@pytest.mark.parametrize("name", ["star", "star wide", "star one slot", "funnel", "grid", "grid extras"])
+def test_exact_ties(dev, name):
+    """Scores on a grid of 0.25: whole paths tie, and the order (score desc, arc asc, rank asc) decides every entry --
+    within a chunk of 64 lanes, between the carry list in lane 63 and the later chunks of a state with 200 out-arcs, and
+    where the list is cut at k.  The packing of the tile programs must not matter: k-best reads the canonical arcs."""
+    lats, theta, asc, opts = E.tie_cases()[name]
+    lat = LatticeBatch.from_synth(lats, device=dev, **opts)
+    refs, _ = _run_all_k_general(f"ties {name}", lat, lats, theta, dev, asc)
+    for ref in refs:
+        assert E.tied_entries(ref) >= 2
+    if name.startswith("star"):  # all 200 paths score -1.0: the top 64 are the star's out-arcs 1 .. 64 in order
+        assert np.all(refs[0]["best"] == np.float32(-1.0))
+        assert [p[1] for p in refs[0]["arcs"]] == list(range(1, 65))
+    if name == "funnel":  # the tied top 64 take arcs from more than one chunk of each of the two heavy states
+        for pos in (1, 3):
+            assert len({E.sweep_chunk(lats[0], p[pos]) for p in refs[0]["arcs"]}) >= 2
+
+
+# ----------------------------------------------------------------------------- B2: labels at -inf
+@pytest.mark.parametrize("with_arc_scores", [False, True])
+def test_labels_at_minus_infinity(dev, with_arc_scores):
+    """Six labels at -inf (over 120 dead arcs per lattice): states whose whole list is empty, no dead label on any
+    returned path; with arc scores, one of +inf on a dead arc of every lattice: +inf + -inf = NaN is no candidate."""
+    lats = E.weighted_batch()
+    lat = LatticeBatch.from_synth(lats, device=dev)
+    theta = E.dead_label_theta()
+    asc = None
+    if with_arc_scores:
+        asc = np.random.default_rng(0).normal(0.0, 0.3, size=lat.total_arcs).astype(np.float32)
+        for b, l in enumerate(lats):
+            asc[int(lat.arc_off[b]) + E.reachable_dead_arc(l)] = np.inf
+    refs, out = _run_all_k_general("dead labels", lat, lats, theta, dev, asc)
+    paths, lens = out[64].paths.cpu().numpy(), out[64].lengths.cpu().numpy()
+    for b, l in enumerate(lats):
+        assert np.isin(l.label, E.DEAD).sum() > 120 and refs[b]["n_paths"] == 64
+        for j in range(64):
+            assert not np.isin(paths[b, j, :lens[b, j]], E.DEAD).any()
+
+
+def test_fewer_finite_paths_than_k(dev):
+    """Dead labels leave one lattice of the mixed batch 14 finite paths: 0 < n_paths < k at k = 20 and 64, and the
+    padding convention (best = -inf, length 0, pad, -1) holds on a real lattice."""
+    lats, theta, b, n = E.few_paths_case()
+    assert 0 < n < 20 and n == 14
+    lat = LatticeBatch.from_synth(lats, device=dev)
+    refs, out = _run_all_k_general("few paths", lat, lats, theta, dev)
+    assert refs[b]["n_paths"] == n
+    for k in (20, 64):
+        assert int(out[k].n_paths[b]) == n
+        assert bool(torch.isneginf(out[k].best[b, n:]).all()) and bool((out[k].lengths[b, n:] == 0).all())
+
+
+# ----------------------------------------------------------------------------- B3: no finite path
+@pytest.mark.parametrize("weighted", [False, True])
+def test_lattices_without_a_finite_path(dev, weighted):
+    lats, theta = E.no_path_case(weighted)
+    lat = LatticeBatch.from_synth(lats, device=dev)
+    asc = np.random.default_rng(13).normal(0.0, 0.3, size=lat.total_arcs).astype(np.float32) if weighted else None
+    refs, out = _run_all_k_general("no finite path", lat, lats, theta, dev, asc, ks=(1, 7, 64))
+    assert [r["n_paths"] == 0 for r in refs] == [False, True, False, True, False]
+    for k, r in out.items():
+        for b in (1, 3):
+            assert int(r.n_paths[b]) == 0 and bool(torch.isneginf(r.best[b]).all()) and bool((r.lengths[b] == 0).all())
+            assert bool((r.paths[b] == PAD).all()) and bool((r.arcs[b] == -1).all())
+
+
+# ----------------------------------------------------------------------------- B4: LDS above 64 KiB
+def test_large_lattice_beside_a_small_one(dev):
+    """8151 rows: k_kbest_levels takes 12 bytes of dynamic LDS per row and k_kbest_sweep 8 bytes per row + 16 KiB,
+    both above the 64 KiB a kernel gets without asking."""
+    lats = E.large_pair(8150)
+    lat = LatticeBatch.from_synth(lats, device=dev)
+    assert int(lat.max_rows) * 12 + 16 > 64 * 1024 and 16 * 1024 + (2 * int(lat.max_rows) + 1) * 4 > 64 * 1024
+    theta = synth.label_scores(6, 64)
+    asc = np.random.default_rng(5).normal(0.0, 0.3, size=lat.total_arcs).astype(np.float32)
+    _run_all_k_general("large", lat, lats, theta, dev, asc, ks=(1, 64))  # (scores against ops.score_paths at k = 64)
+
+
+# ----------------------------------------------------------------------------- B5: more lattices than compute units
+def test_more_lattices_than_compute_units(dev):
+    lats, theta, asc = E.many_small()
+    lat = LatticeBatch.from_synth(lats, device=dev)
+    assert lat.n_lattices == 330
+    _run_all_k_general("330 lattices", lat, lats, theta, dev, asc, ks=(1, 20))

@@ -26,6 +26,7 @@ from nfst_amd import _lib, ops, synth
 from nfst_amd.lattice import LatticeBatch
 from nfst_amd.ops import BackwardResult, _ptr, _stream
 from oracle import oracle as O
+from tests import edge_cases as E
 from tests import paths_ref as P
 from tests.test_gpu_fuzz import _draw_batch
 
@@ -114,9 +115,7 @@ def _viterbi_case(tag, dev, lats, theta_np, asc_np=None, tw_order=None, guard_ev
     return refs["general"]
 
 
-def _weighted_lats(weighted, vocab=48):
-    return [synth.layered_lattice(s, n_states=n, avg_degree=6.0, vocab=vocab, width=7, span=3, weighted=weighted)
-            for s, n in enumerate((150, 170, 190, 210, 700))]
+_weighted_lats = E.weighted_lats  # (one definition: tests/edge_cases.py)
 
 
 def _asc(lats, seed, std=0.3):
@@ -176,19 +175,15 @@ def test_viterbi_large_lattice(dev, n_states):
     """7800 states leave the tile-wave kernel its smallest ring (eight slots beside 16 bytes per row); 8150 leave fewer
     and the launcher falls back to the general kernel.  No public call tells which kernel ran: the bits are held to the
     references under both tunings."""
-    big = synth.layered_lattice(77, n_states=n_states, avg_degree=4.0, vocab=64, width=16, span=4, weighted=True)
-    small = synth.layered_lattice(78, n_states=200, avg_degree=4.0, vocab=64, width=8, span=4, weighted=True)
+    big, small = E.large_pair(n_states)
     lat = LatticeBatch.from_synth([big, small])
     assert (lat.max_rows * 16 + 1024 > 160 * 1024 - 8 * 4096) == (n_states == 8150)
     _viterbi_case(f"large {n_states}", dev, [big, small], synth.label_scores(6, 64), _asc([big, small], 5))
 
 
 def test_viterbi_more_lattices_than_compute_units(dev):
-    rng = np.random.default_rng(6)
-    lats = [synth.layered_lattice(2000 + i, n_states=int(rng.integers(8, 60)), avg_degree=3.0, vocab=40, width=int(rng.choice([1, 2, 4])),
-                                  span=2, max_degree=8, weighted=True) for i in range(330)]
-    theta = rng.normal(-1.0, 1.0, size=(len(lats), 40)).astype(F32)
-    _viterbi_case("330 lattices", dev, lats, theta, _asc(lats, 7), tw_order="tile_waves", guard_every=7)
+    lats, theta, asc = E.many_small()
+    _viterbi_case("330 lattices", dev, lats, theta, asc, tw_order="tile_waves", guard_every=7)
 
 
 @pytest.mark.parametrize("extras", [False, True])
@@ -216,7 +211,7 @@ def test_viterbi_exact_ties(dev, extras):
 def test_viterbi_labels_at_minus_infinity(dev, extras):
     lats = _weighted_lats(extras)
     theta = np.random.default_rng(10).normal(-2.0, 0.7, size=48).astype(F32)
-    dead = np.array([4, 9, 15, 22, 30, 41])
+    dead = E.DEAD
     theta[dead] = -np.inf
     refs = _viterbi_case("dead labels", dev, lats, theta, _asc(lats, 11) if extras else None, tw_order="tile_waves")
     for l, r in zip(lats, refs):
@@ -228,10 +223,7 @@ def test_viterbi_without_a_finite_path(dev, extras):
     """The convention of include/nfst_hip.h: a lattice all of whose paths cross a label at -inf gets best = -inf,
     length 0, labels all pad and arcs all -1 (entry 0 of nfst_kbest), from both kernels; its neighbours in the batch
     are not disturbed."""
-    lats = _weighted_lats(extras)
-    theta = np.random.default_rng(12).normal(-2.0, 0.7, size=(len(lats), 48)).astype(F32)
-    theta[1, EOS] = -np.inf  # every path of lattice 1 ends by eos
-    theta[3, BOS] = -np.inf  # ... and every path of lattice 3 starts by bos
+    lats, theta = E.no_path_case(extras)  # (eos at -inf for lattice 1, bos at -inf for lattice 3)
     asc = _asc(lats, 13) if extras else None
     refs = _viterbi_case("no finite path", dev, lats, theta, asc, tw_order="tile_waves")
     assert [bool(np.isneginf(r["best"])) for r in refs] == [False, True, False, True, False]

@@ -8,6 +8,7 @@ import pytest
 
 from nfst_amd import synth
 from oracle import oracle as O
+from tests import edge_cases as E
 from tests import kbest_ref as R
 
 V = 16
@@ -103,6 +104,107 @@ def test_reference_k1_equals_oracle_viterbi_bit_for_bit(seed):
         best, path, arcs = O.viterbi(l.n_rows, l.src, l.label, l.dst, theta[l.label], 4000)
         assert np.float32(best) == got["best"][0]
         assert got["arcs"][0] == list(arcs)
+
+
+# ----------------------------------------------------------------------------- ties, dead labels: the edges the GPU tests lean on
+def _canonical_order(l, score64, sink):
+    """Every finite path by (score desc, arcs in lexicographic order): the order of nfst_kbest where sums are exact."""
+    paths = R.enumerate_paths(l.n_rows, l.src, l.dst, score64, sink)
+    return sorted(paths, key=lambda x: (-x[0], x[1]))
+
+
+@pytest.mark.parametrize("i", range(4))
+@pytest.mark.parametrize("dead_label", [False, True])
+def test_scores_on_a_grid_tie_and_are_ordered_by_arc(i, dead_label):
+    """Scores on a grid of 0.25: float32 sums are exact, so the reference's list must be the enumeration's in the order
+    (score desc, then the smaller canonical arc at the first state where two paths part) -- with one label at -inf too."""
+    l = _small_lattices()[i]
+    theta = E.quarter(_theta(20 + i))
+    if l.weight is not None:
+        l.weight = E.quarter(l.weight)
+    sink = l.n_rows - 1
+    if dead_label:
+        total = R.count_finite_paths(l.n_rows, l.src, l.dst, np.zeros(l.n_arcs), sink)
+        for lab in np.argsort(-np.bincount(l.label, minlength=V), kind="stable"):
+            t = theta.copy()
+            t[lab] = -np.inf
+            if 0 < R.count_finite_paths(l.n_rows, l.src, l.dst, t[l.label].astype(np.float64), sink) < total:
+                break
+        else:
+            pytest.fail("no label kills some paths and not all")
+        theta = t
+    th, e = R.arc_terms(l, theta)
+    ref = _canonical_order(l, th.astype(np.float64) + e.astype(np.float64), sink)
+    for k in (1, 3, 7, 64):
+        got = R.k_best(l.n_rows, l.src, l.dst, th, e, k, sink)
+        n = min(k, len(ref))
+        assert got["n_paths"] == n and np.all(got["best"][n:] == NEG)
+        assert [float(x) for x in got["best"][:n]] == [s for s, _ in ref[:n]]
+        assert got["arcs"] == [p for _, p in ref[:n]]
+        if dead_label:
+            assert not any(np.isneginf(theta[l.label[p]]).any() for p in got["arcs"])
+    assert len({s for s, _ in ref[:64]}) < min(64, len(ref))  # (there are ties among the listed paths)
+
+
+def test_plus_infinity_on_a_dead_arc_is_no_candidate():
+    l = _small_lattices()[1]
+    theta = _theta(3)
+    a = int(np.nonzero(l.src == 0)[0][0])
+    nxt = np.nonzero(l.src == l.dst[a])[0]
+    theta[l.label[nxt[0]]] = -np.inf
+    asc = np.zeros(l.n_arcs, np.float32)
+    asc[nxt[0]] = np.inf  # +inf + -inf = NaN
+    th, e = R.arc_terms(l, theta, asc)
+    with np.errstate(invalid="ignore"):
+        got = R.k_best(l.n_rows, l.src, l.dst, th, e, 64, l.n_rows - 1)
+    assert np.all(np.isfinite(got["best"][:got["n_paths"]])) and not np.isnan(got["best"]).any()
+    assert not any(int(nxt[0]) in p for p in got["arcs"])
+    asc[nxt[0]] = 0.0
+    th, e = R.arc_terms(l, theta, asc)
+    same = R.k_best(l.n_rows, l.src, l.dst, th, e, 64, l.n_rows - 1)
+    assert same["arcs"] == got["arcs"] and np.array_equal(same["best"], got["best"])
+
+
+def test_tie_cases_really_tie():
+    """The conditions of test_gpu_kbest.test_exact_ties, on the reference alone."""
+    for name, (lats, theta, asc, _) in E.tie_cases().items():
+        refs = E.kbest_refs(lats, theta, asc)
+        for l, sl, ref in zip(lats, E.arc_slices(lats), refs):
+            assert E.tied_entries(ref) >= 2, name
+            # exact sums: the float32 scores are the float64 ones
+            s64 = E.score64(l, theta, None if asc is None else asc[sl])
+            assert [float(x) for x in ref["best"][:ref["n_paths"]]] == [float(s64[p].sum()) for p in ref["arcs"]]
+        if name.startswith("star"):
+            assert np.all(refs[0]["best"] == np.float32(-1.0))
+            assert [p[1] for p in refs[0]["arcs"]] == list(range(1, 65))
+        if name == "funnel":
+            for pos in (1, 3):
+                assert len({E.sweep_chunk(lats[0], p[pos]) for p in refs[0]["arcs"]}) >= 2
+
+
+def test_sweep_chunk():
+    l = E.star()
+    assert [E.sweep_chunk(l, a) for a in (1, 64, 65, 127, 128, 190, 191, 200)] == [0, 0, 1, 1, 2, 2, 3, 3]
+
+
+def test_few_paths_case_has_between_one_and_63_finite_paths():
+    lats, theta, b, n = E.few_paths_case()
+    assert 0 < n < 20 and n == 14
+    for i, l in enumerate(lats):
+        if i != b:
+            full = R.count_finite_paths(l.n_rows, l.src, l.dst, E.score64(l, theta[i]), l.n_rows - 1)
+            assert full == R.count_finite_paths(l.n_rows, l.src, l.dst, np.zeros(l.n_arcs), l.n_rows - 1)
+
+
+def test_dead_label_and_no_path_cases_on_the_reference():
+    lats = E.weighted_batch()
+    theta = E.dead_label_theta()
+    for l, ref in zip(lats, E.kbest_refs(lats, theta)):
+        assert np.isin(l.label, E.DEAD).sum() > 120 and ref["n_paths"] == 64
+        assert not any(np.isin(l.label[p], E.DEAD).any() for p in ref["arcs"])
+        assert l.label[E.reachable_dead_arc(l)] in E.DEAD
+    lats, theta = E.no_path_case(True)
+    assert [r["n_paths"] == 0 for r in E.kbest_refs(lats, theta, k=7)] == [False, True, False, True, False]
 
 
 # ----------------------------------------------------------------------------- the C entry point

@@ -45,6 +45,8 @@
  *                                      evaluate/rerank.py reranks (read from an outside system
  *                                      there) and the exact form of JointProb.forward's "best of
  *                                      K samples" (lightning.py:474-479)
+ *   nfst_beam_step, nfst_beam_backtrack  lattice-constrained beam search for path-dependent scorers: the
+ *                                      deterministic twin of the proposal sampler's step
  *
  * Conventions
  *   - plain C: pointers and sizes only, no C++/torch types.
@@ -507,6 +509,45 @@ int64_t nfst_kbest_ws_bytes(const nfst_batch *lat, int32_t k);
 int nfst_kbest(const nfst_batch *lat, const nfst_scores *scores, int32_t k, void *ws, int64_t ws_bytes, float *best,
                int32_t *paths, int32_t *path_arcs, int32_t *lengths, int32_t *n_paths, int32_t max_len, int32_t pad,
                int32_t *status, void *stream);
+
+/*
+ * One step of lattice-constrained beam search (DESIGN.md sections 2 and 4.9) for N = n_lattices * k slots: slot n
+ * belongs to lattice n / k and has rank n % k in its beam, 1 <= k <= 64.  Reads the canonical arrays only (row_ptr,
+ * arc_label, arc_dst, arc_w): any batch, compact or not, with or without chunked programs, with the same bits.
+ * Inputs (device): state [N] int64, the state after inp was consumed; inp [N] int64, the previous mark; beam_score [N]
+ * float32, -inf marks a dead slot; scores [N, vocab] float32, the network's outputs for this step as the caller
+ * normalised them; lookahead [total_rows] float32 (optional), row-indexed.
+ * A candidate is (j, a): a live slot j (beam_score > -inf, state in range) and a canonical arc a out of its state with
+ * label l, legal under the rules of nfst_proposal_step: l != bos; l == pad exactly when inp[j] is eos or pad; with
+ * has_to_end a slot that has not ended takes eos only.  All arithmetic is float32, in this order:
+ *     c = beam_score[j] + (x + w_a),   x = scores[j, l] (0.0f for l == pad: the pad entry is never read),
+ *                                      w_a = arc_w[a] if weighted, else 0.0f
+ *     r = c + lookahead[row_off + dst_a]   (r = c without lookahead)
+ * and the candidate is dropped unless c > -inf and r > -inf (NaN is dropped too).  Candidates are ordered by (r desc,
+ * j asc, l asc), -0.0 and +0.0 alike; lattices are deterministic, so the order is total and the result is determined.
+ * Outputs (device), rank i < min(k, candidates) of every lattice: score = c (not r), parent = j (int32, the rank in the
+ * lattice's beam), symbol = l, next_state = dst_a; the remaining ranks get -inf, -1, pad, 0.  n_candidates [B]
+ * (optional): the candidates before truncation.  n_open (optional, one device word, zeroed by the caller) receives the
+ * number of output slots that are live with a symbol other than pad: zero means every hypothesis has ended or died.
+ * The outputs may be the inputs' buffers.  A lattice's candidates (at most k * its largest out-degree) are kept in LDS
+ * up to nfst_beam_lds_candidates() of them and computed again in every pass of the selection beyond that.
+ * k < 1, null required pointers or a pad outside the vocabulary: NFST_ERR_ARG; k > 64: NFST_ERR_LIMIT; all on the host
+ * before any launch.
+ */
+int32_t nfst_beam_lds_candidates(void);
+int nfst_beam_step(const nfst_batch *lat, const int64_t *state, const int64_t *inp, const float *beam_score, const float *scores,
+                   const float *lookahead, int32_t pad, int32_t bos, int32_t eos, int32_t has_to_end, int32_t k, float *score,
+                   int32_t *parent, int64_t *symbol, int64_t *next_state, int32_t *n_candidates, int32_t *n_open, void *stream);
+
+/*
+ * The paths of a finished beam search: parent and symbol [T, N] (rows of N = n_lattices * k, as nfst_beam_step wrote
+ * them step by step), score [N] the scores of the last step, n_steps <= max_len the steps to follow.  Slot n follows
+ * its parents from step n_steps - 1 back to step 0; paths [n_lattices, k, max_len] int32 receives its marks other than
+ * pad, in order, right-padded with pad, lengths [n_lattices, k] their number.  A slot whose score is -inf gets length 0.
+ * k < 1, n_steps > max_len or null pointers: NFST_ERR_ARG; k > 64: NFST_ERR_LIMIT.
+ */
+int nfst_beam_backtrack(const int32_t *parent, const int64_t *symbol, const float *score, int32_t n_steps, int32_t n_lattices,
+                        int32_t k, int32_t max_len, int32_t pad, int32_t *paths, int32_t *lengths, void *stream);
 
 /*
  * Arc slack, the max-plus counterpart of the arc posteriors, and beam masks (DESIGN.md sections 2 and 4.7).  A path

@@ -37,6 +37,7 @@ using namespace nfst_tile;
 #include "chunk_kernels.h"
 #include "expect_kernels.h"
 #include "kbest_kernels.h"
+#include "beam_kernels.h"
 #include "slack_kernels.h"
 #include "intersect_kernels.h"
 
@@ -908,6 +909,35 @@ int nfst_kbest(const nfst_batch *lat, const nfst_scores *scores, int32_t k, void
     return rc;
   return launch(k_kbest_walk, dim3(lat->n_lattices), dim3(64), 0, st, *lat, (int)k, w, best, paths, path_arcs, lengths, n_paths,
                 (int)max_len, (int)pad, status);
+}
+
+// ------------------------------------------------------------------ beam search (beam_kernels.h)
+int32_t nfst_beam_lds_candidates(void) { return kBeamLdsCand; }
+
+int nfst_beam_step(const nfst_batch *lat, const int64_t *state, const int64_t *inp, const float *beam_score, const float *scores,
+                   const float *lookahead, int32_t pad, int32_t bos, int32_t eos, int32_t has_to_end, int32_t k, float *score,
+                   int32_t *parent, int64_t *symbol, int64_t *next_state, int32_t *n_candidates, int32_t *n_open, void *stream) {
+  int rc = check_batch(lat);
+  if (rc) return rc;
+  if (k < 1) return NFST_ERR_ARG;
+  if (k > kBeamMaxK) return NFST_ERR_LIMIT;
+  if (!state || !inp || !beam_score || !scores || !score || !parent || !symbol || !next_state) return NFST_ERR_ARG;
+  if (pad < 0 || pad >= lat->vocab) return NFST_ERR_ARG;
+  const int64_t all = (int64_t)k * lat->vocab;  // a slot has at most one arc per label
+  const int cap = (int)(all < kBeamLdsCand ? all : kBeamLdsCand);
+  const BeamIn in{state, inp, beam_score, scores, lookahead, (int)pad, (int)bos, (int)eos, (int)has_to_end, (int)k};
+  const BeamOut out{score, parent, symbol, next_state, n_candidates, n_open};
+  return launch(k_beam_step, dim3(lat->n_lattices), dim3(kBeamThreads), (int64_t)cap * 8, (hipStream_t)stream, *lat, in, out, cap);
+}
+
+int nfst_beam_backtrack(const int32_t *parent, const int64_t *symbol, const float *score, int32_t n_steps, int32_t n_lattices,
+                        int32_t k, int32_t max_len, int32_t pad, int32_t *paths, int32_t *lengths, void *stream) {
+  if (k < 1 || n_lattices < 1 || n_steps < 0 || max_len < 1 || n_steps > max_len) return NFST_ERR_ARG;
+  if (k > kBeamMaxK) return NFST_ERR_LIMIT;
+  if (!score || !paths || !lengths || (n_steps > 0 && (!parent || !symbol))) return NFST_ERR_ARG;
+  const int64_t n = (int64_t)n_lattices * k;
+  return launch(k_beam_backtrack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, parent, symbol, score,
+                (int)n_steps, (int)n_lattices, (int)k, (int)max_len, (int)pad, paths, lengths);
 }
 
 // ------------------------------------------------------------------ arc slack and beam masks (slack_kernels.h)

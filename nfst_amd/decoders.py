@@ -1,0 +1,112 @@
+"""Lattice-constrained beam search for path-dependent scorers.
+
+The exact decoders (``ops.viterbi``, ``ops.k_best``) need a score that decomposes over arcs.  A recurrent or
+autoregressive scorer (the reference's ``StaticRNNScorer``, its GPT-2 wrapper, the learned proposal) gives weights that
+depend on the whole prefix; for those ``BeamDecoder`` keeps k hypotheses per lattice and runs the loop of
+``ProposalSampler.stateful_sample`` with the sampler's draw replaced by "the best k of all legal extensions": one
+``score_fn`` call and one fused ``nfst_beam_step`` launch per mark (DESIGN.md sections 2 and 4.9).
+"""
+from __future__ import annotations
+
+from typing import NamedTuple, Optional, Union
+
+import torch
+
+from . import ops
+from .scorers import LatticeScorer
+
+
+class BeamResult(NamedTuple):
+    paths: torch.Tensor    # [B, k, T] int32: marks after the implicit bos up to eos, right-padded with pad
+    lengths: torch.Tensor  # [B, k] int32 marks per path (0 on empty ranks)
+    scores: torch.Tensor   # [B, k] float32: sum of the step scores along the path, best first; -inf on empty ranks
+    n_steps: int           # steps that were kept (the last one is the first at which every hypothesis had ended or died)
+
+
+def reorder_by_parent(hx, index: torch.Tensor):
+    """``hx`` (a tensor with the slots along dim 0, or a tuple / list of such, or None) gathered by ``index`` [N]."""
+    if hx is None:
+        return None
+    if isinstance(hx, (tuple, list)):
+        return type(hx)(reorder_by_parent(h, index) for h in hx)
+    return hx.index_select(0, index)
+
+
+class BeamDecoder:
+    """``score_fn(hx, inp) -> (new_hx, scores [N, V])`` is the network, as for ``ProposalSampler``: ``inp`` [N] int64 are
+    the marks consumed last (bos first), ``scores`` what the step adds per next mark -- log probabilities if the scores
+    are to be comparable across lengths; the decoder fuses no softmax.  N = B * k slots, slot n = rank n % k of lattice
+    n // k.  After every step ``reorder_fn(new_hx, parent)`` moves the recurrent state to the survivors: ``parent`` [N]
+    int64 is the global slot each survivor extends (an empty rank names itself); the default gathers along dim 0 and
+    walks tuples.  ``sync_every``: steps between two looks at the device-side "every hypothesis has ended" counters."""
+
+    def __init__(self, model: LatticeScorer, score_fn, reorder_fn=None, sync_every: int = 8):
+        self.model = model
+        self.score_fn = score_fn
+        self.reorder_fn = reorder_by_parent if reorder_fn is None else reorder_fn
+        self.sync_every = max(1, int(sync_every))
+
+    def _lookahead(self, lookahead) -> Optional[torch.Tensor]:
+        m = self.model
+        lat = m._lat()
+        if lookahead is None:
+            return None
+        if isinstance(lookahead, str):
+            if lookahead == "viterbi":  # best score from the row to the sink under theta; -inf rows stay -inf
+                return ops.arc_slack(lat, m.theta.detach(), want_rows=True).vbeta
+            if lookahead == "log_beta":
+                return m.compute_log_beta()[:: m.k].reshape(-1).contiguous()
+            raise ValueError(f"lookahead must be None, 'viterbi', 'log_beta' or a [total_rows] tensor, not {lookahead!r}")
+        return lookahead.detach().to(device=lat.device, dtype=torch.float32).reshape(-1)
+
+    @torch.no_grad()
+    def decode(self, k: int, lookahead: Union[None, str, torch.Tensor] = None, max_len: Optional[int] = None, hx=None) -> BeamResult:
+        """Beam search with k hypotheses per lattice.  ``lookahead``: a row-indexed [total_rows] value added to a
+        candidate's score for ranking only -- ``"viterbi"`` the exact best completion under the scorer's ``theta``
+        (with a scorer that is ``theta`` itself, k = 1 then finds the best path), ``"log_beta"`` the scorer's
+        ``compute_log_beta()``.  ``max_len`` replaces the scorer's ``max_length``: there are ``max_len + 1`` steps and
+        on the last one only eos (or pad, for a hypothesis that has ended) is legal; a hypothesis that cannot end
+        there dies.  ``hx`` is the recurrent state handed to the first ``score_fn`` call (slots along dim 0)."""
+        m = self.model
+        lat = m._lat()
+        dev = lat.device
+        B = lat.n_lattices
+        N = B * k
+        look = self._lookahead(lookahead)
+        L = m.max_length if max_len is None else int(max_len)
+        T = L + 1
+        base = torch.arange(N, device=dev, dtype=torch.int64)
+        base -= base % k  # first slot of the lattice
+        own = torch.arange(N, device=dev, dtype=torch.int64)
+        inp = torch.full((N,), m.__bos__, dtype=torch.int64, device=dev)
+        # the implicit bos is consumed first, unscored, as the sampler does
+        state = ops.step(lat, torch.zeros(N, dtype=torch.int64, device=dev), inp, k=k)
+        score = torch.full((N,), float("-inf"), dtype=torch.float32, device=dev)
+        score[::k] = 0.0
+        # the outputs of all steps live in buffers allocated once; n_open[t] is read back every sync_every steps
+        score_all = torch.empty((T, N), dtype=torch.float32, device=dev)
+        parent_all = torch.empty((T, N), dtype=torch.int32, device=dev)
+        sym_all = torch.empty((T, N), dtype=torch.int64, device=dev)
+        nxt_all = torch.empty((T, N), dtype=torch.int64, device=dev)
+        ncand_all = torch.empty((T, B), dtype=torch.int32, device=dev)
+        n_open = torch.zeros(T, dtype=torch.int32, device=dev)
+        CHECK = self.sync_every
+        n_steps = 0
+        for t in range(T):
+            hx, scores = self.score_fn(hx, inp)
+            r = ops.beam_step(lat, state, inp, score, scores, k, lookahead=look, pad=m.__pad__, bos=m.__bos__, eos=m.__eos__,
+                              has_to_end=(t + 1) > L, out=(score_all[t], parent_all[t], sym_all[t], nxt_all[t], ncand_all[t]),
+                              n_open=n_open[t:t + 1])
+            p = r.parent.to(torch.int64)
+            hx = self.reorder_fn(hx, torch.where(p >= 0, base + p, own))
+            state, inp, score = r.next_state, r.symbol, r.score
+            n_steps = t + 1
+            if n_steps % CHECK == 0 or n_steps == T:
+                first = n_steps - (CHECK if n_steps % CHECK == 0 else n_steps % CHECK)
+                ended = (n_open[first:n_steps] == 0).nonzero()
+                if ended.numel():
+                    n_steps = first + int(ended[0]) + 1  # the first step after which nothing is open; later steps are dropped
+                    break
+        final = score_all[n_steps - 1]
+        paths, lengths = ops.beam_backtrack(parent_all, sym_all, final, B, k, n_steps=n_steps, max_len=T, pad=m.__pad__)
+        return BeamResult(paths, lengths, final.reshape(B, k).clone(), n_steps)

@@ -839,6 +839,94 @@ def proposal_step(lat: LatticeBatch, state: torch.Tensor, scores: torch.Tensor, 
     return ProposalStep(*_ProposalStep.apply(lat, scores, values, cfg))
 
 
+class BeamStep(NamedTuple):
+    score: torch.Tensor         # [N] float32: the survivors' scores c (without the look-ahead), -inf on empty ranks
+    parent: torch.Tensor        # [N] int32: the rank in the lattice's beam the survivor extends, -1 on empty ranks
+    symbol: torch.Tensor        # [N] int64: its new mark (pad on empty ranks)
+    next_state: torch.Tensor    # [N] int64: the state after the mark (0 on empty ranks)
+    n_candidates: torch.Tensor  # [B] int32: candidates before the cut to k
+
+
+def beam_lds_candidates() -> int:
+    """The candidates of one lattice that ``nfst_beam_step`` keeps in LDS; beyond that (or beyond k * vocab, if smaller)
+    every pass of its selection computes them again."""
+    return int(lib.nfst_beam_lds_candidates())
+
+
+def beam_step(lat: LatticeBatch, state: torch.Tensor, inp: torch.Tensor, beam_score: torch.Tensor, scores: torch.Tensor,
+              k: int, lookahead: Optional[torch.Tensor] = None, pad: int = 0, bos: int = 1, eos: int = 2,
+              has_to_end: bool = False, out=None, n_open: Optional[torch.Tensor] = None) -> BeamStep:
+    """One step of lattice-constrained beam search (``nfst_beam_step``, DESIGN.md sections 2 and 4.9): the deterministic
+    twin of ``proposal_step``.  N = B * k slots, slot n = rank n % k of lattice n // k.  ``state`` [N] is the state after
+    ``inp`` [N], the previous mark, was consumed; ``beam_score`` [N] float32 (-inf: a dead slot); ``scores`` [N, V] the
+    network's outputs for this step, normalised by the caller; ``lookahead`` [total_rows] (optional) is added to a
+    candidate's score for ranking only.  Every live slot expands by the legal marks of its state (the bos/pad/eos rules
+    of ``proposal_step``); a candidate scores ``c = beam_score + (scores[j, l] + arc_w)`` (pad scores 0) and the best k
+    per lattice by (c + lookahead desc, slot asc, mark asc) survive.  ``out`` = (score, parent, symbol, next_state,
+    n_candidates) tensors of a previous call or rows of buffers allocated once per search; ``n_open``: an int32 device
+    word (zeroed by the caller) that receives the number of survivors whose mark is not ``pad`` (zero: every hypothesis
+    has ended or died).  Not differentiable: re-score the paths with ``path_logprob``."""
+    _need_gpu(lat)
+    dev = lat.device
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise ValueError(f"k must be an int, not {k!r}")
+    N, B = lat.n_lattices * max(k, 0), lat.n_lattices
+
+    def arg(x, dtype, shape, name):
+        if not isinstance(x, torch.Tensor) or x.dtype != dtype or tuple(x.shape) != shape:
+            raise ValueError(f"{name} must be a {dtype} tensor of shape {list(shape)}")
+        return x.to(device=dev).contiguous()
+
+    state, inp = arg(state, torch.int64, (N,), "state"), arg(inp, torch.int64, (N,), "inp")
+    beam_score = arg(beam_score, torch.float32, (N,), "beam_score")
+    scores = arg(scores.detach(), torch.float32, (N, lat.vocab), "scores")
+    if lookahead is not None:
+        lookahead = arg(lookahead.detach(), torch.float32, (lat.total_rows,), "lookahead")
+    if n_open is not None and (n_open.dtype != torch.int32 or n_open.numel() != 1 or n_open.device != dev):
+        raise ValueError("n_open must be one int32 word on the batch's device")
+    want = ((torch.float32, N), (torch.int32, N), (torch.int64, N), (torch.int64, N), (torch.int32, B))
+    if out is not None:
+        if len(out) != 5 or any(o.dtype != d or o.shape != (n,) or o.device != dev or not o.is_contiguous() for o, (d, n) in zip(out, want)):
+            raise ValueError("out must be (score float32 [N], parent int32 [N], symbol int64 [N], next_state int64 [N], "
+                             "n_candidates int32 [B]) on the batch's device")
+    else:
+        out = tuple(torch.empty(n, dtype=d, device=dev) for d, n in want)
+    check(lib.nfst_beam_step(C.byref(lat.c_struct()), _ptr(state), _ptr(inp), _ptr(beam_score), _ptr(scores), _ptr(lookahead),
+                             int(pad), int(bos), int(eos), int(bool(has_to_end)), int(k), *(_ptr(o) for o in out), _ptr(n_open),
+                             _stream()), "nfst_beam_step")
+    return BeamStep(*out)
+
+
+def beam_backtrack(parent: torch.Tensor, symbol: torch.Tensor, score: torch.Tensor, n_lattices: int, k: int,
+                   n_steps: Optional[int] = None, max_len: Optional[int] = None, pad: int = 0):
+    """``(paths [B, k, max_len] int32, lengths [B, k] int32)`` of a finished beam search (``nfst_beam_backtrack``):
+    ``parent`` (int32) and ``symbol`` (int64) [T, B * k] as ``beam_step`` wrote them step by step, ``score`` [B * k] of
+    the last step followed.  Every final slot follows its parents from step ``n_steps - 1`` (default T) back to step 0;
+    its marks other than ``pad`` are written in order and the row is right-padded with ``pad`` (``max_len`` defaults to
+    T).  A slot whose score is -inf gets length 0."""
+    if parent.device.type != "cuda":
+        raise RuntimeError("nfst_amd: beam_backtrack runs on the MI355X only (no CPU fallback)")
+    dev = parent.device
+    N = int(n_lattices) * int(k)
+    if parent.dim() != 2 or parent.shape[1] != N or parent.dtype != torch.int32:
+        raise ValueError("parent must be int32 [T, n_lattices * k]")
+    T = parent.shape[0]
+    if symbol.shape != parent.shape or symbol.dtype != torch.int64 or symbol.device != dev:
+        raise ValueError("symbol must be int64 [T, n_lattices * k] on parent's device")
+    if score.shape != (N,) or score.dtype != torch.float32 or score.device != dev:
+        raise ValueError("score must be float32 [n_lattices * k] on parent's device")
+    n_steps = T if n_steps is None else int(n_steps)
+    max_len = max(T, 1) if max_len is None else int(max_len)
+    if not 0 <= n_steps <= T:
+        raise ValueError(f"n_steps must lie in [0, {T}]")
+    parent, symbol, score = parent.contiguous(), symbol.contiguous(), score.contiguous()
+    paths = torch.empty((n_lattices, k, max_len), dtype=torch.int32, device=dev)
+    lengths = torch.empty((n_lattices, k), dtype=torch.int32, device=dev)
+    check(lib.nfst_beam_backtrack(_ptr(parent), _ptr(symbol), _ptr(score), n_steps, int(n_lattices), int(k), max_len, int(pad),
+                                  _ptr(paths), _ptr(lengths), _stream()), "nfst_beam_backtrack")
+    return paths, lengths
+
+
 class NeuralBeta(NamedTuple):
     log_beta: torch.Tensor   # [total_rows] natural log of the reference's beta
     beta_hat: torch.Tensor   # [total_rows, H]

@@ -86,6 +86,13 @@ class LatticeScorer(torch.nn.Module):
         differentiable in theta)."""
         return ops.k_best(self._lat(), self.theta, k, max_len=max_len, pad=self.__pad__)
 
+    def beam_decoder(self, score_fn, reorder_fn=None, sync_every: int = 8):
+        """A ``decoders.BeamDecoder`` over the scorer's lattice for a path-dependent ``score_fn(hx, inp) -> (hx,
+        scores [N, V])``: ``.decode(k, lookahead=...)`` keeps k hypotheses per lattice."""
+        from .decoders import BeamDecoder
+
+        return BeamDecoder(self, score_fn, reorder_fn=reorder_fn, sync_every=sync_every)
+
     def prune(self, beam, **pack_opts) -> "ops.PruneResult":
         """The scorer's lattice cut down to the arcs within ``beam`` of each lattice's best path under ``theta``
         (``ops.prune``): ``(lat, arc_map, n_kept, best)``.  The scorer keeps its own lattice; hand the result to

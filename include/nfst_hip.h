@@ -47,6 +47,9 @@
  *                                      K samples" (lightning.py:474-479)
  *   nfst_beam_step, nfst_beam_backtrack  lattice-constrained beam search for path-dependent scorers: the
  *                                      deterministic twin of the proposal sampler's step
+ *   nfst_positional, nfst_positional_viterbi  exact sweeps under scores that depend on the position of an arc on the
+ *                                      path ([B, T, V] logits) and under a length budget: what the sampler side only
+ *                                      truncates (emission_mask(has_to_end = length > max_length), NFST_ERR_LENGTH)
  *
  * Conventions
  *   - plain C: pointers and sizes only, no C++/torch types.
@@ -624,6 +627,69 @@ int nfst_intersect_count(const nfst_batch *lat, const int8_t *delta_t, int64_t d
 int nfst_intersect_write(const nfst_batch *lat, const int8_t *delta_t, int64_t delta_stride, int32_t n_q, void *ws,
                          int64_t ws_bytes, const int64_t *out_row_off, const int64_t *out_arc_off, int32_t *src, int32_t *label,
                          int32_t *dst, int64_t *arc_map, int32_t *arc_q, int32_t *row_state, int32_t *row_q, void *stream);
+
+/*
+ * Position-dependent scores: time-synchronous sweeps (DESIGN.md sections 2 and 4.10).  A path pi = a_0 .. a_{L-1} runs
+ * from state 0 to the sink over canonical arcs; self loops (the sink's pad loop) are on no path.  Arc a_t is "at
+ * position t": the bos arc at position 0, the eos arc at L - 1.  The caller gives T >= 1 positions and optionally pos
+ * (device float32): one [T, V] table (pos_stride = 0) or [B, T, V] (pos_stride = T * V).  With s_a the arc log weight of
+ * nfst_scores,
+ *     S_T(pi) = sum_t ( s_{a_t} + pos[b, t, label(a_t)] ),     Z_T = sum over the paths with L <= T of exp S_T(pi).
+ * Paths of more than T arcs are not counted.  pos = NULL: the term is absent (no add happens, it is not "zeros").  An
+ * entry of pos may be -inf: the arc has weight zero at that position (how a caller forces or forbids a mark at a
+ * position).  Every label of a path is read, bos and eos included; the pad label lies on no path, so pos[.., pad] enters
+ * no output (it may hold anything).  NaN or +inf in pos is the caller's business: nothing scans for it.
+ *
+ * nfst_positional (sum-product).  Outputs on the device, optional unless stated, every element written exactly once
+ * (no zeroing by the caller):
+ *     logz64 [B] (required), logz32 [B]   log Z_T
+ *     len_logz [B, T + 1] float64         entry L = log of the total weight of the paths of exactly L arcs, entry 0 = -inf;
+ *                                         logsumexp over L = logz64, len_logz - logz64 = the length distribution under
+ *                                         truncation at T
+ *     pos_post [B, T, V] float32          sum over the arcs with label l of P(that arc is at position t)
+ *                                         = d log Z_T / d pos[b, t, l]; zeros at positions no path reaches.  Summed as
+ *                                         integers in units of 2^-44 (label_post of nfst_expectation): independent of
+ *                                         the order, bit-identical from launch to launch
+ *     arc_post [total_arcs] float32       sum_t P(arc a is at position t); 0 on self loops
+ * Identities: sum_l pos_post[b, t, l] = P(L > t); pos_post[b, 0, bos] = 1; sum_t pos_post[b, t, l] = the sum of arc_post
+ * over the arcs with label l; with pos = NULL and T >= the lattice's NFST_META_DEPTH logz64 and arc_post are
+ * nfst_forward_backward's log Z and posterior.  A lattice without a path of finite score and L <= T gets logz = -inf,
+ * len_logz = -inf and zero posteriors (never a NaN) and does not disturb the other lattices (nfst_expectation's rule).
+ * Arithmetic: (float64 mantissa, int32 exponent) throughout, for every T (float32 mantissas repeat one rounding error
+ * per label at every position); fixed summation order, no float atomics: every output is bit-identical from launch to
+ * launch and for every packing of the same lattices.
+ *
+ * nfst_positional_viterbi (max-plus).  Plain float32 in a fixed order, from position T backwards:
+ *     vb_T(sink) = 0, vb_T(s) = -inf for every other s;  vb_t(sink) = 0 for every t
+ *     vb_t(s) = max over the out-arcs of s without self loops of  c = e_a + ((theta[l] + pos[b, t, l]) + vb_{t+1}(dst_a)),
+ *     e_a as in nfst_kbest; without pos the inner add is absent: c = e_a + (theta[l] + vb_{t+1}(dst_a))
+ *     best[b] = vb_0(0)
+ * The path is read forwards from state 0: at position t the out-arc that attains vb_t(state), the smallest canonical arc
+ * on exact ties (nfst_kbest's rule).  paths [B, T] int32 labels padded with `pad`, path_arcs (optional) [B, T] padded
+ * with -1, lengths [B]; best = -inf gives length 0.  Without pos and with T >= depth: nfst_kbest's entry 0 bit for bit.
+ *
+ * Both read the canonical arrays only (row_ptr, arc_src, arc_dst, arc_label, arc_w): any batch, compact or not, with or
+ * without chunked programs.  One workgroup per lattice advances all its states one position per step, T steps per
+ * direction.
+ * ws: device workspace of nfst_positional_ws_bytes(lat, T, flags) bytes (16-byte aligned, overwritten); every part is
+ * rounded up to 256 bytes.  flags = 0 (log Z only): 12 bytes per arc.  NFST_POS_WS_POSTERIOR (any of len_logz, pos_post,
+ * arc_post): + 12 * (T + 1) * total_rows -- EVERY beta row of every position is stored, (T + 1) * rows values per
+ * lattice: this is the cost of the op -- + 20 bytes per arc + 4 per row.  NFST_POS_WS_VITERBI: 12 per arc +
+ * 4 * (T + 1) * total_rows.
+ * LDS: nfst_positional 24 max_rows + 20 vocab + 4112 bytes, nfst_positional_viterbi 8 max_rows + 4 vocab + 16 bytes; more
+ * than 160 KiB returns NFST_ERR_LIMIT.  When 4 (max_rows + 1 + arcs of the largest lattice) + 16 more bytes fit, the arc
+ * records are staged in LDS; otherwise the step loops read the canonical arrays (the same bits, slower steps).  Null required pointers, T < 1, a stride that is neither 0 nor T * vocab or a
+ * short workspace return NFST_ERR_ARG.  All checks run on the host before any launch.
+ */
+#define NFST_POS_WS_POSTERIOR 1
+#define NFST_POS_WS_VITERBI 2
+int64_t nfst_positional_ws_bytes(const nfst_batch *lat, int32_t T, int32_t flags);
+int nfst_positional(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T, void *ws,
+                    int64_t ws_bytes, double *logz64, float *logz32, double *len_logz, float *pos_post, float *arc_post,
+                    void *stream);
+int nfst_positional_viterbi(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T,
+                            void *ws, int64_t ws_bytes, float *best, int32_t *paths, int32_t *path_arcs, int32_t *lengths,
+                            int32_t pad, void *stream);
 
 /*
  * Viterbi: best[b] = max path score (float32), paths [B, max_len] int32 labels

@@ -158,6 +158,9 @@ def _load():
         "nfst_intersect_ws_bytes": (i64, [BP, i32]),
         "nfst_intersect_count": (C.c_int, [BP, vp, i64, vp, i64, i32, vp, i64, vp, vp, vp]),
         "nfst_intersect_write": (C.c_int, [BP, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "nfst_positional_ws_bytes": (i64, [BP, i32, i32]),
+        "nfst_positional": (C.c_int, [BP, SP, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp]),
+        "nfst_positional_viterbi": (C.c_int, [BP, SP, vp, i64, i32, vp, i64, vp, vp, vp, vp, i32, vp]),
         "nfst_path_logprob": (C.c_int, [vp, vp, i64, i32, i32, i32, i32, i32, i32, f32, i32, f32, i32, vp, vp]),
         "nfst_path_logprob_backward": (C.c_int, [vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, f32, i32, f32, i32, vp, vp]),
         "nfst_iwae": (C.c_int, [vp, vp, i32, i32, vp, vp, vp]),

@@ -95,7 +95,7 @@ def check_resources(res: dict) -> list:
         if fused and (r.get("agprs") != 32 or r.get("vgpr_spill", 0) != 0):
             bad.append(f"{name}: fused sweep needs AGPRs == 32 and no VGPR spill, got AGPRs {r.get('agprs')}, "
                        f"VGPR spill {r.get('vgpr_spill')}")
-        if (re.search(r"k_(forward_backward|backward|viterbi_tw)<", name) or re.search(r"k_(expect|kbest)_sweep\b|k_arc_slack\b|k_beam_step\b", name)) \
+        if (re.search(r"k_(forward_backward|backward|viterbi_tw)<", name) or re.search(r"k_(expect|kbest)_sweep\b|k_arc_slack\b|k_beam_step\b|k_positional", name)) \
                 and r.get("vgpr_spill", 0) != 0:
             bad.append(f"{name}: VGPR spill {r.get('vgpr_spill')} in a sweep kernel")
         if not fused and re.search(r"k_(forward_backward|backward)<", name) and r.get("agprs", 0) != 0:

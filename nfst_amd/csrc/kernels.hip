@@ -40,6 +40,7 @@ using namespace nfst_tile;
 #include "beam_kernels.h"
 #include "slack_kernels.h"
 #include "intersect_kernels.h"
+#include "positional_kernels.h"
 
 // ------------------------------------------------------------------ host helpers
 int check_batch(const nfst_batch *lat) {
@@ -977,6 +978,97 @@ int nfst_arc_slack(const nfst_batch *lat, const nfst_scores *scores, const float
 #else
   return launch(k_arc_slack, dim3(lat->n_lattices), dim3(kSlkThreads), lds, st, *lat, *scores, w, (int)kSlkAll, o);
 #endif
+}
+
+// ------------------------------------------------------------------ position-dependent scores (positional_kernels.h)
+// workspace: the weights of the per-arc extras; with NFST_POS_WS_POSTERIOR the stored beta rows ((T + 1) rows of
+// (float64, int32) per row of the batch), the by-destination order and the per-arc sums; with NFST_POS_WS_VITERBI the
+// stored max-plus rows
+static int64_t pos_ws_layout(const nfst_batch *lat, int64_t T, int flags, char *base, PosWs *w) {
+  const int64_t TR = lat->total_rows, A = lat->total_arcs, B = lat->n_lattices, rows = (T + 1) * TR;
+  WsCarve c{base};
+  PosWs r = {};
+  r.ewm = (double *)c.take(8 * A);
+  r.ewe = (int *)c.take(4 * A);
+  if (flags & NFST_POS_WS_POSTERIOR) {
+    r.bm = (double *)c.take(8 * rows);
+    r.be = (int *)c.take(4 * rows);
+    r.in_ptr = (int *)c.take(4 * (TR + B));
+    r.in_tmp = (int *)c.take(4 * A);
+    r.in_rec = (int2 *)c.take(8 * A);
+    r.acc = (double *)c.take(8 * A);
+  }
+  if (flags & NFST_POS_WS_VITERBI) r.vb = (float *)c.take(4 * rows);
+  if (w) *w = r;
+  return c.size;
+}
+static int pos_check(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T, const void *ws,
+                     int64_t ws_bytes, int flags) {
+  int rc = check_batch(lat);
+  if (rc) return rc;
+  if ((rc = check_scores(lat, scores))) return rc;
+  if (T < 1) return NFST_ERR_ARG;
+  if (pos && pos_stride != 0 && pos_stride != (int64_t)T * lat->vocab) return NFST_ERR_ARG;
+  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < pos_ws_layout(lat, T, flags, nullptr, nullptr)) return NFST_ERR_ARG;
+  return NFST_OK;
+}
+
+// LDS for the staged arc records (4 bytes per row and per arc of the largest lattice) when they fit beside `lds`
+// bytes, else 0: the step loops then read the canonical arrays
+static int64_t pos_staged_bytes(const nfst_batch *lat, int64_t lds) {
+  const int64_t arcs = max_lattice_arcs(lat);
+  if (arcs <= 0 || arcs >= NFST_BATCH_MAX_ARCS_CAP) return 0;  // (not recorded, or "unknown, large")
+  const int64_t bytes = ((int64_t)lat->max_rows + 1 + arcs) * 4 + 16;
+  return lds + bytes <= kMaxLds ? bytes : 0;
+}
+
+int64_t nfst_positional_ws_bytes(const nfst_batch *lat, int32_t T, int32_t flags) {
+  const int rc = check_batch(lat);
+  if (rc) return rc;
+  if (T < 1 || (flags & ~(NFST_POS_WS_POSTERIOR | NFST_POS_WS_VITERBI))) return NFST_ERR_ARG;
+  return pos_ws_layout(lat, T, flags, nullptr, nullptr);
+}
+
+int nfst_positional(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T, void *ws,
+                    int64_t ws_bytes, double *logz64, float *logz32, double *len_logz, float *pos_post, float *arc_post,
+                    void *stream) {
+  const int need_alpha = len_logz || pos_post || arc_post;
+  const int flags = need_alpha ? NFST_POS_WS_POSTERIOR : 0;
+  int rc = pos_check(lat, scores, pos, pos_stride, T, ws, ws_bytes, flags);
+  if (rc) return rc;
+  if (!logz64) return NFST_ERR_ARG;
+  const int64_t lds = (int64_t)lat->max_rows * 24 + (int64_t)lat->vocab * 20 + kPosThreads * 4 + 16;
+  if (lds > kMaxLds) return NFST_ERR_LIMIT;
+  const int64_t staged = pos_staged_bytes(lat, lds);
+  PosWs w;
+  pos_ws_layout(lat, T, flags, (char *)ws, &w);
+  const PosIn in = {*scores, pos, pos ? pos_stride : 0, (int)T};
+  const PosOut o = {logz64, logz32, len_logz, pos_post, arc_post};
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(lat->n_lattices), block(kPosThreads);
+  if (extras_case(lat, scores))
+    return staged ? launch(k_positional<true, true>, grid, block, lds + staged, st, *lat, in, w, o, need_alpha)
+                  : launch(k_positional<true, false>, grid, block, lds, st, *lat, in, w, o, need_alpha);
+  return staged ? launch(k_positional<false, true>, grid, block, lds + staged, st, *lat, in, w, o, need_alpha)
+                : launch(k_positional<false, false>, grid, block, lds, st, *lat, in, w, o, need_alpha);
+}
+
+int nfst_positional_viterbi(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T,
+                            void *ws, int64_t ws_bytes, float *best, int32_t *paths, int32_t *path_arcs, int32_t *lengths,
+                            int32_t pad, void *stream) {
+  int rc = pos_check(lat, scores, pos, pos_stride, T, ws, ws_bytes, NFST_POS_WS_VITERBI);
+  if (rc) return rc;
+  if (!best || !paths || !lengths) return NFST_ERR_ARG;
+  const int64_t lds = (int64_t)lat->max_rows * 8 + (int64_t)lat->vocab * 4 + 16;
+  if (lds > kMaxLds) return NFST_ERR_LIMIT;
+  const int64_t staged = pos_staged_bytes(lat, lds);
+  PosWs w;
+  pos_ws_layout(lat, T, NFST_POS_WS_VITERBI, (char *)ws, &w);
+  const PosIn in = {*scores, pos, pos ? pos_stride : 0, (int)T};
+  const PosVitOut o = {best, paths, path_arcs, lengths, (int)pad};
+  if (staged)
+    return launch(k_positional_viterbi<true>, dim3(lat->n_lattices), dim3(kPosThreads), lds + staged, (hipStream_t)stream, *lat, in, w, o);
+  return launch(k_positional_viterbi<false>, dim3(lat->n_lattices), dim3(kPosThreads), lds, (hipStream_t)stream, *lat, in, w, o);
 }
 
 // ------------------------------------------------------------------ product with a label automaton (intersect_kernels.h)

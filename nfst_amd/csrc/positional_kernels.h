@@ -1,0 +1,445 @@
+// positional_kernels.h -- time-synchronous sweeps: arc scores that depend on the position of the arc on the path
+// Part of the single translation unit kernels.hip (device code in an anonymous namespace).  DESIGN.md sections 2 and 4.10.
+#pragma once
+
+// A path a_0 .. a_{L-1} from state 0 to the sink takes arc a_t "at position t" and scores it
+//     s_a + pos[b, t, label(a)]          (s_a as nfst_scores defines it; pos optional)
+// Only paths of L <= T arcs count.  Both kernels advance ALL states one position per step (the level-scheduled
+// sweeps cannot: a state of these lattices is reached at many path lengths), one workgroup per lattice, on the
+// canonical arrays only (row_ptr, arc_src, arc_dst, arc_label, arc_w):
+//   k_positional          sum-product: beta_t(s) = total weight of the ways to finish from s with at most T - t arcs,
+//                         backwards in time (log Z_T = log beta_0(0)); on request alpha_t forwards in time over a
+//                         by-destination order built once per launch, with the posteriors of every (position, label)
+//                         and every arc and the weight of every path length
+//   k_positional_viterbi  the same backward pass in max-plus (plain float32), then one thread walks the best path
+// The backward pass is ONE function template over the semiring (PosSum / PosMax), not a copy.
+//
+// Arithmetic of the sum-product kernel: (float64 mantissa, int32 exponent) THROUGHOUT, for every T -- label weights by
+// exp_split64, sums in float64.  float32 mantissas would repeat one rounding error per label at every position
+// (1.5e-5 at 900 levels); this op is bound by its barriers, not by its multiplies (section 4.10),
+// so there is no float32 flavour and no threshold in T.  Per step exp(theta[l] + pos[b, t, l]) is split once per LABEL
+// into an LDS table; the weights of per-arc extras are split once per launch into the workspace: no transcendental per
+// arc and step.
+//
+// A state's arcs are shared by a group of G lanes (G = 1 .. 64, a power of two chosen per lattice from its mean degree);
+// the group's partial sums are combined by butterfly shuffles in a fixed order: no float atomics anywhere, the same bits
+// at every launch and for every packing.
+constexpr int kPosThreads = 1024;
+constexpr int kPosPostBits = kExpPostBits;  // per-label posterior sums in fixed point, as label_post of nfst_expectation
+
+struct PosIn {
+  nfst_scores sc;
+  const float *pos;    // [T, V] (stride 0) or [B, T, V] (stride T * V); nullptr: no position term
+  int64_t pos_stride;
+  int T;
+};
+// the caller's workspace (nfst_positional_ws_bytes); lattice b owns rows (T + 1) * row_off .. of the stored rows
+struct PosWs {
+  double *ewm;   // [total_arcs] weight of the arc's extras (arc_w + arc_scores), mantissa ...
+  int *ewe;      // [total_arcs] ... and exponent (only read when the batch has extras)
+  double *bm;    // [(T + 1) * total_rows] beta_t(s), mantissa ...
+  int *be;       // [(T + 1) * total_rows] ... and exponent
+  int *in_ptr;   // [total_rows + n_lattices] first in-entry of every state (relative to the lattice), then the end
+  int *in_tmp;   // [total_arcs] the in-entries before they are put in canonical order
+  int2 *in_rec;  // [total_arcs] in-entries by (destination, canonical arc): (arc in lattice, src | label << 16)
+  double *acc;   // [total_arcs] per in-entry: sum over t of P(the arc is at position t)
+  float *vb;     // [(T + 1) * total_rows] max-plus rows of k_positional_viterbi
+};
+struct PosOut {
+  double *logz64;
+  float *logz32;
+  double *len_logz;  // [B, T + 1]
+  float *pos_post;   // [B, T, V]
+  float *arc_post;   // [total_arcs]
+};
+struct PosVitOut {
+  float *best;
+  int32_t *paths, *path_arcs, *lengths;
+  int pad;
+};
+
+// ---- the two semirings of the backward pass ---------------------------------------------------------------------
+struct PosSum {  // sum-product in (float64 mantissa, exponent)
+  typedef ME64 V;
+  struct Rows {  // the values of two positions, and the label table of the current step, in LDS
+    double *m;
+    int *e;
+    __device__ __forceinline__ V get(int i) const { return {m[i], e[i]}; }
+    __device__ __forceinline__ void set(int i, V v) const { m[i] = v.m; e[i] = v.e; }
+  };
+  struct Store {  // the stored rows of one lattice in the workspace
+    double *m;
+    int *e;
+    __device__ __forceinline__ void set(size_t i, V v) const { m[i] = v.m; e[i] = v.e; }
+    __device__ __forceinline__ bool on() const { return m != nullptr; }
+  };
+  static __device__ __forceinline__ V zero() { return {0.0, kEZero}; }
+  static __device__ __forceinline__ V one() { return {0.5, 1}; }
+  static __device__ __forceinline__ V label(float th) { return exp_split64((double)th); }
+  static __device__ __forceinline__ V label(float th, float p) { return exp_split64((double)th + (double)p); }
+  static __device__ __forceinline__ V times(V lab, V nxt) { return {lab.m * nxt.m, lab.e + nxt.e}; }
+  static __device__ __forceinline__ void plus(V &acc, V x) {
+    if (x.m != 0.0) {
+      if (x.e > acc.e) { acc.m = __builtin_amdgcn_ldexp(acc.m, acc.e - x.e); acc.e = x.e; }
+      acc.m += __builtin_amdgcn_ldexp(x.m, x.e - acc.e);
+    }
+  }
+  // the same value in both partners of a butterfly stage: the sum is commutative
+  static __device__ __forceinline__ void combine(V &acc, int o) {
+    const double om = __shfl_xor(acc.m, o);
+    const int oe = __shfl_xor(acc.e, o);
+    const int E = max(acc.e, oe);
+    acc.m = __builtin_amdgcn_ldexp(acc.m, acc.e - E) + __builtin_amdgcn_ldexp(om, oe - E);
+    acc.e = E;
+  }
+  static __device__ __forceinline__ V norm(V acc) {
+    const Rec64 r = me_pack64(acc.m, acc.e);
+    return {r.m, r.e};
+  }
+};
+struct PosMax {  // max-plus in plain float32: c = e_a + ((theta[l] + pos[b, t, l]) + vb_{t+1}(dst)), in this order
+  typedef float V;
+  struct Rows {
+    float *v;
+    __device__ __forceinline__ V get(int i) const { return v[i]; }
+    __device__ __forceinline__ void set(int i, V x) const { v[i] = x; }
+  };
+  struct Store {
+    float *v;
+    __device__ __forceinline__ void set(size_t i, V x) const { v[i] = x; }
+    __device__ __forceinline__ bool on() const { return v != nullptr; }
+  };
+  static __device__ __forceinline__ V zero() { return kNegInf; }
+  static __device__ __forceinline__ V one() { return 0.0f; }
+  static __device__ __forceinline__ V label(float th) { return th; }
+  static __device__ __forceinline__ V label(float th, float p) { return th + p; }
+  static __device__ __forceinline__ V times(V lab, V nxt) { return lab + nxt; }
+  static __device__ __forceinline__ void plus(V &acc, V x) { acc = x > acc ? x : acc; }
+  static __device__ __forceinline__ void combine(V &acc, int o) {
+    const float x = __shfl_xor(acc, o);
+    acc = x > acc ? x : acc;
+  }
+  static __device__ __forceinline__ V norm(V acc) { return acc; }
+};
+
+// lanes per state: the largest power of two <= half the mean out-degree, widened while lanes would idle
+__device__ __forceinline__ int pos_group(const Meta &m) {
+  const int n = max(m.n_reach, 1), avg = m.n_dp / n;
+  int g = 1;
+  while (g < 64 && g * 2 <= avg) g <<= 1;
+  while (g < 64 && g < avg && m.n_rows * g * 2 <= kPosThreads) g <<= 1;
+  return g;
+}
+
+// The arcs of the step loops: read from the canonical arrays in HBM / L2, or -- when the lattice's arcs fit next to the
+// value rows (the launcher decides) -- from 4-byte records staged in LDS once per pass, so that a step touches no
+// global memory but the stored rows.  A record is (other state | label << 16): rows < 2^13, labels < 2^15.
+struct PosArcsGlobal {
+  const int32_t *rp, *other, *label;  // rp: the lattice's row pointers (absolute arcs)
+  int a_lo, a_hi;
+  __device__ __forceinline__ int lo(int s) const { return max(rp[s], a_lo); }
+  __device__ __forceinline__ int hi(int s) const { return min(rp[s + 1], a_hi); }
+  __device__ __forceinline__ uint32_t rec(int a) const { return (uint32_t)other[a] | ((uint32_t)label[a] << 16); }
+};
+struct PosArcsLds {
+  const int *rp;         // LDS: first entry of every state, relative to the lattice, then the end
+  const uint32_t *recs;  // LDS
+  int a_lo;
+  __device__ __forceinline__ int lo(int s) const { return rp[s] + a_lo; }
+  __device__ __forceinline__ int hi(int s) const { return rp[s + 1] + a_lo; }
+  __device__ __forceinline__ uint32_t rec(int a) const { return recs[a - a_lo]; }
+};
+// stage the out-arcs of a lattice (before a barrier of the caller)
+__device__ __forceinline__ void pos_stage_out(const nfst_batch &lat, const Meta &m, int b, int *rp_l, uint32_t *recs) {
+  const int32_t *rp = lat.row_ptr + m.row_off + b;
+  const int a_lo = m.arc_off, a_hi = m.arc_off + m.n_arcs;
+  for (int s = threadIdx.x; s <= m.n_rows; s += kPosThreads) rp_l[s] = min(max(rp[s], a_lo), a_hi) - a_lo;
+  for (int i = threadIdx.x; i < m.n_arcs; i += kPosThreads)
+    recs[i] = (uint32_t)lat.arc_dst[a_lo + i] | ((uint32_t)lat.arc_label[a_lo + i] << 16);
+}
+
+// the label table of position t: one entry per label, shared by every arc of the step
+template <class S>
+__device__ __forceinline__ void pos_fill_table(const typename S::Rows &tab, const float *theta, const float *pos_t, int V) {
+  for (int l = threadIdx.x; l < V; l += kPosThreads) tab.set(l, pos_t ? S::label(theta[l], pos_t[l]) : S::label(theta[l]));
+}
+
+// The backward pass, positions T .. 0: val holds two rows of R values (the row of position t is at (t & 1) * R).
+// ext(a) multiplies (adds, in max-plus) the per-arc extras in.  Row t of the lattice goes to `st` when it is on.
+template <class S, class Arcs, class ExtF>
+__device__ __forceinline__ void pos_beta_pass(const nfst_batch &lat, const Meta &m, const Arcs &arcs, const float *theta,
+                                              const float *pos_b, int T, int R, int G, const typename S::Rows &val,
+                                              const typename S::Rows &tab, const typename S::Store &st, ExtF ext) {
+  typedef typename S::V Val;
+  const int tid = threadIdx.x, n = m.n_rows, V = lat.vocab;
+  const int slots = kPosThreads / G, slot = tid / G, gl = tid % G;
+  for (int i = tid; i < n; i += kPosThreads) {
+    const Val v = i == m.sink ? S::one() : S::zero();
+    val.set((T & 1) * R + i, v);
+    if (st.on()) st.set((size_t)T * n + i, v);
+  }
+  if (!pos_b) pos_fill_table<S>(tab, theta, nullptr, V);
+  for (int t = T - 1; t >= 0; --t) {
+    if (pos_b) pos_fill_table<S>(tab, theta, pos_b + (size_t)t * V, V);
+    __syncthreads();  // the table and the row of position t + 1 are complete
+    const int nxt = ((t + 1) & 1) * R, cur = (t & 1) * R;
+    for (int base = 0; base < n; base += slots) {
+      const int s = base + slot;
+      const bool act = s < n && s != m.sink;
+      const int a0 = act ? arcs.lo(s) : 0, a1 = act ? arcs.hi(s) : 0;
+      Val acc = S::zero();
+      for (int a = a0 + gl; a < a1; a += G) {
+        const uint32_t rec = arcs.rec(a);
+        const int d = (int)(rec & 0xffffu);
+        if (d == s) continue;  // self loops are on no path
+        S::plus(acc, ext(a, S::times(tab.get((int)(rec >> 16)), val.get(nxt + d))));
+      }
+      for (int o = 1; o < G; o <<= 1) S::combine(acc, o);
+      if (gl == 0 && s < n) {
+        const Val v = s == m.sink ? S::one() : S::norm(acc);
+        val.set(cur + s, v);
+        if (st.on()) st.set((size_t)t * n + s, v);
+      }
+    }
+    __syncthreads();  // (the next step overwrites the table and the row of position t + 1)
+  }
+}
+
+// LDS: two rows of (float64, int32) values, the label table (float64, int32), the label histogram (64-bit) and one
+// int per thread for the prefix sums: 24 max_rows + 20 vocab + 4 kPosThreads bytes.
+// STAGED: + 4 (max_rows + 1) + 4 (arcs of the largest lattice) bytes for the arc records.
+template <bool EXTRA, bool STAGED>
+__global__ __launch_bounds__(kPosThreads) void k_positional(nfst_batch lat, PosIn in, PosWs w, PosOut o, int need_alpha) {
+  extern __shared__ double pos_lds[];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const Meta m = load_meta(lat.meta, b);
+  const int R = lat.max_rows, V = lat.vocab, T = in.T, n = m.n_rows;
+  double *vm = pos_lds, *tm = vm + 2 * R;
+  unsigned long long *hist = (unsigned long long *)(tm + V);
+  int *ve = (int *)(hist + V), *te = ve + 2 * R, *scan = te + V;
+  int *rp_l = scan + kPosThreads;
+  uint32_t *recs = (uint32_t *)(rp_l + R + 1);
+  typedef typename std::conditional<STAGED, PosArcsLds, PosArcsGlobal>::type Arcs;
+  const PosSum::Rows val = {vm, ve}, tab = {tm, te};
+  const float *theta = in.sc.theta + (size_t)in.sc.theta_stride * b;
+  const float *pos_b = in.pos ? in.pos + (size_t)in.pos_stride * b : nullptr;
+  const int G = pos_group(m);
+  const int slots = kPosThreads / G, slot = tid / G, gl = tid % G;
+
+  // ---- once per launch: the weights of the extras, and the arcs by (destination, canonical arc) -------------------
+  if (EXTRA) {
+    for (int a = m.arc_off + tid; a < m.arc_off + m.n_arcs; a += kPosThreads) {
+      double e = 0.0;
+      if (lat.weighted) e += (double)lat.arc_w[a];
+      if (in.sc.arc_scores) e += (double)in.sc.arc_scores[a];
+      const ME64 x = exp_split64(e);
+      w.ewm[a] = x.m;
+      w.ewe[a] = x.e;
+    }
+  }
+  int *in_ptr = w.in_ptr + m.row_off + b;
+  if (need_alpha) {
+    int *cnt = (int *)vm, *fill = cnt + n + 1;  // (the value rows are not in use yet: 8 n + 4 <= 16 max_rows bytes)
+    for (int i = tid; i <= n; i += kPosThreads) cnt[i] = 0;
+    __syncthreads();
+    for (int i = tid; i < m.n_arcs; i += kPosThreads) {
+      const int a = m.arc_off + i, s = lat.arc_src[a], d = lat.arc_dst[a];
+      if (s != d) atomicAdd(&cnt[d], 1);  // (integers: the order does not matter)
+      w.acc[a] = 0.0;
+    }
+    __syncthreads();
+    const int chunk = (n + kPosThreads - 1) / kPosThreads, c0 = min(tid * chunk, n), c1 = min(c0 + chunk, n);
+    int part = 0;
+    for (int i = c0; i < c1; ++i) part += cnt[i];
+    scan[tid] = part;
+    __syncthreads();
+    if (tid == 0) {
+      int run = 0;
+      for (int i = 0; i < kPosThreads; ++i) { const int v = scan[i]; scan[i] = run; run += v; }
+      cnt[n] = run;
+      in_ptr[n] = run;
+    }
+    __syncthreads();
+    int run = scan[tid];
+    for (int i = c0; i < c1; ++i) {
+      const int v = cnt[i];
+      cnt[i] = run;
+      fill[i] = run;
+      in_ptr[i] = run;
+      run += v;
+    }
+    __syncthreads();
+    for (int i = tid; i < m.n_arcs; i += kPosThreads) {
+      const int a = m.arc_off + i, s = lat.arc_src[a], d = lat.arc_dst[a];
+      if (s != d) w.in_tmp[m.arc_off + atomicAdd(&fill[d], 1)] = i;
+    }
+    __syncthreads();
+    // a state's in-entries were filled in any order: every arc finds its rank among them (stable, canonical order)
+    for (int i = tid; i < m.n_arcs; i += kPosThreads) {
+      const int a = m.arc_off + i, s = lat.arc_src[a], d = lat.arc_dst[a];
+      if (s == d) continue;
+      const int j0 = cnt[d], j1 = cnt[d + 1];
+      int rank = 0;
+      for (int j = j0; j < j1; ++j) rank += w.in_tmp[m.arc_off + j] < i;
+      w.in_rec[m.arc_off + j0 + rank] = make_int2(i, s | (lat.arc_label[a] << 16));
+    }
+    __syncthreads();
+  }
+
+  // ---- backwards in time ----------------------------------------------------------------------------------------
+  const size_t ro = (size_t)(T + 1) * m.row_off;
+  const PosSum::Store st = {need_alpha ? w.bm + ro : nullptr, need_alpha ? w.be + ro : nullptr};
+  auto ext = [&](int a, ME64 x) -> ME64 {
+    if (EXTRA) { x.m *= w.ewm[a]; x.e += w.ewe[a]; }
+    return x;
+  };
+  Arcs out_arcs;
+  if constexpr (STAGED) {
+    pos_stage_out(lat, m, b, rp_l, recs);  // (the pass begins with a barrier)
+    out_arcs = {rp_l, recs, m.arc_off};
+  } else {
+    out_arcs = {lat.row_ptr + m.row_off + b, lat.arc_dst, lat.arc_label, m.arc_off, m.arc_off + m.n_arcs};
+  }
+  pos_beta_pass<PosSum>(lat, m, out_arcs, theta, pos_b, T, R, G, val, tab, st, ext);
+  const ME64 z = val.get(0);  // beta_0(0) is in row 0 of the pair (position 0)
+  const double logz = z.m > 0.0 ? log(z.m) + (double)z.e * 0.693147180559945309417232 : -__builtin_huge_val();
+  if (tid == 0) {
+    o.logz64[b] = logz;
+    if (o.logz32) o.logz32[b] = (float)logz;
+    if (o.len_logz) o.len_logz[(size_t)b * (T + 1)] = -__builtin_huge_val();
+  }
+  if (!need_alpha) return;
+  __syncthreads();  // (everyone has read beta_0(0))
+
+  // ---- forwards in time -------------------------------------------------------------------------------------------
+  const double rz = z.m > 0.0 ? 1.0 / z.m : 0.0;
+  const bool want_p = o.pos_post != nullptr || o.arc_post != nullptr;
+  for (int i = tid; i < n; i += kPosThreads) val.set(i, i == 0 ? PosSum::one() : PosSum::zero());
+  for (int l = tid; l < V; l += kPosThreads) hist[l] = 0ull;
+  const int2 *in_rec = w.in_rec + m.arc_off;
+  double *acc_e = w.acc + m.arc_off;
+  if constexpr (STAGED) {  // the same LDS, now by destination: (src | label << 16) of every in-entry
+    const int n_in = in_ptr[n];
+    for (int d = tid; d <= n; d += kPosThreads) rp_l[d] = in_ptr[d];
+    for (int j = tid; j < n_in; j += kPosThreads) recs[j] = (uint32_t)in_rec[j].y;
+  }
+  for (int t = 0; t < T; ++t) {
+    if (pos_b) pos_fill_table<PosSum>(tab, theta, pos_b + (size_t)t * V, V);
+    __syncthreads();
+    const int cur = (t & 1) * R, nxt = ((t + 1) & 1) * R;
+    const double *brm = st.m + (size_t)(t + 1) * n;
+    const int *bre = st.e + (size_t)(t + 1) * n;
+    for (int base = 0; base < n; base += slots) {
+      const int d = base + slot;
+      const bool act = d < n;
+      const int j0 = act ? (STAGED ? rp_l[d] : in_ptr[d]) : 0, j1 = act ? (STAGED ? rp_l[d + 1] : in_ptr[d + 1]) : 0;
+      const double bmd = act ? brm[d] * rz : 0.0;
+      const int bed = act ? bre[d] - z.e : 0;
+      ME64 acc = PosSum::zero();
+      for (int j = j0 + gl; j < j1; j += G) {
+        int2 rec;
+        if (STAGED) {
+          rec.y = (int)recs[j];
+          rec.x = EXTRA ? in_rec[j].x : 0;
+        } else {
+          rec = in_rec[j];
+        }
+        const ME64 x = ext(m.arc_off + rec.x, PosSum::times(tab.get(rec.y >> 16), val.get(cur + (rec.y & 0xffff))));
+        PosSum::plus(acc, x);
+        if (want_p) {
+          const double pm = x.m * bmd;
+          if (pm != 0.0) {
+            const double p = __builtin_amdgcn_ldexp(pm, x.e + bed);
+            if (o.pos_post) atomicAdd(&hist[rec.y >> 16], (unsigned long long)llrint(__builtin_amdgcn_ldexp(p, kPosPostBits)));
+            if (o.arc_post) acc_e[j] += p;  // (entry j belongs to this lane at every step)
+          }
+        }
+      }
+      for (int og = 1; og < G; og <<= 1) PosSum::combine(acc, og);
+      if (gl == 0 && act) {
+        const ME64 v = PosSum::norm(acc);
+        val.set(nxt + d, v);
+        if (d == m.sink && o.len_logz)  // the paths of exactly t + 1 arcs
+          o.len_logz[(size_t)b * (T + 1) + t + 1] = v.m > 0.0 ? log(v.m) + (double)v.e * 0.693147180559945309417232 : -__builtin_huge_val();
+      }
+    }
+    __syncthreads();
+    if (o.pos_post) {
+      float *out = o.pos_post + ((size_t)b * T + t) * V;
+      for (int l = tid; l < V; l += kPosThreads) {
+        out[l] = (float)__builtin_amdgcn_ldexp((double)hist[l], -kPosPostBits);
+        hist[l] = 0ull;
+      }
+    }
+  }
+  if (o.arc_post) {
+    for (int i = tid; i < m.n_arcs; i += kPosThreads)
+      if (lat.arc_src[m.arc_off + i] == lat.arc_dst[m.arc_off + i]) o.arc_post[m.arc_off + i] = 0.0f;
+    const int n_in = in_ptr[n];
+    for (int j = tid; j < n_in; j += kPosThreads) o.arc_post[m.arc_off + in_rec[j].x] = (float)acc_e[j];
+  }
+}
+
+// Max-plus: the same backward pass, every row stored; then thread 0 reads the path forwards from state 0: at position
+// t the smallest canonical arc whose candidate has the bits of vb_t(state).  LDS: 8 max_rows + 4 vocab + 16 bytes
+// (STAGED: + the arc records, as k_positional).
+template <bool STAGED>
+__global__ __launch_bounds__(kPosThreads) void k_positional_viterbi(nfst_batch lat, PosIn in, PosWs w, PosVitOut o) {
+  extern __shared__ double pos_lds[];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const Meta m = load_meta(lat.meta, b);
+  const int R = lat.max_rows, V = lat.vocab, T = in.T, n = m.n_rows;
+  float *vv = (float *)pos_lds, *tf = vv + 2 * R;
+  int *len_s = (int *)(tf + V), *rp_l = len_s + 4;
+  uint32_t *recs = (uint32_t *)(rp_l + R + 1);
+  typedef typename std::conditional<STAGED, PosArcsLds, PosArcsGlobal>::type Arcs;
+  Arcs out_arcs;
+  if constexpr (STAGED) {
+    pos_stage_out(lat, m, b, rp_l, recs);
+    out_arcs = {rp_l, recs, m.arc_off};
+  } else {
+    out_arcs = {lat.row_ptr + m.row_off + b, lat.arc_dst, lat.arc_label, m.arc_off, m.arc_off + m.n_arcs};
+  }
+  const PosMax::Rows val = {vv}, tab = {tf};
+  const float *theta = in.sc.theta + (size_t)in.sc.theta_stride * b;
+  const float *pos_b = in.pos ? in.pos + (size_t)in.pos_stride * b : nullptr;
+  const Extra ex = {lat.weighted ? lat.arc_w : nullptr, in.sc.arc_scores};
+  float *rows = w.vb + (size_t)(T + 1) * m.row_off;
+  const PosMax::Store st = {rows};
+  auto ext = [&](int a, float x) -> float { return ex.at(a) + x; };
+  pos_beta_pass<PosMax>(lat, m, out_arcs, theta, pos_b, T, R, pos_group(m), val, tab, st, ext);
+  int32_t *po = o.paths + (size_t)b * T;
+  int32_t *ao = o.path_arcs ? o.path_arcs + (size_t)b * T : nullptr;
+  if (tid == 0) {
+    const int32_t *rp = lat.row_ptr + m.row_off + b;
+    const float v0 = rows[0];
+    o.best[b] = v0;
+    int s = 0, len = 0;
+    if (v0 > kNegInf) {
+      for (int t = 0; t < T && s != m.sink; ++t) {
+        const float v = rows[(size_t)t * n + s];
+        const float *nx = rows + (size_t)(t + 1) * n;
+        const int a0 = max(rp[s], m.arc_off), a1 = min(rp[s + 1], m.arc_off + m.n_arcs);
+        int pick = -1;
+        for (int a = a0; a < a1 && pick < 0; ++a) {
+          const int d = lat.arc_dst[a], l = lat.arc_label[a];
+          if (d == s) continue;
+          const float lab = pos_b ? theta[l] + pos_b[(size_t)t * V + l] : theta[l];
+          if (ex.at(a) + (lab + nx[d]) == v) pick = a;
+        }
+        if (pick < 0) break;  // (never: some arc attains the maximum)
+        po[len] = lat.arc_label[pick];
+        if (ao) ao[len] = pick;
+        ++len;
+        s = lat.arc_dst[pick];
+      }
+    }
+    o.lengths[b] = len;
+    *len_s = len;
+  }
+  __syncthreads();
+  for (int t = *len_s + tid; t < T; t += kPosThreads) {
+    po[t] = o.pad;
+    if (ao) ao[t] = -1;
+  }
+}

@@ -612,6 +612,167 @@ def intersect(lat: LatticeBatch, dfa, **pack_opts) -> IntersectResult:
     return lat.intersect(dfa, **pack_opts)
 
 
+# ----------------------------------------------------------------------------- position-dependent scores
+class PositionalResult(NamedTuple):
+    logz: torch.Tensor  # [B] float32 log Z_T
+    logz64: torch.Tensor  # [B] float64
+    pos_posterior: Optional[torch.Tensor]  # [B, T, V] float32: P(the mark at position t is l) = d log Z_T / d pos_scores
+    arc_posterior: Optional[torch.Tensor]  # [total_arcs] float32: sum over t of P(arc a is at position t)
+    len_logz: Optional[torch.Tensor]  # [B, T + 1] float64: log weight of the paths of exactly L arcs (entry 0: -inf)
+
+
+class PositionalViterbiResult(NamedTuple):
+    best: torch.Tensor  # [B] float32
+    paths: torch.Tensor  # [B, T] int32 labels (bos .. eos), pad-terminated
+    path_arcs: torch.Tensor  # [B, T] int32 canonical arc ids, -1 padded
+    lengths: torch.Tensor  # [B] int32 (0 where best is -inf)
+
+
+def _positions(lat: LatticeBatch, pos_scores, T):
+    """(pos_scores as contiguous float32 or None, its stride, T) of the positional ops, checked: ``pos_scores`` is
+    [T, V] (one table for the batch) or [B, T, V] on the batch's device; ``T`` defaults to its length, and without
+    ``pos_scores`` to the longest path of the batch."""
+    if T is not None and (isinstance(T, bool) or not isinstance(T, int) or T < 1):
+        raise ValueError(f"T must be an int >= 1, not {T!r}")
+    if pos_scores is None:
+        return None, 0, int(lat.depth.max()) if T is None else T
+    if not isinstance(pos_scores, torch.Tensor):
+        raise ValueError(f"pos_scores must be a torch.Tensor, not {type(pos_scores).__name__}")
+    if pos_scores.device != lat.device:
+        raise ValueError(f"pos_scores is on {pos_scores.device}, the lattice batch on {lat.device}")
+    if not pos_scores.is_floating_point():
+        raise ValueError(f"pos_scores must be a floating-point tensor, not {pos_scores.dtype}")
+    if pos_scores.dim() not in (2, 3) or pos_scores.shape[-1] != lat.vocab or pos_scores.shape[-2] < 1 \
+            or (pos_scores.dim() == 3 and pos_scores.shape[0] != lat.n_lattices):
+        raise ValueError(f"pos_scores must be [T, {lat.vocab}] or [{lat.n_lattices}, T, {lat.vocab}] with T >= 1, "
+                         f"not {list(pos_scores.shape)}")
+    if T is None:
+        T = int(pos_scores.shape[-2])
+    elif T != pos_scores.shape[-2]:
+        raise ValueError(f"T = {T}, but pos_scores has {pos_scores.shape[-2]} positions")
+    return pos_scores.to(torch.float32).contiguous(), (0 if pos_scores.dim() == 2 else T * lat.vocab), T
+
+
+def _positional_ws(lat: LatticeBatch, T: int, flags: int) -> tuple:
+    ws_bytes = int(lib.nfst_positional_ws_bytes(C.byref(lat.c_struct()), T, flags))
+    check(min(ws_bytes, 0), "nfst_positional_ws_bytes")
+    return torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=lat.device), ws_bytes
+
+
+def positional_forward_backward(lat: LatticeBatch, theta, pos_scores=None, T: Optional[int] = None, arc_scores=None,
+                                want_pos_posterior: bool = True, want_arc_posterior: bool = False,
+                                want_len: bool = False) -> PositionalResult:
+    """One launch of ``nfst_positional`` (no autograd; DESIGN.md sections 2 and 4.10): exact sums over the paths of at
+    most ``T`` arcs when the arc at position t of a path also scores ``pos_scores[(b,) t, label]`` -- per-position
+    logits of a tagger or encoder -- on top of ``theta`` [V] or [B, V] and ``arc_scores`` [total_arcs].  Entries of
+    ``pos_scores`` may be -inf (the mark is forbidden at that position); NaN or +inf are the caller's business (nothing
+    scans for them); the pad column enters no result.  ``T`` defaults to ``pos_scores.shape[-2]``, without
+    ``pos_scores`` to the longest path of the batch (then log Z and the arc posteriors are ``forward_backward``'s).
+    Paths longer than ``T`` are not counted; a lattice without a path of finite score within ``T`` gets -inf and zero
+    posteriors.  The workspace stores every beta row of every position: 12 (T + 1) total_rows bytes."""
+    _need_gpu(lat)
+    theta = _input(lat, theta, "theta", True, False)
+    arc_scores = _input(lat, arc_scores, "arc_scores", False, True)
+    pos, stride, T = _positions(lat, pos_scores, T)
+    sc, keep = _scores(lat, theta, arc_scores)
+    dev = lat.device
+    B = lat.n_lattices
+    need = want_pos_posterior or want_arc_posterior or want_len
+    ws, ws_bytes = _positional_ws(lat, T, 1 if need else 0)
+    z64 = torch.empty(B, dtype=torch.float64, device=dev)
+    z32 = torch.empty(B, dtype=torch.float32, device=dev)
+    pp = torch.empty((B, T, lat.vocab), dtype=torch.float32, device=dev) if want_pos_posterior else None
+    ap = torch.empty(lat.total_arcs, dtype=torch.float32, device=dev) if want_arc_posterior else None
+    ll = torch.empty((B, T + 1), dtype=torch.float64, device=dev) if want_len else None
+    check(lib.nfst_positional(C.byref(lat.c_struct()), C.byref(sc), _ptr(pos), stride, T, ws.data_ptr(), ws_bytes, _ptr(z64),
+                              _ptr(z32), _ptr(ll), _ptr(pp), _ptr(ap), _stream()), "nfst_positional")
+    return PositionalResult(z32, z64, pp, ap, ll)
+
+
+class _PositionalLogZ(torch.autograd.Function):
+    """log Z_T with d/d pos_scores = the position posteriors, d/d theta = their sums over t, d/d arc_scores = the arc
+    posteriors.  First order only: a double backward raises (once_differentiable)."""
+
+    @staticmethod
+    def forward(ctx, lat, theta, pos_scores, arc_scores):
+        nt, npos, na = ctx.needs_input_grad[1:4]
+        r = positional_forward_backward(lat, theta.detach(), pos_scores.detach(), None,
+                                        None if arc_scores is None else arc_scores.detach(),
+                                        want_pos_posterior=nt or npos, want_arc_posterior=na)
+        ctx.lat = lat
+        ctx.shared = (theta.dim() == 1, pos_scores.dim() == 2)
+        ctx.like = (theta, pos_scores, arc_scores)
+        ctx.save_for_backward(r.pos_posterior, r.arc_posterior)
+        return r.logz
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        pp, ap = ctx.saved_tensors
+        nt, npos, na = ctx.needs_input_grad[1:4]
+        theta, pos_scores, arc_scores = ctx.like
+        g = g.to(torch.float32)
+        d_theta = d_pos = d_arc = None
+        if nt:
+            d_theta = _per_label(pp.sum(dim=1), g, ctx.shared[0]).to(theta.dtype)
+        if npos:
+            d_pos = pp * g[:, None, None]
+            d_pos = (d_pos.sum(dim=0) if ctx.shared[1] else d_pos).to(pos_scores.dtype)
+        if na:
+            d_arc = (ap * g[ctx.lat.arc_lattice()]).to(arc_scores.dtype)
+        return None, d_theta, d_pos, d_arc
+
+
+def positional_log_z(lat: LatticeBatch, theta: torch.Tensor, pos_scores: torch.Tensor,
+                     arc_scores: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Differentiable exact log Z_T per lattice, float32 [B], under per-position scores ``pos_scores`` [T, V] or
+    [B, T, V] (see ``positional_forward_backward``).  Gradients: ``pos_scores`` gets the position posteriors, ``theta``
+    their sums over the positions, ``arc_scores`` the arc posteriors (each summed over the lattices for a shared
+    tensor).  First derivatives only: a second backward raises."""
+    _need_gpu(lat)
+    theta = _input(lat, theta, "theta", True, False)
+    arc_scores = _input(lat, arc_scores, "arc_scores", False, True)
+    if pos_scores is None:
+        raise ValueError("positional_log_z needs pos_scores; without them use log_z")
+    _positions(lat, pos_scores, None)
+    return _PositionalLogZ.apply(lat, theta, pos_scores, arc_scores)
+
+
+def length_distribution(lat: LatticeBatch, theta, T: Optional[int] = None, arc_scores=None):
+    """(``log_p`` [B, T + 1] float64, ``logz64`` [B]): log P(the path has exactly L arcs) under truncation at ``T`` arcs
+    (``T`` defaults to the longest path of the batch: no truncation), and the log Z over the paths that fit.  Entry 0 is
+    -inf; a lattice without a path within ``T`` gets NaN-free -inf everywhere."""
+    r = positional_forward_backward(lat, theta, None, T, arc_scores, want_pos_posterior=False, want_len=True)
+    z = r.logz64[:, None]
+    return torch.where(torch.isfinite(z), r.len_logz - z, torch.full_like(r.len_logz, float("-inf"))), r.logz64
+
+
+def positional_viterbi(lat: LatticeBatch, theta, pos_scores=None, T: Optional[int] = None, arc_scores=None,
+                       pad: int = 0) -> PositionalViterbiResult:
+    """The best path of at most ``T`` arcs under per-position scores (``nfst_positional_viterbi``): plain float32
+    max-plus from position T backwards, ties to the smaller canonical arc.  Without ``pos_scores`` and with ``T`` >= the
+    longest path it is ``k_best(k=1)`` bit for bit.  A lattice without a path of finite score within ``T`` gets
+    ``best`` -inf and length 0.  Not differentiable."""
+    _need_gpu(lat)
+    theta = _input(lat, theta, "theta", True, False)
+    arc_scores = _input(lat, arc_scores, "arc_scores", False, True)
+    pos, stride, T = _positions(lat, pos_scores, T)
+    sc, keep = _scores(lat, theta.detach(), None if arc_scores is None else arc_scores.detach())
+    if pos is not None:
+        pos = pos.detach()
+    dev = lat.device
+    B = lat.n_lattices
+    ws, ws_bytes = _positional_ws(lat, T, 2)
+    best = torch.empty(B, dtype=torch.float32, device=dev)
+    paths = torch.empty((B, T), dtype=torch.int32, device=dev)
+    arcs = torch.empty((B, T), dtype=torch.int32, device=dev)
+    lens = torch.empty(B, dtype=torch.int32, device=dev)
+    check(lib.nfst_positional_viterbi(C.byref(lat.c_struct()), C.byref(sc), _ptr(pos), stride, T, ws.data_ptr(), ws_bytes,
+                                      _ptr(best), _ptr(paths), _ptr(arcs), _ptr(lens), int(pad), _stream()),
+          "nfst_positional_viterbi")
+    return PositionalViterbiResult(best, paths, arcs, lens)
+
+
 class SampleResult(NamedTuple):
     paths: torch.Tensor  # [B, K, max_len] int32 labels, pad-terminated
     arcs: torch.Tensor  # [B, K, max_len] int32 canonical arc ids

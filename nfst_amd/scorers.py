@@ -86,6 +86,19 @@ class LatticeScorer(torch.nn.Module):
         differentiable in theta)."""
         return ops.k_best(self._lat(), self.theta, k, max_len=max_len, pad=self.__pad__)
 
+    def positional_log_z(self, pos_scores: torch.Tensor) -> torch.Tensor:
+        """Differentiable exact log Z per lattice ``[B]`` when the mark at position t also scores ``pos_scores[(b,) t,
+        mark]`` (``ops.positional_log_z``): per-position logits of a tagger, marginalised over the lattice."""
+        return ops.positional_log_z(self._lat(), self.theta, pos_scores)
+
+    def length_distribution(self, T: Optional[int] = None):
+        """``(log P(L = t) [B, T + 1], logz64 [B])`` over the paths of at most ``T`` arcs (``ops.length_distribution``)."""
+        return ops.length_distribution(self._lat(), self.theta.detach(), T=T)
+
+    def positional_viterbi(self, pos_scores: torch.Tensor) -> "ops.PositionalViterbiResult":
+        """The best path under ``theta`` plus per-position scores (``ops.positional_viterbi``)."""
+        return ops.positional_viterbi(self._lat(), self.theta.detach(), pos_scores, pad=self.__pad__)
+
     def beam_decoder(self, score_fn, reorder_fn=None, sync_every: int = 8):
         """A ``decoders.BeamDecoder`` over the scorer's lattice for a path-dependent ``score_fn(hx, inp) -> (hx,
         scores [N, V])``: ``.decode(k, lookahead=...)`` keeps k hypotheses per lattice."""

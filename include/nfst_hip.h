@@ -680,10 +680,17 @@ int nfst_intersect_write(const nfst_batch *lat, const int8_t *delta_t, int64_t d
  * than 160 KiB returns NFST_ERR_LIMIT.  When 4 (max_rows + 1 + arcs of the largest lattice) + 16 more bytes fit, the arc
  * records are staged in LDS; otherwise the step loops read the canonical arrays (the same bits, slower steps).  Null required pointers, T < 1, a stride that is neither 0 nor T * vocab or a
  * short workspace return NFST_ERR_ARG.  All checks run on the host before any launch.
+ *
+ * nfst_positional_plan(lat, viterbi, lds_bytes, staged) is that decision, asked on the host (it touches no device and
+ * takes a host-packed batch): for nfst_positional (viterbi = 0) or nfst_positional_viterbi (viterbi != 0) it writes the
+ * dynamic LDS of the launch, arc records included, to *lds_bytes and 1 or 0 to *staged (either may be null) and returns
+ * NFST_OK, or returns NFST_ERR_LIMIT exactly when the op itself would.  Both launchers call it: there is no second copy
+ * of the rule.
  */
 #define NFST_POS_WS_POSTERIOR 1
 #define NFST_POS_WS_VITERBI 2
 int64_t nfst_positional_ws_bytes(const nfst_batch *lat, int32_t T, int32_t flags);
+int nfst_positional_plan(const nfst_batch *lat, int32_t viterbi, int64_t *lds_bytes, int32_t *staged);
 int nfst_positional(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T, void *ws,
                     int64_t ws_bytes, double *logz64, float *logz32, double *len_logz, float *pos_post, float *arc_post,
                     void *stream);

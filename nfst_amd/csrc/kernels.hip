@@ -1029,6 +1029,21 @@ int64_t nfst_positional_ws_bytes(const nfst_batch *lat, int32_t T, int32_t flags
   return pos_ws_layout(lat, T, flags, nullptr, nullptr);
 }
 
+// The one place that decides what a launch of either op takes: the LDS of its kernel and whether the arc records are
+// staged beside it.  Host only (no device is touched): both launchers call it, and so may a caller that wants to know
+// which flavour a batch gets.
+int nfst_positional_plan(const nfst_batch *lat, int32_t viterbi, int64_t *lds_bytes, int32_t *staged) {
+  const int rc = check_batch(lat);
+  if (rc) return rc;
+  const int64_t lds = viterbi ? (int64_t)lat->max_rows * 8 + (int64_t)lat->vocab * 4 + 16
+                              : (int64_t)lat->max_rows * 24 + (int64_t)lat->vocab * 20 + kPosThreads * 4 + 16;
+  if (lds > kMaxLds) return NFST_ERR_LIMIT;
+  const int64_t more = pos_staged_bytes(lat, lds);
+  if (lds_bytes) *lds_bytes = lds + more;
+  if (staged) *staged = more > 0;
+  return NFST_OK;
+}
+
 int nfst_positional(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T, void *ws,
                     int64_t ws_bytes, double *logz64, float *logz32, double *len_logz, float *pos_post, float *arc_post,
                     void *stream) {
@@ -1037,9 +1052,9 @@ int nfst_positional(const nfst_batch *lat, const nfst_scores *scores, const floa
   int rc = pos_check(lat, scores, pos, pos_stride, T, ws, ws_bytes, flags);
   if (rc) return rc;
   if (!logz64) return NFST_ERR_ARG;
-  const int64_t lds = (int64_t)lat->max_rows * 24 + (int64_t)lat->vocab * 20 + kPosThreads * 4 + 16;
-  if (lds > kMaxLds) return NFST_ERR_LIMIT;
-  const int64_t staged = pos_staged_bytes(lat, lds);
+  int64_t lds;
+  int32_t staged;
+  if ((rc = nfst_positional_plan(lat, 0, &lds, &staged))) return rc;
   PosWs w;
   pos_ws_layout(lat, T, flags, (char *)ws, &w);
   const PosIn in = {*scores, pos, pos ? pos_stride : 0, (int)T};
@@ -1047,9 +1062,9 @@ int nfst_positional(const nfst_batch *lat, const nfst_scores *scores, const floa
   const hipStream_t st = (hipStream_t)stream;
   const dim3 grid(lat->n_lattices), block(kPosThreads);
   if (extras_case(lat, scores))
-    return staged ? launch(k_positional<true, true>, grid, block, lds + staged, st, *lat, in, w, o, need_alpha)
+    return staged ? launch(k_positional<true, true>, grid, block, lds, st, *lat, in, w, o, need_alpha)
                   : launch(k_positional<true, false>, grid, block, lds, st, *lat, in, w, o, need_alpha);
-  return staged ? launch(k_positional<false, true>, grid, block, lds + staged, st, *lat, in, w, o, need_alpha)
+  return staged ? launch(k_positional<false, true>, grid, block, lds, st, *lat, in, w, o, need_alpha)
                 : launch(k_positional<false, false>, grid, block, lds, st, *lat, in, w, o, need_alpha);
 }
 
@@ -1059,15 +1074,15 @@ int nfst_positional_viterbi(const nfst_batch *lat, const nfst_scores *scores, co
   int rc = pos_check(lat, scores, pos, pos_stride, T, ws, ws_bytes, NFST_POS_WS_VITERBI);
   if (rc) return rc;
   if (!best || !paths || !lengths) return NFST_ERR_ARG;
-  const int64_t lds = (int64_t)lat->max_rows * 8 + (int64_t)lat->vocab * 4 + 16;
-  if (lds > kMaxLds) return NFST_ERR_LIMIT;
-  const int64_t staged = pos_staged_bytes(lat, lds);
+  int64_t lds;
+  int32_t staged;
+  if ((rc = nfst_positional_plan(lat, 1, &lds, &staged))) return rc;
   PosWs w;
   pos_ws_layout(lat, T, NFST_POS_WS_VITERBI, (char *)ws, &w);
   const PosIn in = {*scores, pos, pos ? pos_stride : 0, (int)T};
   const PosVitOut o = {best, paths, path_arcs, lengths, (int)pad};
   if (staged)
-    return launch(k_positional_viterbi<true>, dim3(lat->n_lattices), dim3(kPosThreads), lds + staged, (hipStream_t)stream, *lat, in, w, o);
+    return launch(k_positional_viterbi<true>, dim3(lat->n_lattices), dim3(kPosThreads), lds, (hipStream_t)stream, *lat, in, w, o);
   return launch(k_positional_viterbi<false>, dim3(lat->n_lattices), dim3(kPosThreads), lds, (hipStream_t)stream, *lat, in, w, o);
 }
 

@@ -122,7 +122,8 @@ struct PosMax {  // max-plus in plain float32: c = e_a + ((theta[l] + pos[b, t, 
   static __device__ __forceinline__ V norm(V acc) { return acc; }
 };
 
-// lanes per state: the largest power of two <= half the mean out-degree, widened while lanes would idle
+// lanes per state: the largest power of two <= the mean out-degree (n_dp / n_reach, rounded down), doubled while it
+// is below that mean and twice as many lanes per state still fit the workgroup (lanes would idle otherwise)
 __device__ __forceinline__ int pos_group(const Meta &m) {
   const int n = max(m.n_reach, 1), avg = m.n_dp / n;
   int g = 1;

@@ -659,6 +659,18 @@ def _positional_ws(lat: LatticeBatch, T: int, flags: int) -> tuple:
     return torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=lat.device), ws_bytes
 
 
+def positional_plan(lat: LatticeBatch, viterbi: bool = False) -> tuple:
+    """(``lds_bytes``, ``staged``) of the launch ``positional_forward_backward`` (``viterbi=True``:
+    ``positional_viterbi``) makes for this batch (``nfst_positional_plan``, the rule the launchers themselves call): the
+    dynamic LDS of the kernel, and whether it keeps the arc records of the largest lattice there instead of reading the
+    canonical arrays at every step.  Asked on the host: the batch may be host-packed, and no GPU is needed.  A batch
+    beyond the op's LDS limit raises ``NfstError`` (-6), as the op would."""
+    lds, staged = C.c_int64(0), C.c_int32(0)
+    check(lib.nfst_positional_plan(C.byref(lat.c_struct()), 1 if viterbi else 0, C.byref(lds), C.byref(staged)),
+          "nfst_positional_plan")
+    return int(lds.value), bool(staged.value)
+
+
 def positional_forward_backward(lat: LatticeBatch, theta, pos_scores=None, T: Optional[int] = None, arc_scores=None,
                                 want_pos_posterior: bool = True, want_arc_posterior: bool = False,
                                 want_len: bool = False) -> PositionalResult:

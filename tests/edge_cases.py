@@ -1,9 +1,10 @@
-"""Inputs of the edge-case tests of the expectation and k-best kernels (test helper, not a test module).
+"""Inputs of the edge-case tests of the expectation, k-best and positional kernels (test helper, not a test module).
 
 tests/test_gpu_expectation.py and tests/test_gpu_kbest.py run the kernels on these inputs; tests/test_expectation_cpu.py
 and tests/test_kbest_cpu.py prove on the references alone that the inputs are what their tests need (posteriors that
 have not collapsed to one path, a lattice with fewer than k finite paths, scores that really tie).  Both sides build
-their inputs here, so they cannot drift apart.
+their inputs here, so they cannot drift apart.  The positional section at the end serves tests/test_gpu_positional.py
+and tests/test_positional_cpu.py in the same way.
 """
 from __future__ import annotations
 
@@ -69,6 +70,12 @@ def double_funnel():  # fan-out 200, fan-in, fan-out, fan-in (test_beta_neural_g
     lab = [BOS] + list(range(3, 203)) + [5] * 200 + list(range(3, 203)) + [6] * 200 + [EOS]
     dst = [1] + list(range(2, 202)) + [202] * 200 + list(range(203, 403)) + [403] * 200 + [404]
     return synth._finish(405, 256, src, lab, dst)
+
+
+# the ten packings the edge-case tests run: narrow and wide groups, one, two and four slots per lane, compact tiles or not
+STAR_PACKINGS = [dict(), dict(group_mode=1), dict(group_mode=2), dict(group_mode=1, slots_per_lane=1), dict(group_mode=2, slots_per_lane=1),
+                 dict(group_mode=1, slots_per_lane=2), dict(group_mode=2, slots_per_lane=2), dict(slots_per_lane=4),
+                 dict(group_mode=1, slots_per_lane=4, no_compact=True), dict(group_mode=2, slots_per_lane=4, no_compact=True)]
 
 
 def packing_lattices():
@@ -228,3 +235,85 @@ def reachable_dead_arc(l, dead=DEAD):
     reads the arc's candidate)."""
     a = np.nonzero(np.isin(l.label, dead) & (l.src != l.dst))[0]
     return int(a[len(a) // 2])
+
+
+# ----------------------------------------------------------------------------- positional sweeps (nfst_positional*)
+# tests/test_gpu_positional.py runs these; tests/test_positional_cpu.py proves, on the reference and the host-side plan
+# query alone, that they are what their cases need (which flavour a batch takes, the group sizes, the exponent range, the
+# limits, scores that really tie).  Builders return fresh lattices: callers may change them.
+POS_V = 140
+POS_LARGE = {"big": 480, "mid": 440}  # n_states: (unstaged, unstaged) and (sum-product unstaged, max-plus staged)
+# (n_states, avg_degree) -> (G by the mean degree alone, G after the widening loop), from the packed meta words
+POS_DEGREE_CLASSES = {(120, 12.0): (8, 8), (120, 20.0): (16, 16), (120, 44.0): (32, 32), (30, 20.0): (16, 16),
+                      (60, 6.0): (4, 8), (60, 12.0): (8, 16), (30, 24.0): (16, 32)}
+# n_states of pos_rowmax whose batch packs to the most rows nfst_positional takes beside 256 labels: 24 * 6442 + 20 * 256 +
+# 4112 = 163840 (chosen on the packed batch's own max_rows, which counts the packer's scratch rows)
+POS_ROWMAX_STATES = 6437
+POS_LDS_LIMIT = 160 * 1024
+POS_WIDE_VOCAB = 32767  # NFST_MAX_VOCAB
+# seeds of the position scores of the tie cases, chosen on the reference, and the lattices of each case whose walk
+# meets a state at which two or more live arcs attain vb_t(state) (tests/test_positional_cpu.py asserts them)
+POS_TIE_SEED = {"star": 4, "star wide": 4, "star one slot": 4, "funnel": 4, "grid": 7, "grid extras": 135}
+POS_TIE_LATTICES = {"star": 1, "star wide": 1, "star one slot": 1, "funnel": 1, "grid": 5, "grid extras": 6}
+
+
+def pos_large(name, weighted=False):
+    return synth.layered_lattice(27, n_states=POS_LARGE[name], avg_degree=90.0, vocab=POS_V, width=8, span=3, max_degree=130,
+                                 weighted=weighted)
+
+
+def pos_neighbour(vocab=POS_V, weighted=False):  # 13 rows
+    return synth.layered_lattice(3, n_states=12, avg_degree=2.0, vocab=vocab, width=3, span=3, max_degree=4, weighted=weighted)
+
+
+def pos_degree_classes():
+    return [synth.layered_lattice(92, n_states=n, avg_degree=d, vocab=POS_V, width=8, span=3, max_degree=130)
+            for n, d in POS_DEGREE_CLASSES]
+
+
+def pos_rowmax_batch(over=0):
+    """[pos_rowmax lattice, 13-row neighbour]: the most rows nfst_positional takes at vocabulary 256, or ``over`` more."""
+    return [pos_rowmax(POS_ROWMAX_STATES + over), pos_neighbour(256)]
+
+
+def pos_rowmax(n_states=POS_ROWMAX_STATES):
+    return synth.layered_lattice(91, n_states=n_states, avg_degree=4.0, vocab=256, width=128, span=4)
+
+
+def pos_wide(vocab=POS_WIDE_VOCAB):  # 13 rows, 28 arcs
+    return synth.layered_lattice(26, n_states=12, avg_degree=2.0, vocab=vocab, width=3, span=3, max_degree=4)
+
+
+def pos_sum_lds(max_rows, vocab):
+    """Dynamic LDS of nfst_positional without staged arcs (include/nfst_hip.h)."""
+    return 24 * int(max_rows) + 20 * int(vocab) + 4112
+
+
+def pos_vocab_limit(max_rows):
+    """The largest vocabulary nfst_positional takes beside ``max_rows`` rows."""
+    return (POS_LDS_LIMIT - 4112 - 24 * int(max_rows)) // 20
+
+
+def pos_range_inputs(name):
+    """(lats, theta [V], arc_scores, pos [B, T, V], T) of a range case under position scores: T is the batch's longest
+    path, pos of lattice b is drawn from default_rng(90 + b)."""
+    from tests import positional_ref as P
+
+    lats, theta, asc, _ = range_case(name)
+    T = max(P.min_max_len(l)[1] for l in lats)
+    V = lats[0].vocab
+    pos = np.stack([np.random.default_rng(90 + b).normal(0.0, 1.0, size=(T, V)) for b in range(len(lats))]).astype(F32)
+    return lats, theta, asc, pos, T
+
+
+def pos_tie_inputs(name):
+    """(lats, theta, arc_scores or None, pos [B, T, V], T) of a tie case: ``tie_cases()[name]`` with position scores on
+    the 0.25 grid, T the batch's longest path."""
+    from tests import positional_ref as P
+
+    lats, theta, asc, _ = tie_cases()[name]
+    T = max(P.min_max_len(l)[1] for l in lats)
+    V = lats[0].vocab
+    rng = np.random.default_rng(POS_TIE_SEED[name])
+    pos = quarter(rng.normal(0.0, 1.0, size=(len(lats), T, V)))
+    return lats, theta, asc, pos, T

@@ -92,9 +92,9 @@ def sum_product(l, score, pos, T: int) -> dict:
 
 
 def max_plus(l, theta_b, pos, T: int, arc_scores=None) -> dict:
-    """{"best" float32, "arcs" list (relative to the lattice), "labels", "vb" [T + 1, n] float32}: plain float32 in the
-    engine's order, from position T backwards; the walk takes the smallest canonical arc whose candidate has the bits
-    of vb_t(state)."""
+    """{"best" float32, "arcs" list (relative to the lattice), "labels", "vb" [T + 1, n] float32, "ties"}: plain float32
+    in the engine's order, from position T backwards; the walk takes the smallest canonical arc whose candidate has the
+    bits of vb_t(state).  ``ties[t]`` is the number of live arcs of the walked state that attain it at step t."""
     n, sink = l.n_rows, l.n_rows - 1
     th = np.asarray(theta_b, F32)
     e = np.zeros(l.n_arcs, F32)
@@ -123,7 +123,7 @@ def max_plus(l, theta_b, pos, T: int, arc_scores=None) -> dict:
         row[sink] = 0.0
         vb[t] = row
     best = vb[0, 0]
-    arcs = []
+    arcs, ties = [], []
     if best > NEG:
         st = 0
         for t in range(T):
@@ -132,8 +132,33 @@ def max_plus(l, theta_b, pos, T: int, arc_scores=None) -> dict:
             k = np.nonzero((s == st) & (cs[t] == vb[t, st]))[0]
             a = int(live[k[0]])  # (live is ascending: the smallest canonical arc)
             arcs.append(a)
+            ties.append(len(k))
             st = int(l.dst[a])
-    return {"best": F32(best), "arcs": arcs, "labels": [int(l.label[a]) for a in arcs], "vb": vb}
+    return {"best": F32(best), "arcs": arcs, "labels": [int(l.label[a]) for a in arcs], "vb": vb, "ties": ties}
+
+
+POS_THREADS = 1024  # kPosThreads of csrc/positional_kernels.h
+
+
+def pos_group(n_dp: int, n_reach: int, n_rows: int) -> int:
+    """Restatement of ``pos_group`` (csrc/positional_kernels.h) from the meta words the kernel reads: the lanes that share
+    a state's arcs -- the largest power of two <= the mean out-degree (n_dp / n_reach, integer division as in C), doubled
+    while it is below that mean and twice as many lanes per state still fit the workgroup."""
+    avg = int(n_dp) // max(int(n_reach), 1)
+    g = 1
+    while g < 64 and g * 2 <= avg:
+        g <<= 1
+    while g < 64 and g < avg and int(n_rows) * g * 2 <= POS_THREADS:
+        g <<= 1
+    return g
+
+
+def batch_groups(lat) -> list:
+    """``pos_group`` of every lattice of a packed batch, from its meta words."""
+    from nfst_amd import _lib
+
+    m = lat.meta_host
+    return [pos_group(r[_lib.META_N_DP], r[_lib.META_N_REACH], r[_lib.META_N_ROWS]) for r in m]
 
 
 def enumerate_paths(l, cap: int = 10000):

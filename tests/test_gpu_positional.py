@@ -7,6 +7,7 @@ Bounds.  The sum-product kernel computes in (float64 mantissa, int32 exponent) e
 nfst_expectation's; the float32 log Z to the project's 1e-5 * max(1, |ref|); posteriors to 2e-6 absolute; the max-plus
 outputs (best, labels, arcs, lengths) to the float32 restatement bit for bit.  The largest error of every kind goes to
 positional_errors.json in the directory of run outputs (profiles/README.md)."""
+import ctypes as C
 import dataclasses
 import glob
 import json
@@ -16,9 +17,10 @@ import numpy as np
 import pytest
 import torch
 
-from nfst_amd import ops, synth
+from nfst_amd import _lib, ops, synth
 from nfst_amd.lattice import LatticeBatch
 from nfst_amd.scorers import LatticeScorer
+from tests import edge_cases as E
 from tests import positional_ref as R
 from tests.test_positional_cpu import small_lattices, truncations
 
@@ -92,12 +94,12 @@ def run(lat, theta, pos, T, dev, asc=None):
     return r, v
 
 
-def check(tag, lat, lats, r, v, refs, T):
+def check_sum(tag, lat, lats, r, refs, T):
     z64, z32 = r.logz64.cpu().numpy(), r.logz.cpu().numpy()
     ll, pp, ap = r.len_logz.cpu().numpy(), r.pos_posterior.cpu().numpy(), r.arc_posterior.cpu().numpy()
-    best, paths, arcs, lens = (x.cpu().numpy() for x in v)
-    assert pp.shape == (len(lats), T, lat.vocab) and ll.shape == (len(lats), T + 1) and paths.shape == (len(lats), T)
+    assert pp.shape == (len(lats), T, lat.vocab) and ll.shape == (len(lats), T + 1)
     assert not np.isnan(z64).any() and not np.isnan(ll).any() and not np.isnan(pp).any() and not np.isnan(ap).any()
+    assert not np.isnan(z32).any()
     for b, (l, ref) in enumerate(zip(lats, refs)):
         a0 = int(lat.arc_off[b])
         if np.isfinite(ref["logz"]):
@@ -113,12 +115,24 @@ def check(tag, lat, lats, r, v, refs, T):
             assert rec(tag + ".len_logz", e.max()) <= TOL64, (tag, b)
         assert rec(tag + ".pos_post", np.abs(pp[b] - ref["pos_post"]).max()) <= TOLP, (tag, b)
         assert rec(tag + ".arc_post", np.abs(ap[a0:a0 + l.n_arcs] - ref["arc_post"]).max()) <= TOLP, (tag, b)
+
+
+def check_vit(tag, lat, lats, v, refs, T):
+    best, paths, arcs, lens = (x.cpu().numpy() for x in v)
+    assert paths.shape == (len(lats), T) and arcs.shape == (len(lats), T)
+    for b, (l, ref) in enumerate(zip(lats, refs)):
+        a0 = int(lat.arc_off[b])
         mp = ref["mp"]
         assert best[b:b + 1].view(np.int32)[0] == mp["best"].view(np.int32), (tag, b, best[b], mp["best"])
         n = len(mp["arcs"])
         assert lens[b] == n, (tag, b)
         assert np.array_equal(arcs[b, :n] - a0, mp["arcs"]) and np.array_equal(paths[b, :n], mp["labels"]), (tag, b)
         assert np.all(paths[b, n:] == PAD) and np.all(arcs[b, n:] == -1), (tag, b)
+
+
+def check(tag, lat, lats, r, v, refs, T):
+    check_sum(tag, lat, lats, r, refs, T)
+    check_vit(tag, lat, lats, v, refs, T)
 
 
 def _all_T(lats):
@@ -423,3 +437,343 @@ def test_length_distribution_and_scorer_methods(dev):
     assert torch.equal(v.best, ops.positional_viterbi(lat, theta, pos.detach(), pad=PAD).best)
     logp, _ = sc.length_distribution()
     assert torch.equal(logp, ops.length_distribution(lat, theta)[0])
+
+
+# =============================================================================================================
+# Every launch branch (inputs: the positional section of tests/edge_cases.py; tests/test_positional_cpu.py proves on the
+# reference and the plan query alone that they are what the cases need).  ops.positional_plan is the rule the launchers
+# themselves call, so "staged" below is what the launch took.
+_CACHE = {}
+
+
+def cached(key, make):
+    if key not in _CACHE:
+        _CACHE[key] = make()
+    return _CACHE[key]
+
+
+def large(which, weighted=False):
+    """`big` or `mid` of tests/edge_cases.py and its longest path, built once per module (nothing here changes a lattice)."""
+    def make():
+        l = E.pos_large(which, weighted)
+        return l, R.min_max_len(l)[1]
+    return cached(("large", which, weighted), make)
+
+
+def staged(lat):
+    """(nfst_positional stages its arcs, nfst_positional_viterbi does)."""
+    return ops.positional_plan(lat, False)[1], ops.positional_plan(lat, True)[1]
+
+
+def out_bits(lat, lats, r, v):
+    """Per lattice, every output as raw bytes (path_arcs relative to the lattice)."""
+    z64, z32, ll, pp, ap = (None if x is None else x.cpu().numpy() for x in (r.logz64, r.logz, r.len_logz, r.pos_posterior, r.arc_posterior))
+    best, paths, arcs, lens = (x.cpu().numpy() for x in v)
+    out = []
+    for b, l in enumerate(lats):
+        a0 = int(lat.arc_off[b])
+        rel = np.where(arcs[b] >= 0, arcs[b] - a0, -1).astype(np.int32)
+        per = dict(logz64=z64[b:b + 1], logz=z32[b:b + 1], best=best[b:b + 1], paths=paths[b], lengths=lens[b:b + 1], path_arcs=rel)
+        if ll is not None:
+            per["len_logz"] = ll[b]
+        if pp is not None:
+            per["pos_posterior"] = pp[b]
+        if ap is not None:
+            per["arc_posterior"] = ap[a0:a0 + l.n_arcs]
+        out.append({k: np.ascontiguousarray(x).view(np.uint8).copy() for k, x in per.items()})
+    return out
+
+
+def same_bits(x, y, where):
+    assert x.keys() == y.keys(), where
+    for k in x:
+        assert np.array_equal(x[k], y[k]), (where, k)
+
+
+ALL_OUTPUTS = {"logz64", "logz", "len_logz", "pos_posterior", "arc_posterior", "best", "paths", "lengths", "path_arcs"}
+
+
+# ----------------------------------------------------------------------------- (a) the STAGED = false flavours
+def _large_case(which, variant):
+    """(lats, theta, pos, asc, T): `big` beside a 13-row neighbour, or `mid` alone, at its longest path.  Every variant
+    has inputs of its own (no table, a shared one, one per lattice, extras), so each has a reference of its own."""
+    weighted = variant == "extras"
+    l, T = large(which, weighted)
+    lats = [l] + ([cached(("neighbour", weighted), lambda: E.pos_neighbour(weighted=weighted))] if which == "big" else [])
+    theta, pos = _inputs(lats, 270 + len(variant), T, shared_pos=variant == "shared", shared_theta=variant != "per lattice")
+    if variant == "no pos":
+        pos = None
+    asc = np.random.default_rng(271).normal(0.0, 0.3, size=sum(l.n_arcs for l in lats)).astype(np.float32) if weighted else None
+    return lats, theta, pos, asc, T
+
+
+@pytest.mark.parametrize("variant", ["no pos", "shared", "per lattice", "extras"])
+@pytest.mark.parametrize("which", ["big", "mid"])
+def test_unstaged_flavours(dev, which, variant):
+    """k_positional<EXTRA, false> and k_positional_viterbi<false> (PosArcsGlobal, the forward pass over in_ptr / in_rec of
+    the workspace) against the reference; on `mid` the sum-product reads the canonical arrays while max-plus stages."""
+    lats, theta, pos, asc, T = _large_case(which, variant)
+    assert T == (62 if which == "big" else 57)
+    lat = LatticeBatch.from_synth(lats, device=dev)
+    assert staged(lat) == ((False, False) if which == "big" else (False, True))
+    assert (lat.weighted != 0) == (variant == "extras")
+    refs = reference(lat, lats, theta, pos, T, asc)
+    assert all(np.isfinite(x["logz"]) for x in refs)
+    if which == "big":
+        assert np.isfinite(refs[0]["len_logz"]).sum() == 41
+    r, v = run(lat, theta, pos, T, dev, asc)
+    check(f"unstaged.{which}.{variant}", lat, lats, r, v, refs, T)
+
+
+# ----------------------------------------------------------------------------- (b) staged and unstaged: the same bits
+def degree_classes():
+    return list(cached("degree classes", E.pos_degree_classes))
+
+
+def shared_lattices():  # the six small lattices and the degree classes at one vocabulary
+    return list(cached("shared", lambda: [dataclasses.replace(l, vocab=E.POS_V) for l in small_lattices()] + degree_classes()))
+
+
+@pytest.mark.parametrize("extras", [False, True])
+def test_staged_and_unstaged_give_the_same_bits(dev, extras):
+    """"the same bits".  The same lattices and inputs in a batch whose arcs are staged in LDS and, beside
+    `big`, in one that reads the canonical arrays."""
+    lats = shared_lattices()
+    assert all(l.vocab == E.POS_V for l in lats)
+    big = large("big")[0]
+    T = cached("shared T", lambda: max(R.min_max_len(l)[1] for l in lats))
+    theta, pos = _inputs(lats + [big], 280, T)
+    n = sum(l.n_arcs for l in lats)
+    asc = np.random.default_rng(281).normal(0.0, 0.3, size=n + big.n_arcs).astype(np.float32) if extras else None
+    lat_s = LatticeBatch.from_synth(lats, device=dev)
+    lat_u = LatticeBatch.from_synth(lats + [big], device=dev)
+    assert staged(lat_s) == (True, True) and staged(lat_u) == (False, False)
+    rs, vs = run(lat_s, theta, pos[:-1], T, dev, None if asc is None else asc[:n])
+    ru, vu = run(lat_u, theta, pos, T, dev, asc)
+    bs, bu = out_bits(lat_s, lats, rs, vs), out_bits(lat_u, lats, ru, vu)
+    for b in range(len(lats)):
+        assert set(bs[b]) == ALL_OUTPUTS
+        same_bits(bs[b], bu[b], b)
+    refs = reference(lat_s, lats, theta, pos[:-1], T, None if asc is None else asc[:n])
+    check(f"bits.{int(extras)}", lat_s, lats, rs, vs, refs, T)
+    assert sum(np.isfinite(x["logz"]) for x in refs) == len(lats)
+
+
+# ----------------------------------------------------------------------------- (c) every group size
+def test_every_group_size(dev):
+    """G = 8, 16 and 32 (by the mean degree alone and through the widening loop) against the reference, at the longest
+    path and at a truncation; with the other batches of this file every G the kernel can choose."""
+    lats = degree_classes()
+    lat = LatticeBatch.from_synth(lats, device=dev)
+    groups = R.batch_groups(lat)
+    assert groups == [g for _, g in E.POS_DEGREE_CLASSES.values()] and {8, 16, 32} == set(groups)
+    everything = set(groups)
+    for other in (small6(), E.mixed_batch(), [large("big")[0]], E.packing_lattices()):
+        everything |= set(R.batch_groups(LatticeBatch.from_synth(other)))
+    assert everything == {1, 2, 4, 8, 16, 32, 64}
+    hi = max(R.min_max_len(l)[1] for l in lats)
+    assert hi == 17
+    for T in (hi, 6):
+        theta, pos = _inputs(lats, 290 + T, T)
+        refs = reference(lat, lats, theta, pos, T)
+        live = [np.isfinite(x["logz"]) for x in refs]
+        assert all(live) if T == hi else (any(live) and not all(live))
+        r, v = run(lat, theta, pos, T, dev)
+        check(f"groups.{T}", lat, lats, r, v, refs, T)
+
+
+# ----------------------------------------------------------------------------- (d) output subsets, need_alpha == 0
+def test_output_subsets(dev, monkeypatch):
+    lats = E.mixed_batch()
+    lat = LatticeBatch.from_synth(lats, device=dev)
+    T = 46
+    theta_np, pos_np = _inputs(lats, 300, T)  # (NaN in the pad column: no subset of the outputs may read it)
+    theta, pos = torch.from_numpy(theta_np).to(dev), torch.from_numpy(pos_np).to(dev)
+    seen = []
+    real = ops._positional_ws
+
+    def spy(lat, T, flags):
+        ws, n = real(lat, T, flags)
+        seen.append((flags, n))
+        return ws, n
+
+    monkeypatch.setattr(ops, "_positional_ws", spy)
+    full = ops.positional_forward_backward(lat, theta, pos, want_pos_posterior=True, want_arc_posterior=True, want_len=True)
+    refs = reference(lat, lats, theta_np, pos_np, T)
+    check_sum("subsets", lat, lats, full, refs, T)
+    eq = lambda x, y: torch.equal(x.view(torch.uint8), y.view(torch.uint8))
+    for want in range(8):
+        wp, wa, wl = bool(want & 1), bool(want & 2), bool(want & 4)
+        r = ops.positional_forward_backward(lat, theta, pos, want_pos_posterior=wp, want_arc_posterior=wa, want_len=wl)
+        assert eq(r.logz64, full.logz64) and eq(r.logz, full.logz), want
+        for got, ref, on in ((r.pos_posterior, full.pos_posterior, wp), (r.arc_posterior, full.arc_posterior, wa), (r.len_logz, full.len_logz, wl)):
+            assert (got is not None) == on, want
+            if on:
+                assert eq(got, ref), want
+        if want == 0:  # log Z only: the flags-0 workspace of 12 bytes per arc, no stored rows
+            flags, n = seen[-1]
+            small = _lib.lib.nfst_positional_ws_bytes(C.byref(lat.c_struct()), T, 0)
+            assert flags == 0 and n == small and 12 * lat.total_arcs <= small < 12 * lat.total_arcs + 2 * 256 + 1
+            assert small < 12 * (T + 1) * lat.total_rows <= _lib.lib.nfst_positional_ws_bytes(C.byref(lat.c_struct()), T, 1)
+        else:
+            assert seen[-1][0] == 1
+    z = ops.positional_log_z(lat, theta, pos)  # nothing requires a gradient: log Z only
+    assert seen[-1][0] == 0 and not z.requires_grad
+    assert eq(z, full.logz)
+
+
+# ----------------------------------------------------------------------------- (e) every packing, chunked programs
+PACKING_A, PACKING_B = 0, 3  # the default packing and (group_mode=1, slots_per_lane=1): 412 and 430 rows
+
+
+def _packing_case():
+    lats = E.packing_lattices()
+    T = max(R.min_max_len(l)[1] for l in lats)
+    theta, pos = _inputs(lats, 310, T)
+    lat = LatticeBatch.from_synth(lats)
+    return lats, theta, pos, T, reference(lat, lats, theta, pos, T)
+
+
+@pytest.mark.parametrize("i", range(len(E.STAR_PACKINGS)), ids=[str(i) for i in range(len(E.STAR_PACKINGS))])
+def test_every_packing(dev, i):
+    """The kernels read the canonical arrays only, but max_rows -- the stride of the two LDS rows and of every LDS carve-up
+    -- is the packing's (scratch rows).  Fan-out 200 and fan-in 200 at G = 1."""
+    lats, theta, pos, T, refs = cached("packing", _packing_case)
+    assert T == 15
+    rows = cached("packing rows", lambda: [int(LatticeBatch.from_synth(lats, **o).max_rows) for o in E.STAR_PACKINGS])
+    assert len(set(rows)) >= 2
+    lat = LatticeBatch.from_synth(lats, device=dev, **E.STAR_PACKINGS[i])
+    assert int(lat.max_rows) == rows[i] and R.batch_groups(lat)[:2] == [1, 1]
+    r, v = run(lat, theta, pos, T, dev)
+    check(f"packing.{i}", lat, lats, r, v, refs, T)
+    mine = out_bits(lat, lats, r, v)
+
+    def bits_of(j):  # (run on demand, once per module: the comparison holds whichever cases are selected, in any order)
+        lat_j = LatticeBatch.from_synth(lats, device=dev, **E.STAR_PACKINGS[j])
+        return out_bits(lat_j, lats, *run(lat_j, theta, pos, T, dev))
+
+    # against two fixed packings with different scratch rows: never against this run alone
+    assert rows[PACKING_A] != rows[PACKING_B]
+    for j in (PACKING_A, PACKING_B):
+        other = cached(("packing bits", j), lambda: bits_of(j))
+        for b in range(len(lats)):
+            same_bits(other[b], mine[b], (j, i, b))
+
+
+def test_snips_shaped_batch_with_and_without_chunked_programs(dev):
+    lats = synth.snips_shaped_batch(4, vocab=250)
+    T = max(R.min_max_len(l)[1] for l in lats)
+    theta, pos = _inputs(lats, 320, T)
+    plain = LatticeBatch.from_synth(lats).to(dev, auto_chunks=False)
+    host = LatticeBatch.from_synth(lats)
+    assert host.build_chunks(force=True)
+    chunked = host.to(dev)
+    assert chunked.chunks is not None and plain.chunks is None and plain.device.type == "cuda"
+    refs = reference(plain, lats, theta, pos, T)
+    r1, v1 = run(plain, theta, pos, T, dev)
+    check("snips", plain, lats, r1, v1, refs, T)
+    r2, v2 = run(chunked, theta, pos, T, dev)
+    for b, (x, y) in enumerate(zip(out_bits(plain, lats, r1, v1), out_bits(chunked, lats, r2, v2))):
+        same_bits(x, y, b)
+
+
+# ----------------------------------------------------------------------------- (f) exponent range
+@pytest.mark.parametrize("name", E.RANGE_CASES)
+def test_exponent_range(dev, name):
+    """|log Z| up to 2.6e5: what the (mantissa, exponent) pairs are for."""
+    lats, theta, asc, pos, T = E.pos_range_inputs(name)
+    lat = LatticeBatch.from_synth(lats, device=dev)
+    refs = reference(lat, lats, theta, pos, T, asc)
+    assert max(abs(x["logz"]) for x in refs) > E.RANGE_LOGZ[name]
+    for x in refs:
+        for p in (x["arc_post"], x["pos_post"]):
+            assert np.sum((p > 0.01) & (p < 0.99)) >= E.SPREAD_MIN
+    r, v = run(lat, theta, pos, T, dev, asc)
+    assert all(torch.isfinite(x).all() for x in (r.logz64, r.logz, r.pos_posterior, r.arc_posterior, v.best))
+    check(f"range.{name}", lat, lats, r, v, refs, T)
+
+
+# ----------------------------------------------------------------------------- (g) limits
+def _refused(fn):
+    with pytest.raises(_lib.NfstError) as e:
+        fn()
+    assert e.value.code == -6
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("over", [0, 1])
+def test_row_limit(dev, over):
+    """The most rows nfst_positional takes at vocabulary 256 (160 KiB of LDS to the byte), and one row more: refused
+    on the host, while nfst_positional_viterbi still runs."""
+    lats = E.pos_rowmax_batch(over)
+    lat = LatticeBatch.from_synth(lats, device=dev)
+    assert E.pos_sum_lds(lat.max_rows, lat.vocab) == E.POS_LDS_LIMIT + 24 * over
+    T = 53
+    assert max(R.min_max_len(l)[1] for l in lats) == T
+    theta, pos = _inputs(lats, 330 + over, T)
+    refs = reference(lat, lats, theta, pos, T)
+    t = lambda x: torch.from_numpy(x).to(dev)
+    assert ops.positional_plan(lat, True)[1] is False
+    v = ops.positional_viterbi(lat, t(theta), t(pos), T=T, pad=PAD)
+    check_vit(f"rows+{over}", lat, lats, v, refs, T)
+    fb = lambda: ops.positional_forward_backward(lat, t(theta), t(pos), T=T, want_pos_posterior=True, want_arc_posterior=True, want_len=True)
+    if over:
+        _refused(lambda: ops.positional_plan(lat, False))
+        _refused(fb)
+        _refused(lambda: ops.positional_forward_backward(lat, t(theta), t(pos), T=T, want_pos_posterior=False))
+    else:
+        assert ops.positional_plan(lat, False) == (E.POS_LDS_LIMIT, False)
+        check_sum("rows+0", lat, lats, fb(), refs, T)
+
+
+@pytest.mark.parametrize("over", [0, 1, "max"])
+def test_vocabulary_limit(dev, over):
+    """13 rows: vocabulary 7 970 is the last nfst_positional takes; nfst_positional_viterbi runs up to NFST_MAX_VOCAB,
+    where a staged record carries a label in bits 16 .. 30."""
+    V = E.POS_WIDE_VOCAB if over == "max" else E.pos_vocab_limit(13) + over
+    lats = [E.pos_wide(V)]
+    lat = LatticeBatch.from_synth(lats, device=dev)
+    assert lat.max_rows == 13 and V == {0: 7970, 1: 7971, "max": 32767}[over]
+    T = 6
+    theta, pos = _inputs(lats, 340, T)
+    refs = reference(lat, lats, theta, pos, T)
+    t = lambda x: torch.from_numpy(x).to(dev)
+    assert ops.positional_plan(lat, True)[1] is True
+    v = ops.positional_viterbi(lat, t(theta), t(pos), T=T, pad=PAD)
+    check_vit(f"vocab.{over}", lat, lats, v, refs, T)
+    if over == "max":
+        assert lats[0].label.max() >= 1 << 14
+    fb = lambda: ops.positional_forward_backward(lat, t(theta), t(pos), T=T, want_pos_posterior=True, want_arc_posterior=True, want_len=True)
+    if over:
+        _refused(fb)
+    else:
+        assert ops.positional_plan(lat, False)[1] is False
+        check_sum("vocab.0", lat, lats, fb(), refs, T)
+
+
+# ----------------------------------------------------------------------------- (h) truncation extremes
+@pytest.mark.parametrize("T", [1, 9, 90])
+def test_truncation_extremes(dev, T):
+    """A single-arc lattice beside paths of up to 90 arcs: one position, a truncation that cuts most lattices, all of it."""
+    lats = E.mixed_batch()
+    lat = LatticeBatch.from_synth(lats, device=dev)
+    theta, pos = _inputs(lats, 350 + T, T)
+    refs = reference(lat, lats, theta, pos, T)
+    live = [bool(np.isfinite(x["logz"])) for x in refs]
+    assert live == {1: [False] * 5 + [True], 9: [True, True, False, False, True, True], 90: [True] * 6}[T]
+    r, v = run(lat, theta, pos, T, dev)
+    check(f"trunc.{T}", lat, lats, r, v, refs, T)
+
+
+# ----------------------------------------------------------------------------- (i) exact ties on the walk
+@pytest.mark.parametrize("name", sorted(E.POS_TIE_SEED))
+def test_exact_ties(dev, name):
+    """Scores on the 0.25 grid: float32 sums are exact and candidates tie bit for bit, so "the smallest canonical arc"
+    decides the path (tests/test_positional_cpu.py: it does, on the walked path of these inputs)."""
+    lats, theta, asc, pos, T = E.pos_tie_inputs(name)
+    opts = E.tie_cases()[name][3]
+    lat = LatticeBatch.from_synth(lats, device=dev, **opts)
+    refs = reference(lat, lats, theta, pos, T, asc)
+    assert sum(max(x["mp"]["ties"]) >= 2 for x in refs) >= E.POS_TIE_LATTICES[name]
+    r, v = run(lat, theta, pos, T, dev, asc)
+    check(f"ties.{name}", lat, lats, r, v, refs, T)

@@ -11,6 +11,7 @@ from nfst_amd.scorers import LatticeScorer
 from oracle import oracle as O
 from tests import kbest_ref as K
 from tests import slack_ref as R
+from tests.edge_cases import STAR_PACKINGS
 
 pytestmark = pytest.mark.gpu
 PAD, BOS, EOS = synth.PAD, synth.BOS, synth.EOS
@@ -105,9 +106,7 @@ def test_per_lattice_theta(dev):
     _check("per-lattice", lat, lats, theta, dev)
 
 
-STAR_OPTS = [dict(), dict(group_mode=1), dict(group_mode=2), dict(group_mode=1, slots_per_lane=1), dict(group_mode=2, slots_per_lane=1),
-             dict(group_mode=1, slots_per_lane=2), dict(group_mode=2, slots_per_lane=2), dict(slots_per_lane=4),
-             dict(group_mode=1, slots_per_lane=4, no_compact=True), dict(group_mode=2, slots_per_lane=4, no_compact=True)]
+STAR_OPTS = STAR_PACKINGS  # (the ten packings are data: tests/edge_cases.py; other GPU modules import the name from here)
 
 
 @pytest.mark.parametrize("opts", STAR_OPTS)

@@ -2,14 +2,19 @@
 ops.positional_* rely on: against path enumeration, against finite differences of its own log Z, the identities of the
 semantics at every truncation case, and -- without position scores and with T >= depth -- against
 the oracle's forward-backward and the k-best reference bit for bit.  Then the C entry points' argument checks (host side,
-before any launch) and the register guard of the new kernels."""
+before any launch), the register guard of the new kernels, the plan query the launchers share (nfst_positional_plan)
+against the formulas of include/nfst_hip.h, and the proofs that the inputs of tests/edge_cases.py are what the cases of
+tests/test_gpu_positional.py need: which flavour a batch takes, the group sizes, the exponent range with posteriors that
+have not collapsed, the limits, and scores that tie on the walked path."""
 import ctypes as C
+import dataclasses
 
 import numpy as np
 import pytest
 
 from nfst_amd import synth
 from oracle import oracle as O
+from tests import edge_cases as E
 from tests import kbest_ref as K
 from tests import positional_ref as R
 
@@ -295,3 +300,201 @@ def test_build_guard_covers_the_positional_kernels():
     for name in ("k_positional<true>", "k_positional<false>", "k_positional_viterbi"):
         assert check_resources({name: {"vgpr_spill": 4, "agprs": 0}})
         assert not check_resources({name: {"vgpr_spill": 0, "agprs": 0}})
+
+
+# ----------------------------------------------------------------------------- the plan query and the inputs of the GPU cases
+LDS_LIMIT = 160 * 1024
+
+
+def _pack(lats, **opts):
+    from nfst_amd.lattice import LatticeBatch
+
+    return LatticeBatch.from_synth(lats, **opts)  # host-packed: nothing here touches a device
+
+
+def _plan(lat, viterbi):
+    """(lds_bytes, staged) of ops.positional_plan, or the error code."""
+    from nfst_amd import _lib, ops
+
+    try:
+        return ops.positional_plan(lat, viterbi)
+    except _lib.NfstError as e:
+        return e.code
+
+
+def _plan_by_the_header(lat, lats, viterbi):
+    """The two expressions of include/nfst_hip.h, restated."""
+    R_, V = int(lat.max_rows), int(lat.vocab)
+    lds = 8 * R_ + 4 * V + 16 if viterbi else 24 * R_ + 20 * V + 4112
+    if lds > LDS_LIMIT:
+        return ERR_LIMIT
+    more = 4 * (R_ + 1 + max(l.n_arcs for l in lats)) + 16
+    return (lds + more, True) if lds + more <= LDS_LIMIT else (lds, False)
+
+
+def test_plan_query_is_the_rule_of_the_header():
+    from nfst_amd import _lib
+
+    batches = {"small": small_lattices()[:3], "mixed": E.mixed_batch(), "big": [E.pos_large("big"), E.pos_neighbour()],
+               "mid": [E.pos_large("mid")], "degrees": E.pos_degree_classes(), "rowmax": E.pos_rowmax_batch(),
+               "rowmax + 1": E.pos_rowmax_batch(1), "wide": [E.pos_wide()], "7000 rows": [
+                   synth.layered_lattice(5, n_states=7000, avg_degree=2.0, vocab=16, width=8, span=2, max_degree=4)]}
+    seen = set()
+    for name, lats in batches.items():
+        lat = _pack(lats)
+        for viterbi in (False, True):
+            got = _plan(lat, viterbi)
+            assert got == _plan_by_the_header(lat, lats, viterbi), (name, viterbi, got)
+            seen.add((viterbi, got if got == ERR_LIMIT else got[1]))
+    assert seen == {(False, True), (False, False), (False, ERR_LIMIT), (True, True), (True, False)}
+    # either output may be null; a null batch is an argument error
+    lat = _pack(batches["small"])
+    bs = C.byref(lat.c_struct())
+    lds, staged = C.c_int64(-1), C.c_int32(-1)
+    assert _lib.lib.nfst_positional_plan(bs, 0, None, None) == 0
+    assert _lib.lib.nfst_positional_plan(bs, 0, C.byref(lds), None) == 0 and lds.value == _plan(lat, False)[0]
+    assert _lib.lib.nfst_positional_plan(bs, 7, None, C.byref(staged)) == 0 and staged.value == 1
+    assert _lib.lib.nfst_positional_plan(None, 0, C.byref(lds), C.byref(staged)) == ERR_ARG
+
+
+def test_large_lattices_take_the_unstaged_flavours():
+    """big: neither kernel stages its arcs; mid: the sum-product does not, max-plus does.  With table weights (the
+    EXTRA flavours) the same."""
+    for weighted in (False, True):
+        big, mid = E.pos_large("big", weighted), E.pos_large("mid", weighted)
+        assert (big.n_rows, big.n_arcs, R.min_max_len(big)) == (481, 42718, (22, 62))
+        assert (mid.n_rows, mid.n_arcs, R.min_max_len(mid)[1]) == (441, 39105, 57)
+        assert (big.weight is not None) == weighted
+        lat = _pack([big, E.pos_neighbour(weighted=weighted)])
+        assert E.pos_neighbour().n_rows == 13 and bool(lat.weighted) == weighted
+        assert _plan(lat, False)[1] is False and _plan(lat, True)[1] is False
+        assert R.batch_groups(lat) == [64, 2]
+        lat = _pack([mid])
+        assert _plan(lat, False)[1] is False and _plan(lat, True)[1] is True
+
+
+def test_big_has_many_path_lengths():
+    big = E.pos_large("big")
+    T = 62
+    theta, pos = _inputs(big, 27, T)
+    ref = R.sum_product(big, R.arc_score64(big, theta), pos, T)
+    assert np.isfinite(ref["len_logz"]).sum() == 41 and np.isfinite(ref["logz"])
+
+
+def test_pos_group_restatement_and_the_degree_classes():
+    """Every width of the butterfly, 8, 16 and 32 both by the mean degree alone and through the widening loop; with the
+    other inputs of tests/test_gpu_positional.py every G of the kernel."""
+    from nfst_amd import _lib
+
+    assert [R.pos_group(d * 100, 100, 5000) for d in (0, 1, 2, 3, 4, 7, 8, 31, 32, 63, 64, 1000)] == [1, 1, 2, 2, 4, 4, 8, 16, 32, 32, 64, 64]
+    assert R.pos_group(500, 100, 200) == 4 and R.pos_group(500, 100, 128) == 8  # 5 arcs per state: widened while 2 G rows <= 1024
+    assert R.pos_group(300, 100, 10) == 4 and R.pos_group(100, 0, 1) == 64
+    lats = E.pos_degree_classes()
+    lat = _pack(lats)
+    m = lat.meta_host
+    for b, ((n, d), (g_mean, g)) in enumerate(E.POS_DEGREE_CLASSES.items()):
+        avg = int(m[b, _lib.META_N_DP]) // int(m[b, _lib.META_N_REACH])
+        assert lats[b].n_rows == n + 1 == m[b, _lib.META_N_ROWS]
+        assert g_mean <= avg < 2 * g_mean, (n, d, avg)
+        assert R.batch_groups(lat)[b] == g, (n, d)
+    got = set(E.POS_DEGREE_CLASSES.values())
+    assert {8, 16, 32} <= {g for g0, g in got if g0 == g} and {8, 16, 32} <= {g for g0, g in got if g0 < g}
+    assert _plan(lat, False)[1] is True and _plan(lat, True)[1] is True
+    everything = set(R.batch_groups(lat))
+    small = [dataclasses.replace(l, vocab=E.POS_V) for l in small_lattices()]
+    for other in (small, E.mixed_batch(), [E.pos_large("big")], E.packing_lattices()):
+        everything |= set(R.batch_groups(_pack(other)))
+    assert everything == {1, 2, 4, 8, 16, 32, 64}
+    # fan-out 200 and fan-in 200 at one lane per state
+    star, funnel = E.packing_lattices()[:2]
+    assert R.batch_groups(_pack([star, funnel])) == [1, 1]
+    assert np.bincount(star.src).max() == 200 and np.bincount(funnel.dst).max() == 200
+
+
+def test_staged_and_unstaged_batches_of_the_bit_comparison():
+    shared = [dataclasses.replace(l, vocab=E.POS_V) for l in small_lattices()] + E.pos_degree_classes()
+    lat = _pack(shared)
+    assert _plan(lat, False)[1] is True and _plan(lat, True)[1] is True
+    lat = _pack(shared + [E.pos_large("big")])
+    assert _plan(lat, False)[1] is False and _plan(lat, True)[1] is False
+
+
+def test_row_and_vocabulary_limits():
+    lats = E.pos_rowmax_batch()
+    lat = _pack(lats)
+    assert E.pos_sum_lds(lat.max_rows, lat.vocab) == LDS_LIMIT and lat.vocab == 256  # the last byte
+    assert _plan(lat, False) == (LDS_LIMIT, False) and _plan(lat, True)[1] is False
+    assert R.min_max_len(lats[0]) == (16, 53)
+    over = _pack(E.pos_rowmax_batch(1))
+    assert over.max_rows == lat.max_rows + 1
+    assert _plan(over, False) == ERR_LIMIT and _plan(over, True)[1] is False
+    l = E.pos_wide(64)
+    V = E.pos_vocab_limit(_pack([l]).max_rows)
+    assert l.n_rows == 13 and V == 7970
+    lat = _pack([E.pos_wide(V)])
+    assert lat.max_rows == 13 and E.pos_sum_lds(13, V) <= LDS_LIMIT < E.pos_sum_lds(13, V + 1)
+    assert _plan(lat, False)[1] is False and _plan(lat, True)[1] is True
+    lat = _pack([E.pos_wide(V + 1)])
+    assert lat.max_rows == 13 and _plan(lat, False) == ERR_LIMIT and _plan(lat, True)[1] is True
+    w = E.pos_wide()
+    assert (w.vocab, w.n_rows, w.n_arcs, int(w.label.max()), R.min_max_len(w)) == (32767, 13, 28, 30650, (4, 6))
+    assert w.label.max() >= 1 << 14  # bit 30 of a staged record
+    lat = _pack([w])
+    assert _plan(lat, False) == ERR_LIMIT and _plan(lat, True)[1] is True
+
+
+@pytest.mark.parametrize("name", E.RANGE_CASES)
+def test_range_inputs_reach_the_exponents_without_collapsing(name):
+    lats, theta, asc, pos, T = E.pos_range_inputs(name)
+    assert T == max(R.min_max_len(l)[1] for l in lats) and pos.shape == (len(lats), T, lats[0].vocab)
+    big = 0.0
+    for b, (l, sl) in enumerate(zip(lats, E.arc_slices(lats))):
+        ref = R.sum_product(l, R.arc_score64(l, theta, asc[sl]), pos[b], T)
+        assert np.isfinite(ref["logz"])
+        big = max(big, abs(ref["logz"]))
+        for p in (ref["arc_post"], ref["pos_post"]):
+            assert np.sum((p > 0.01) & (p < 0.99)) >= E.SPREAD_MIN, (name, b)
+        assert check_identities(l, ref, T) <= 1e-9
+    assert big > E.RANGE_LOGZ[name]
+
+
+@pytest.mark.parametrize("name", sorted(E.POS_TIE_SEED))
+def test_tie_inputs_tie_on_the_walked_path(name):
+    """At some step of the reference's walk at least two live arcs of the walked state attain vb_t(state): the rule
+    "the smallest canonical arc" decides the path."""
+    lats, theta, asc, pos, T = E.pos_tie_inputs(name)
+    assert np.array_equal(pos, E.quarter(pos)) and np.array_equal(theta, E.quarter(theta))
+    tied = 0
+    for b, (l, sl) in enumerate(zip(lats, E.arc_slices(lats))):
+        mp = R.max_plus(l, theta, pos[b], T, None if asc is None else asc[sl])
+        assert np.isfinite(mp["best"]) and len(mp["ties"]) == len(mp["arcs"])
+        if max(mp["ties"]) >= 2:
+            tied += 1
+            t = int(np.argmax(np.asarray(mp["ties"]) >= 2))  # the walk took the smallest of the tied arcs
+            st = int(l.src[mp["arcs"][t]])
+            c = {a: _candidate(l, theta, pos[b], None if asc is None else asc[sl], mp["vb"], t, a)
+                 for a in np.nonzero((l.src == st) & (l.dst != st))[0]}
+            top = [a for a, x in c.items() if x == mp["vb"][t, st]]
+            assert len(top) == mp["ties"][t] and mp["arcs"][t] == min(top)
+    assert tied >= E.POS_TIE_LATTICES[name] >= 1
+
+
+def _candidate(l, theta, pos, asc, vb, t, a):
+    e = np.float32(0.0)
+    if l.weight is not None:
+        e = np.float32(e + np.float32(l.weight[a]))
+    if asc is not None:
+        e = np.float32(e + np.float32(asc[a]))
+    return np.float32(e + np.float32(np.float32(theta[l.label[a]] + pos[t, l.label[a]]) + vb[t + 1, l.dst[a]]))
+
+
+def test_packings_change_the_scratch_rows():
+    assert len(E.STAR_PACKINGS) == 10
+    rows = [int(_pack(E.packing_lattices(), **opts).max_rows) for opts in E.STAR_PACKINGS]
+    assert len(set(rows)) >= 2 and max(rows) > min(rows) >= max(l.n_rows for l in E.packing_lattices())
+
+
+def test_mixed_batch_has_the_truncation_extremes():
+    lens = [R.min_max_len(l) for l in E.mixed_batch()]
+    assert min(lo for lo, _ in lens) == 1 and max(hi for _, hi in lens) == 90
+    assert E.mixed_batch()[-1].n_arcs - 1 == 1  # one arc and the sink's pad loop

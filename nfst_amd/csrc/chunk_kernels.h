@@ -377,7 +377,7 @@ __global__ __launch_bounds__(256) void k_chunk_post(nfst_batch lat, nfst_scores 
         const int ee = max(va[j].e + x.e + vb[j].e - z.e, -4000);  // (zeros carry kEZero: far below, never wraps)
         p = (float)ldexp(mm, min(ee, 4000));
       }
-      if (posterior) __builtin_nontemporal_store(p, posterior + a[j]);
+      if (posterior) out_store4_bulk(posterior + a[j], p);  // (4 bytes per lane; out_store.h)
       if (grad_theta && p > 0.0f) atomicAdd(&gth[lab[j]], p);
     }
   }

@@ -30,6 +30,46 @@ struct LdsPlan {
 // per CU those phases are latency-bound and get 16 waves; with several lattices per CU the
 // co-resident workgroups hide each other's latencies and 4 waves are cheaper.
 
+// ------------------------------------------------------------------ row outputs
+// log alpha, log beta and the (mantissa, exponent) pairs of beta of one lattice's rows, from LDS.  Every thread converts
+// four consecutive rows and stores 16 bytes per array (beta_me: 2 x 16) over the aligned interior of the lattice's row
+// range, as the arc pass does; the at most 3 + 3 rows in front of and behind it go out one by one.  Pointers that are
+// not 16-byte aligned take the scalar route for every row.
+template <int NT, class VT>
+__device__ __forceinline__ void store_rows(const VT *alpha, const VT *beta, int row_off, int n_rows, int tid,
+                                           float *logalpha, float *logbeta, float2 *beta_me) {
+  if (!logalpha && !logbeta && !beta_me) return;
+  const int r_lo = row_off, r_hi = row_off + n_rows;
+  const bool wide = (((uintptr_t)logalpha | (uintptr_t)logbeta | (uintptr_t)beta_me) & 15) == 0;
+  const int v_lo = wide ? (r_lo + 3) & ~3 : r_hi, v_hi = wide ? r_hi & ~3 : r_hi;
+  for (int r = v_lo + 4 * tid; r < v_hi; r += 4 * NT) {
+    const int i = r - r_lo;
+    if (logalpha) out_store16(logalpha + r, make_float4(me_log32(alpha[i]), me_log32(alpha[i + 1]), me_log32(alpha[i + 2]), me_log32(alpha[i + 3])));
+    if (logbeta || beta_me) {
+      const float2 b0 = me_f2(beta[i]), b1 = me_f2(beta[i + 1]), b2 = me_f2(beta[i + 2]), b3 = me_f2(beta[i + 3]);
+      if (logbeta) out_store16(logbeta + r, make_float4(me_log32(b0), me_log32(b1), me_log32(b2), me_log32(b3)));
+      if (beta_me) {
+        out_store16(reinterpret_cast<float *>(beta_me + r), make_float4(b0.x, b0.y, b1.x, b1.y));
+        out_store16(reinterpret_cast<float *>(beta_me + r + 2), make_float4(b2.x, b2.y, b3.x, b3.y));
+      }
+    }
+  }
+  // head [r_lo, min(v_lo, r_hi)) and tail [v_hi, r_hi) (no tail when the interior is empty: the head has every row);
+  // without 16-byte stores v_lo = v_hi = r_hi: every row is "head"
+  const int n_head = min(v_lo, r_hi) - r_lo;
+  const int n_tail = (v_hi >= v_lo) ? r_hi - v_hi : 0;
+  for (int k = tid; k < n_head + n_tail; k += NT) {
+    const int r = k < n_head ? r_lo + k : v_hi + (k - n_head), i = r - r_lo;
+    if (logalpha) out_store4(logalpha + r, me_log32(alpha[i]));
+    if (logbeta) out_store4(logbeta + r, me_log32(beta[i]));
+    if (beta_me) {
+      const float2 bv = me_f2(beta[i]);
+      out_store4(reinterpret_cast<float *>(beta_me + r), bv.x);
+      out_store4(reinterpret_cast<float *>(beta_me + r) + 1, bv.y);
+    }
+  }
+}
+
 // ------------------------------------------------------------------ backward only
 // Wave 0 sweeps the by-source program from the sink, wave 1 decodes for it, wave 2 loads
 // for the decoder; with per-arc extras the last four (two) waves are the extras waves; every wave
@@ -105,10 +145,7 @@ __global__ __launch_bounds__(NT) void k_backward(nfst_batch lat, nfst_scores sc,
     if (logz64) logz64[b] = z;
     if (logz32) logz32[b] = (float)z;
   }
-  for (int i = tid; i < m.n_rows; i += NT) {
-    if (logbeta) logbeta[m.row_off + i] = me_log32(beta[i]);
-    if (beta_me) beta_me[m.row_off + i] = me_f2(beta[i]);
-  }
+  store_rows<NT, VT>(nullptr, beta, m.row_off, m.n_rows, tid, nullptr, logbeta, beta_me);
 }
 
 // ------------------------------------------------------------------ forward-backward
@@ -263,7 +300,11 @@ __global__ __launch_bounds__(NT) void k_forward_backward(
   // posterior pass starts on data that is already there.
   constexpr int kSweepThreads = 256;
   constexpr int kHelpers = NT - kSweepThreads;
-  constexpr int kPre = (kHelpers > 0) ? 7 : 0;  // 7 x 768 x 4 = 21.5k arcs: a whole BASELINE lattice
+  // 7 x 768 x 4 = 21.5k arcs: the median BASELINE lattice (8 - 16 % of them have up to 760 arcs more: the remainder loop.
+  // 8 or 9 groups chosen from the batch's largest lattice, with the remainder's first loads in front of the barrier, took
+  // the remainder's 1.6 - 1.9 us off those workgroups and nothing measurable off the launch: DESIGN.md section 4.1)
+  constexpr int kPre = (kHelpers > 0) ? 7 : 0;
+  constexpr int kPB = 4;  // arc groups per iteration of the remainder loop
   // src | dst << 16 and the label of 4 consecutive canonical arcs: 16 + 8 bytes
   uint4 psd[kPre > 0 ? kPre : 1];
   uint2 plb[kPre > 0 ? kPre : 1];
@@ -353,19 +394,47 @@ __global__ __launch_bounds__(NT) void k_forward_backward(
     const int xev[4] = {xe.x, xe.y, xe.z, xe.w};
     const uint32_t sdv[4] = {sd.x, sd.y, sd.z, sd.w};
     const int ll[4] = {(int)(lb.x & 0xffffu), (int)(lb.x >> 16), (int)(lb.y & 0xffffu), (int)(lb.y >> 16)};
+    // The twelve gathers of the group first, for every arc (a self loop's rows are rows of the lattice like any other),
+    // then the arithmetic, a self loop's result replaced by zero: written as `s0 != d0 ? posterior(gathers) : 0` each arc
+    // became a branch around its own three LDS reads and a full wait for them -- four dependent LDS round trips per group,
+    // 28 per helper thread: 4.4 -> 3.4 us between the barrier and a helper wave's last store (profiles/epilogue_stamps*.txt).
+    // (with per-arc extras the kernels are at 116 of 128 registers: two arcs' gathers at a time there; the flavours with
+    // several workgroups per CU hide each other's round trips and keep their registers, i.e. their occupancy: one arc)
+    constexpr int kG = NT != 1024 ? 1 : has_extra ? 2 : 4;
     float pp[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int s0 = (int)(sdv[q] & 0xffffu), d0 = (int)(sdv[q] >> 16);
-      pp[q] = (s0 != d0) ? arc_posterior(me_f2(alpha[s0]), me_f2(beta[d0]), me_f2(th[ll[q]]), rz, ez, has_extra, xmv[q], xev[q]) : 0.0f;
-      if (grad_theta && pp[q] > 0.0f) atomicAdd(&gth[ll[q]], pp[q]);
+    for (int q0 = 0; q0 < 4; q0 += kG) {
+      float2 av[kG], bv[kG], tv[kG];
+#pragma unroll
+      for (int q = 0; q < kG; ++q) {
+        av[q] = me_f2(alpha[(int)(sdv[q0 + q] & 0xffffu)]);
+        bv[q] = me_f2(beta[(int)(sdv[q0 + q] >> 16)]);
+        tv[q] = me_f2(th[ll[q0 + q]]);
+      }
+#pragma unroll
+      for (int q = 0; q < kG; ++q) {
+        const float p = arc_posterior(av[q], bv[q], tv[q], rz, ez, has_extra, xmv[q0 + q], xev[q0 + q]);
+        pp[q0 + q] = ((sdv[q0 + q] & 0xffffu) != (sdv[q0 + q] >> 16)) ? p : 0.0f;
+      }
     }
-    if (posterior) {
-      // non-temporal: nobody reads the 20 MB of posteriors back inside this launch, and as ordinary stores they went through
-      // the L2 in one burst behind the barrier (39.6 -> 38.6 us cold, 36.0 -> 34.8 replayed; profiles/tune/ab_variants.sh)
-      typedef float f4v __attribute__((ext_vector_type(4)));
-      __builtin_nontemporal_store(f4v{pp[0], pp[1], pp[2], pp[3]}, reinterpret_cast<f4v *>(posterior + a));
+    if (grad_theta) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (pp[q] > 0.0f) atomicAdd(&gth[ll[q]], pp[q]);
     }
+    // (out_store.h; non-temporal by default: nobody reads the 20 MB of posteriors back inside this launch, and as ordinary
+    // stores they went through the L2 in one burst behind the barrier: 39.6 -> 38.6 us cold, 36.0 -> 34.8 replayed)
+    if (posterior) out_store16(posterior + a, make_float4(pp[0], pp[1], pp[2], pp[3]));
+  };
+  // a group whose extras are still logarithms
+  auto do_group_x = [&](const uint4 sd, const uint2 lb, int a, const float4 x) {
+    float4 gm = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+    int4 ge = make_int4(0, 0, 0, 0);
+    if (has_extra) {
+      exp_me_fast(x.x, gm.x, ge.x); exp_me_fast(x.y, gm.y, ge.y);
+      exp_me_fast(x.z, gm.z, ge.z); exp_me_fast(x.w, gm.w, ge.w);
+    }
+    do_group(sd, lb, a, gm, ge);
   };
   if (kPre > 0 && tid >= kSweepThreads && want_post) {
 #pragma unroll
@@ -374,17 +443,14 @@ __global__ __launch_bounds__(NT) void k_forward_backward(
       if (a < v_end) do_group(psd[u], plb[u], a, pxm[u], pxe[u]);
     }
   }
+  if (TW && wv == 10) NFST_STAMP(8);  // a helper wave (not a tile wave) has issued the stores of its preloaded groups
   // the row outputs: every thread (the sweep waves start here, the others come when their preloaded
   // arc groups are done)
-  for (int i = tid; i < m.n_rows; i += NT) {
-    if (logalpha) __builtin_nontemporal_store(me_log32(alpha[i]), logalpha + m.row_off + i);
-    if (logbeta) __builtin_nontemporal_store(me_log32(beta[i]), logbeta + m.row_off + i);
-    if (beta_me) beta_me[m.row_off + i] = me_f2(beta[i]);
-  }
+  store_rows<NT, VT>(alpha, beta, m.row_off, m.n_rows, tid, logalpha, logbeta, beta_me);
+  if (tid == 0) NFST_STAMP(9);
   if (want_post) {
     // the arc groups that were not preloaded: kPB groups per iteration, all loads issued
     // before the first use
-    constexpr int kPB = 4;
     for (int a0 = v_begin + 4 * (kPre * kHelpers + tid); a0 < v_end; a0 += NT * 4 * kPB) {
       uint4 sd[kPB];
       uint2 lb[kPB];
@@ -400,15 +466,10 @@ __global__ __launch_bounds__(NT) void k_forward_backward(
       for (int u = 0; u < kPB; ++u) {
         const int a = a0 + u * NT * 4;
         if (a >= v_end) break;
-        float4 gm = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
-        int4 ge = make_int4(0, 0, 0, 0);
-        if (has_extra) {
-          exp_me_fast(xe[u].x, gm.x, ge.x); exp_me_fast(xe[u].y, gm.y, ge.y);
-          exp_me_fast(xe[u].z, gm.z, ge.z); exp_me_fast(xe[u].w, gm.w, ge.w);
-        }
-        do_group(sd[u], lb[u], a, gm, ge);
+        do_group_x(sd[u], lb[u], a, xe[u]);
       }
     }
+    if (tid == 0) NFST_STAMP(10);
     // unaligned head and tail (at most 3 arcs each)
     const int n_head = min(v_begin, a_end) - a_begin;
     const int n_tail = (v_end >= v_begin) ? a_end - v_end : 0;
@@ -419,16 +480,22 @@ __global__ __launch_bounds__(NT) void k_forward_backward(
       int he = 0;
       if (has_extra) exp_me_fast(kCached ? xc[a - xc_first] : ex.at(a), hm, he);
       const float p = (s0 != d0) ? arc_posterior(me_f2(alpha[s0]), me_f2(beta[d0]), me_f2(th[l0]), rz, ez, has_extra, hm, he) : 0.0f;
-      if (posterior) posterior[a] = p;
+      if (posterior) out_store4(posterior + a, p);
       if (grad_theta && p > 0.0f) atomicAdd(&gth[l0], p);
     }
     if (grad_theta) {
       __syncthreads();
+      // (rows of lat.vocab floats: 16 bytes at a time where the row and the array allow it)
       float *gout = grad_theta + (size_t)b * lat.vocab;
-      for (int l = tid; l < lat.vocab; l += NT) gout[l] = gth[l];
+      if ((lat.vocab & 3) == 0 && ((uintptr_t)grad_theta & 15) == 0) {
+        for (int l = 4 * tid; l < lat.vocab; l += 4 * NT) out_store16(gout + l, make_float4(gth[l], gth[l + 1], gth[l + 2], gth[l + 3]));
+      } else {
+        for (int l = tid; l < lat.vocab; l += NT) out_store4(gout + l, gth[l]);
+      }
     }
   }
 #ifdef NFST_PROF
+  out_store_drain();  // every store of this wave has left the CU, then every wave's
   __syncthreads();
   if (tid == 0) NFST_STAMP(7);
 #endif

@@ -29,6 +29,7 @@ using namespace nfst_tile;
 
 #include "semiring.h"
 #include "tile_pipeline.h"
+#include "out_store.h"
 #include "fb_kernels.h"
 #include "path_kernels.h"
 #include "neural_kernels.h"

@@ -1238,8 +1238,9 @@ __device__ __forceinline__ int tile_math3(const Dec2<U> &c, const v2f (&vv)[U], 
 // addresses are one base plus immediates; tile t's wave is t mod 4, so the four flags -- one 16-byte read -- are
 // checked once per trip for the four tiles the trip fetches; `prog` is published every other tile).
 #ifdef NFST_PROF
-__device__ unsigned long long fb_prof[4096 * 8];  // per workgroup: stamps of the profiling build (profiles/tune/stamps.py)
-#define NFST_STAMP(k) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 4096) fb_prof[blockIdx.x * 8 + (k)] = wall_clock64(); } while (0)
+constexpr int kProfSlots = 16;  // stamps per workgroup of the profiling build (profiles/tune/stamps.py, tail_stamps.py)
+__device__ unsigned long long fb_prof[4096 * kProfSlots];
+#define NFST_STAMP(k) do { if ((threadIdx.x & 63) == 0 && blockIdx.x < 4096) fb_prof[blockIdx.x * kProfSlots + (k)] = wall_clock64(); } while (0)
 #else
 #define NFST_STAMP(k) do { } while (0)
 #endif

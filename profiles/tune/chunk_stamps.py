@@ -24,9 +24,10 @@ for _ in range(5):
 torch.cuda.synchronize()
 raw = C.CDLL(_lib.LIB_PATH)
 n = 2 * B
-buf = np.zeros(n * 8, np.uint64)
-assert raw.nfst_prof_read(buf.ctypes.data_as(C.c_void_p), n * 8) == 0
-t = buf.reshape(n, 8).astype(np.int64)
+S = 16  # stamp slots per workgroup (kProfSlots, tile_pipeline.h)
+buf = np.zeros(n * S, np.uint64)
+assert raw.nfst_prof_read(buf.ctypes.data_as(C.c_void_p), n * S) == 0
+t = buf.reshape(n, S)[:, :8].astype(np.int64)
 own = (t[:, 1:5] - t[:, :4]) / 100.0
 rel_end = (t[:, 4] - t[:, 0].min()) / 100.0
 m = lat.chunks.meta_host.reshape(n, 8)

@@ -18,9 +18,10 @@ for it in range(10 * rot + 1):  # the last launch is batch 0 again, after the ot
     outs[r] = ops.forward_backward(lats[r], theta, out=outs[r])
 torch.cuda.synchronize()
 raw = C.CDLL(_lib.LIB_PATH)
-buf = np.zeros(B * 8, np.uint64)
-assert raw.nfst_prof_read(buf.ctypes.data_as(C.c_void_p), B * 8) == 0
-t = buf.reshape(B, 8).astype(np.int64)
+S = 16  # stamp slots per workgroup (kProfSlots, tile_pipeline.h); the epilogue's slots 8 .. 10: tail_stamps.py
+buf = np.zeros(B * S, np.uint64)
+assert raw.nfst_prof_read(buf.ctypes.data_as(C.c_void_p), B * S) == 0
+t = buf.reshape(B, S)[:, :8].astype(np.int64)
 rel = (t - t[:, 0].min()) / 100.0  # us since the first workgroup's entry
 lat = lats[0]
 tiles = np.maximum(lat.meta_host[:, _lib.META_BWD_TILES], lat.meta_host[:, _lib.META_FWD_TILES])

@@ -72,46 +72,20 @@ __global__ __launch_bounds__(kExpPrepThreads) void k_expect_prep(nfst_batch lat,
   }
 }
 
-// segmented reductions over a state's 2^g lanes (stage partners as seg_max / seg_sum64 of tile_pipeline.h); gmax is
-// the tile's largest g, the same in every lane
-__device__ __forceinline__ int exp_seg_max(int E, int g, int gmax) {
-  if (gmax > 0) { const int o = dpp_i<0xB1>(E); E = (g >= 1) ? max(E, o) : E; }
-  if (gmax > 1) { const int o = dpp_i<0x4E>(E); E = (g >= 2) ? max(E, o) : E; }
-  if (gmax > 2) { const int o = dpp_i<0x141>(E); E = (g >= 3) ? max(E, o) : E; }
-  if (gmax > 3) { const int o = dpp_i<0x140>(E); E = (g >= 4) ? max(E, o) : E; }
-  if (gmax > 4) { const int o = __shfl_xor(E, 16); E = (g >= 5) ? max(E, o) : E; }
-  if (gmax > 5) { const int o = __shfl_xor(E, 32); E = (g >= 6) ? max(E, o) : E; }
-  return E;
-}
-__device__ __forceinline__ void exp_seg_sum2(double &M, double &N, int g, int gmax) {
-#define NFST_EXP_STAGE(S, FN)                       \
-  if (gmax > S) {                                   \
-    const double om = FN(M), on = FN(N);            \
-    M = (g > S) ? M + om : M;                       \
-    N = (g > S) ? N + on : N;                       \
-  }
-#define NFST_SHFL16(x) __shfl_xor(x, 16)
-#define NFST_SHFL32(x) __shfl_xor(x, 32)
-  NFST_EXP_STAGE(0, dpp_d<0xB1>)
-  NFST_EXP_STAGE(1, dpp_d<0x4E>)
-  NFST_EXP_STAGE(2, dpp_d<0x141>)
-  NFST_EXP_STAGE(3, dpp_d<0x140>)
-  NFST_EXP_STAGE(4, NFST_SHFL16)
-  NFST_EXP_STAGE(5, NFST_SHFL32)
-#undef NFST_EXP_STAGE
-#undef NFST_SHFL16
-#undef NFST_SHFL32
-}
+// the two numerators of a row, reduced together; their partner in a stage of the ladder, member by member
+struct ExpSums { double M, N; };
+template <int S>
+__device__ __forceinline__ ExpSums wave_partner(ExpSums x) { return {wave_partner<S>(x.M), wave_partner<S>(x.N)}; }
 
-// Pass 2, grid (B, 2): one workgroup per lattice and direction sweeps the general tile program (the prefetching
-// structure of k_viterbi).  Per row it carries the path mass A as (float64 mantissa, int32 exponent) -- the precise
+// Pass 2, grid (B, 2): one workgroup per lattice and direction sweeps the general tile program (the reader of
+// tile_pipeline.h).  Per row it carries the path mass A as (float64 mantissa, int32 exponent) -- the precise
 // flavour of DESIGN.md section 2, for every program -- and R = E[value of the path so far | the row] in float64:
 //   A(row) = sum_in A(op) w_a,   R(row) = sum_in A(op) w_a (R(op) + v_a) / A(row).
 // A tile's slots and the state's lanes reduce both numerators with one shared exponent; R is the ratio of the two
 // sums, so it stays bounded whatever the path masses.  Carry records and the combine records of tree-summed states
 // (unit label V + 1) have weight one and value zero: they pass the (A, R) of the row they read on unchanged.
 // LDS: 20 bytes per row (16-byte (mantissa, R) record + exponent) + 16: max_rows <= 8191 in 160 KiB.
-constexpr int kExpThreads = 256, kExpAhead = 12;
+constexpr int kExpThreads = 256;
 __global__ __launch_bounds__(kExpThreads) void k_expect_sweep(nfst_batch lat, ExpWs w) {
   extern __shared__ double2 exl[];
   const int b = blockIdx.x, dir = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
@@ -145,7 +119,7 @@ __global__ __launch_bounds__(kExpThreads) void k_expect_sweep(nfst_batch lat, Ex
     double sink_d = 0.0;
     const int prog_lines = (ST * 4 + 127) / 128, wm_lines = (64 * U * 8 + 127) / 128, sv_lines = (64 * U * 4 + 127) / 128;
     for (int T = wv - 1; T < tiles; T += kExpThreads / 64 - 1) {
-      while (T > lds_flag_load(progress) + kExpAhead) __builtin_amdgcn_s_sleep(8);
+      while (T > lds_flag_load(progress) + kTileAhead) __builtin_amdgcn_s_sleep(8);
       if (lane < prog_lines) sink_i += (int)prog[(size_t)T * ST + min(lane * 32, ST - 1)];
       if (lane < wm_lines) sink_d += wm[(size_t)T * 64 * U + min(lane * 16, 64 * U - 1)];
       if (lane < sv_lines) {
@@ -155,13 +129,14 @@ __global__ __launch_bounds__(kExpThreads) void k_expect_sweep(nfst_batch lat, Ex
     }
     if (sink_i == 0x12345678 && sink_d == 1.2345e-300) w.rr[0] = 0.0;  // keeps the loads alive, never true
   } else {
-    struct ExpTile { uint4 x; uint32_t w[4]; double m[4]; int e[4]; float v[4]; };
+    struct ExpTile { TileWords p; double m[4]; int e[4]; float v[4]; };
     auto sweep = [&](auto compact_tag) {
       constexpr bool kCompact = decltype(compact_tag)::value;
+      // (not tile_load_arcs: three slot arrays in slot order, 16-byte loads in the compact tile)
       auto load_tile = [&](int T, ExpTile &t) {
         const size_t sb = (size_t)T * 64 * U + (size_t)lane * U;
         if (kCompact) {  // control word + four 24-bit records per lane; four slots per lane (32 + 16 + 16 bytes, aligned)
-          t.x = *reinterpret_cast<const uint4 *>(prog + (size_t)T * ST + lane * 4);
+          t.p.x = *reinterpret_cast<const uint4 *>(prog + (size_t)T * ST + lane * 4);
           const double2 m01 = *reinterpret_cast<const double2 *>(wm + sb), m23 = *reinterpret_cast<const double2 *>(wm + sb + 2);
           const int4 e4 = *reinterpret_cast<const int4 *>(we + sb);
           const float4 v4 = *reinterpret_cast<const float4 *>(sv + sb);
@@ -170,30 +145,20 @@ __global__ __launch_bounds__(kExpThreads) void k_expect_sweep(nfst_batch lat, Ex
           t.v[0] = v4.x; t.v[1] = v4.y; t.v[2] = v4.z; t.v[3] = v4.w;
           return;
         }
-        t.x.x = prog[(size_t)T * ST + lane];
+        t.p.x.x = prog[(size_t)T * ST + lane];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int jj = min(j, U - 1);
-          t.w[j] = prog[(size_t)T * ST + 64 + lane * U + jj];
+          t.p.w[j] = prog[(size_t)T * ST + 64 + lane * U + jj];
           t.m[j] = wm[sb + jj];
           t.e[j] = we[sb + jj];
           t.v[j] = sv[sb + jj];
         }
       };
-      auto step = [&](int T, const ExpTile &cur, ExpTile &nxt) {
-        load_tile(min(T + 1, tiles - 1), nxt);
-        const uint32_t ctl = cur.x.x;
+      auto step = [&](const ExpTile &cur) {
+        const uint32_t ctl = cur.p.ctl();
         uint32_t rcs[4];
-        if (kCompact) {
-          const uint4 x = cur.x;
-          uint32_t r[4];
-          unpack24(x.y, x.z, x.w, r);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) rcs[j] = rec24_to_32(r[j]);
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) rcs[j] = cur.w[j];
-        }
+        tile_records<kCompact>(cur.p, rcs);
         double tm[4], tr[4];
         int te[4];
 #pragma unroll
@@ -211,33 +176,27 @@ __global__ __launch_bounds__(kExpThreads) void k_expect_sweep(nfst_batch lat, Ex
         const int E = max(max(te[0], te[1]), max(te[2], te[3]));
         const int gl = (int)ctl_g(ctl);
         const int gmax = (int)ctl_gmax(__builtin_amdgcn_readfirstlane(ctl));
-        const int Eg = exp_seg_max(E, gl, gmax);
-        double M = 0.0, N = 0.0;
+        const int Eg = seg_reduce<6>(E, gl, gmax, OpMax{});
+        ExpSums s = {0.0, 0.0};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          M += __builtin_amdgcn_ldexp(tm[j], te[j] - Eg);
-          N += __builtin_amdgcn_ldexp(tr[j], te[j] - Eg);
+          s.M += __builtin_amdgcn_ldexp(tm[j], te[j] - Eg);
+          s.N += __builtin_amdgcn_ldexp(tr[j], te[j] - Eg);
         }
-        exp_seg_sum2(M, N, gl, gmax);
+        seg_ladder<6>(s, gl, gmax, [](ExpSums &x, const ExpSums &o, bool take) {
+          x.M = take ? x.M + o.M : x.M;
+          x.N = take ? x.N + o.N : x.N;
+        });
         if (ctl_leader(ctl)) {
           const uint32_t sid = ctl_state(ctl);
-          const Rec64 a = me_pack64(M, Eg);
-          mr[sid] = make_double2(a.m, (M != 0.0) ? N / M : 0.0);
+          const Rec64 a = me_pack64(s.M, Eg);
+          mr[sid] = make_double2(a.m, (s.M != 0.0) ? s.N / s.M : 0.0);
           ex[sid] = a.e;
         }
-        // LDS accesses of one wave execute in order: the next tile's loads see these stores
-        asm volatile("" ::: "memory");
-        if ((T & 3) == 3) lds_flag_store(progress, T);
       };
-      ExpTile ta, tb;
-      if (tiles > 0) load_tile(0, ta);
-      for (int T = 0; T < tiles; T += 2) {  // (two tiles per trip: the register roles alternate without copies)
-        step(T, ta, tb);
-        if (T + 1 >= tiles) break;
-        step(T + 1, tb, ta);
-      }
+      tile_run<ExpTile>(tiles, progress, load_tile, step);
     };
-    if (F == 8) sweep(std::true_type{});
+    if (F == kFmtCompact) sweep(std::true_type{});
     else sweep(std::false_type{});
   }
   __syncthreads();

@@ -73,27 +73,20 @@ __global__ __launch_bounds__(kKbLevelThreads) void k_kbest_levels(nfst_batch lat
   if (tid == 0) w.n_lev[b] = L;
 }
 
-// maximum of a 64-bit key over the wave: four DPP stages leave every 16-lane row with its maximum, the four rows are
-// combined in scalar registers
-template <int CTRL>
-__device__ __forceinline__ void kb_dpp_max(uint32_t &hi, uint32_t &lo) {
-  const uint32_t oh = (uint32_t)dpp_i<CTRL>((int)hi), ol = (uint32_t)dpp_i<CTRL>((int)lo);
-  const bool t = (((uint64_t)oh << 32) | ol) > (((uint64_t)hi << 32) | lo);
-  hi = t ? oh : hi;
-  lo = t ? ol : lo;
-}
+// maximum of a 64-bit key over the wave: the four DPP stages of wave_ops.h on its halves leave every 16-lane row with
+// its maximum, the four rows are combined in scalar registers
+struct KbKey { uint32_t hi, lo; };
+template <int S>
+__device__ __forceinline__ KbKey wave_partner(KbKey x) { return {wave_partner<S>(x.hi), wave_partner<S>(x.lo)}; }
 __device__ __forceinline__ uint64_t kb_wave_max(uint64_t key) {
-  uint32_t hi = (uint32_t)(key >> 32), lo = (uint32_t)key;
-  kb_dpp_max<0xB1>(hi, lo);   // lane ^ 1
-  kb_dpp_max<0x4E>(hi, lo);   // lane ^ 2
-  kb_dpp_max<0x141>(hi, lo);  // half-row mirror
-  kb_dpp_max<0x140>(hi, lo);  // row mirror
+  const KbKey x = butterfly<4>(KbKey{(uint32_t)(key >> 32), (uint32_t)key}, [](KbKey a, KbKey o) {
+    return (((uint64_t)o.hi << 32) | o.lo) > (((uint64_t)a.hi << 32) | a.lo) ? o : a;
+  });
   uint64_t r = 0;
 #pragma unroll
   for (int row = 0; row < 4; ++row) {
-    const uint64_t x = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)hi, row * 16) << 32) |
-                       (uint32_t)__builtin_amdgcn_readlane((int)lo, row * 16);
-    r = x > r ? x : r;
+    const uint64_t v = ((uint64_t)(uint32_t)read_lane((int)x.hi, row * 16) << 32) | (uint32_t)read_lane((int)x.lo, row * 16);
+    r = v > r ? v : r;
   }
   return r;
 }
@@ -149,8 +142,7 @@ __global__ __launch_bounds__(kKbSweepThreads) void k_kbest_sweep(nfst_batch lat,
           const int dst = lat.arc_dst[a];
           if (dst != s) {
             th = theta[lat.arc_label[a]];
-            if (arc_w) e += arc_w[a];
-            if (sc.arc_scores) e += sc.arc_scores[a];
+            e = Extra{arc_w, sc.arc_scores}.at(a);
             lst = lists + (size_t)dst * k;
             const uint2 h = lst[0];
             if (k > 1) nxt = lst[1];

@@ -28,6 +28,7 @@ namespace {
 using namespace nfst_tile;
 
 #include "semiring.h"
+#include "wave_ops.h"
 #include "tile_pipeline.h"
 #include "out_store.h"
 #include "fb_kernels.h"

@@ -79,16 +79,6 @@ __device__ __forceinline__ float neu_tanh(float x) {
   return fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
 }
 
-__device__ __forceinline__ int wave_max_i(int v) {
-  v = max(v, dpp_i<0xB1>(v));
-  v = max(v, dpp_i<0x4E>(v));
-  v = max(v, dpp_i<0x141>(v));
-  v = max(v, dpp_i<0x140>(v));
-  const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16), c = __builtin_amdgcn_readlane(v, 32),
-            d = __builtin_amdgcn_readlane(v, 48);
-  return max(max(a, b), max(c, d));
-}
-
 // 2^-d for d >= 0 (0 when the term is too small to matter)
 __device__ __forceinline__ float neu_scale(int d) { return d > 120 ? 0.0f : __int_as_float((127 - d) << 23); }
 
@@ -105,7 +95,8 @@ __device__ __forceinline__ void neu_stage_tile(const uint32_t *prog, const int32
   uint32_t *ctl = st, *rec = st + 64;
   int *cas = (int *)(st + 320), *lead = (int *)(st + 576), *nlead = (int *)(st + 640);
   uint32_t c;
-  if (F == 8) {
+  if (F == kFmtCompact) {
+    // (the decode of tile_records, kept in place: sharing it changes this file's kernels)
     const uint4 x = *reinterpret_cast<const uint4 *>(prog + (size_t)T * ST + lane * 4);
     c = x.x;
     uint32_t r[4];
@@ -442,7 +433,7 @@ __global__ __launch_bounds__(kNeuThreads) void k_backward_neural(nfst_batch lat,
           float wm = act ? bo.x * (ca_l >= 0 ? w.m : 1.0f) : 0.0f;
           int we = max(__float_as_int(bo.y) + (ca_l >= 0 ? w.e : 0), kEZero);
           if (!(wm > 0.0f)) we = kEZero;
-          const int en = max(eacc, wave_max_i(we));
+          const int en = max(eacc, wave_max(we));
           const float so = neu_scale(en - eacc);
           const float q_l = wm * neu_scale(en - we);
           macc = fmaf(macc, so, wave_sum(q_l));
@@ -451,7 +442,7 @@ __global__ __launch_bounds__(kNeuThreads) void k_backward_neural(nfst_batch lat,
           for (int c = 0; c < HC; ++c) tacc[c] *= so;
 #pragma unroll
           for (int k = 0; k < D; ++k) {
-            const float qk = k < nb ? read_lane_f(q_l, buf[k].p) : 0.0f;
+            const float qk = k < nb ? read_lane(q_l, buf[k].p) : 0.0f;
 #pragma unroll
             for (int c = 0; c < HC; ++c) tacc[c] = fmaf(qk, vec[k][c], tacc[c]);
           }
@@ -518,13 +509,9 @@ __global__ __launch_bounds__(kNeuThreads) void k_backward_neural(nfst_batch lat,
 // barrier per tile.
 template <int LPR>
 __device__ __forceinline__ float neu_group_sum(float v) {  // sum over the LPR lanes of a record slot, in all of them
-  v += dpp_f<0xB1>(v);   // lane ^ 1
-  v += dpp_f<0x4E>(v);   // lane ^ 2
-  if (LPR >= 8) v += dpp_f<0x141>(v);   // half mirror
-  if (LPR >= 16) v += dpp_f<0x140>(v);  // row mirror
-  if (LPR >= 32) v += __shfl_xor(v, 16);
-  if (LPR >= 64) v += __shfl_xor(v, 32);
-  return v;
+  static_assert(LPR >= 4 && (LPR & (LPR - 1)) == 0, "");
+  constexpr int NS = LPR >= 64 ? 6 : LPR >= 32 ? 5 : LPR >= 16 ? 4 : LPR >= 8 ? 3 : 2;
+  return butterfly<NS>(v, OpSum{});
 }
 
 template <int LPR>
@@ -631,7 +618,7 @@ __global__ __launch_bounds__(kNeuThreads) void k_backward_neural_small(nfst_batc
       const float bh = tacc * inv;
       float u = 0.0f;
 #pragma unroll
-      for (int j = 0; j < LPR; ++j) u = fmaf(whr[j], read_lane_f(bh, j), u);
+      for (int j = 0; j < LPR; ++j) u = fmaf(whr[j], read_lane(bh, j), u);
       if (sub == 0 && hv) {
         bh_row(sid)[h] = bh;
         if (sid < m.n_rows) u_w[(size_t)sid * hid + h] = u;
@@ -821,8 +808,8 @@ __global__ __launch_bounds__(kNeuThreads) void k_backward_neural_grad(
               }
               const float sc = wave_sum(p1), dot = wave_sum(p2);
               // wave-uniform: p = exp(sc + table weight) beta(d) / beta(s)
-              const float xs = read_lane_f(x_l, cur.p), lam_s = read_lane_f(lam_l, cur.p);
-              const float bsm = read_lane_f(bs_l.x, cur.p);
+              const float xs = read_lane(x_l, cur.p), lam_s = read_lane(lam_l, cur.p);
+              const float bsm = read_lane(bs_l.x, cur.p);
               const int bse = __builtin_amdgcn_readlane(__float_as_int(bs_l.y), cur.p);
               const ME w = exp_split(sc + xs);
               const float pm = bsm > 0.0f ? w.m * bd.x / bsm : 0.0f;
@@ -843,7 +830,7 @@ __global__ __launch_bounds__(kNeuThreads) void k_backward_neural_grad(
                 }
               }
             } else {
-              lacc += read_lane_f(lam_l, cur.p);
+              lacc += read_lane(lam_l, cur.p);
 #pragma unroll
               for (int c = 0; c < HC; ++c) gacc[c] += (c * 64 + lane < hid) ? cur.a[c] : 0.0f;
             }
@@ -1016,7 +1003,7 @@ __global__ __launch_bounds__(kNeuThreads) void k_backward_neural_grad_small(
       if (sid < m.n_rows && !continuation) lacc += g_logbeta[m.row_off + sid];
       float eta = 0.0f;
 #pragma unroll
-      for (int j = 0; j < LPR; ++j) eta = fmaf(whr[j], read_lane_f(gacc, j), eta);
+      for (int j = 0; j < LPR; ++j) eta = fmaf(whr[j], read_lane(gacc, j), eta);
       if (sub == 0 && hv) {
         gam_row(sid)[h] = gacc;
         if (sid < m.n_rows)

@@ -14,10 +14,9 @@ __device__ __forceinline__ void vit_take(float &bv, int &ba, int &bn, float ov, 
   bn = t ? on : bn;  // the arc's other end
 }
 
-// Wave 0 runs the program; waves 1 .. 3 run ahead of it and pull the tiles it will read
-// (program words, slot -> arc map, per-arc extras) into the L2 cache, throttled by wave 0's
-// progress counter in LDS, so that its dependent loads are L2 hits instead of HBM misses.
-constexpr int kVitThreads = 256, kVitAhead = 12;
+// Wave 0 runs the program through the reader of tile_pipeline.h; waves 1 .. 3 pull the tiles it will read (program
+// words, slot -> arc map, per-arc extras) into the L2 cache.
+constexpr int kVitThreads = 256;
 __global__ __launch_bounds__(kVitThreads) void k_viterbi(nfst_batch lat, nfst_scores sc, float *best,
                                                          int32_t *paths, int32_t *path_arcs,
                                                          int32_t *lengths, int max_len, int pad) {
@@ -47,7 +46,7 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(nfst_batch lat, nfst_sc
     float sink_f = 0.0f;
     int sink_i = 0;
     for (int T = wv - 1; T < m.bwd_tiles; T += kVitThreads / 64 - 1) {
-      while (T > lds_flag_load(progress) + kVitAhead) __builtin_amdgcn_s_sleep(8);
+      while (T > lds_flag_load(progress) + kTileAhead) __builtin_amdgcn_s_sleep(8);
       // one 128-byte line per lane
       const int prog_lines = (ST * 4 + 127) / 128, perm_lines = (64 * U * 4 + 127) / 128;
       if (lane < prog_lines) sink_i += (int)prog[(size_t)T * ST + min(lane * 32, ST - 1)];
@@ -65,50 +64,24 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(nfst_batch lat, nfst_sc
     }
     if (sink_f == 1.2345e-33f && sink_i == 0x12345678) best[b] = 0.0f;  // keeps the loads alive, never true
   } else {
-  // The words of tile T+1 are loaded while tile T is computed: loads only, nothing is unpacked
-  // before the tile's turn (a use would make the wave wait for the L2 round trip right away), and
-  // the format is a compile-time constant of the loop (a branch around loads ends in a full wait).
-  struct VitTile { uint4 x; uint32_t w[4]; int cas[4]; };
   auto sweep = [&](auto compact_tag, auto extra_tag) {
   constexpr bool kCompact = decltype(compact_tag)::value, kExtra = decltype(extra_tag)::value;
-  auto load_tile = [&](int T, VitTile &t) {
-    if (kCompact) {  // control word + four 24-bit records per lane
-      t.x = *reinterpret_cast<const uint4 *>(prog + (size_t)T * ST + lane * 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) t.cas[j] = perm[(size_t)T * 256 + lane * 4 + j];
-      return;
-    }
-    t.x.x = prog[(size_t)T * ST + lane];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int jj = min(j, U - 1);
-      t.cas[j] = perm[(size_t)T * 64 * U + lane * U + jj];
-      t.w[j] = prog[(size_t)T * ST + 64 + lane * U + jj];
-    }
-  };
-  // iteration T: `cur` = tile T, `nxt` receives tile T+1
-  auto step = [&](int T, const VitTile &cur, VitTile &nxt) {
+  auto load_tile = [&](int T, ArcTile &t) { tile_load_arcs<kCompact>(prog, perm, U, ST, T, lane, t); };
+  // iteration T: `cur` = tile T, `nxt` receives tile T+1.  (Not tile_run, nor Extra::at below: either
+  // reorders this kernel's instructions)
+  auto step = [&](int T, const ArcTile &cur, ArcTile &nxt) {
     load_tile(min(T + 1, m.bwd_tiles - 1), nxt);
-    const uint32_t ctl = cur.x.x;
+    const uint32_t ctl = cur.p.ctl();
     int cas[4];
     uint32_t rcs[4];
     float xs[4];
-    if (kCompact) {
-      const uint4 x = cur.x;
-      uint32_t r[4];
-      unpack24(x.y, x.z, x.w, r);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) rcs[j] = rec24_to_32(r[j]);  // as a 32-bit record
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) rcs[j] = cur.w[j];
-    }
+    tile_records<kCompact>(cur.p, rcs);
 #pragma unroll
     for (int j = 0; j < 4; ++j) cas[j] = (j < U) ? cur.cas[j] : -1;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       xs[j] = 0.0f;
-      if (kExtra && cas[j] >= 0) {  // (a loop without extras has no load but the prefetch)
+      if (kExtra && cas[j] >= 0) {  // (a loop without extras has no load but the prefetch; Extra::at's adds, in place)
         if (arc_w) xs[j] += arc_w[cas[j]];
         if (sc.arc_scores) xs[j] += sc.arc_scores[cas[j]];
       }
@@ -138,22 +111,24 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(nfst_batch lat, nfst_sc
     }
     const int gl = (int)ctl_g(ctl);
     const int gmax = (int)ctl_gmax(__builtin_amdgcn_readfirstlane(ctl));
-    // segmented max over the state's lanes: quad permutes and row mirrors (DPP), then the
-    // two cross-row stages; every lane of a state ends with the same (value, arc, next state)
-#define NFST_VIT_STAGE(ST, FV, FI)                                          \
+    // segmented max over the state's lanes; every lane of a state ends with the same (value, arc, next state).  Not
+    // the seg_ladder of wave_ops.h: with the cross-row shuffles behind wave_partner<4> / <5> this kernel needs two
+    // more SGPRs and one more VGPR, so the stages are written out and the last two shuffle
+    // in place.
+#define NFST_VIT_STAGE(ST, PARTNER)                                         \
     if (gmax > ST) {                                                        \
-      const float ov = FV(bv);                                              \
-      const int oa = FI(ba), on = FI(bn);                                   \
+      const float ov = PARTNER(bv);                                         \
+      const int oa = PARTNER(ba), on = PARTNER(bn);                         \
       vit_take(bv, ba, bn, ov, oa, on, gl > ST);                            \
     }
 #define NFST_SHFL16(x) __shfl_xor(x, 16)
 #define NFST_SHFL32(x) __shfl_xor(x, 32)
-    NFST_VIT_STAGE(0, dpp_f<0xB1>, dpp_i<0xB1>)
-    NFST_VIT_STAGE(1, dpp_f<0x4E>, dpp_i<0x4E>)
-    NFST_VIT_STAGE(2, dpp_f<0x141>, dpp_i<0x141>)
-    NFST_VIT_STAGE(3, dpp_f<0x140>, dpp_i<0x140>)
-    NFST_VIT_STAGE(4, NFST_SHFL16, NFST_SHFL16)
-    NFST_VIT_STAGE(5, NFST_SHFL32, NFST_SHFL32)
+    NFST_VIT_STAGE(0, wave_partner<0>)
+    NFST_VIT_STAGE(1, wave_partner<1>)
+    NFST_VIT_STAGE(2, wave_partner<2>)
+    NFST_VIT_STAGE(3, wave_partner<3>)
+    NFST_VIT_STAGE(4, NFST_SHFL16)
+    NFST_VIT_STAGE(5, NFST_SHFL32)
 #undef NFST_VIT_STAGE
 #undef NFST_SHFL16
 #undef NFST_SHFL32
@@ -163,22 +138,18 @@ __global__ __launch_bounds__(kVitThreads) void k_viterbi(nfst_batch lat, nfst_sc
       bp[sid] = (ba == kNone) ? -1 : ba;
       ns[sid] = bn;
     }
-    // LDS accesses of one wave execute in order: the next tile's loads see these stores
-    asm volatile("" ::: "memory");
-    if ((T & 3) == 3) lds_flag_store(progress, T);
+    tile_done(progress, T);
   };
-  VitTile ta, tb;
+  ArcTile ta, tb;
   if (m.bwd_tiles > 0) load_tile(0, ta);
-  // two iterations per trip so that the register roles alternate without copies (a copy of
-  // registers with a load in flight would wait for it)
-  for (int T = 0; T < m.bwd_tiles; T += 2) {
+  for (int T = 0; T < m.bwd_tiles; T += 2) {  // (two tiles per trip, as tile_run)
     step(T, ta, tb);
     if (T + 1 >= m.bwd_tiles) break;
     step(T + 1, tb, ta);
   }
   };
   const bool extras = arc_w != nullptr || sc.arc_scores != nullptr;
-  if (F == 8) { if (extras) sweep(std::true_type{}, std::true_type{}); else sweep(std::true_type{}, std::false_type{}); }
+  if (F == kFmtCompact) { if (extras) sweep(std::true_type{}, std::true_type{}); else sweep(std::true_type{}, std::false_type{}); }
   else { if (extras) sweep(std::false_type{}, std::true_type{}); else sweep(std::false_type{}, std::false_type{}); }
   }
   // lane 0 walks the back pointers inside LDS (arc ids go to the list `pa`, which reuses the
@@ -433,24 +404,21 @@ __global__ __launch_bounds__(kVitTwThreads) void k_viterbi_tw(nfst_batch lat, nf
         }
       }
       // segmented maximum over the state's lanes: a partner outside the state's group is masked to the smallest key
-#define NFST_VIT_STAGE2(MASK, FI)                                            \
+      // (the masks are precomputed, so this is not the seg_ladder of wave_ops.h; the partners are its partners)
+#define NFST_VIT_STAGE2(MASK, S)                                             \
       {                                                                     \
-        const uint32_t oh = (uint32_t)FI((int)bh) & (MASK), ol = (uint32_t)FI((int)bl), on = (uint32_t)FI((int)bn); \
+        const uint32_t oh = wave_partner<S>(bh) & (MASK), ol = wave_partner<S>(bl), on = wave_partner<S>(bn); \
         const bool t = key(oh, ol) > key(bh, bl);                           \
         bh = t ? oh : bh; bl = t ? ol : bl; bn = t ? on : bn;               \
       }
-      NFST_VIT_STAGE2(cur.m0, dpp_i<0xB1>)
-      NFST_VIT_STAGE2(cur.m1, dpp_i<0x4E>)
-      NFST_VIT_STAGE2(cur.m2, dpp_i<0x141>)
+      NFST_VIT_STAGE2(cur.m0, 0)
+      NFST_VIT_STAGE2(cur.m1, 1)
+      NFST_VIT_STAGE2(cur.m2, 2)
       if (WIDE) {
         const int gl = (int)((cur.w0 >> 18) & 7u), gmax = (int)((cu >> 21) & 7u);
-#define NFST_SHFL16(x) __shfl_xor(x, 16)
-#define NFST_SHFL32(x) __shfl_xor(x, 32)
-        if (gmax > 3) NFST_VIT_STAGE2(gl > 3 ? ~0u : 0u, dpp_i<0x140>)
-        if (gmax > 4) NFST_VIT_STAGE2(gl > 4 ? ~0u : 0u, NFST_SHFL16)
-        if (gmax > 5) NFST_VIT_STAGE2(gl > 5 ? ~0u : 0u, NFST_SHFL32)
-#undef NFST_SHFL16
-#undef NFST_SHFL32
+        if (gmax > 3) NFST_VIT_STAGE2(gl > 3 ? ~0u : 0u, 3)
+        if (gmax > 4) NFST_VIT_STAGE2(gl > 4 ? ~0u : 0u, 4)
+        if (gmax > 5) NFST_VIT_STAGE2(gl > 5 ? ~0u : 0u, 5)
       }
 #undef NFST_VIT_STAGE2
       const uint32_t vb = bh ^ (uint32_t)((~(int)bh >> 31) | (int)0x80000000);  // back to float bits
@@ -655,10 +623,10 @@ __global__ __launch_bounds__(1024) void k_sample(nfst_batch lat, nfst_scores sc,
       const int dv0 = (int)d16[i0];
       const float prev0 = row_shr_zero<1>(cum0);
       int key = (valid0 && u < cum0 && !(u < prev0)) ? (((r << 16) | dv0) + 1) : 0;
-      key = max(key, dpp_i<0xB1>(key));
-      key = max(key, dpp_i<0x4E>(key));
-      key = max(key, dpp_i<0x141>(key));
-      key = max(key, dpp_i<0x140>(key));
+      key = max(key, wave_partner<0>(key));
+      key = max(key, wave_partner<1>(key));
+      key = max(key, wave_partner<2>(key));
+      key = max(key, wave_partner<3>(key));
       float cum_base = 0.0f;
       int chosen = key ? a0 + ((key - 1) >> 16) : -1, last = -1, d_ch = (key - 1) & 0xffff, d_last = 0;
       bool more = active & (a0 < a1) & (key == 0);
@@ -937,28 +905,6 @@ __device__ __forceinline__ float seq_mask(int v, int t, int prev, int pad, int b
   return mk;
 }
 
-// wave64 all-reduce without LDS traffic: quad permutes and row mirrors (DPP) reduce each
-// row of 16 lanes, v_readlane collects the four row results
-__device__ __forceinline__ float read_lane_f(float v, int l) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ float wave_max(float v) {
-  v = fmaxf(v, dpp_f<0xB1>(v));
-  v = fmaxf(v, dpp_f<0x4E>(v));
-  v = fmaxf(v, dpp_f<0x141>(v));
-  v = fmaxf(v, dpp_f<0x140>(v));
-  const float a = read_lane_f(v, 0), b = read_lane_f(v, 16), c = read_lane_f(v, 32), d = read_lane_f(v, 48);
-  return fmaxf(fmaxf(a, b), fmaxf(c, d));
-}
-__device__ __forceinline__ float wave_sum(float v) {
-  v += dpp_f<0xB1>(v);
-  v += dpp_f<0x4E>(v);
-  v += dpp_f<0x141>(v);
-  v += dpp_f<0x140>(v);
-  const float a = read_lane_f(v, 0), b = read_lane_f(v, 16), c = read_lane_f(v, 32), d = read_lane_f(v, 48);
-  return (a + b) + (c + d);
-}
-
 // Streaming version for V % 4 == 0, V <= 1024: every wave keeps RB rows in registers
 // (16-byte loads, RB * NV of them in flight per lane -- the kernel is HBM-bound and would be
 // latency-bound with one row at a time), two-pass softmax per row (max, then sum of exp).
@@ -967,29 +913,8 @@ __device__ __forceinline__ float wave_sum(float v) {
 // L = 16 and five slots per lane, 75 of 128 with a wave per row) and share the per-row
 // instructions (reductions, masks) among the rows of a wave; the launcher uses 16 up to V = 512
 // and 32 above.  Measured at V = 300: 3.1 TB/s with L = 64, 4.2 with L = 32, 5.3 with L = 16.
-template <int L>
-__device__ __forceinline__ float row_max(float v) {
-  v = fmaxf(v, dpp_f<0xB1>(v));
-  v = fmaxf(v, dpp_f<0x4E>(v));
-  v = fmaxf(v, dpp_f<0x141>(v));
-  v = fmaxf(v, dpp_f<0x140>(v));
-  if (L == 16) return v;  // a DPP row: every lane holds its row's result
-  const float a = read_lane_f(v, 0), b = read_lane_f(v, 16), c = read_lane_f(v, 32), d = read_lane_f(v, 48);
-  if (L == 64) return fmaxf(fmaxf(a, b), fmaxf(c, d));
-  return (threadIdx.x & 32) ? fmaxf(c, d) : fmaxf(a, b);
-}
-template <int L>
-__device__ __forceinline__ float row_sum(float v) {
-  v += dpp_f<0xB1>(v);
-  v += dpp_f<0x4E>(v);
-  v += dpp_f<0x141>(v);
-  v += dpp_f<0x140>(v);
-  if (L == 16) return v;
-  const float a = read_lane_f(v, 0), b = read_lane_f(v, 16), c = read_lane_f(v, 32), d = read_lane_f(v, 48);
-  if (L == 64) return (a + b) + (c + d);
-  return (threadIdx.x & 32) ? (c + d) : (a + b);
-}
-
+// (The row reductions over L lanes are row_max<L> / row_sum<L> of wave_ops.h.)
+//
 // Row-level legality (scorers.py:59-83) only depends on three row flags; which of a lane's 4 NV
 // columns are illegal under each is a lane constant, one bit per column:
 //   normal / first row: bos, pad;  after eos or pad: everything but pad;  forced end: everything but eos.
@@ -1117,8 +1042,8 @@ __global__ __launch_bounds__(256) void k_path_logprob_v4(const float *__restrict
     }
   }
   // every lane of a row's lanes holds the same acc
-  if (HR == 2) acc += read_lane_f(acc, 32);
-  if (HR == 4) acc = (read_lane_f(acc, 0) + read_lane_f(acc, 16)) + (read_lane_f(acc, 32) + read_lane_f(acc, 48));
+  if (HR == 2) acc += read_lane(acc, 32);
+  if (HR == 4) acc = (read_lane(acc, 0) + read_lane(acc, 16)) + (read_lane(acc, 32) + read_lane(acc, 48));
   if (lane == 0) part[wave] = acc;
   __syncthreads();
   if (threadIdx.x == 0) out[n] = ((part[0] + part[1]) + part[2]) + part[3];

@@ -11,7 +11,7 @@
 // groups and combine records of tree-summed states -- does not change a bit: every packing of a lattice gives the
 // same results.  beta* and delta of all rows (scratch rows included) live in LDS, 4 bytes per row each, beside the
 // label scores [V + 2] (the null label: -inf, the unit label of carry and combine records: 0).
-constexpr int kSlkThreads = 1024, kSlkAhead = 12;
+constexpr int kSlkThreads = 1024;
 constexpr int kSlkBeta = 1, kSlkGap = 2, kSlkDelta = 4, kSlkArcs = 8, kSlkAll = 15;
 constexpr float kPosInf = __builtin_huge_valf();
 
@@ -29,51 +29,34 @@ struct SlkOut {
   int32_t *n_kept;
 };
 
-// e_a and c_a with the adds of nfst_kbest, in its order
-__device__ __forceinline__ float slk_extra(const float *arc_w, const float *arc_scores, int a) {
-  float e = 0.0f;
-  if (arc_w) e += arc_w[a];
-  if (arc_scores) e += arc_scores[a];
-  return e;
-}
+// c_a with the adds of nfst_kbest, in its order (e_a: Extra::at)
 __device__ __forceinline__ float slk_cand(float e, float th, float vd) { return e + (th + vd); }
 
-// segmented max (kMax) or min over a state's 2^g lanes (stage partners as exp_seg_max)
 template <bool kMax>
 __device__ __forceinline__ float slk_pick(float a, float b) { return kMax ? fmaxf(a, b) : fminf(a, b); }
-template <bool kMax>
-__device__ __forceinline__ float slk_seg(float x, int g, int gmax) {
-  if (gmax > 0) { const float o = dpp_f<0xB1>(x); x = (g >= 1) ? slk_pick<kMax>(x, o) : x; }
-  if (gmax > 1) { const float o = dpp_f<0x4E>(x); x = (g >= 2) ? slk_pick<kMax>(x, o) : x; }
-  if (gmax > 2) { const float o = dpp_f<0x141>(x); x = (g >= 3) ? slk_pick<kMax>(x, o) : x; }
-  if (gmax > 3) { const float o = dpp_f<0x140>(x); x = (g >= 4) ? slk_pick<kMax>(x, o) : x; }
-  if (gmax > 4) { const float o = __shfl_xor(x, 16); x = (g >= 5) ? slk_pick<kMax>(x, o) : x; }
-  if (gmax > 5) { const float o = __shfl_xor(x, 32); x = (g >= 6) ? slk_pick<kMax>(x, o) : x; }
-  return x;
-}
 
-// One sweep of a general tile program (the prefetching structure of k_viterbi and k_expect_sweep): wave 0 runs the
-// tiles in order, loading tile T + 1 while it computes tile T; waves 1 .. 3 run a bounded distance ahead of it and pull
+// One sweep of a general tile program through the reader of tile_pipeline.h: wave 0 runs the tiles, waves 1 .. 3 pull
 // what it will read -- program words, the slot -> arc map and the per-arc values gathered through it -- into the L2
 // cache; the other waves go straight to the barrier that follows.
 //   kBeta:  val = beta* rows, a slot's candidate is e_a + (tl[label] + val[operand]), a state takes the maximum;
 //           arc_x / arc_y are the per-arc extras (arc_w, arc_scores; either may be null)
 //   !kBeta: val = delta rows, a slot's candidate is val[operand] + gap_a (0 for a unit-label record, +inf for an empty
 //           slot), a state takes the minimum; arc_x is the gap array
-// A lane's slots beyond U repeat its last slot (as the loads of k_viterbi do): a repeated candidate changes no max or min.
+// A lane's slots beyond U repeat its last slot (tile_load_arcs): a repeated candidate changes no max or min.
 template <bool kBeta>
 __device__ __forceinline__ void slk_sweep(const uint32_t *prog, const int32_t *perm, int F, int tiles, int V, float *val,
                                           const float *tl, int *progress, const float *arc_x, const float *arc_y, int wv,
                                           int lane, float *keep_alive) {
   const int U = fmt_u(F), ST = fmt_words(F);
-  const bool gather = kBeta ? (arc_x != nullptr || arc_y != nullptr) : true;
+  const Extra ex = {arc_x, arc_y};
+  const bool gather = kBeta ? ex.any() : true;
   if (wv > 3) return;
   if (wv > 0) {
     float sink_f = 0.0f;
     int sink_i = 0;
     const int prog_lines = (ST * 4 + 127) / 128, perm_lines = (64 * U * 4 + 127) / 128;
     for (int T = wv - 1; T < tiles; T += 3) {
-      while (T > lds_flag_load(progress) + kSlkAhead) __builtin_amdgcn_s_sleep(8);
+      while (T > lds_flag_load(progress) + kTileAhead) __builtin_amdgcn_s_sleep(8);
       if (lane < prog_lines) sink_i += (int)prog[(size_t)T * ST + min(lane * 32, ST - 1)];
       if (!gather) {
         if (lane < perm_lines) sink_i += perm[(size_t)T * 64 * U + min(lane * 32, 64 * U - 1)];
@@ -90,45 +73,20 @@ __device__ __forceinline__ void slk_sweep(const uint32_t *prog, const int32_t *p
     if (sink_f == 1.2345e-33f && sink_i == 0x12345678) *keep_alive = 0.0f;  // keeps the loads alive, never true
     return;
   }
-  struct SlkTile { uint4 x; uint32_t w[4]; int cas[4]; };
   auto sweep = [&](auto compact_tag, auto gather_tag) {
     constexpr bool kCompact = decltype(compact_tag)::value, kGather = decltype(gather_tag)::value;
-    auto load_tile = [&](int T, SlkTile &t) {
-      if (kCompact) {  // control word + four 24-bit records per lane
-        t.x = *reinterpret_cast<const uint4 *>(prog + (size_t)T * ST + lane * 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) t.cas[j] = perm[(size_t)T * 256 + lane * 4 + j];
-        return;
-      }
-      t.x.x = prog[(size_t)T * ST + lane];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int jj = min(j, U - 1);
-        t.cas[j] = perm[(size_t)T * 64 * U + lane * U + jj];
-        t.w[j] = prog[(size_t)T * ST + 64 + lane * U + jj];
-      }
-    };
-    auto step = [&](int T, const SlkTile &cur, SlkTile &nxt) {
-      load_tile(min(T + 1, tiles - 1), nxt);
-      const uint32_t ctl = cur.x.x;
+    auto load_tile = [&](int T, ArcTile &t) { tile_load_arcs<kCompact>(prog, perm, U, ST, T, lane, t); };
+    auto step = [&](const ArcTile &cur) {
+      const uint32_t ctl = cur.p.ctl();
       uint32_t rcs[4];
-      if (kCompact) {
-        const uint4 x = cur.x;
-        uint32_t r[4];
-        unpack24(x.y, x.z, x.w, r);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) rcs[j] = rec24_to_32(r[j]);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) rcs[j] = cur.w[j];
-      }
+      tile_records<kCompact>(cur.p, rcs);
       float xs[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {  // the per-arc value of the slot: e_a, or gap_a
         const int ca = cur.cas[j];
         if (kBeta) {
           xs[j] = 0.0f;
-          if (kGather && ca >= 0) xs[j] = slk_extra(arc_x, arc_y, ca);
+          if (kGather && ca >= 0) xs[j] = ex.at(ca);
         } else {
           xs[j] = ((int)rec32_label(rcs[j]) == V + 1) ? 0.0f : kPosInf;
           if (ca >= 0) xs[j] = arc_x[ca];
@@ -142,21 +100,12 @@ __device__ __forceinline__ void slk_sweep(const uint32_t *prog, const int32_t *p
         const float c = kBeta ? slk_cand(xs[j], tl[rec32_label(rcs[j])], o) : o + xs[j];
         acc = slk_pick<kBeta>(acc, c);
       }
-      const int gl = (int)ctl_g(ctl);
-      const int gmax = (int)ctl_gmax(__builtin_amdgcn_readfirstlane(ctl));
-      acc = slk_seg<kBeta>(acc, gl, gmax);
+      // segmented max (kBeta) or min over the state's 2^g lanes
+      acc = seg_reduce<6>(acc, (int)ctl_g(ctl), (int)ctl_gmax(__builtin_amdgcn_readfirstlane(ctl)),
+                          [](float a, float o) { return slk_pick<kBeta>(a, o); });
       if (ctl_leader(ctl)) val[ctl_state(ctl)] = acc;
-      // LDS accesses of one wave execute in order: the next tile's loads see these stores
-      asm volatile("" ::: "memory");
-      if ((T & 3) == 3) lds_flag_store(progress, T);
     };
-    SlkTile ta, tb;
-    if (tiles > 0) load_tile(0, ta);
-    for (int T = 0; T < tiles; T += 2) {  // (two tiles per trip: the register roles alternate without copies)
-      step(T, ta, tb);
-      if (T + 1 >= tiles) break;
-      step(T + 1, tb, ta);
-    }
+    tile_run<ArcTile>(tiles, progress, load_tile, step);
   };
   if (F == kFmtCompact) { if (gather) sweep(std::true_type{}, std::true_type{}); else sweep(std::true_type{}, std::false_type{}); }
   else { if (gather) sweep(std::false_type{}, std::true_type{}); else sweep(std::false_type{}, std::false_type{}); }
@@ -197,7 +146,7 @@ __global__ __launch_bounds__(kSlkThreads) void k_arc_slack(nfst_batch lat, nfst_
     for (int i = tid; i < m.n_arcs; i += kSlkThreads) {
       const int a = m.arc_off + i;
       const int s0 = lat.arc_src[a], d0 = lat.arc_dst[a];
-      const float c = slk_cand(slk_extra(arc_w, sc.arc_scores, a), tl[lat.arc_label[a]], v[d0]);
+      const float c = slk_cand(Extra{arc_w, sc.arc_scores}.at(a), tl[lat.arc_label[a]], v[d0]);
       // (a self loop lies on no path: gap 0, so that slack = delta(s) + gap serves every arc)
       w.gap[a] = (s0 == d0) ? 0.0f : (c > kNegInf ? v[s0] - c : kPosInf);
     }

@@ -33,47 +33,13 @@ constexpr int kSlotWordsP = 1280;               // ... of its precise flavour (f
 constexpr int kPreciseTiles = 192;              // programs with more tiles than this run the precise flavour (semiring.h)
 constexpr int kMaxRing = 12, kMinRing = 3;       // ring slots per sweep (chosen at launch from the LDS budget)
 
-template <int CTRL>
-__device__ __forceinline__ int dpp_i(int v) {
-  return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-
-// Segmented all-reduce of (M, E) partial sums: a lane whose state owns 2^g lanes takes
-// part in stages 0 .. g-1.  Stage partners: lane^1, lane^2 (quad permutes), 7-lane and
-// 15-lane mirrors inside a row (DPP modifiers, no LDS traffic), then lane^16 and
-// lane^32 (shuffles).  GMAX (the tile's largest g) bounds the stages executed.  All
-// lanes of a state end with bitwise the same (M, E): max of exponents, one rescale,
-// then the sum.
-// Segmented all-reduce of (M, E) partial sums: a lane whose state owns 2^g lanes takes
-// part in stages 0 .. g-1.  Stage partners: lane^1, lane^2 (quad permutes), 7-lane and
-// 15-lane mirrors inside a row (DPP modifiers, no LDS traffic), then lane^16 and
-// lane^32 (shuffles).  Stages 0..2 always run (one predicated select each, no
-// branch); stages 3..5 only when the tile's largest g needs them.  All lanes of a state
-// end with bitwise the same (M, E): max of exponents, one rescale, then the sum.
+// Segmented all-reduce of (M, E) partial sums over a state's 2^g lanes (seg_reduce of wave_ops.h with a constant
+// bound: STAGES stages are compiled, one predicated select each, no branch).  All lanes of a state end with bitwise
+// the same (M, E): max of exponents, one rescale, then the sum.
 template <int STAGES>
-__device__ __forceinline__ int seg_max(int Em, int g) {
-  if (STAGES >= 1) { const int o = dpp_i<0xB1>(Em); Em = (g >= 1) ? max(Em, o) : Em; }
-  if (STAGES >= 2) { const int o = dpp_i<0x4E>(Em); Em = (g >= 2) ? max(Em, o) : Em; }
-  if (STAGES >= 3) { const int o = dpp_i<0x141>(Em); Em = (g >= 3) ? max(Em, o) : Em; }
-  if (STAGES >= 4) { const int o = dpp_i<0x140>(Em); Em = (g >= 4) ? max(Em, o) : Em; }
-  if (STAGES >= 5) { const int o = __shfl_xor(Em, 16); Em = (g >= 5) ? max(Em, o) : Em; }
-  if (STAGES >= 6) { const int o = __shfl_xor(Em, 32); Em = (g >= 6) ? max(Em, o) : Em; }
-  return Em;
-}
+__device__ __forceinline__ int seg_max(int Em, int g) { return seg_reduce<STAGES>(Em, g, 6, OpMax{}); }
 template <int STAGES>
-__device__ __forceinline__ float seg_sum(float M, int g) {
-  if (STAGES >= 1) { const float o = dpp_f<0xB1>(M); M = (g >= 1) ? M + o : M; }
-  if (STAGES >= 2) { const float o = dpp_f<0x4E>(M); M = (g >= 2) ? M + o : M; }
-  if (STAGES >= 3) { const float o = dpp_f<0x141>(M); M = (g >= 3) ? M + o : M; }
-  if (STAGES >= 4) { const float o = dpp_f<0x140>(M); M = (g >= 4) ? M + o : M; }
-  if (STAGES >= 5) { const float o = __shfl_xor(M, 16); M = (g >= 5) ? M + o : M; }
-  if (STAGES >= 6) { const float o = __shfl_xor(M, 32); M = (g >= 6) ? M + o : M; }
-  return M;
-}
+__device__ __forceinline__ float seg_sum(float M, int g) { return seg_reduce<STAGES>(M, g, 6, OpSum{}); }
 // The same reduction for groups of up to 8 lanes with the per-lane select replaced by the
 // execution mask: m[s] = lanes whose state owns more than 2^s lanes (wave masks, computed
 // off the dependency chain); a DPP instruction executed under m[s] updates exactly the
@@ -151,6 +117,84 @@ __device__ __forceinline__ void lds_flag_store(int *p, int v) {
   __atomic_store_n(p, v, __ATOMIC_RELAXED);
 }
 
+// ---------------------------------------------------------------- reader of a general tile program
+// The path-side sweeps (k_viterbi, k_expect_sweep, slk_sweep of k_arc_slack) run a tile program of any format straight
+// from global memory: wave 0 runs the tiles in order and loads tile T + 1 while it computes tile T; helper waves run a
+// bounded distance ahead of it (kTileAhead tiles, each kernel's own loop: one 128-byte line per lane of what the sweep
+// will read) and pull it into the L2 cache, throttled by wave 0's progress word in LDS, so that its dependent loads
+// are L2 hits instead of HBM misses.  What is shared is the reading; each kernel keeps its own arithmetic per tile
+// (DESIGN.md section 4.11).
+constexpr int kTileAhead = 12;
+
+// A lane's program words of one tile: compact, the control word and three words of four 24-bit records (one 16-byte
+// load); otherwise the control word in x.x and U record words in w, slots beyond U repeating the last one.
+struct TileWords {
+  uint4 x;
+  uint32_t w[4];
+  __device__ __forceinline__ uint32_t ctl() const { return x.x; }
+};
+// The tile of a sweep that gathers per canonical arc (k_viterbi, slk_sweep): the program words and the lane's four
+// entries of the slot -> arc map.  Loads only: nothing is unpacked before the tile's turn (a use would make the wave
+// wait for the L2 round trip right away), and the format is a compile-time constant of the loop (a branch around loads
+// ends in a full wait).  The arguments are references on purpose: the callers are lambdas that capture these values
+// by reference, and by-value copies compile to other scalar address arithmetic.
+struct ArcTile {
+  TileWords p;
+  int cas[4];
+};
+template <bool kCompact>
+__device__ __forceinline__ void tile_load_arcs(const uint32_t *const &prog, const int32_t *const &perm, const int &U,
+                                               const int &ST, int T, const int &lane, ArcTile &t) {
+  if (kCompact) {  // control word + four 24-bit records per lane
+    t.p.x = *reinterpret_cast<const uint4 *>(prog + (size_t)T * ST + lane * 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) t.cas[j] = perm[(size_t)T * 256 + lane * 4 + j];
+    return;
+  }
+  t.p.x.x = prog[(size_t)T * ST + lane];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int jj = min(j, U - 1);
+    t.cas[j] = perm[(size_t)T * 64 * U + lane * U + jj];
+    t.p.w[j] = prog[(size_t)T * ST + 64 + lane * U + jj];
+  }
+}
+// the tile's four records as 32-bit records
+template <bool kCompact>
+__device__ __forceinline__ void tile_records(const TileWords &t, uint32_t (&rcs)[4]) {
+  if (kCompact) {
+    uint32_t r[4];
+    unpack24(t.x.y, t.x.z, t.x.w, r);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) rcs[j] = rec24_to_32(r[j]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) rcs[j] = t.w[j];
+  }
+}
+// LDS accesses of one wave execute in order, so the next tile's loads see this tile's stores: a compiler barrier is all
+// they need.  Every fourth tile tells the helper waves how far the sweep is.
+__device__ __forceinline__ void tile_done(int *progress, int T) {
+  asm volatile("" ::: "memory");
+  if ((T & 3) == 3) lds_flag_store(progress, T);
+}
+// The sweep wave's loop: load(T, tile) issues the loads of tile T, step(tile) is the kernel's arithmetic.  Two tiles
+// per trip, so that the two tile registers swap roles without copies (a copy of registers with a load in flight would
+// wait for it).
+template <class Tile, class Load, class Step>
+__device__ __forceinline__ void tile_run(const int &tiles, int *const &progress, const Load &load, const Step &step) {
+  Tile ta, tb;
+  if (tiles > 0) load(0, ta);
+  for (int T = 0; T < tiles; T += 2) {
+    load(min(T + 1, tiles - 1), tb);
+    step(ta);
+    tile_done(progress, T);
+    if (T + 1 >= tiles) break;
+    load(min(T + 2, tiles - 1), ta);
+    step(tb);
+    tile_done(progress, T + 1);
+  }
+}
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef uint32_t v2u __attribute__((ext_vector_type(2)));
@@ -1355,22 +1399,9 @@ __device__ __forceinline__ void dec2p_fetch(uint32_t sb, int lane, Dec2P &d) {
   d.wm[2] = __hiloint2double((int)q.y, (int)q.x); d.wm[3] = __hiloint2double((int)q.w, (int)q.z);
   d.we[0] = (int)e.x; d.we[1] = (int)e.y; d.we[2] = (int)e.z; d.we[3] = (int)e.w;
 }
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-  return __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false),
-                          __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false));
-}
-// segmented sum of float64 partial sums that share an exponent: a lane whose state owns 2^g lanes takes part in stages 0 .. g-1
+// segmented sum of float64 partial sums that share an exponent
 template <int STAGES>
-__device__ __forceinline__ double seg_sum64(double M, int g) {
-  if (STAGES >= 1) { const double o = dpp_d<0xB1>(M); M = (g >= 1) ? M + o : M; }
-  if (STAGES >= 2) { const double o = dpp_d<0x4E>(M); M = (g >= 2) ? M + o : M; }
-  if (STAGES >= 3) { const double o = dpp_d<0x141>(M); M = (g >= 3) ? M + o : M; }
-  if (STAGES >= 4) { const double o = dpp_d<0x140>(M); M = (g >= 4) ? M + o : M; }
-  if (STAGES >= 5) { const double o = __shfl_xor(M, 16); M = (g >= 5) ? M + o : M; }
-  if (STAGES >= 6) { const double o = __shfl_xor(M, 32); M = (g >= 6) ? M + o : M; }
-  return M;
-}
+__device__ __forceinline__ double seg_sum64(double M, int g) { return seg_reduce<STAGES>(M, g, 6, OpSum{}); }
 __device__ __forceinline__ double ldexp_clamped(double m, int d) {  // (exponent differences may be near -2^28: zero then)
   return ldexp(m, max(d, -2000));
 }

@@ -182,13 +182,17 @@ __device__ __forceinline__ float arc_posterior(const float2 av, const float2 bv,
 // TW (1024 threads): tile waves -- no loader, no staging ring, no decoder: the eight waves 2, 3, 6, 7, 10, 11, 14, 15
 // (the SIMDs the sweep waves are not on) decode every fourth tile of their sweep's program straight from
 // HBM into the decoded ring, label weights and per-arc extras included (WeightWave<.., FULL>).
-template <int NT, int EXTRA, bool FUSED = false, bool TW = false, bool PREC = false>
+// PTH (tile waves, no extras, float32, launches without grad_theta): the helper threads gather the label weights of their
+// preloaded arc groups in front of the barrier and keep them in registers in place of the labels; no label histogram.
+template <int NT, int EXTRA, bool FUSED = false, bool TW = false, bool PREC = false, bool PTH = false>
 __global__ __launch_bounds__(NT) void k_forward_backward(
     nfst_batch lat, nfst_scores sc, int R, int RS, float *__restrict__ logalpha, float *__restrict__ logbeta,
     double *__restrict__ logz64, float *__restrict__ logz32, double *__restrict__ logz_total, int total_slot,
     float *__restrict__ posterior,
-    float *__restrict__ grad_theta, float2 *__restrict__ beta_me) {
+    float *__restrict__ grad_theta_arg, float2 *__restrict__ beta_me) {
   static_assert(!PREC || (TW && EXTRA != 3), "precise flavour: tile waves, per-arc extras from HBM / L2");
+  static_assert(!PTH || (TW && EXTRA == 0 && !PREC), "preloaded label weights: float32 tile waves without per-arc extras");
+  float *const grad_theta = PTH ? nullptr : grad_theta_arg;  // (PTH: the launcher passes none; the label sums compile out)
   typedef typename ValOf<PREC>::T VT;
   extern __shared__ float2 lds_raw[];
   VT *lds = reinterpret_cast<VT *>(lds_raw);
@@ -308,6 +312,8 @@ __global__ __launch_bounds__(NT) void k_forward_backward(
   // src | dst << 16 and the label of 4 consecutive canonical arcs: 16 + 8 bytes
   uint4 psd[kPre > 0 ? kPre : 1];
   uint2 plb[kPre > 0 ? kPre : 1];
+  // PTH: th[label] of those arcs instead, gathered while the sweeps run (load_theta finished the table before the first tile)
+  float4 pt01[PTH ? kPre : 1], pt23[PTH ? kPre : 1];  // (m0, e0, m1, e1), (m2, e2, m3, e3)
   // exp of their per-arc extras as (mantissa, exponent), computed while the sweeps run: fetched and exponentiated after the
   // sweeps they doubled the posterior pass (7.5 -> 15 us)
   float4 pxm[kPre > 0 ? kPre : 1];
@@ -325,7 +331,28 @@ __global__ __launch_bounds__(NT) void k_forward_backward(
     }
     return x;
   };
+  // PTH: the helper waves that are no tile waves (10 .. 15) gather the label weights; a tile wave gets here when its tiles are
+  // done, ~1 us before the sweeps end, and its arc loads come back after them (waiting for them in front of the barrier moved
+  // the barrier of the last workgroups by 1.6 us): it keeps the labels, in the registers of the weights, and gathers behind
+  // the barrier as before
+  const bool pre_th = PTH && !x_wave;
   auto preload_arcs = [&]() {
+    if (PTH && !pre_th) {
+      // (the wave's last tile loads -- past its last tile, never used -- are still in flight: waited for here, where they
+      // are the only ones, instead of wherever one of their registers is taken again, with arc loads behind them)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int u = 0; u < kPre; ++u) {
+        const int a = v_begin + 4 * (u * kHelpers + (tid - kSweepThreads));
+        if (a < v_end) {
+          psd[u] = *reinterpret_cast<const uint4 *>(lat.arc_sd + a);
+          const uint2 lb = *reinterpret_cast<const uint2 *>(lat.arc_l16 + a);
+          pt01[u].x = __uint_as_float(lb.x);
+          pt01[u].y = __uint_as_float(lb.y);
+        }
+      }
+      return;
+    }
 #pragma unroll
     for (int u = 0; u < kPre; ++u) {
       const int a = v_begin + 4 * (u * kHelpers + (tid - kSweepThreads));
@@ -333,6 +360,18 @@ __global__ __launch_bounds__(NT) void k_forward_backward(
         psd[u] = *reinterpret_cast<const uint4 *>(lat.arc_sd + a);
         plb[u] = *reinterpret_cast<const uint2 *>(lat.arc_l16 + a);
         if (has_extra) pxm[u] = extras4(a);
+      }
+    }
+    if (PTH) {
+#pragma unroll
+      for (int u = 0; u < kPre; ++u) {
+        const int a = v_begin + 4 * (u * kHelpers + (tid - kSweepThreads));
+        if (a < v_end) {
+          const float2 t0 = me_f2(th[(int)(plb[u].x & 0xffffu)]), t1 = me_f2(th[(int)(plb[u].x >> 16)]);
+          const float2 t2 = me_f2(th[(int)(plb[u].y & 0xffffu)]), t3 = me_f2(th[(int)(plb[u].y >> 16)]);
+          pt01[u] = make_float4(t0.x, t0.y, t1.x, t1.y);
+          pt23[u] = make_float4(t2.x, t2.y, t3.x, t3.y);
+        }
       }
     }
     if (has_extra) {
@@ -389,7 +428,10 @@ __global__ __launch_bounds__(NT) void k_forward_backward(
   }
   const float rz = (zme.x > 0.0f) ? 1.0f / zme.x : 0.0f;
   const int ez = __float_as_int(zme.y);
-  auto do_group = [&](const uint4 sd, const uint2 lb, int a, const float4 xm, const int4 xe) {
+  // pre: the group's label weights were gathered in front of the barrier (PTH: t01, t23), otherwise they come from lb
+  auto do_group = [&](const uint4 sd, const uint2 lb, const bool pre, const float4 t01, const float4 t23, int a, const float4 xm,
+                      const int4 xe) {
+    const float2 tpre[4] = {make_float2(t01.x, t01.y), make_float2(t01.z, t01.w), make_float2(t23.x, t23.y), make_float2(t23.z, t23.w)};
     const float xmv[4] = {xm.x, xm.y, xm.z, xm.w};
     const int xev[4] = {xe.x, xe.y, xe.z, xe.w};
     const uint32_t sdv[4] = {sd.x, sd.y, sd.z, sd.w};
@@ -409,7 +451,7 @@ __global__ __launch_bounds__(NT) void k_forward_backward(
       for (int q = 0; q < kG; ++q) {
         av[q] = me_f2(alpha[(int)(sdv[q0 + q] & 0xffffu)]);
         bv[q] = me_f2(beta[(int)(sdv[q0 + q] >> 16)]);
-        tv[q] = me_f2(th[ll[q0 + q]]);
+        tv[q] = pre ? tpre[q0 + q] : me_f2(th[ll[q0 + q]]);
       }
 #pragma unroll
       for (int q = 0; q < kG; ++q) {
@@ -434,13 +476,20 @@ __global__ __launch_bounds__(NT) void k_forward_backward(
       exp_me_fast(x.x, gm.x, ge.x); exp_me_fast(x.y, gm.y, ge.y);
       exp_me_fast(x.z, gm.z, ge.z); exp_me_fast(x.w, gm.w, ge.w);
     }
-    do_group(sd, lb, a, gm, ge);
+    do_group(sd, lb, false, gm, gm, a, gm, ge);
   };
-  if (kPre > 0 && tid >= kSweepThreads && want_post) {
+  if (PTH && tid >= kSweepThreads && want_post && !pre_th) {
 #pragma unroll
     for (int u = 0; u < kPre; ++u) {
       const int a = v_begin + 4 * (u * kHelpers + (tid - kSweepThreads));
-      if (a < v_end) do_group(psd[u], plb[u], a, pxm[u], pxe[u]);
+      const uint2 lb = make_uint2(__float_as_uint(pt01[PTH ? u : 0].x), __float_as_uint(pt01[PTH ? u : 0].y));
+      if (a < v_end) do_group(psd[u], lb, false, pt01[0], pt01[0], a, pxm[u], pxe[u]);
+    }
+  } else if (kPre > 0 && tid >= kSweepThreads && want_post) {
+#pragma unroll
+    for (int u = 0; u < kPre; ++u) {
+      const int a = v_begin + 4 * (u * kHelpers + (tid - kSweepThreads));
+      if (a < v_end) do_group(psd[u], plb[u], PTH, pt01[PTH ? u : 0], pt23[PTH ? u : 0], a, pxm[u], pxe[u]);
     }
   }
   if (TW && wv == 10) NFST_STAMP(8);  // a helper wave (not a tile wave) has issued the stores of its preloaded groups

@@ -220,7 +220,9 @@ bool ring_config(const LdsPlan &plan, bool fb, bool deep, RingCfg *c) {
 //   fused:      forward-backward of all-compact batches without extras, more lattices than CUs (no rings at all);
 //   general:    Viterbi from global memory.
 enum class Flavour { precise, tile_waves, pipeline, fused, general };
-struct SweepPlan { Flavour flavour; int nt, ex, R, RS; int64_t lds; };
+//   pre_theta (forward-backward tile waves without extras, launches that want no label sums): the helper threads gather
+//   the label weights of their preloaded arcs while the sweeps run (fb_kernels.h, PTH).
+struct SweepPlan { Flavour flavour; int nt, ex, R, RS; int64_t lds; bool pre_theta = false; };
 
 int plan_backward(const nfst_batch *lat, const nfst_scores *sc, SweepPlan *p) {
   const int ex = extras_case(lat, sc);
@@ -241,7 +243,7 @@ int plan_backward(const nfst_batch *lat, const nfst_scores *sc, SweepPlan *p) {
   return NFST_OK;
 }
 
-int plan_forward_backward(const nfst_batch *lat, const nfst_scores *sc, SweepPlan *p) {
+int plan_forward_backward(const nfst_batch *lat, const nfst_scores *sc, bool want_grad_theta, SweepPlan *p) {
   const int ex = extras_case(lat, sc);
   if (ex && (((uintptr_t)lat->fwd_perm | (uintptr_t)lat->bwd_perm | (uintptr_t)lat->arc_w | (uintptr_t)sc->arc_scores) & 15))
     return NFST_ERR_ARG;  // (maps and extras are read 16 bytes at a time)
@@ -267,7 +269,7 @@ int plan_forward_backward(const nfst_batch *lat, const nfst_scores *sc, SweepPla
     const int64_t slot = (int64_t)kSlotWords2 * 4 * 2, fixed = plan.fb_bytes(0, 0);
     const int R = ring_slots(fixed, slot, lds_reserve());
     if (R < 4) return NFST_ERR_LIMIT;
-    *p = {Flavour::tile_waves, 1024, ex, R, 0, fixed + (int64_t)R * slot};
+    *p = {Flavour::tile_waves, 1024, ex, R, 0, fixed + (int64_t)R * slot, !ex && !want_grad_theta};
     // per-arc extras staged in LDS (the sum of both arrays, 4 bytes per arc of the largest lattice) when a ring of at least
     // eight slots per sweep still fits beside them (lattices up to ~14k arcs at 2k states); RS carries the room in floats
     const int64_t max_arcs = max_lattice_arcs(lat);
@@ -328,14 +330,16 @@ int launch_backward(const nfst_batch *lat, const nfst_scores *sc, const SweepOut
 
 int launch_forward_backward(const nfst_batch *lat, const nfst_scores *sc, const SweepOut &o, hipStream_t st) {
   SweepPlan p;
-  if (int rc = plan_forward_backward(lat, sc, &p)) return rc;
+  if (int rc = plan_forward_backward(lat, sc, o.grad_theta != nullptr, &p)) return rc;
   auto go = [&](auto kernel) {
     return launch(kernel, dim3(lat->n_lattices), dim3(p.nt), p.lds, st, *lat, *sc, p.R, p.RS, o.logalpha, o.logbeta, o.logz64,
                   o.logz32, o.logz_total, o.total_slot, o.posterior, o.grad_theta, (float2 *)o.beta_me);
   };
   switch (p.flavour) {
     case Flavour::precise: return with_extras(p.ex, [&](auto EX) { return go(k_forward_backward<1024, EX, false, true, true>); });
-    case Flavour::tile_waves: return with_extras<true>(p.ex, [&](auto EX) { return go(k_forward_backward<1024, EX, false, true>); });
+    case Flavour::tile_waves:
+      if (p.pre_theta) return go(k_forward_backward<1024, 0, false, true, false, true>);
+      return with_extras<true>(p.ex, [&](auto EX) { return go(k_forward_backward<1024, EX, false, true>); });
     case Flavour::fused: return with_threads<false>(p.nt, [&](auto NT) { return go(k_forward_backward<NT, 0, true>); });
     default:
       return with_threads<true>(p.nt, [&](auto NT) {

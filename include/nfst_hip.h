@@ -50,6 +50,8 @@
  *   nfst_positional, nfst_positional_viterbi  exact sweeps under scores that depend on the position of an arc on the
  *                                      path ([B, T, V] logits) and under a length budget: what the sampler side only
  *                                      truncates (emission_mask(has_to_end = length > max_length), NFST_ERR_LENGTH)
+ *   nfst_positional_sample, nfst_positional_score_paths  exact draws from that distribution (no draw overruns the
+ *                                      budget) with their log-probabilities, and forced scores of given marks
  *
  * Conventions
  *   - plain C: pointers and sizes only, no C++/torch types.
@@ -686,10 +688,53 @@ int nfst_intersect_write(const nfst_batch *lat, const int8_t *delta_t, int64_t d
  * dynamic LDS of the launch, arc records included, to *lds_bytes and 1 or 0 to *staged (either may be null) and returns
  * NFST_OK, or returns NFST_ERR_LIMIT exactly when the op itself would.  Both launchers call it: there is no second copy
  * of the rule.
+ *
+ * nfst_positional_sample (draws).  K exact draws per lattice from p_T(pi) = exp(S_T(pi)) / Z_T over the paths of at most
+ * T arcs; paths, positions, pos, pos_stride, T and -inf entries are exactly those of nfst_positional.  The launch runs
+ * the backward pass of nfst_positional with every beta row stored and NO forward pass (the same kernel: logz64 / logz32
+ * are the bits nfst_positional writes for the same inputs), then one wave per walk, the grid over all B * K walks.
+ * Walk (b, k) starts in state 0.  At position t in state s != sink it looks at the out-arcs of s without self loops, in
+ * canonical order; arc a has
+ *     p_a = w_t(a) beta_{t+1}(dst_a) / beta_t(s),     w_t(a) = exp(s_a + pos[b, t, label_a]),
+ * in the arithmetic of the backward pass ((float64 mantissa, int32 exponent), exp_split64).  With u = uniforms[b, k, t]
+ * (device float32 in [0, 1), shape [B, K, T]) the walk takes the FIRST arc whose running sum of w beta_{t+1} exceeds
+ * u beta_t(s) -- compared without a division.  An arc of weight zero is never taken; if rounding leaves no arc above the
+ * target, the last arc of positive weight is.  The walk ends at the sink.  beta_T(s) = 0 off the sink, so a walk never
+ * needs more than T arcs: there is no status word and no NFST_ERR_LENGTH (nfst_sample_paths truncates; this does not).
+ * uniforms = NULL: Philox4x32-10 exactly as nfst_sample_paths uses it (key = seed, counter = (walk, step / 4),
+ * walk = b K + k, one block for four steps).  Outputs, every element written exactly once:
+ *     paths [B, K, T] int32 labels padded with `pad`; path_arcs (optional) [B, K, T] canonical arc ids padded with -1;
+ *     lengths [B, K];  logq [B, K] float32 = S_T(pi) - log Z_T, S summed in float64 from the float32 inputs and rounded
+ *     once;  logz64 [B] (required), logz32 [B] (optional).
+ * A lattice with log Z_T = -inf gets length 0, labels `pad`, arcs -1 and logq = 0 (so log p - log q stays -inf, never a
+ * NaN) and does not disturb its neighbours.  The op reads the canonical arrays only and shares nothing between walks: the
+ * same bits for every packing (staged or not, with or without chunked programs) and at every launch; walk (b, k) depends
+ * on nothing but its own uniforms (not on K).
+ * ws: nfst_positional_ws_bytes(lat, T, NFST_POS_WS_SAMPLE) = 12 bytes per arc + 12 * (T + 1) * total_rows: EVERY beta row
+ * of every position, as NFST_POS_WS_POSTERIOR stores them (no checkpointing).  LDS and NFST_ERR_LIMIT: nfst_positional's,
+ * through nfst_positional_plan; more than 2^31 - 1 walks (B * K; the walk is a 32-bit word of the Philox counter) also
+ * return NFST_ERR_LIMIT.  k < 1, T < 1, a bad stride, null required pointers or a short workspace return NFST_ERR_ARG.
+ * All checks run on the host before any launch.
+ *
+ * nfst_positional_score_paths (forced scores).  The forced walk of marks [B, K, T] (device int32, pad-terminated) from
+ * state 0 under the same scores: the mark at position t takes the arc of the current state with that label and scores
+ * s_a + pos[b, t, label].  The sink's pad loop scores nothing.
+ *     path_score [B, K] float32   the float64 sum rounded once; -inf if a mark has no arc or an entry is -inf
+ *     end_state [B, K]            the state reached; 0 if the walk fell off the lattice (nfst_score_paths' rule)
+ *     lengths [B, K]              the marks before the first pad
+ * With pos = NULL it is nfst_score_paths up to float32 rounding (that op adds an arc's terms in float32 first).
+ * k < 1, T < 1, a bad stride or null pointers return NFST_ERR_ARG, k above 64 * 65535 NFST_ERR_LIMIT; on the host.
  */
 #define NFST_POS_WS_POSTERIOR 1
 #define NFST_POS_WS_VITERBI 2
+#define NFST_POS_WS_SAMPLE 8 /* 12 bytes per arc + 12 (T + 1) total_rows: every beta row of every position */
 int64_t nfst_positional_ws_bytes(const nfst_batch *lat, int32_t T, int32_t flags);
+int nfst_positional_sample(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T,
+                           int32_t k, const float *uniforms, uint64_t seed, int32_t pad, void *ws, int64_t ws_bytes, double *logz64,
+                           float *logz32, int32_t *paths, int32_t *path_arcs, int32_t *lengths, float *logq, void *stream);
+int nfst_positional_score_paths(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T,
+                                const int32_t *marks, int32_t k, float *path_score, int32_t *end_state, int32_t *lengths,
+                                void *stream);
 int nfst_positional_plan(const nfst_batch *lat, int32_t viterbi, int64_t *lds_bytes, int32_t *staged);
 int nfst_positional(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T, void *ws,
                     int64_t ws_bytes, double *logz64, float *logz32, double *len_logz, float *pos_post, float *arc_post,

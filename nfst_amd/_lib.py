@@ -28,6 +28,7 @@ CHK_SUM_WORDS = 8  # summary of a program cut on the device (nfst_pack_chunks_de
 
 OK = 0
 ERR_LENGTH = -9
+POS_WS_POSTERIOR, POS_WS_VITERBI, POS_WS_SAMPLE = 1, 2, 8  # flags of nfst_positional_ws_bytes
 
 
 class NfstError(RuntimeError):
@@ -162,6 +163,8 @@ def _load():
         "nfst_positional_plan": (C.c_int, [BP, i32, C.POINTER(i64), C.POINTER(i32)]),
         "nfst_positional": (C.c_int, [BP, SP, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp]),
         "nfst_positional_viterbi": (C.c_int, [BP, SP, vp, i64, i32, vp, i64, vp, vp, vp, vp, i32, vp]),
+        "nfst_positional_sample": (C.c_int, [BP, SP, vp, i64, i32, i32, vp, u64, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "nfst_positional_score_paths": (C.c_int, [BP, SP, vp, i64, i32, vp, i32, vp, vp, vp, vp]),
         "nfst_path_logprob": (C.c_int, [vp, vp, i64, i32, i32, i32, i32, i32, i32, f32, i32, f32, i32, vp, vp]),
         "nfst_path_logprob_backward": (C.c_int, [vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, f32, i32, f32, i32, vp, vp]),
         "nfst_iwae": (C.c_int, [vp, vp, i32, i32, vp, vp, vp]),

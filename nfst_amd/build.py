@@ -87,7 +87,10 @@ def check_resources(res: dict) -> list:
       a0 .. a31 from inline asm: the compiler must have allocated exactly those 32 AGPRs (``AGPRs: 32``; more
       would mean it uses AGPRs itself -- it may then pick a0 .. a31 between two asm statements, the abort of
       round 2) and spilled no VGPR (its spills go to AGPRs first);
-    * no sweep kernel may spill vector registers: the tile / sweep loops are latency chains.
+    * no sweep kernel may spill vector registers: the tile / sweep loops are latency chains.  The pattern
+      ``k_positional`` is a prefix on purpose: it covers ``k_positional<..>``, ``k_positional_viterbi<..>`` and the
+      kernels of the draws, ``k_positional_walk<..>`` (a chain of dependent loads and scan stages per position) and
+      ``k_positional_score``.
     """
     bad = []
     for name, r in res.items():

@@ -988,17 +988,19 @@ int nfst_arc_slack(const nfst_batch *lat, const nfst_scores *scores, const float
 
 // ------------------------------------------------------------------ position-dependent scores (positional_kernels.h)
 // workspace: the weights of the per-arc extras; with NFST_POS_WS_POSTERIOR the stored beta rows ((T + 1) rows of
-// (float64, int32) per row of the batch), the by-destination order and the per-arc sums; with NFST_POS_WS_VITERBI the
-// stored max-plus rows
+// (float64, int32) per row of the batch), the by-destination order and the per-arc sums; with NFST_POS_WS_SAMPLE the
+// stored beta rows alone; with NFST_POS_WS_VITERBI the stored max-plus rows
 static int64_t pos_ws_layout(const nfst_batch *lat, int64_t T, int flags, char *base, PosWs *w) {
   const int64_t TR = lat->total_rows, A = lat->total_arcs, B = lat->n_lattices, rows = (T + 1) * TR;
   WsCarve c{base};
   PosWs r = {};
   r.ewm = (double *)c.take(8 * A);
   r.ewe = (int *)c.take(4 * A);
-  if (flags & NFST_POS_WS_POSTERIOR) {
+  if (flags & (NFST_POS_WS_POSTERIOR | NFST_POS_WS_SAMPLE)) {
     r.bm = (double *)c.take(8 * rows);
     r.be = (int *)c.take(4 * rows);
+  }
+  if (flags & NFST_POS_WS_POSTERIOR) {
     r.in_ptr = (int *)c.take(4 * (TR + B));
     r.in_tmp = (int *)c.take(4 * A);
     r.in_rec = (int2 *)c.take(8 * A);
@@ -1031,7 +1033,7 @@ static int64_t pos_staged_bytes(const nfst_batch *lat, int64_t lds) {
 int64_t nfst_positional_ws_bytes(const nfst_batch *lat, int32_t T, int32_t flags) {
   const int rc = check_batch(lat);
   if (rc) return rc;
-  if (T < 1 || (flags & ~(NFST_POS_WS_POSTERIOR | NFST_POS_WS_VITERBI))) return NFST_ERR_ARG;
+  if (T < 1 || (flags & ~(NFST_POS_WS_POSTERIOR | NFST_POS_WS_VITERBI | NFST_POS_WS_SAMPLE))) return NFST_ERR_ARG;
   return pos_ws_layout(lat, T, flags, nullptr, nullptr);
 }
 
@@ -1050,6 +1052,21 @@ int nfst_positional_plan(const nfst_batch *lat, int32_t viterbi, int64_t *lds_by
   return NFST_OK;
 }
 
+// one launch of k_positional in the flavour nfst_positional_plan chose (mode: kPosModeLogz / Alpha / Rows)
+static int pos_launch_sum(const nfst_batch *lat, const nfst_scores *scores, const PosIn &in, const PosWs &w, const PosOut &o, int mode,
+                          hipStream_t st) {
+  int64_t lds;
+  int32_t staged;
+  const int rc = nfst_positional_plan(lat, 0, &lds, &staged);
+  if (rc) return rc;
+  const dim3 grid(lat->n_lattices), block(kPosThreads);
+  if (extras_case(lat, scores))
+    return staged ? launch(k_positional<true, true>, grid, block, lds, st, *lat, in, w, o, mode)
+                  : launch(k_positional<true, false>, grid, block, lds, st, *lat, in, w, o, mode);
+  return staged ? launch(k_positional<false, true>, grid, block, lds, st, *lat, in, w, o, mode)
+                : launch(k_positional<false, false>, grid, block, lds, st, *lat, in, w, o, mode);
+}
+
 int nfst_positional(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T, void *ws,
                     int64_t ws_bytes, double *logz64, float *logz32, double *len_logz, float *pos_post, float *arc_post,
                     void *stream) {
@@ -1058,20 +1075,47 @@ int nfst_positional(const nfst_batch *lat, const nfst_scores *scores, const floa
   int rc = pos_check(lat, scores, pos, pos_stride, T, ws, ws_bytes, flags);
   if (rc) return rc;
   if (!logz64) return NFST_ERR_ARG;
-  int64_t lds;
-  int32_t staged;
-  if ((rc = nfst_positional_plan(lat, 0, &lds, &staged))) return rc;
   PosWs w;
   pos_ws_layout(lat, T, flags, (char *)ws, &w);
   const PosIn in = {*scores, pos, pos ? pos_stride : 0, (int)T};
   const PosOut o = {logz64, logz32, len_logz, pos_post, arc_post};
+  return pos_launch_sum(lat, scores, in, w, o, need_alpha ? kPosModeAlpha : kPosModeLogz, (hipStream_t)stream);
+}
+
+// the backward pass of nfst_positional alone with every beta row stored (the same kernel, the same bits, no forward
+// pass), then one wave per walk over all B * K walks
+int nfst_positional_sample(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T,
+                           int32_t k, const float *uniforms, uint64_t seed, int32_t pad, void *ws, int64_t ws_bytes, double *logz64,
+                           float *logz32, int32_t *paths, int32_t *path_arcs, int32_t *lengths, float *logq, void *stream) {
+  int rc = pos_check(lat, scores, pos, pos_stride, T, ws, ws_bytes, NFST_POS_WS_SAMPLE);
+  if (rc) return rc;
+  if (k < 1 || !logz64 || !paths || !lengths || !logq) return NFST_ERR_ARG;
+  const int64_t walks = (int64_t)lat->n_lattices * k;
+  if (walks > INT32_MAX) return NFST_ERR_LIMIT;  // (the walk is a 32-bit word of the Philox counter, as in nfst_sample_paths)
+  PosWs w;
+  pos_ws_layout(lat, T, NFST_POS_WS_SAMPLE, (char *)ws, &w);
+  const PosIn in = {*scores, pos, pos ? pos_stride : 0, (int)T};
+  const PosOut o = {logz64, logz32, nullptr, nullptr, nullptr};
   const hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(lat->n_lattices), block(kPosThreads);
-  if (extras_case(lat, scores))
-    return staged ? launch(k_positional<true, true>, grid, block, lds, st, *lat, in, w, o, need_alpha)
-                  : launch(k_positional<true, false>, grid, block, lds, st, *lat, in, w, o, need_alpha);
-  return staged ? launch(k_positional<false, true>, grid, block, lds, st, *lat, in, w, o, need_alpha)
-                : launch(k_positional<false, false>, grid, block, lds, st, *lat, in, w, o, need_alpha);
+  if ((rc = pos_launch_sum(lat, scores, in, w, o, kPosModeRows, st))) return rc;
+  const PosWalkOut wo = {logz64, paths, path_arcs, lengths, logq, (int)pad};
+  const dim3 grid((unsigned)((walks + kPosWalkWaves - 1) / kPosWalkWaves)), block(kPosWalkWaves * 64);
+  if (extras_case(lat, scores)) return launch(k_positional_walk<true>, grid, block, 0, st, *lat, in, w, (int)k, uniforms, seed, wo);
+  return launch(k_positional_walk<false>, grid, block, 0, st, *lat, in, w, (int)k, uniforms, seed, wo);
+}
+
+int nfst_positional_score_paths(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T,
+                                const int32_t *marks, int32_t k, float *path_score, int32_t *end_state, int32_t *lengths,
+                                void *stream) {
+  int rc = check_batch(lat);
+  if (rc) return rc;
+  if ((rc = check_scores(lat, scores))) return rc;
+  if (T < 1 || k < 1 || (pos && pos_stride != 0 && pos_stride != (int64_t)T * lat->vocab)) return NFST_ERR_ARG;
+  if (!marks || !path_score || !end_state || !lengths) return NFST_ERR_ARG;
+  if (((int64_t)k + 63) / 64 > 65535) return NFST_ERR_LIMIT;  // (the y dimension of the grid)
+  const PosIn in = {*scores, pos, pos ? pos_stride : 0, (int)T};
+  return launch(k_positional_score, dim3(lat->n_lattices, (k + 63) / 64), dim3(64), 0, (hipStream_t)stream, *lat, in, marks, (int)k,
+                path_score, end_state, lengths);
 }
 
 int nfst_positional_viterbi(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T,

@@ -12,6 +12,8 @@
 //                         by-destination order built once per launch, with the posteriors of every (position, label)
 //                         and every arc and the weight of every path length
 //   k_positional_viterbi  the same backward pass in max-plus (plain float32), then one thread walks the best path
+//   k_positional_walk     exact draws: one wave per walk reads the beta rows that k_positional stored (kPosModeRows: the
+//                         backward pass alone, no forward pass); k_positional_score is the forced walk of given marks
 // The backward pass is ONE function template over the semiring (PosSum / PosMax), not a copy.
 //
 // Arithmetic of the sum-product kernel: (float64 mantissa, int32 exponent) THROUGHOUT, for every T -- label weights by
@@ -26,6 +28,10 @@
 // at every launch and for every packing.
 constexpr int kPosThreads = 1024;
 constexpr int kPosPostBits = kExpPostBits;  // per-label posterior sums in fixed point, as label_post of nfst_expectation
+// what a launch of k_positional does after the backward pass: nothing (log Z only), the forward pass over the stored
+// beta rows (posteriors, lengths), or nothing but with every beta row stored for k_positional_walk
+constexpr int kPosModeLogz = 0, kPosModeAlpha = 1, kPosModeRows = 2;
+constexpr int kPosWalkWaves = 4;  // walks (waves) per workgroup of k_positional_walk
 
 struct PosIn {
   nfst_scores sc;
@@ -210,9 +216,10 @@ __device__ __forceinline__ void pos_beta_pass(const nfst_batch &lat, const Meta 
 // int per thread for the prefix sums: 24 max_rows + 20 vocab + 4 kPosThreads bytes.
 // STAGED: + 4 (max_rows + 1) + 4 (arcs of the largest lattice) bytes for the arc records.
 template <bool EXTRA, bool STAGED>
-__global__ __launch_bounds__(kPosThreads) void k_positional(nfst_batch lat, PosIn in, PosWs w, PosOut o, int need_alpha) {
+__global__ __launch_bounds__(kPosThreads) void k_positional(nfst_batch lat, PosIn in, PosWs w, PosOut o, int mode) {
   extern __shared__ double pos_lds[];
   const int b = blockIdx.x, tid = threadIdx.x;
+  const bool need_alpha = mode == kPosModeAlpha, store = mode != kPosModeLogz;
   const Meta m = load_meta(lat.meta, b);
   const int R = lat.max_rows, V = lat.vocab, T = in.T, n = m.n_rows;
   double *vm = pos_lds, *tm = vm + 2 * R;
@@ -289,7 +296,7 @@ __global__ __launch_bounds__(kPosThreads) void k_positional(nfst_batch lat, PosI
 
   // ---- backwards in time ----------------------------------------------------------------------------------------
   const size_t ro = (size_t)(T + 1) * m.row_off;
-  const PosSum::Store st = {need_alpha ? w.bm + ro : nullptr, need_alpha ? w.be + ro : nullptr};
+  const PosSum::Store st = {store ? w.bm + ro : nullptr, store ? w.be + ro : nullptr};
   auto ext = [&](int a, ME64 x) -> ME64 {
     if (EXTRA) { x.m *= w.ewm[a]; x.e += w.ewe[a]; }
     return x;
@@ -443,4 +450,178 @@ __global__ __launch_bounds__(kPosThreads) void k_positional_viterbi(nfst_batch l
     po[t] = o.pad;
     if (ao) ao[t] = -1;
   }
+}
+
+// ------------------------------------------------------------------ draws and forced scores
+// k_positional_walk draws from p_T(pi) = exp(S_T(pi)) / Z_T over the paths of at most T arcs, after a launch of
+// k_positional in kPosModeRows has stored every beta row.  One wave per walk (b, k), kPosWalkWaves walks per workgroup,
+// the grid over all B * K walks.  At position t in state s the lanes take the out-arcs of s in canonical order, 64 per
+// round: lane i computes x_i = w_t(a_i) * beta_{t+1}(dst) (exp_split64 on demand, the extras' weights from the
+// workspace; zero for a self loop), the wave scans the x_i inclusively by the six butterfly stages of wave_ops.h, and
+// the first lane with x_i > 0 whose running sum exceeds u * beta_t(s) wins (a ballot).  The running sum is carried
+// from round to round.  If rounding leaves nobody above the target the last arc of positive weight is taken.
+// beta_T is zero off the sink, so the arc at position T - 1 enters the sink: no walk overruns T.  Nothing is shared
+// between walks and nothing is accumulated with atomics: a walk is a function of its own uniforms.
+struct PosWalkOut {
+  const double *logz64;  // [B], written by the k_positional launch before this one
+  int32_t *paths, *path_arcs, *lengths;
+  float *logq;
+  int pad;
+};
+
+// a + b rescaled to the larger exponent, as PosSum::combine: the same bits whichever operand comes first
+__device__ __forceinline__ ME64 pos_add(ME64 a, ME64 b) {
+  const int E = max(a.e, b.e);
+  return {__builtin_amdgcn_ldexp(a.m, a.e - E) + __builtin_amdgcn_ldexp(b.m, b.e - E), E};
+}
+// a > b
+__device__ __forceinline__ bool pos_above(ME64 a, ME64 b) {
+  const int E = max(a.e, b.e);
+  return __builtin_amdgcn_ldexp(a.m, a.e - E) > __builtin_amdgcn_ldexp(b.m, b.e - E);
+}
+// Stage S of the inclusive scan over a wave: groups of 2^S lanes, each lane with its prefix `pre` inside the group and
+// the group's total `tot` (the same bits in all its lanes), merge in pairs; the upper group adds the lower one's total.
+template <int S>
+__device__ __forceinline__ void pos_scan_stage(ME64 &pre, ME64 &tot, int lane) {
+  const ME64 o = {wave_partner<S>(tot.m), wave_partner<S>(tot.e)};
+  const ME64 up = pos_add(o, pre);
+  const bool upper = (lane >> S) & 1;
+  pre.m = upper ? up.m : pre.m;
+  pre.e = upper ? up.e : pre.e;
+  tot = pos_add(tot, o);
+}
+
+template <bool EXTRA>
+__global__ __launch_bounds__(kPosWalkWaves * 64) void k_positional_walk(nfst_batch lat, PosIn in, PosWs w, int K, const float *uniforms,
+                                                                       uint64_t seed, PosWalkOut o) {
+  const int lane = threadIdx.x & 63;
+  const int64_t walk = (int64_t)blockIdx.x * kPosWalkWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (walk >= (int64_t)lat.n_lattices * K) return;  // (a whole wave: the lanes of a walk stay together throughout)
+  const int b = (int)(walk / K);
+  const Meta m = load_meta(lat.meta, b);
+  const int T = in.T, V = lat.vocab, n = m.n_rows;
+  const float *theta = in.sc.theta + (size_t)in.sc.theta_stride * b;
+  const float *pos_b = in.pos ? in.pos + (size_t)in.pos_stride * b : nullptr;
+  const float *arc_w = lat.weighted ? lat.arc_w : nullptr;
+  const int32_t *rp = lat.row_ptr + m.row_off + b;
+  const int a_lo = m.arc_off, a_hi = m.arc_off + m.n_arcs;
+  const size_t ro = (size_t)(T + 1) * m.row_off;
+  const double *bm = w.bm + ro;
+  const int *be = w.be + ro;
+  int32_t *po = o.paths + (size_t)walk * T;
+  int32_t *ao = o.path_arcs ? o.path_arcs + (size_t)walk * T : nullptr;
+  const double logz = o.logz64[b];
+  int s = 0, len = 0;
+  double tot = 0.0;
+  float ublk[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (logz > -__builtin_huge_val()) {
+    for (int t = 0; t < T && s != m.sink; ++t) {
+      float u;
+      if (uniforms) {
+        u = uniforms[(size_t)walk * T + t];
+      } else {  // one Philox block serves four steps
+        if ((t & 3) == 0) philox_uniform4(seed, (uint32_t)walk, (uint32_t)(t >> 2), ublk);
+        u = (t & 3) == 0 ? ublk[0] : ((t & 3) == 1 ? ublk[1] : ((t & 3) == 2 ? ublk[2] : ublk[3]));
+      }
+      const ME64 target = {(double)u * bm[(size_t)t * n + s], be[(size_t)t * n + s]};
+      const double *nm = bm + (size_t)(t + 1) * n;
+      const int *ne = be + (size_t)(t + 1) * n;
+      const int a0 = max(rp[s], a_lo), a1 = min(rp[s + 1], a_hi);
+      ME64 run = PosSum::zero();
+      int chosen = -1, last = -1;
+      for (int c = a0; c < a1 && chosen < 0; c += 64) {
+        const int a = c + lane;
+        ME64 x = PosSum::zero();
+        if (a < a1) {
+          const int d = lat.arc_dst[a];
+          if (d != s) {  // self loops are on no path
+            const int l = lat.arc_label[a];
+            x = PosSum::times(pos_b ? PosSum::label(theta[l], pos_b[(size_t)t * V + l]) : PosSum::label(theta[l]), {nm[d], ne[d]});
+            if (EXTRA) { x.m *= w.ewm[a]; x.e += w.ewe[a]; }
+            if (x.m == 0.0) x.e = kEZero;
+          }
+        }
+        ME64 pre = x, sum = x;
+        pos_scan_stage<0>(pre, sum, lane);
+        pos_scan_stage<1>(pre, sum, lane);
+        pos_scan_stage<2>(pre, sum, lane);
+        pos_scan_stage<3>(pre, sum, lane);
+        pos_scan_stage<4>(pre, sum, lane);
+        pos_scan_stage<5>(pre, sum, lane);
+        const bool live = x.m > 0.0;
+        const unsigned long long hit = __ballot(live && pos_above(pos_add(run, pre), target));
+        const unsigned long long any = __ballot(live);
+        if (hit) chosen = c + __builtin_ctzll(hit);
+        else if (any) last = c + 63 - __builtin_clzll(any);
+        run = pos_add(run, sum);
+      }
+      if (chosen < 0) chosen = last;
+      if (chosen < 0) break;  // (never: beta_t(s) > 0 on a walk, so some arc of s has positive weight)
+      const int l = lat.arc_label[chosen];
+      double x = (double)theta[l];
+      if (pos_b) x += (double)pos_b[(size_t)t * V + l];
+      if (EXTRA) {
+        if (arc_w) x += (double)arc_w[chosen];
+        if (in.sc.arc_scores) x += (double)in.sc.arc_scores[chosen];
+      }
+      tot += x;
+      if (lane == 0) {
+        po[len] = l;
+        if (ao) ao[len] = chosen;
+      }
+      ++len;
+      s = __builtin_amdgcn_readfirstlane(lat.arc_dst[chosen]);
+    }
+  }
+  if (lane == 0) {  // (log Z_T = -inf: no path of finite weight within T, the empty result)
+    o.lengths[walk] = len;
+    o.logq[walk] = len > 0 ? (float)(tot - logz) : 0.0f;
+  }
+  for (int t = len + lane; t < T; t += 64) {
+    po[t] = o.pad;
+    if (ao) ao[t] = -1;
+  }
+}
+
+// The forced walk of marks [B, K, T] from state 0, one thread per (b, k): the mark at position t takes the arc of the
+// current state with that label (the arcs of a state are sorted by label) and scores s_a + pos[b, t, label], summed in
+// float64.  The sink's pad loop scores nothing and ends the count of `lengths`; a mark without an arc gives -inf and
+// end state 0, as k_score_paths.
+__global__ __launch_bounds__(64) void k_positional_score(nfst_batch lat, PosIn in, const int32_t *marks, int K, float *path_score,
+                                                         int32_t *end_state, int32_t *lengths) {
+  const int b = blockIdx.x;
+  const int k = blockIdx.y * 64 + threadIdx.x;
+  if (k >= K) return;
+  const Meta m = load_meta(lat.meta, b);
+  const int T = in.T, V = lat.vocab;
+  const float *theta = in.sc.theta + (size_t)in.sc.theta_stride * b;
+  const float *pos_b = in.pos ? in.pos + (size_t)in.pos_stride * b : nullptr;
+  const Extra ex = {lat.weighted ? lat.arc_w : nullptr, in.sc.arc_scores};
+  const int32_t *rp = lat.row_ptr + m.row_off + b;
+  const int a_lo = m.arc_off, a_hi = m.arc_off + m.n_arcs;
+  const size_t walk = (size_t)b * K + k;
+  const int32_t *mk = marks + walk * T;
+  int s = 0, len = 0;
+  bool counting = true;
+  double tot = 0.0;
+  for (int t = 0; t < T; ++t) {
+    const int l = mk[t];
+    const int a = (l >= 0 && l < V) ? find_arc(lat.arc_label, max(rp[s], a_lo), min(rp[s + 1], a_hi), l) : -1;
+    if (a < 0) { tot = (double)kNegInf; s = 0; break; }
+    const int d = lat.arc_dst[a];
+    if (d != s) {
+      double x = (double)theta[l];
+      if (pos_b) x += (double)pos_b[(size_t)t * V + l];
+      if (ex.arc_w) x += (double)ex.arc_w[a];
+      if (ex.arc_scores) x += (double)ex.arc_scores[a];
+      tot += x;
+      len += counting;
+    } else {
+      counting = false;
+    }
+    s = d;
+  }
+  path_score[walk] = (float)tot;
+  end_state[walk] = s;
+  lengths[walk] = len;
 }

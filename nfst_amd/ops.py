@@ -785,6 +785,85 @@ def positional_viterbi(lat: LatticeBatch, theta, pos_scores=None, T: Optional[in
     return PositionalViterbiResult(best, paths, arcs, lens)
 
 
+class PositionalSampleResult(NamedTuple):
+    paths: torch.Tensor  # [B, K, T] int32 labels, pad-terminated
+    arcs: Optional[torch.Tensor]  # [B, K, T] int32 canonical arc ids, -1 padded (None with want_arcs=False)
+    lengths: torch.Tensor  # [B, K] int32 (0 where logz is -inf)
+    logq: torch.Tensor  # [B, K] float32 = S_T(path) - log Z_T (0 where logz is -inf)
+    logz: torch.Tensor  # [B] float32 log Z_T
+    logz64: torch.Tensor  # [B] float64: the bits of positional_forward_backward
+
+
+def positional_sample_paths(lat: LatticeBatch, theta, k: int, pos_scores=None, T: Optional[int] = None, arc_scores=None,
+                            uniforms: Optional[torch.Tensor] = None, seed: int = 0, pad: int = 0,
+                            want_arcs: bool = True) -> PositionalSampleResult:
+    """``k`` exact draws per lattice from p_T(path) = exp(S_T(path)) / Z_T over the paths of at most ``T`` arcs, under
+    the scores of ``positional_forward_backward`` (``nfst_positional_sample``; DESIGN.md sections 2 and 4.10).  No draw
+    overruns ``T`` and nothing is truncated: there is no "ran out of length budget".  ``logq`` is each draw's exact
+    log-probability.  ``uniforms`` [B, k, T] float32 in [0, 1) decide the walks (walk (b, j) reads its own row only);
+    without them Philox4x32-10 keyed by ``seed``, as ``sample_paths``.  A lattice without a path of finite score within
+    ``T`` gets length 0, ``pad`` labels and ``logq`` 0.  One backward pass (every beta row stored: 12 (T + 1) total_rows
+    bytes of workspace) and one wave per walk; the same bits at every launch and for every packing.  Not
+    differentiable."""
+    _need_gpu(lat)
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"k must be an int >= 1, not {k!r}")
+    theta = _input(lat, theta, "theta", True, False)
+    arc_scores = _input(lat, arc_scores, "arc_scores", False, True)
+    pos, stride, T = _positions(lat, pos_scores, T)
+    sc, keep = _scores(lat, theta.detach(), None if arc_scores is None else arc_scores.detach())
+    if pos is not None:
+        pos = pos.detach()
+    dev = lat.device
+    B = lat.n_lattices
+    if uniforms is not None:
+        if not isinstance(uniforms, torch.Tensor) or tuple(uniforms.shape) != (B, k, T):
+            raise ValueError(f"uniforms must be a tensor of shape [{B}, {k}, {T}]")
+        uniforms = uniforms.detach().to(device=dev, dtype=torch.float32).contiguous()
+    ws, ws_bytes = _positional_ws(lat, T, _lib.POS_WS_SAMPLE)
+    z64 = torch.empty(B, dtype=torch.float64, device=dev)
+    z32 = torch.empty(B, dtype=torch.float32, device=dev)
+    paths = torch.empty((B, k, T), dtype=torch.int32, device=dev)
+    arcs = torch.empty((B, k, T), dtype=torch.int32, device=dev) if want_arcs else None
+    lens = torch.empty((B, k), dtype=torch.int32, device=dev)
+    logq = torch.empty((B, k), dtype=torch.float32, device=dev)
+    check(lib.nfst_positional_sample(C.byref(lat.c_struct()), C.byref(sc), _ptr(pos), stride, T, k, _ptr(uniforms),
+                                     C.c_uint64(seed & (2 ** 64 - 1)), int(pad), ws.data_ptr(), ws_bytes, _ptr(z64), _ptr(z32),
+                                     _ptr(paths), _ptr(arcs), _ptr(lens), _ptr(logq), _stream()), "nfst_positional_sample")
+    return PositionalSampleResult(paths, arcs, lens, logq, z32, z64)
+
+
+def positional_score_paths(lat: LatticeBatch, theta, marks: torch.Tensor, pos_scores=None, T: Optional[int] = None,
+                           arc_scores=None):
+    """Forced walk of ``marks`` [B, K, T] (pad-terminated labels) under the scores of ``positional_forward_backward``
+    (``nfst_positional_score_paths``): (``path_score`` [B, K] float32 -- -inf if a mark has no arc or an entry is -inf,
+    ``end_state`` [B, K] -- 0 if the walk fell off the lattice, ``lengths`` [B, K] -- the marks before the first pad).
+    ``T`` defaults to ``pos_scores.shape[-2]``, without ``pos_scores`` to ``marks.shape[-1]``.  The log p side of an
+    importance weight whose log q is ``positional_sample_paths``'s.  Not differentiable."""
+    _need_gpu(lat)
+    theta = _input(lat, theta, "theta", True, False)
+    arc_scores = _input(lat, arc_scores, "arc_scores", False, True)
+    if not isinstance(marks, torch.Tensor) or marks.dim() != 3 or marks.shape[0] != lat.n_lattices or marks.shape[1] < 1 \
+            or marks.is_floating_point():
+        raise ValueError(f"marks must be an integer tensor [{lat.n_lattices}, K, T] with K >= 1")
+    if pos_scores is None and T is None:
+        T = int(marks.shape[2])
+    pos, stride, T = _positions(lat, pos_scores, T)
+    if marks.shape[2] != T:
+        raise ValueError(f"marks has {marks.shape[2]} positions, T = {T}")
+    sc, keep = _scores(lat, theta.detach(), None if arc_scores is None else arc_scores.detach())
+    if pos is not None:
+        pos = pos.detach()
+    marks = marks.to(device=lat.device, dtype=torch.int32).contiguous()
+    B, K = int(marks.shape[0]), int(marks.shape[1])
+    tot = torch.empty((B, K), dtype=torch.float32, device=lat.device)
+    end = torch.empty((B, K), dtype=torch.int32, device=lat.device)
+    lens = torch.empty((B, K), dtype=torch.int32, device=lat.device)
+    check(lib.nfst_positional_score_paths(C.byref(lat.c_struct()), C.byref(sc), _ptr(pos), stride, T, _ptr(marks), K, _ptr(tot),
+                                          _ptr(end), _ptr(lens), _stream()), "nfst_positional_score_paths")
+    return tot, end, lens
+
+
 class SampleResult(NamedTuple):
     paths: torch.Tensor  # [B, K, max_len] int32 labels, pad-terminated
     arcs: torch.Tensor  # [B, K, max_len] int32 canonical arc ids

@@ -99,6 +99,17 @@ class LatticeScorer(torch.nn.Module):
         """The best path under ``theta`` plus per-position scores (``ops.positional_viterbi``)."""
         return ops.positional_viterbi(self._lat(), self.theta.detach(), pos_scores, pad=self.__pad__)
 
+    def positional_sample(self, pos_scores: torch.Tensor, k: int, **kw) -> "ops.PositionalSampleResult":
+        """``k`` exact draws per lattice under ``theta`` plus per-position scores, each with its log-probability
+        (``ops.positional_sample_paths``; ``kw``: ``T``, ``uniforms``, ``seed``, ``want_arcs``)."""
+        kw.setdefault("pad", self.__pad__)
+        return ops.positional_sample_paths(self._lat(), self.theta.detach(), k, pos_scores, **kw)
+
+    def positional_score(self, pos_scores: torch.Tensor, marks: torch.Tensor):
+        """``(path_score, end_state, lengths)`` of the forced walk of ``marks`` [B, K, T] under the same scores
+        (``ops.positional_score_paths``)."""
+        return ops.positional_score_paths(self._lat(), self.theta.detach(), marks, pos_scores)
+
     def beam_decoder(self, score_fn, reorder_fn=None, sync_every: int = 8):
         """A ``decoders.BeamDecoder`` over the scorer's lattice for a path-dependent ``score_fn(hx, inp) -> (hx,
         scores [N, V])``: ``.decode(k, lookahead=...)`` keeps k hypotheses per lattice."""

@@ -52,6 +52,8 @@
  *                                      truncates (emission_mask(has_to_end = length > max_length), NFST_ERR_LENGTH)
  *   nfst_positional_sample, nfst_positional_score_paths  exact draws from that distribution (no draw overruns the
  *                                      budget) with their log-probabilities, and forced scores of given marks
+ *   nfst_positional_kbest              the k best paths under those scores and that budget: the reranker's n-best
+ *                                      list for a tagger's or encoder's per-position logits
  *
  * Conventions
  *   - plain C: pointers and sizes only, no C++/torch types.
@@ -724,6 +726,36 @@ int nfst_intersect_write(const nfst_batch *lat, const int8_t *delta_t, int64_t d
  *     lengths [B, K]              the marks before the first pad
  * With pos = NULL it is nfst_score_paths up to float32 rounding (that op adds an arc's terms in float32 first).
  * k < 1, T < 1, a bad stride or null pointers return NFST_ERR_ARG, k above 64 * 65535 NFST_ERR_LIMIT; on the host.
+ *
+ * nfst_positional_kbest (the k best paths).  Paths, positions, pos, pos_stride, T, -inf entries and e_a are exactly those
+ * of nfst_positional_viterbi.  For every position t in [0, T] and state s a list of at most k float32 scores
+ * v(t, s, r), r = 0, 1, ..:
+ *     the sink holds the single entry 0.0f at every t; every other state has an empty list at t = T;
+ *     for s != sink and t < T the list is the top k of the candidates (a, r), a over the out-arcs of s without self
+ *     loops, r over the entries of the list of (t + 1, dst_a), with
+ *         c = e_a + ((theta[l] + pos[b, t, l]) + v(t + 1, dst_a, r))      (without pos: c = e_a + (theta[l] + v))
+ *     Only candidates with c > -inf count; the order is (c descending, canonical arc ascending, r ascending): the
+ *     arithmetic of nfst_positional_viterbi and the rule of nfst_kbest.
+ * The result is the list of (0, state 0); path j is read forwards from there by following (arc, rank).  Outputs on the
+ * device, every element written exactly once:
+ *     best [B, k] float32 path scores, best first;  paths [B, k, T] int32 labels padded with `pad`;  path_arcs (optional)
+ *     [B, k, T] canonical arc ids padded with -1;  lengths [B, k] arcs per path;  n_paths [B] the number of real entries.
+ * Entries j >= n_paths[b] have score -inf, length 0, labels `pad` and arcs -1.  No path exceeds T arcs: there is no
+ * max_len and no status word.  A lattice without a path of finite score and L <= T has n_paths = 0 and does not disturb
+ * its neighbours.  float32 addition is monotone, so the top k of a state depends only on the top k of its successors:
+ * entry 0 is nfst_positional_viterbi's best, labels, arcs and length bit for bit; with pos = NULL and T >= the batch's
+ * depth every output is nfst_kbest's bit for bit (the padded width aside); with pos = NULL and T below the depth the
+ * result is nfst_kbest's list without the paths longer than T, in the same order and bits, as long as neither list is
+ * truncated.  The op reads the canonical arrays only: the same bits for every packing, with or without chunked programs,
+ * at every launch.  One workgroup per lattice, T barrier-separated steps; there is one launch flavour.  Only the pairs
+ * (t, s) that state 0 reaches in exactly t arcs are swept (a forward pass marks them): no other list is ever read.
+ * ws: device workspace of nfst_positional_kbest_ws_bytes(lat, T, k) bytes (16-byte aligned, overwritten, need not be
+ * zeroed) = 8 * (T + 1) * total_rows * k (the lists) + (T + 1) * total_rows (the marks), each part rounded up to 256:
+ * EVERY list of every position (no checkpointing, no lazy enumeration) -- 0.58 GB * k for the 516 236 rows of the
+ * 256-lattice benchmark batch at T = 140.  LDS: 16 392 + 4 max_rows + 4 vocab bytes.
+ * 1 <= k <= 64: k < 1 returns NFST_ERR_ARG, k > 64 NFST_ERR_LIMIT.  T < 1, a bad stride, null required pointers or a
+ * short workspace return NFST_ERR_ARG; 2^24 or more arcs in one lattice (nfst_kbest's payload limit) or more than
+ * 160 KiB of LDS return NFST_ERR_LIMIT.  All checks run on the host before any launch.
  */
 #define NFST_POS_WS_POSTERIOR 1
 #define NFST_POS_WS_VITERBI 2
@@ -742,6 +774,10 @@ int nfst_positional(const nfst_batch *lat, const nfst_scores *scores, const floa
 int nfst_positional_viterbi(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T,
                             void *ws, int64_t ws_bytes, float *best, int32_t *paths, int32_t *path_arcs, int32_t *lengths,
                             int32_t pad, void *stream);
+int64_t nfst_positional_kbest_ws_bytes(const nfst_batch *lat, int32_t T, int32_t k);
+int nfst_positional_kbest(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T, int32_t k,
+                          void *ws, int64_t ws_bytes, float *best, int32_t *paths, int32_t *path_arcs, int32_t *lengths,
+                          int32_t *n_paths, int32_t pad, void *stream);
 
 /*
  * Viterbi: best[b] = max path score (float32), paths [B, max_len] int32 labels

@@ -165,6 +165,8 @@ def _load():
         "nfst_positional_viterbi": (C.c_int, [BP, SP, vp, i64, i32, vp, i64, vp, vp, vp, vp, i32, vp]),
         "nfst_positional_sample": (C.c_int, [BP, SP, vp, i64, i32, i32, vp, u64, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "nfst_positional_score_paths": (C.c_int, [BP, SP, vp, i64, i32, vp, i32, vp, vp, vp, vp]),
+        "nfst_positional_kbest_ws_bytes": (i64, [BP, i32, i32]),
+        "nfst_positional_kbest": (C.c_int, [BP, SP, vp, i64, i32, i32, vp, i64, vp, vp, vp, vp, vp, i32, vp]),
         "nfst_path_logprob": (C.c_int, [vp, vp, i64, i32, i32, i32, i32, i32, i32, f32, i32, f32, i32, vp, vp]),
         "nfst_path_logprob_backward": (C.c_int, [vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, f32, i32, f32, i32, vp, vp]),
         "nfst_iwae": (C.c_int, [vp, vp, i32, i32, vp, vp, vp]),

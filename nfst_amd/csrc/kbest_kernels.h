@@ -7,7 +7,8 @@
 //   k_kbest_levels  Kahn's algorithm in LDS over the arcs without self loops: a topological order of the states that
 //                   state 0 reaches, cut into levels (longest distance from state 0)
 //   k_kbest_sweep   the levels in reverse: every state merges its successors' lists, each shifted by its arc's score,
-//                   into its own top k (one wave per state, one lane per out-arc holding that list's head)
+//                   into its own top k (one wave per state, one lane per out-arc holding that list's head); the merge
+//                   is kb_merge_state, which k_positional_kbest_sweep (positional_kbest_kernels.h) shares
 //   k_kbest_walk    k lanes follow the back pointers from state 0 and write labels, arcs and lengths
 // A list entry is (float score, uint32 payload), payload = arc_in_lattice << 6 | rank in the successor's list; the
 // sink's one entry is (0.0f, kKbSinkPay).  A list shorter than k ends with an entry of score -inf.
@@ -91,11 +92,77 @@ __device__ __forceinline__ uint64_t kb_wave_max(uint64_t key) {
   return r;
 }
 
-// Pass 2: the backward k-best sweep.  A wave owns one state of a level at a time.  Its out-arcs go to the lanes in
-// chunks: the first chunk has 64 arcs, every further one 63 arcs and, in lane 63, the list merged so far (the
+// The merge of one state s (not the sink) into its list `out`, by one wave.  The out-arcs a0 .. a0 + d of s go to the
+// lanes in chunks: the first chunk has 64 arcs, every further one 63 arcs and, in lane 63, the list merged so far (the
 // "carry", in LDS).  A lane holds its list's head (and the entry after it, loaded ahead); each pop is a wave maximum of
-// the lanes' keys, and the winning lane advances.  LDS: order and level starts of the lattice (8 bytes per row) and two
-// k-entry buffers per wave.
+// the lanes' keys, and the winning lane advances.  `lists` holds the successors' lists (k entries per state), lab(l) the
+// label term of a candidate, buf0 two k-entry buffers of this wave in LDS.
+template <class LabF>
+__device__ __forceinline__ void kb_merge_state(const nfst_batch &lat, const Meta &m, const Extra &ex, LabF lab, const uint2 *lists,
+                                               int k, int s, int a0, int d, uint2 *buf0, int lane, uint2 *out) {
+  const uint2 kNone = make_uint2(__float_as_uint(kNegInf), 0u);
+  int cnt = 0, sel = 0;
+  for (int base = 0; base < d || base == 0; base += (base == 0 ? 64 : 63)) {
+    const uint2 *prev = buf0 + sel * 64;
+    uint2 *cur = buf0 + (sel ^ 1) * 64;
+    const bool carry = base > 0 && lane == 63;
+    const int pc = cnt;  // entries of the carry list
+    const int a = a0 + base + lane;
+    const bool live = !carry && base + lane < d;
+    // this lane's list: its head (score c, payload) and the entry after it
+    int r = 0;
+    float c = kNegInf, e = 0.0f, th = 0.0f;
+    uint32_t pay = 0, arel = 0;
+    const uint2 *lst = nullptr;
+    uint2 nxt = kNone;
+    if (live) {
+      const int dst = lat.arc_dst[a];
+      if (dst != s) {
+        th = lab(lat.arc_label[a]);
+        e = ex.at(a);
+        lst = lists + (size_t)dst * k;
+        const uint2 h = lst[0];
+        if (k > 1) nxt = lst[1];
+        arel = (uint32_t)(a - m.arc_off);
+        c = e + (th + __uint_as_float(h.x));  // the adds of k_viterbi, in its order
+        pay = arel << 6;
+      }
+    } else if (carry && pc > 0) {
+      const uint2 h = prev[0];
+      c = __uint_as_float(h.x);
+      pay = h.y;
+    }
+    uint64_t key = kb_key(c, pay);
+    cnt = 0;
+    for (; cnt < k; ++cnt) {
+      const uint64_t mx = kb_wave_max(key);
+      if (mx == 0) break;
+      if (key == mx) {
+        cur[cnt] = make_uint2(__float_as_uint(c), pay);
+        ++r;
+        if (carry) {
+          const uint2 h = r < pc ? prev[r] : kNone;
+          c = __uint_as_float(h.x);
+          pay = h.y;
+        } else {
+          const uint2 h = nxt;
+          if (r + 1 < k) nxt = lst[r + 1];
+          c = r < k ? e + (th + __uint_as_float(h.x)) : kNegInf;
+          pay = (arel << 6) | (uint32_t)r;
+        }
+        key = kb_key(c, pay);
+      }
+    }
+    // LDS accesses of one wave execute in order; the next chunk's carry and the copy below read `cur`
+    asm volatile("" ::: "memory");
+    sel ^= 1;
+  }
+  if (lane < k) out[lane] = lane < cnt ? buf0[sel * 64 + lane] : kNone;
+  asm volatile("" ::: "memory");
+}
+
+// Pass 2: the backward k-best sweep.  A wave owns one state of a level at a time (kb_merge_state).  LDS: order and level
+// starts of the lattice (8 bytes per row) and two k-entry buffers per wave.
 __global__ __launch_bounds__(kKbSweepThreads) void k_kbest_sweep(nfst_batch lat, nfst_scores sc, int k, KbWs w) {
   extern __shared__ int kb_lds[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
@@ -110,7 +177,7 @@ __global__ __launch_bounds__(kKbSweepThreads) void k_kbest_sweep(nfst_batch lat,
   __syncthreads();
   const int32_t *rp = lat.row_ptr + m.row_off + b;
   const float *theta = sc.theta + (size_t)sc.theta_stride * b;
-  const float *arc_w = lat.weighted ? lat.arc_w : nullptr;
+  const Extra ex = {lat.weighted ? lat.arc_w : nullptr, sc.arc_scores};
   uint2 *lists = w.lists + (size_t)m.row_off * k;
   const uint2 kNone = make_uint2(__float_as_uint(kNegInf), 0u);
   uint2 *buf0 = bufs + wv * 128;
@@ -123,65 +190,8 @@ __global__ __launch_bounds__(kKbSweepThreads) void k_kbest_sweep(nfst_batch lat,
         if (lane < k) out[lane] = lane == 0 ? make_uint2(__float_as_uint(0.0f), kKbSinkPay) : kNone;
         continue;
       }
-      const int a0 = rp[s], d = rp[s + 1] - a0;
-      int cnt = 0, sel = 0;
-      for (int base = 0; base < d || base == 0; base += (base == 0 ? 64 : 63)) {
-        const uint2 *prev = buf0 + sel * 64;
-        uint2 *cur = buf0 + (sel ^ 1) * 64;
-        const bool carry = base > 0 && lane == 63;
-        const int pc = cnt;  // entries of the carry list
-        const int a = a0 + base + lane;
-        const bool live = !carry && base + lane < d;
-        // this lane's list: its head (score c, payload) and the entry after it
-        int r = 0;
-        float c = kNegInf, e = 0.0f, th = 0.0f;
-        uint32_t pay = 0, arel = 0;
-        const uint2 *lst = nullptr;
-        uint2 nxt = kNone;
-        if (live) {
-          const int dst = lat.arc_dst[a];
-          if (dst != s) {
-            th = theta[lat.arc_label[a]];
-            e = Extra{arc_w, sc.arc_scores}.at(a);
-            lst = lists + (size_t)dst * k;
-            const uint2 h = lst[0];
-            if (k > 1) nxt = lst[1];
-            arel = (uint32_t)(a - m.arc_off);
-            c = e + (th + __uint_as_float(h.x));  // the adds of k_viterbi, in its order
-            pay = arel << 6;
-          }
-        } else if (carry && pc > 0) {
-          const uint2 h = prev[0];
-          c = __uint_as_float(h.x);
-          pay = h.y;
-        }
-        uint64_t key = kb_key(c, pay);
-        cnt = 0;
-        for (; cnt < k; ++cnt) {
-          const uint64_t mx = kb_wave_max(key);
-          if (mx == 0) break;
-          if (key == mx) {
-            cur[cnt] = make_uint2(__float_as_uint(c), pay);
-            ++r;
-            if (carry) {
-              const uint2 h = r < pc ? prev[r] : kNone;
-              c = __uint_as_float(h.x);
-              pay = h.y;
-            } else {
-              const uint2 h = nxt;
-              if (r + 1 < k) nxt = lst[r + 1];
-              c = r < k ? e + (th + __uint_as_float(h.x)) : kNegInf;
-              pay = (arel << 6) | (uint32_t)r;
-            }
-            key = kb_key(c, pay);
-          }
-        }
-        // LDS accesses of one wave execute in order; the next chunk's carry and the copy below read `cur`
-        asm volatile("" ::: "memory");
-        sel ^= 1;
-      }
-      if (lane < k) out[lane] = lane < cnt ? buf0[sel * 64 + lane] : kNone;
-      asm volatile("" ::: "memory");
+      const int a0 = rp[s];
+      kb_merge_state(lat, m, ex, [&](int l) { return theta[l]; }, lists, k, s, a0, rp[s + 1] - a0, buf0, lane, out);
     }
     __syncthreads();  // (the lists of this level are visible to the waves of the next one)
   }

@@ -43,6 +43,7 @@ using namespace nfst_tile;
 #include "slack_kernels.h"
 #include "intersect_kernels.h"
 #include "positional_kernels.h"
+#include "positional_kbest_kernels.h"
 
 // ------------------------------------------------------------------ host helpers
 int check_batch(const nfst_batch *lat) {
@@ -1134,6 +1135,48 @@ int nfst_positional_viterbi(const nfst_batch *lat, const nfst_scores *scores, co
   if (staged)
     return launch(k_positional_viterbi<true>, dim3(lat->n_lattices), dim3(kPosThreads), lds, (hipStream_t)stream, *lat, in, w, o);
   return launch(k_positional_viterbi<false>, dim3(lat->n_lattices), dim3(kPosThreads), lds, (hipStream_t)stream, *lat, in, w, o);
+}
+
+// ------------------------------------------------------------------ k best paths under positional scores (positional_kbest_kernels.h)
+// workspace: the k-best lists of every (position, row), 8 (T + 1) total_rows k bytes, then one byte per (position, row):
+// reached from state 0 in exactly that many arcs
+static int64_t pkb_ws_layout(const nfst_batch *lat, int64_t T, int64_t k, char *base, PkbWs *w) {
+  const int64_t pairs = (T + 1) * lat->total_rows;
+  WsCarve c{base};
+  char *li = c.take(8 * pairs * k), *re = c.take(pairs);
+  if (w) *w = {(uint2 *)li, (uint8_t *)re};
+  return c.size;
+}
+
+int64_t nfst_positional_kbest_ws_bytes(const nfst_batch *lat, int32_t T, int32_t k) {
+  int rc = check_batch(lat);
+  if (rc) return rc;
+  if (T < 1) return NFST_ERR_ARG;
+  if ((rc = kb_check_k(k))) return rc;
+  return pkb_ws_layout(lat, T, k, nullptr, nullptr);
+}
+
+int nfst_positional_kbest(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T, int32_t k,
+                          void *ws, int64_t ws_bytes, float *best, int32_t *paths, int32_t *path_arcs, int32_t *lengths,
+                          int32_t *n_paths, int32_t pad, void *stream) {
+  int rc = check_batch(lat);
+  if (rc) return rc;
+  if ((rc = check_scores(lat, scores))) return rc;
+  if (T < 1 || (pos && pos_stride != 0 && pos_stride != (int64_t)T * lat->vocab)) return NFST_ERR_ARG;
+  if ((rc = kb_check_k(k))) return rc;
+  if (!best || !paths || !lengths || !n_paths) return NFST_ERR_ARG;
+  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < pkb_ws_layout(lat, T, k, nullptr, nullptr)) return NFST_ERR_ARG;
+  // nfst_kbest's payload: (arc in lattice, rank) in 32 bits
+  if (max_lattice_arcs(lat) >= NFST_BATCH_MAX_ARCS_CAP && lat->total_arcs >= ((int64_t)1 << 24)) return NFST_ERR_LIMIT;
+  const int64_t lds = (int64_t)kKbSweepWaves * 2 * 64 * 8 + ((int64_t)lat->max_rows + 2 + lat->vocab) * 4;
+  if (lds > kMaxLds) return NFST_ERR_LIMIT;
+  PkbWs w;
+  pkb_ws_layout(lat, T, k, (char *)ws, &w);
+  const PosIn in = {*scores, pos, pos ? pos_stride : 0, (int)T};
+  const hipStream_t st = (hipStream_t)stream;
+  if ((rc = launch(k_positional_kbest_sweep, dim3(lat->n_lattices), dim3(kKbSweepThreads), lds, st, *lat, in, (int)k, w))) return rc;
+  return launch(k_positional_kbest_walk, dim3(lat->n_lattices), dim3(64), 0, st, *lat, (int)T, (int)k, w, best, paths, path_arcs, lengths,
+                n_paths, (int)pad);
 }
 
 // ------------------------------------------------------------------ product with a label automaton (intersect_kernels.h)

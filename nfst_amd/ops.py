@@ -785,6 +785,114 @@ def positional_viterbi(lat: LatticeBatch, theta, pos_scores=None, T: Optional[in
     return PositionalViterbiResult(best, paths, arcs, lens)
 
 
+class PositionalKBestResult(NamedTuple):
+    best: torch.Tensor  # [B, k] float32, non-increasing; -inf beyond n_paths
+    paths: torch.Tensor  # [B, k, T] int32 labels (bos .. eos), pad-terminated
+    arcs: torch.Tensor  # [B, k, T] int32 canonical arc ids, -1 padded
+    lengths: torch.Tensor  # [B, k] int32 arcs per path (0 beyond n_paths)
+    n_paths: torch.Tensor  # [B] int32 min(k, paths of at most T arcs and score > -inf)
+
+
+def positional_k_best_terms(lat: LatticeBatch, theta, k: int, pos_scores=None, T: Optional[int] = None, arc_scores=None,
+                            pad: int = 0) -> PositionalKBestResult:
+    """One launch of ``nfst_positional_kbest`` (no autograd); see ``positional_k_best``."""
+    _need_gpu(lat)
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
+        raise ValueError(f"k must be an int in [1, {MAX_K}], not {k!r}")
+    theta = _input(lat, theta, "theta", True, False)
+    arc_scores = _input(lat, arc_scores, "arc_scores", False, True)
+    pos, stride, T = _positions(lat, pos_scores, T)
+    sc, keep = _scores(lat, theta.detach(), None if arc_scores is None else arc_scores.detach())
+    if pos is not None:
+        pos = pos.detach()
+    dev = lat.device
+    B = lat.n_lattices
+    ws_bytes = int(lib.nfst_positional_kbest_ws_bytes(C.byref(lat.c_struct()), T, k))
+    check(min(ws_bytes, 0), "nfst_positional_kbest_ws_bytes")
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    best = torch.empty((B, k), dtype=torch.float32, device=dev)
+    paths = torch.empty((B, k, T), dtype=torch.int32, device=dev)
+    arcs = torch.empty((B, k, T), dtype=torch.int32, device=dev)
+    lens = torch.empty((B, k), dtype=torch.int32, device=dev)
+    n_paths = torch.empty(B, dtype=torch.int32, device=dev)
+    check(lib.nfst_positional_kbest(C.byref(lat.c_struct()), C.byref(sc), _ptr(pos), stride, T, k, ws.data_ptr(), ws_bytes,
+                                    _ptr(best), _ptr(paths), _ptr(arcs), _ptr(lens), _ptr(n_paths), int(pad), _stream()),
+          "nfst_positional_kbest")
+    return PositionalKBestResult(best, paths, arcs, lens, n_paths)
+
+
+class _PositionalKBest(torch.autograd.Function):
+    """best[b, j] = the sum of the terms of path j: d/d arc_scores[a] = 1 on its arcs, d/d theta counts its labels,
+    d/d pos_scores marks (t, label) of each of its positions (each summed over the lattices for a shared tensor);
+    -inf entries (no path) get no gradient."""
+
+    @staticmethod
+    def forward(ctx, lat, theta, pos_scores, arc_scores, k, T, pad):
+        r = positional_k_best_terms(lat, theta, k, pos_scores, T, arc_scores, pad)
+        ctx.lat = lat
+        ctx.like = (theta, pos_scores, arc_scores)
+        ctx.save_for_backward(r.arcs)
+        ctx.mark_non_differentiable(r.paths, r.arcs, r.lengths, r.n_paths)
+        return r.best, r.paths, r.arcs, r.lengths, r.n_paths
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, *_):
+        (arcs,) = ctx.saved_tensors
+        nt, npos, na = ctx.needs_input_grad[1:4]
+        theta, pos_scores, arc_scores = ctx.like
+        lat = ctx.lat
+        B, K, T = arcs.shape
+        V = lat.vocab
+        a = arcs.to(torch.int64)
+        on = a >= 0  # (-inf entries have no arcs)
+        gg = torch.where(torch.isfinite(g), g, torch.zeros_like(g)).to(torch.float32)
+        w = gg[:, :, None].expand(B, K, T)[on]
+        idx = a[on]
+        f32 = dict(dtype=torch.float32, device=arcs.device)
+        d_theta = d_pos = d_arc = None
+        if na:
+            d_arc = torch.zeros(lat.total_arcs, **f32).index_add_(0, idx, w).to(arc_scores.dtype)
+        if nt or npos:
+            lab = lat.arc_label.to(torch.int64)[idx]
+            row = torch.arange(B, device=arcs.device)[:, None, None].expand(B, K, T)[on]
+        if nt:
+            if theta.dim() == 1:
+                d_theta = torch.zeros(V, **f32).index_add_(0, lab, w)
+            else:
+                d_theta = torch.zeros(B * V, **f32).index_add_(0, row * V + lab, w).view(B, V)
+            d_theta = d_theta.to(theta.dtype)
+        if npos:
+            t = torch.arange(T, device=arcs.device)[None, None, :].expand(B, K, T)[on]
+            if pos_scores.dim() == 2:
+                d_pos = torch.zeros(T * V, **f32).index_add_(0, t * V + lab, w).view(T, V)
+            else:
+                d_pos = torch.zeros(B * T * V, **f32).index_add_(0, (row * T + t) * V + lab, w).view(B, T, V)
+            d_pos = d_pos.to(pos_scores.dtype)
+        return None, d_theta, d_pos, d_arc, None, None, None
+
+
+def positional_k_best(lat: LatticeBatch, theta, k: int, pos_scores=None, T: Optional[int] = None, arc_scores=None,
+                      pad: int = 0) -> PositionalKBestResult:
+    """The k best paths of at most ``T`` arcs under per-position scores, exact (``nfst_positional_kbest``, DESIGN.md
+    sections 2 and 4.12): the n-best list a reranker consumes when the scores are a tagger's or encoder's logits
+    ``pos_scores`` [T, V] or [B, T, V] on top of ``theta`` [V] or [B, V] and ``arc_scores`` [total_arcs]; 1 <= k <= 64.
+    ``T`` defaults to ``pos_scores.shape[-2]``, without ``pos_scores`` to the longest path of the batch.  Entry 0 is
+    ``positional_viterbi``'s path bit for bit; without ``pos_scores`` and with ``T`` >= the longest path every output is
+    ``k_best``'s.  Ties on exactly equal scores go to the smaller canonical arc, then the smaller rank.  Lattices with
+    fewer than k paths of score > -inf within ``T`` fill the rest with score -inf, length 0, ``pad`` labels and arc -1
+    (``n_paths`` counts the real ones).  The workspace holds every list of every position: (8 k + 1) (T + 1) total_rows bytes.
+    ``best`` is differentiable in theta, arc_scores and pos_scores (first derivatives only): the gradient of a path's
+    score counts its labels, marks its arcs and marks (t, label) of each of its positions."""
+    _need_gpu(lat)
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
+        raise ValueError(f"k must be an int in [1, {MAX_K}], not {k!r}")
+    theta = _input(lat, theta, "theta", True, False)
+    arc_scores = _input(lat, arc_scores, "arc_scores", False, True)
+    _positions(lat, pos_scores, T)
+    return PositionalKBestResult(*_PositionalKBest.apply(lat, theta, pos_scores, arc_scores, k, T, pad))
+
+
 class PositionalSampleResult(NamedTuple):
     paths: torch.Tensor  # [B, K, T] int32 labels, pad-terminated
     arcs: Optional[torch.Tensor]  # [B, K, T] int32 canonical arc ids, -1 padded (None with want_arcs=False)

@@ -99,6 +99,22 @@ class LatticeScorer(torch.nn.Module):
         """The best path under ``theta`` plus per-position scores (``ops.positional_viterbi``)."""
         return ops.positional_viterbi(self._lat(), self.theta.detach(), pos_scores, pad=self.__pad__)
 
+    def positional_k_best(self, pos_scores: torch.Tensor, k: int) -> "ops.PositionalKBestResult":
+        """The k best paths of every lattice under ``theta`` plus per-position scores (``ops.positional_k_best``;
+        ``best`` is differentiable in theta and ``pos_scores``)."""
+        return ops.positional_k_best(self._lat(), self.theta, k, pos_scores, pad=self.__pad__)
+
+    def positional_nbest(self, pos_scores: torch.Tensor, k: int) -> list:
+        """The reranker's list: per lattice ``[(log p, marks), ...]``, best first, of its (at most ``k``) best mark
+        sequences under ``theta`` plus per-position scores, log p = best - log Z_T (float64, the log Z of
+        ``ops.positional_forward_backward``): the exact probability of each entry among the paths of at most T arcs."""
+        lat, theta = self._lat(), self.theta.detach()
+        r = ops.positional_k_best_terms(lat, theta, k, pos_scores, pad=self.__pad__)
+        z = ops.positional_forward_backward(lat, theta, pos_scores, want_pos_posterior=False).logz64
+        logp = (r.best.double() - z[:, None]).cpu().numpy()
+        paths, lens, n = r.paths.cpu().numpy(), r.lengths.cpu().numpy(), r.n_paths.cpu().numpy()
+        return [[(float(logp[b, j]), paths[b, j, :lens[b, j]].tolist()) for j in range(int(n[b]))] for b in range(lat.n_lattices)]
+
     def positional_sample(self, pos_scores: torch.Tensor, k: int, **kw) -> "ops.PositionalSampleResult":
         """``k`` exact draws per lattice under ``theta`` plus per-position scores, each with its log-probability
         (``ops.positional_sample_paths``; ``kw``: ``T``, ``uniforms``, ``seed``, ``want_arcs``)."""

@@ -756,6 +756,41 @@ int nfst_intersect_write(const nfst_batch *lat, const int8_t *delta_t, int64_t d
  * 1 <= k <= 64: k < 1 returns NFST_ERR_ARG, k > 64 NFST_ERR_LIMIT.  T < 1, a bad stride, null required pointers or a
  * short workspace return NFST_ERR_ARG; 2^24 or more arcs in one lattice (nfst_kbest's payload limit) or more than
  * 160 KiB of LDS return NFST_ERR_LIMIT.  All checks run on the host before any launch.
+ *
+ * nfst_positional_expectation (the first-order expectation semiring on the same sweeps).  Paths, positions, pos,
+ * pos_stride, T and -inf entries are exactly those of nfst_positional; p_T(pi) = exp(S_T(pi) - log Z_T).  The arc at
+ * position t of a path carries the value
+ *     v_t(a) = pos_values[b, t, label_a]        (optional; [T, V] with stride 0 or [B, T, V] with stride T * vocab, as pos)
+ *            + label_values[b, label_a]          (optional; [V] with stride 0 or [B, V] with stride vocab)
+ *            + arc_values[a]                     (optional; [total_arcs])
+ *            + score_coef * (s_a + pos[b, t, label_a])
+ * summed in float64 from the float32 inputs, and V(pi) is the sum of v_t(a_t) over the path.  A term of weight zero (a
+ * label, arc score or pos entry at -inf) has no value: its value entries are never multiplied in and may be +-inf or
+ * NaN, and score_coef * s is left out for it.  Outputs on the device, every element written exactly once; logz64 and
+ * ev64 are required, the rest optional:
+ *     logz64 [B], logz32 [B], pos_post [B, T, V], arc_post [total_arcs]: the bits nfst_positional writes for the same
+ *         inputs (the same sums in the same order; the expectation numerators ride beside the path mass under its
+ *         exponent and never enter it)
+ *     ev64 [B], ev32 [B]          E_{p_T}[V]
+ *     pos_cov [B, T, V] float32   the sum over the arcs with label l of c_{a,t} = P(a at t) (E[V | a at t] - E[V])
+ *     arc_cov [total_arcs] float32  the sum over t of c_{a,t}; 0 on self loops
+ * sum pos_cov = sum arc_cov = Cov(L, V).  With score_coef = 1 alone H(p_T) = log Z_T - E[V] and dH/d(score) = -c; for
+ * values that do not depend on the scores pos_cov = d E[V] / d pos = (Hessian of log Z_T) v.  With pos = pos_values =
+ * NULL and T >= the batch's depth, log Z, E[V], arc_post and arc_cov are nfst_expectation's logz64, ev64, posterior
+ * and cov up to rounding.  A lattice without a path of finite score and L <= T gets log Z = -inf, E[V] = 0 and zeros
+ * everywhere (never a NaN) and does not disturb its neighbours.
+ * pos_cov is accumulated per label with float64 LDS atomics: the order of its adds is NOT fixed (as label_cov of
+ * nfst_expectation), so its last bits may differ from launch to launch.  Every other output is bit-identical from
+ * launch to launch and for every packing; only the canonical arrays are read.
+ * ws: nfst_positional_expectation_ws_bytes(lat, T) bytes (16-byte aligned, overwritten), every part rounded up to 256:
+ * 20 * (T + 1) * total_rows -- EVERY (beta, R) row of every position, (float64, int32, float64): the cost of the op, no
+ * checkpointing -- + 48 bytes per arc + 4 per row.
+ * LDS: 40 max_rows + 36 vocab + 4112 bytes; more than 160 KiB returns NFST_ERR_LIMIT.  When 4 (max_rows + 1 + arcs of
+ * the largest lattice) + 16 more bytes fit, the arc records are staged in LDS, otherwise the step loops read the
+ * canonical arrays (the same bits, slower steps).  nfst_positional_expectation_plan(lat, lds_bytes, staged) is that
+ * decision, asked on the host as nfst_positional_plan; the launcher calls it.  Null required pointers, T < 1, a stride
+ * that is neither 0 nor the full one, a non-finite score_coef or a short workspace return NFST_ERR_ARG.  All checks run
+ * on the host before any launch.
  */
 #define NFST_POS_WS_POSTERIOR 1
 #define NFST_POS_WS_VITERBI 2
@@ -774,6 +809,13 @@ int nfst_positional(const nfst_batch *lat, const nfst_scores *scores, const floa
 int nfst_positional_viterbi(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T,
                             void *ws, int64_t ws_bytes, float *best, int32_t *paths, int32_t *path_arcs, int32_t *lengths,
                             int32_t pad, void *stream);
+int64_t nfst_positional_expectation_ws_bytes(const nfst_batch *lat, int32_t T);
+int nfst_positional_expectation_plan(const nfst_batch *lat, int64_t *lds_bytes, int32_t *staged);
+int nfst_positional_expectation(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T,
+                                const float *pos_values, int64_t pos_values_stride, const float *label_values,
+                                int64_t label_values_stride, const float *arc_values, float score_coef, void *ws, int64_t ws_bytes,
+                                double *logz64, float *logz32, double *ev64, float *ev32, float *pos_post, float *arc_post,
+                                float *pos_cov, float *arc_cov, void *stream);
 int64_t nfst_positional_kbest_ws_bytes(const nfst_batch *lat, int32_t T, int32_t k);
 int nfst_positional_kbest(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T, int32_t k,
                           void *ws, int64_t ws_bytes, float *best, int32_t *paths, int32_t *path_arcs, int32_t *lengths,

@@ -43,6 +43,7 @@ using namespace nfst_tile;
 #include "slack_kernels.h"
 #include "intersect_kernels.h"
 #include "positional_kernels.h"
+#include "positional_expect_kernels.h"
 #include "positional_kbest_kernels.h"
 
 // ------------------------------------------------------------------ host helpers
@@ -1135,6 +1136,70 @@ int nfst_positional_viterbi(const nfst_batch *lat, const nfst_scores *scores, co
   if (staged)
     return launch(k_positional_viterbi<true>, dim3(lat->n_lattices), dim3(kPosThreads), lds, (hipStream_t)stream, *lat, in, w, o);
   return launch(k_positional_viterbi<false>, dim3(lat->n_lattices), dim3(kPosThreads), lds, (hipStream_t)stream, *lat, in, w, o);
+}
+
+// ------------------------------------------------------------------ expectations under positional scores (positional_expect_kernels.h)
+// workspace: the NFST_POS_WS_POSTERIOR parts of nfst_positional, then R_t(s) beside every stored beta row, the
+// position-independent value of every arc and the per-arc sums of c
+static int64_t pos_exp_ws_layout(const nfst_batch *lat, int64_t T, char *base, PosWs *w, PosExpWs *xw) {
+  const int64_t first = pos_ws_layout(lat, T, NFST_POS_WS_POSTERIOR, base, w);
+  WsCarve c{base ? base + first : nullptr};
+  char *br = c.take(8 * (T + 1) * lat->total_rows), *av = c.take(8 * lat->total_arcs), *a2 = c.take(8 * lat->total_arcs);
+  if (xw) *xw = {(double *)br, (double *)av, (double *)a2};
+  return first + c.size;
+}
+
+int64_t nfst_positional_expectation_ws_bytes(const nfst_batch *lat, int32_t T) {
+  const int rc = check_batch(lat);
+  if (rc) return rc;
+  if (T < 1) return NFST_ERR_ARG;
+  return pos_exp_ws_layout(lat, T, nullptr, nullptr, nullptr);
+}
+
+// what a launch of nfst_positional_expectation takes, as nfst_positional_plan (host only; the launcher calls it)
+int nfst_positional_expectation_plan(const nfst_batch *lat, int64_t *lds_bytes, int32_t *staged) {
+  const int rc = check_batch(lat);
+  if (rc) return rc;
+  const int64_t lds = (int64_t)lat->max_rows * 40 + (int64_t)lat->vocab * 36 + kPosThreads * 4 + 16;
+  if (lds > kMaxLds) return NFST_ERR_LIMIT;
+  const int64_t more = pos_staged_bytes(lat, lds);
+  if (lds_bytes) *lds_bytes = lds + more;
+  if (staged) *staged = more > 0;
+  return NFST_OK;
+}
+
+int nfst_positional_expectation(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T,
+                                const float *pos_values, int64_t pos_values_stride, const float *label_values,
+                                int64_t label_values_stride, const float *arc_values, float score_coef, void *ws, int64_t ws_bytes,
+                                double *logz64, float *logz32, double *ev64, float *ev32, float *pos_post, float *arc_post,
+                                float *pos_cov, float *arc_cov, void *stream) {
+  int rc = check_batch(lat);
+  if (rc) return rc;
+  if ((rc = check_scores(lat, scores))) return rc;
+  if (T < 1 || !logz64 || !ev64) return NFST_ERR_ARG;
+  const int64_t TV = (int64_t)T * lat->vocab;
+  if (pos && pos_stride != 0 && pos_stride != TV) return NFST_ERR_ARG;
+  if (pos_values && pos_values_stride != 0 && pos_values_stride != TV) return NFST_ERR_ARG;
+  if (label_values && label_values_stride != 0 && label_values_stride != lat->vocab) return NFST_ERR_ARG;
+  if (!(score_coef - score_coef == 0.0f)) return NFST_ERR_ARG;  // NaN or an infinity
+  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < pos_exp_ws_layout(lat, T, nullptr, nullptr, nullptr)) return NFST_ERR_ARG;
+  int64_t lds;
+  int32_t staged;
+  if ((rc = nfst_positional_expectation_plan(lat, &lds, &staged))) return rc;
+  PosWs w;
+  PosExpWs xw;
+  pos_exp_ws_layout(lat, T, (char *)ws, &w, &xw);
+  const PosIn in = {*scores, pos, pos ? pos_stride : 0, (int)T};
+  const PosExpVals x = {pos_values, pos_values ? pos_values_stride : 0, label_values, label_values ? label_values_stride : 0,
+                        arc_values, (double)score_coef};
+  const PosExpOut o = {logz64, logz32, ev64, ev32, pos_post, arc_post, pos_cov, arc_cov};
+  const dim3 grid(lat->n_lattices), block(kPosThreads);
+  const hipStream_t st = (hipStream_t)stream;
+  if (extras_case(lat, scores))
+    return staged ? launch(k_positional_expect<true, true>, grid, block, lds, st, *lat, in, x, w, xw, o)
+                  : launch(k_positional_expect<true, false>, grid, block, lds, st, *lat, in, x, w, xw, o);
+  return staged ? launch(k_positional_expect<false, true>, grid, block, lds, st, *lat, in, x, w, xw, o)
+                : launch(k_positional_expect<false, false>, grid, block, lds, st, *lat, in, x, w, xw, o);
 }
 
 // ------------------------------------------------------------------ k best paths under positional scores (positional_kbest_kernels.h)

@@ -212,6 +212,59 @@ __device__ __forceinline__ void pos_beta_pass(const nfst_batch &lat, const Meta 
   }
 }
 
+// The arcs of a lattice by (destination, canonical arc), built once per launch for the forward passes: in_ptr gets the
+// first in-entry of every state (relative to the lattice) and the end, w.in_rec the entries, and w.acc is zeroed.
+// cnt: 2 n + 1 ints of LDS scratch, scan: one int per thread.  Integers throughout: the result does not depend on the
+// order of the atomic adds.
+__device__ __forceinline__ void pos_in_order(const nfst_batch &lat, const Meta &m, int *cnt, int *scan, int *in_ptr, const PosWs &w) {
+  const int tid = threadIdx.x, n = m.n_rows;
+  int *fill = cnt + n + 1;
+  for (int i = tid; i <= n; i += kPosThreads) cnt[i] = 0;
+  __syncthreads();
+  for (int i = tid; i < m.n_arcs; i += kPosThreads) {
+    const int a = m.arc_off + i, s = lat.arc_src[a], d = lat.arc_dst[a];
+    if (s != d) atomicAdd(&cnt[d], 1);  // (integers: the order does not matter)
+    w.acc[a] = 0.0;
+  }
+  __syncthreads();
+  const int chunk = (n + kPosThreads - 1) / kPosThreads, c0 = min(tid * chunk, n), c1 = min(c0 + chunk, n);
+  int part = 0;
+  for (int i = c0; i < c1; ++i) part += cnt[i];
+  scan[tid] = part;
+  __syncthreads();
+  if (tid == 0) {
+    int run = 0;
+    for (int i = 0; i < kPosThreads; ++i) { const int v = scan[i]; scan[i] = run; run += v; }
+    cnt[n] = run;
+    in_ptr[n] = run;
+  }
+  __syncthreads();
+  int run = scan[tid];
+  for (int i = c0; i < c1; ++i) {
+    const int v = cnt[i];
+    cnt[i] = run;
+    fill[i] = run;
+    in_ptr[i] = run;
+    run += v;
+  }
+  __syncthreads();
+  for (int i = tid; i < m.n_arcs; i += kPosThreads) {
+    const int a = m.arc_off + i, s = lat.arc_src[a], d = lat.arc_dst[a];
+    if (s != d) w.in_tmp[m.arc_off + atomicAdd(&fill[d], 1)] = i;
+  }
+  __syncthreads();
+  // a state's in-entries were filled in any order: every arc finds its rank among them (stable, canonical order)
+  for (int i = tid; i < m.n_arcs; i += kPosThreads) {
+    const int a = m.arc_off + i, s = lat.arc_src[a], d = lat.arc_dst[a];
+    if (s == d) continue;
+    const int j0 = cnt[d], j1 = cnt[d + 1];
+    int rank = 0;
+    for (int j = j0; j < j1; ++j) rank += w.in_tmp[m.arc_off + j] < i;
+    w.in_rec[m.arc_off + j0 + rank] = make_int2(i, s | (lat.arc_label[a] << 16));
+  }
+  __syncthreads();
+}
+
 // LDS: two rows of (float64, int32) values, the label table (float64, int32), the label histogram (64-bit) and one
 // int per thread for the prefix sums: 24 max_rows + 20 vocab + 4 kPosThreads bytes.
 // STAGED: + 4 (max_rows + 1) + 4 (arcs of the largest lattice) bytes for the arc records.
@@ -246,53 +299,7 @@ __global__ __launch_bounds__(kPosThreads) void k_positional(nfst_batch lat, PosI
     }
   }
   int *in_ptr = w.in_ptr + m.row_off + b;
-  if (need_alpha) {
-    int *cnt = (int *)vm, *fill = cnt + n + 1;  // (the value rows are not in use yet: 8 n + 4 <= 16 max_rows bytes)
-    for (int i = tid; i <= n; i += kPosThreads) cnt[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < m.n_arcs; i += kPosThreads) {
-      const int a = m.arc_off + i, s = lat.arc_src[a], d = lat.arc_dst[a];
-      if (s != d) atomicAdd(&cnt[d], 1);  // (integers: the order does not matter)
-      w.acc[a] = 0.0;
-    }
-    __syncthreads();
-    const int chunk = (n + kPosThreads - 1) / kPosThreads, c0 = min(tid * chunk, n), c1 = min(c0 + chunk, n);
-    int part = 0;
-    for (int i = c0; i < c1; ++i) part += cnt[i];
-    scan[tid] = part;
-    __syncthreads();
-    if (tid == 0) {
-      int run = 0;
-      for (int i = 0; i < kPosThreads; ++i) { const int v = scan[i]; scan[i] = run; run += v; }
-      cnt[n] = run;
-      in_ptr[n] = run;
-    }
-    __syncthreads();
-    int run = scan[tid];
-    for (int i = c0; i < c1; ++i) {
-      const int v = cnt[i];
-      cnt[i] = run;
-      fill[i] = run;
-      in_ptr[i] = run;
-      run += v;
-    }
-    __syncthreads();
-    for (int i = tid; i < m.n_arcs; i += kPosThreads) {
-      const int a = m.arc_off + i, s = lat.arc_src[a], d = lat.arc_dst[a];
-      if (s != d) w.in_tmp[m.arc_off + atomicAdd(&fill[d], 1)] = i;
-    }
-    __syncthreads();
-    // a state's in-entries were filled in any order: every arc finds its rank among them (stable, canonical order)
-    for (int i = tid; i < m.n_arcs; i += kPosThreads) {
-      const int a = m.arc_off + i, s = lat.arc_src[a], d = lat.arc_dst[a];
-      if (s == d) continue;
-      const int j0 = cnt[d], j1 = cnt[d + 1];
-      int rank = 0;
-      for (int j = j0; j < j1; ++j) rank += w.in_tmp[m.arc_off + j] < i;
-      w.in_rec[m.arc_off + j0 + rank] = make_int2(i, s | (lat.arc_label[a] << 16));
-    }
-    __syncthreads();
-  }
+  if (need_alpha) pos_in_order(lat, m, (int *)vm, scan, in_ptr, w);  // (the value rows are not in use yet: 8 n + 4 <= 16 max_rows bytes)
 
   // ---- backwards in time ----------------------------------------------------------------------------------------
   const size_t ro = (size_t)(T + 1) * m.row_off;

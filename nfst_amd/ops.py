@@ -740,7 +740,9 @@ def positional_log_z(lat: LatticeBatch, theta: torch.Tensor, pos_scores: torch.T
     """Differentiable exact log Z_T per lattice, float32 [B], under per-position scores ``pos_scores`` [T, V] or
     [B, T, V] (see ``positional_forward_backward``).  Gradients: ``pos_scores`` gets the position posteriors, ``theta``
     their sums over the positions, ``arc_scores`` the arc posteriors (each summed over the lattices for a shared
-    tensor).  First derivatives only: a second backward raises."""
+    tensor).  First derivatives only: a second backward raises.  The Hessian-vector product of log Z_T with
+    (u_pos, u_theta, u_arc) is ``positional_expectation_terms(..., pos_values=u_pos, label_values=u_theta,
+    arc_values=u_arc, want_pos_cov=True, want_arc_cov=True).pos_cov / .arc_cov``."""
     _need_gpu(lat)
     theta = _input(lat, theta, "theta", True, False)
     arc_scores = _input(lat, arc_scores, "arc_scores", False, True)
@@ -757,6 +759,261 @@ def length_distribution(lat: LatticeBatch, theta, T: Optional[int] = None, arc_s
     r = positional_forward_backward(lat, theta, None, T, arc_scores, want_pos_posterior=False, want_len=True)
     z = r.logz64[:, None]
     return torch.where(torch.isfinite(z), r.len_logz - z, torch.full_like(r.len_logz, float("-inf"))), r.logz64
+
+
+# ----------------------------------------------------------------------------- expectations under positional scores
+class PositionalExpectationResult(NamedTuple):
+    logz64: torch.Tensor  # [B] float64 log Z_T
+    logz: torch.Tensor  # [B] float32
+    ev64: torch.Tensor  # [B] float64 E[V]
+    ev: torch.Tensor  # [B] float32
+    pos_posterior: Optional[torch.Tensor]  # [B, T, V] float32, the bits of positional_forward_backward
+    arc_posterior: Optional[torch.Tensor]  # [total_arcs] float32, the bits of positional_forward_backward
+    pos_cov: Optional[torch.Tensor]  # [B, T, V] float32: per label, the sum of c_{a,t} = P(a at t) (E[V | a at t] - E[V])
+    arc_cov: Optional[torch.Tensor]  # [total_arcs] float32: the sum over t of c_{a,t}
+
+
+def _position_values(lat: LatticeBatch, t, T: int, name: str):
+    """(``t`` as contiguous float32 or None, its stride) of a per-position value tensor, checked as ``_positions`` checks
+    ``pos_scores``: [T, V] or [B, T, V] on the batch's device, with the ``T`` of the call."""
+    if t is None:
+        return None, 0
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a torch.Tensor, not {type(t).__name__}")
+    if t.device != lat.device:
+        raise ValueError(f"{name} is on {t.device}, the lattice batch on {lat.device}")
+    if not t.is_floating_point():
+        raise ValueError(f"{name} must be a floating-point tensor, not {t.dtype}")
+    if t.dim() not in (2, 3) or t.shape[-1] != lat.vocab or t.shape[-2] != T or (t.dim() == 3 and t.shape[0] != lat.n_lattices):
+        raise ValueError(f"{name} must be [{T}, {lat.vocab}] or [{lat.n_lattices}, {T}, {lat.vocab}], not {list(t.shape)}")
+    return t.to(torch.float32).contiguous(), (0 if t.dim() == 2 else T * lat.vocab)
+
+
+def positional_expectation_plan(lat: LatticeBatch) -> tuple:
+    """(``lds_bytes``, ``staged``) of the launch ``positional_expectation_terms`` makes for this batch
+    (``nfst_positional_expectation_plan``, the rule the launcher itself calls), as ``positional_plan``: asked on the host,
+    no GPU needed; a batch beyond the op's LDS limit raises ``NfstError`` (-6), as the op would."""
+    lds, staged = C.c_int64(0), C.c_int32(0)
+    check(lib.nfst_positional_expectation_plan(C.byref(lat.c_struct()), C.byref(lds), C.byref(staged)),
+          "nfst_positional_expectation_plan")
+    return int(lds.value), bool(staged.value)
+
+
+def positional_expectation_terms(lat: LatticeBatch, theta, pos_scores=None, T: Optional[int] = None, arc_scores=None,
+                                 pos_values=None, label_values=None, arc_values=None, score_coef: float = 0.0,
+                                 want_pos_posterior: bool = False, want_arc_posterior: bool = False, want_pos_cov: bool = False,
+                                 want_arc_cov: bool = False) -> PositionalExpectationResult:
+    """One launch of ``nfst_positional_expectation`` (no autograd; DESIGN.md sections 2 and 4.13): under the distribution
+    p_T of ``positional_forward_backward`` (same ``theta``, ``pos_scores``, ``T``, ``arc_scores``), with the arc at
+    position t of a path carrying  v_t(a) = pos_values[(b,) t, label] + label_values[(b,) label] + arc_values[a] +
+    score_coef * (s_a + pos_scores[(b,) t, label])  (each term optional), log Z_T, E[V] and on request the posteriors (the
+    bits of ``positional_forward_backward``), ``pos_cov`` and ``arc_cov``: the covariance of every (position, label) and
+    of every arc with V.  For values that do not depend on the scores ``pos_cov`` / ``arc_cov`` are the Hessian of
+    log Z_T times the values.  Value entries behind a score of -inf are never read.  The workspace stores every
+    (beta, R) row of every position: 20 (T + 1) total_rows bytes."""
+    _need_gpu(lat)
+    theta = _input(lat, theta, "theta", True, False)
+    arc_scores = _input(lat, arc_scores, "arc_scores", False, True)
+    label_values = _input(lat, label_values, "label_values", True, False)
+    arc_values = _input(lat, arc_values, "arc_values", False, True)
+    pos, stride, T = _positions(lat, pos_scores, T)
+    pv, pv_stride = _position_values(lat, pos_values, T, "pos_values")
+    coef = float(score_coef)
+    if coef != coef or coef in (float("inf"), float("-inf")):
+        raise ValueError(f"score_coef must be finite, not {score_coef}")
+    sc, keep = _scores(lat, theta, arc_scores)
+    dev = lat.device
+    B, A, V = lat.n_lattices, lat.total_arcs, lat.vocab
+    ws_bytes = int(lib.nfst_positional_expectation_ws_bytes(C.byref(lat.c_struct()), T))
+    check(min(ws_bytes, 0), "nfst_positional_expectation_ws_bytes")
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    z64 = torch.empty(B, dtype=torch.float64, device=dev)
+    ev64 = torch.empty(B, dtype=torch.float64, device=dev)
+    z32, ev32 = torch.empty(B, **f32), torch.empty(B, **f32)
+    pp = torch.empty((B, T, V), **f32) if want_pos_posterior else None
+    ap = torch.empty(A, **f32) if want_arc_posterior else None
+    pc = torch.empty((B, T, V), **f32) if want_pos_cov else None
+    ac = torch.empty(A, **f32) if want_arc_cov else None
+    lv_stride = 0 if label_values is None or label_values.dim() == 1 else V
+    check(lib.nfst_positional_expectation(C.byref(lat.c_struct()), C.byref(sc), _ptr(pos), stride, T, _ptr(pv), pv_stride,
+                                          _ptr(label_values), lv_stride, _ptr(arc_values), coef, ws.data_ptr(), ws_bytes,
+                                          _ptr(z64), _ptr(z32), _ptr(ev64), _ptr(ev32), _ptr(pp), _ptr(ap), _ptr(pc), _ptr(ac),
+                                          _stream()), "nfst_positional_expectation")
+    return PositionalExpectationResult(z64, z32, ev64, ev32, pp, ap, pc, ac)
+
+
+def _det(t):
+    return None if t is None else t.detach()
+
+
+def _per_position(x: torch.Tensor, g: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    """[B, T, V] per-position sums times the incoming gradient [B]; summed over the batch for a shared [T, V] tensor."""
+    y = x * g[:, None, None]
+    return (y.sum(dim=0) if like.dim() == 2 else y).to(like.dtype)
+
+
+class _PositionalExpectation(torch.autograd.Function):
+    """E[V] with d/d pos_scores = pos_cov + coef pos_post, d/d theta its sums over t, d/d arc_scores = arc_cov + coef
+    arc_post, d/d pos_values = pos_post, d/d label_values its sums over t, d/d arc_values = arc_post."""
+
+    @staticmethod
+    def forward(ctx, lat, theta, pos_scores, arc_scores, pos_values, label_values, arc_values, coef, T):
+        nt, npos, na, npv, nlv, nav = ctx.needs_input_grad[1:7]
+        k = coef != 0.0
+        r = positional_expectation_terms(lat, theta.detach(), _det(pos_scores), T, _det(arc_scores), _det(pos_values),
+                                         _det(label_values), _det(arc_values), coef,
+                                         want_pos_posterior=npv or nlv or (k and (nt or npos)), want_arc_posterior=nav or (k and na),
+                                         want_pos_cov=nt or npos, want_arc_cov=na)
+        ctx.lat, ctx.coef = lat, coef
+        ctx.like = (theta, pos_scores, arc_scores, pos_values, label_values, arc_values)
+        ctx.save_for_backward(r.pos_posterior, r.arc_posterior, r.pos_cov, r.arc_cov)
+        return r.ev
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        pp, ap, pc, ac = ctx.saved_tensors
+        nt, npos, na, npv, nlv, nav = ctx.needs_input_grad[1:7]
+        theta, pos_scores, arc_scores, pos_values, label_values, arc_values = ctx.like
+        k = ctx.coef
+        g = g.to(torch.float32)
+        ga = g[ctx.lat.arc_lattice()] if (na or nav) else None
+        d_theta = d_pos = d_arc = d_pv = d_lv = d_av = None
+        if nt or npos:
+            ds = pc if k == 0.0 else pc + k * pp
+            if nt:
+                d_theta = _per_label(ds.sum(dim=1), g, theta.dim() == 1).to(theta.dtype)
+            if npos:
+                d_pos = _per_position(ds, g, pos_scores)
+        if na:
+            d_arc = ((ac if k == 0.0 else ac + k * ap) * ga).to(arc_scores.dtype)
+        if npv:
+            d_pv = _per_position(pp, g, pos_values)
+        if nlv:
+            d_lv = _per_label(pp.sum(dim=1), g, label_values.dim() == 1).to(label_values.dtype)
+        if nav:
+            d_av = (ap * ga).to(arc_values.dtype)
+        return None, d_theta, d_pos, d_arc, d_pv, d_lv, d_av, None, None
+
+
+def positional_expectation(lat: LatticeBatch, theta: torch.Tensor, pos_scores: Optional[torch.Tensor] = None,
+                           T: Optional[int] = None, arc_scores: Optional[torch.Tensor] = None,
+                           pos_values: Optional[torch.Tensor] = None, label_values: Optional[torch.Tensor] = None,
+                           arc_values: Optional[torch.Tensor] = None, score_coef: float = 0.0) -> torch.Tensor:
+    """Exact E_{p_T}[V] per lattice, float32 [B], under per-position scores (see ``positional_expectation_terms``):
+    expected cost of a tagger's output against a gold sequence (``pos_values = cost[b, t, label]``: minimum-risk
+    training, expected Hamming loss), expected length (``label_values`` = ones), expected label counts.  Differentiable
+    in ``theta``, ``pos_scores``, ``arc_scores``, ``pos_values``, ``label_values`` and ``arc_values`` (each gradient
+    summed over the lattices for a shared tensor); one launch, first derivatives only."""
+    _need_gpu(lat)
+    _input(lat, theta, "theta", True, False)
+    return _PositionalExpectation.apply(lat, theta, pos_scores, arc_scores, pos_values, label_values, arc_values,
+                                        float(score_coef), T)
+
+
+class _PositionalEntropy(torch.autograd.Function):
+    """H(p_T) = log Z_T - E[S] from one launch with score_coef = 1; dH/d(score) = -c."""
+
+    @staticmethod
+    def forward(ctx, lat, theta, pos_scores, arc_scores, T):
+        nt, npos, na = ctx.needs_input_grad[1:4]
+        r = positional_expectation_terms(lat, theta.detach(), _det(pos_scores), T, _det(arc_scores), score_coef=1.0,
+                                         want_pos_cov=nt or npos, want_arc_cov=na)
+        ctx.lat = lat
+        ctx.like = (theta, pos_scores, arc_scores)
+        ctx.save_for_backward(r.pos_cov, r.arc_cov)
+        return (r.logz64 - r.ev64).to(torch.float32)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        pc, ac = ctx.saved_tensors
+        nt, npos, na = ctx.needs_input_grad[1:4]
+        theta, pos_scores, arc_scores = ctx.like
+        g = -g.to(torch.float32)
+        d_theta = _per_label(pc.sum(dim=1), g, theta.dim() == 1).to(theta.dtype) if nt else None
+        d_pos = _per_position(pc, g, pos_scores) if npos else None
+        d_arc = (ac * g[ctx.lat.arc_lattice()]).to(arc_scores.dtype) if na else None
+        return None, d_theta, d_pos, d_arc, None
+
+
+def positional_entropy(lat: LatticeBatch, theta: torch.Tensor, pos_scores: Optional[torch.Tensor] = None,
+                       T: Optional[int] = None, arc_scores: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Exact entropy H(p_T) = log Z_T - E[S] per lattice, float32 [B] (nats; the difference is taken in float64), of the
+    distribution over the paths of at most ``T`` arcs under per-position scores.  Differentiable in ``theta``,
+    ``pos_scores`` and ``arc_scores``: dH/d(score) = -Cov(1[arc at t], S).  A lattice without a path within ``T`` gets
+    NaN-free -inf."""
+    _need_gpu(lat)
+    _input(lat, theta, "theta", True, False)
+    return _PositionalEntropy.apply(lat, theta, pos_scores, arc_scores, T)
+
+
+def _diff(p, q):
+    """p - q in float32 where either may be None (None when both are)."""
+    if p is None and q is None:
+        return None
+    if q is None:
+        return p.to(torch.float32)
+    return (p.to(torch.float32) if p is not None else 0.0) - q.to(torch.float32)
+
+
+class _PositionalKL(torch.autograd.Function):
+    """KL(p_T || q_T) = log Z_q - log Z_p + E_p[S_p - S_q] (arc_w cancels); d/d(scores of p) = c(v = S_p - S_q),
+    d/d(scores of q) = post_q - post_p."""
+
+    @staticmethod
+    def forward(ctx, lat, theta_p, pos_p, theta_q, pos_q, arc_scores_p, arc_scores_q, T):
+        ntp, npp, ntq, npq, nap, naq = ctx.needs_input_grad[1:7]
+        tp, tq, pp_, pq_ = theta_p.detach(), theta_q.detach(), _det(pos_p), _det(pos_q)
+        asp, asq = _det(arc_scores_p), _det(arc_scores_q)
+        for name, t in (("theta_p", tp), ("theta_q", tq)):
+            _input(lat, t, name, True, False)
+        for name, t in (("arc_scores_p", asp), ("arc_scores_q", asq)):
+            _input(lat, t, name, False, True)
+        _, _, T = _positions(lat, pp_ if pp_ is not None else pq_, T)
+        _positions(lat, pq_, T)
+        # (-inf - -inf is NaN and finite - -inf is +inf: behind a weight of zero under p neither is read; where p has mass
+        # on something q forbids the result is +inf or NaN, the caller's business)
+        rp = positional_expectation_terms(lat, tp, pp_, T, asp, _diff(pp_, pq_), _diff(tp, tq), _diff(asp, asq), 0.0,
+                                          want_pos_posterior=ntq or npq, want_arc_posterior=naq, want_pos_cov=ntp or npp,
+                                          want_arc_cov=nap)
+        rq = positional_forward_backward(lat, tq, pq_, T, asq, want_pos_posterior=ntq or npq, want_arc_posterior=naq)
+        ctx.lat = lat
+        ctx.like = (theta_p, pos_p, theta_q, pos_q, arc_scores_p, arc_scores_q)
+        ctx.save_for_backward(rp.pos_cov, rp.arc_cov, rp.pos_posterior, rp.arc_posterior, rq.pos_posterior, rq.arc_posterior)
+        return (rq.logz64 - rp.logz64 + rp.ev64).to(torch.float32)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        pc, ac, pp_p, ap_p, pp_q, ap_q = ctx.saved_tensors
+        ntp, npp, ntq, npq, nap, naq = ctx.needs_input_grad[1:7]
+        theta_p, pos_p, theta_q, pos_q, asp, asq = ctx.like
+        g = g.to(torch.float32)
+        ga = g[ctx.lat.arc_lattice()] if (nap or naq) else None
+        dq = pp_q - pp_p if (ntq or npq) else None
+        return (None,
+                _per_label(pc.sum(dim=1), g, theta_p.dim() == 1).to(theta_p.dtype) if ntp else None,
+                _per_position(pc, g, pos_p) if npp else None,
+                _per_label(dq.sum(dim=1), g, theta_q.dim() == 1).to(theta_q.dtype) if ntq else None,
+                _per_position(dq, g, pos_q) if npq else None,
+                (ac * ga).to(asp.dtype) if nap else None,
+                ((ap_q - ap_p) * ga).to(asq.dtype) if naq else None, None)
+
+
+def positional_kl_divergence(lat: LatticeBatch, theta_p: torch.Tensor, pos_p: Optional[torch.Tensor], theta_q: torch.Tensor,
+                             pos_q: Optional[torch.Tensor], T: Optional[int] = None,
+                             arc_scores_p: Optional[torch.Tensor] = None,
+                             arc_scores_q: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Exact KL(p_T || q_T) per lattice, float32 [B], of two positional models over the paths of at most ``T`` arcs of
+    the same batch (distillation): log Z_q - log Z_p + E_p[S_p - S_q], combined in float64.  One expectation launch under
+    p (values ``pos_p - pos_q``, ``theta_p - theta_q`` and the arc-score difference) and one ``nfst_positional`` launch
+    under q.  Differentiable in all six score inputs: d/d(scores of p) = Cov_p(1[arc at t], S_p - S_q), d/d(scores of q)
+    = post_q - post_p -- exactly zero at q = p, the two launches write the same posterior bits.  Where p puts mass on
+    something q forbids (-inf) the result is +inf or NaN: the caller's business, nothing scans for it."""
+    _need_gpu(lat)
+    return _PositionalKL.apply(lat, theta_p, pos_p, theta_q, pos_q, arc_scores_p, arc_scores_q, T)
 
 
 def positional_viterbi(lat: LatticeBatch, theta, pos_scores=None, T: Optional[int] = None, arc_scores=None,

@@ -91,6 +91,23 @@ class LatticeScorer(torch.nn.Module):
         mark]`` (``ops.positional_log_z``): per-position logits of a tagger, marginalised over the lattice."""
         return ops.positional_log_z(self._lat(), self.theta, pos_scores)
 
+    def positional_expectation(self, pos_scores: torch.Tensor, **values) -> torch.Tensor:
+        """Differentiable exact E[V] per lattice ``[B]`` under ``theta`` plus per-position scores
+        (``ops.positional_expectation``; ``values``: ``pos_values``, ``label_values``, ``arc_values``, ``score_coef``,
+        ``T``)."""
+        return ops.positional_expectation(self._lat(), self.theta, pos_scores, **values)
+
+    def positional_entropy(self, pos_scores: torch.Tensor) -> torch.Tensor:
+        """Differentiable exact entropy per lattice ``[B]`` (nats) of the paths of at most T arcs under ``theta`` plus
+        per-position scores (``ops.positional_entropy``)."""
+        return ops.positional_entropy(self._lat(), self.theta, pos_scores)
+
+    def positional_risk(self, pos_scores: torch.Tensor, cost: torch.Tensor) -> torch.Tensor:
+        """The minimum-risk objective: the exact expected cost per lattice ``[B]`` of the tagger's output against
+        ``cost[(b,) t, mark]`` (expected Hamming loss for a 0/1 cost against a gold sequence), differentiable in ``theta``,
+        ``pos_scores`` and ``cost``."""
+        return ops.positional_expectation(self._lat(), self.theta, pos_scores, pos_values=cost)
+
     def length_distribution(self, T: Optional[int] = None):
         """``(log P(L = t) [B, T + 1], logz64 [B])`` over the paths of at most ``T`` arcs (``ops.length_distribution``)."""
         return ops.length_distribution(self._lat(), self.theta.detach(), T=T)

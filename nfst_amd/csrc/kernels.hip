@@ -167,6 +167,14 @@ int with_threads(int nt, F f) {
   return nt == 512 ? f(ic<512>()) : f(ic<256>());
 }
 
+// the flavours of a positional sweep: per-arc extras or none, arc records staged in LDS or read from the canonical arrays
+template <class F>
+int with_pos_flavour(bool extra, bool staged, F f) {
+  typedef std::true_type Y;
+  typedef std::false_type N;
+  return extra ? (staged ? f(Y(), Y()) : f(Y(), N())) : (staged ? f(N(), Y()) : f(N(), N()));
+}
+
 // the largest lattice's arc count; NFST_BATCH_MAX_ARCS_CAP: that many or more
 int64_t max_lattice_arcs(const nfst_batch *lat) { return ((int64_t)lat->reserved0 >> NFST_BATCH_MAX_ARCS_SHIFT) & NFST_BATCH_MAX_ARCS_CAP; }
 
@@ -1012,15 +1020,22 @@ static int64_t pos_ws_layout(const nfst_batch *lat, int64_t T, int flags, char *
   if (w) *w = r;
   return c.size;
 }
-static int pos_check(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T, const void *ws,
-                     int64_t ws_bytes, int flags) {
+// what every positional op checks first: the batch, the scores, T and the stride of pos; then its workspace
+static int pos_check(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T) {
   int rc = check_batch(lat);
   if (rc) return rc;
   if ((rc = check_scores(lat, scores))) return rc;
   if (T < 1) return NFST_ERR_ARG;
   if (pos && pos_stride != 0 && pos_stride != (int64_t)T * lat->vocab) return NFST_ERR_ARG;
-  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < pos_ws_layout(lat, T, flags, nullptr, nullptr)) return NFST_ERR_ARG;
   return NFST_OK;
+}
+static int pos_check_ws(const void *ws, int64_t ws_bytes, int64_t need) {
+  return (!ws || ((uintptr_t)ws & 15) || ws_bytes < need) ? NFST_ERR_ARG : NFST_OK;
+}
+static int pos_check(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T, const void *ws,
+                     int64_t ws_bytes, int flags) {
+  const int rc = pos_check(lat, scores, pos, pos_stride, T);
+  return rc ? rc : pos_check_ws(ws, ws_bytes, pos_ws_layout(lat, T, flags, nullptr, nullptr));
 }
 
 // LDS for the staged arc records (4 bytes per row and per arc of the largest lattice) when they fit beside `lds`
@@ -1039,19 +1054,21 @@ int64_t nfst_positional_ws_bytes(const nfst_batch *lat, int32_t T, int32_t flags
   return pos_ws_layout(lat, T, flags, nullptr, nullptr);
 }
 
-// The one place that decides what a launch of either op takes: the LDS of its kernel and whether the arc records are
-// staged beside it.  Host only (no device is touched): both launchers call it, and so may a caller that wants to know
-// which flavour a batch gets.
-int nfst_positional_plan(const nfst_batch *lat, int32_t viterbi, int64_t *lds_bytes, int32_t *staged) {
+// The one place that decides what a launch of a positional sweep takes: the LDS of its kernel (`row` bytes per row of
+// the largest lattice, `label` per label, `fixed`) and whether the arc records are staged beside it.  Host only (no
+// device is touched): the launchers call it, and so may a caller that wants to know which flavour a batch gets.
+static int pos_plan(const nfst_batch *lat, int64_t row, int64_t label, int64_t fixed, int64_t *lds_bytes, int32_t *staged) {
   const int rc = check_batch(lat);
   if (rc) return rc;
-  const int64_t lds = viterbi ? (int64_t)lat->max_rows * 8 + (int64_t)lat->vocab * 4 + 16
-                              : (int64_t)lat->max_rows * 24 + (int64_t)lat->vocab * 20 + kPosThreads * 4 + 16;
+  const int64_t lds = lat->max_rows * row + lat->vocab * label + fixed;
   if (lds > kMaxLds) return NFST_ERR_LIMIT;
   const int64_t more = pos_staged_bytes(lat, lds);
   if (lds_bytes) *lds_bytes = lds + more;
   if (staged) *staged = more > 0;
   return NFST_OK;
+}
+int nfst_positional_plan(const nfst_batch *lat, int32_t viterbi, int64_t *lds_bytes, int32_t *staged) {
+  return viterbi ? pos_plan(lat, 8, 4, 16, lds_bytes, staged) : pos_plan(lat, 24, 20, kPosThreads * 4 + 16, lds_bytes, staged);
 }
 
 // one launch of k_positional in the flavour nfst_positional_plan chose (mode: kPosModeLogz / Alpha / Rows)
@@ -1061,12 +1078,9 @@ static int pos_launch_sum(const nfst_batch *lat, const nfst_scores *scores, cons
   int32_t staged;
   const int rc = nfst_positional_plan(lat, 0, &lds, &staged);
   if (rc) return rc;
-  const dim3 grid(lat->n_lattices), block(kPosThreads);
-  if (extras_case(lat, scores))
-    return staged ? launch(k_positional<true, true>, grid, block, lds, st, *lat, in, w, o, mode)
-                  : launch(k_positional<true, false>, grid, block, lds, st, *lat, in, w, o, mode);
-  return staged ? launch(k_positional<false, true>, grid, block, lds, st, *lat, in, w, o, mode)
-                : launch(k_positional<false, false>, grid, block, lds, st, *lat, in, w, o, mode);
+  return with_pos_flavour(extras_case(lat, scores), staged, [&](auto EX, auto SG) {
+    return launch(k_positional<EX, SG>, dim3(lat->n_lattices), dim3(kPosThreads), lds, st, *lat, in, w, o, mode);
+  });
 }
 
 int nfst_positional(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T, void *ws,
@@ -1109,11 +1123,9 @@ int nfst_positional_sample(const nfst_batch *lat, const nfst_scores *scores, con
 int nfst_positional_score_paths(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T,
                                 const int32_t *marks, int32_t k, float *path_score, int32_t *end_state, int32_t *lengths,
                                 void *stream) {
-  int rc = check_batch(lat);
+  const int rc = pos_check(lat, scores, pos, pos_stride, T);
   if (rc) return rc;
-  if ((rc = check_scores(lat, scores))) return rc;
-  if (T < 1 || k < 1 || (pos && pos_stride != 0 && pos_stride != (int64_t)T * lat->vocab)) return NFST_ERR_ARG;
-  if (!marks || !path_score || !end_state || !lengths) return NFST_ERR_ARG;
+  if (k < 1 || !marks || !path_score || !end_state || !lengths) return NFST_ERR_ARG;
   if (((int64_t)k + 63) / 64 > 65535) return NFST_ERR_LIMIT;  // (the y dimension of the grid)
   const PosIn in = {*scores, pos, pos ? pos_stride : 0, (int)T};
   return launch(k_positional_score, dim3(lat->n_lattices, (k + 63) / 64), dim3(64), 0, (hipStream_t)stream, *lat, in, marks, (int)k,
@@ -1133,9 +1145,9 @@ int nfst_positional_viterbi(const nfst_batch *lat, const nfst_scores *scores, co
   pos_ws_layout(lat, T, NFST_POS_WS_VITERBI, (char *)ws, &w);
   const PosIn in = {*scores, pos, pos ? pos_stride : 0, (int)T};
   const PosVitOut o = {best, paths, path_arcs, lengths, (int)pad};
-  if (staged)
-    return launch(k_positional_viterbi<true>, dim3(lat->n_lattices), dim3(kPosThreads), lds, (hipStream_t)stream, *lat, in, w, o);
-  return launch(k_positional_viterbi<false>, dim3(lat->n_lattices), dim3(kPosThreads), lds, (hipStream_t)stream, *lat, in, w, o);
+  return with_pos_flavour(false, staged, [&](auto, auto SG) {
+    return launch(k_positional_viterbi<SG>, dim3(lat->n_lattices), dim3(kPosThreads), lds, (hipStream_t)stream, *lat, in, w, o);
+  });
 }
 
 // ------------------------------------------------------------------ expectations under positional scores (positional_expect_kernels.h)
@@ -1158,14 +1170,7 @@ int64_t nfst_positional_expectation_ws_bytes(const nfst_batch *lat, int32_t T) {
 
 // what a launch of nfst_positional_expectation takes, as nfst_positional_plan (host only; the launcher calls it)
 int nfst_positional_expectation_plan(const nfst_batch *lat, int64_t *lds_bytes, int32_t *staged) {
-  const int rc = check_batch(lat);
-  if (rc) return rc;
-  const int64_t lds = (int64_t)lat->max_rows * 40 + (int64_t)lat->vocab * 36 + kPosThreads * 4 + 16;
-  if (lds > kMaxLds) return NFST_ERR_LIMIT;
-  const int64_t more = pos_staged_bytes(lat, lds);
-  if (lds_bytes) *lds_bytes = lds + more;
-  if (staged) *staged = more > 0;
-  return NFST_OK;
+  return pos_plan(lat, 40, 36, kPosThreads * 4 + 16, lds_bytes, staged);
 }
 
 int nfst_positional_expectation(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T,
@@ -1173,16 +1178,13 @@ int nfst_positional_expectation(const nfst_batch *lat, const nfst_scores *scores
                                 int64_t label_values_stride, const float *arc_values, float score_coef, void *ws, int64_t ws_bytes,
                                 double *logz64, float *logz32, double *ev64, float *ev32, float *pos_post, float *arc_post,
                                 float *pos_cov, float *arc_cov, void *stream) {
-  int rc = check_batch(lat);
+  int rc = pos_check(lat, scores, pos, pos_stride, T);
   if (rc) return rc;
-  if ((rc = check_scores(lat, scores))) return rc;
-  if (T < 1 || !logz64 || !ev64) return NFST_ERR_ARG;
-  const int64_t TV = (int64_t)T * lat->vocab;
-  if (pos && pos_stride != 0 && pos_stride != TV) return NFST_ERR_ARG;
-  if (pos_values && pos_values_stride != 0 && pos_values_stride != TV) return NFST_ERR_ARG;
+  if (!logz64 || !ev64) return NFST_ERR_ARG;
+  if (pos_values && pos_values_stride != 0 && pos_values_stride != (int64_t)T * lat->vocab) return NFST_ERR_ARG;
   if (label_values && label_values_stride != 0 && label_values_stride != lat->vocab) return NFST_ERR_ARG;
   if (!(score_coef - score_coef == 0.0f)) return NFST_ERR_ARG;  // NaN or an infinity
-  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < pos_exp_ws_layout(lat, T, nullptr, nullptr, nullptr)) return NFST_ERR_ARG;
+  if ((rc = pos_check_ws(ws, ws_bytes, pos_exp_ws_layout(lat, T, nullptr, nullptr, nullptr)))) return rc;
   int64_t lds;
   int32_t staged;
   if ((rc = nfst_positional_expectation_plan(lat, &lds, &staged))) return rc;
@@ -1193,13 +1195,9 @@ int nfst_positional_expectation(const nfst_batch *lat, const nfst_scores *scores
   const PosExpVals x = {pos_values, pos_values ? pos_values_stride : 0, label_values, label_values ? label_values_stride : 0,
                         arc_values, (double)score_coef};
   const PosExpOut o = {logz64, logz32, ev64, ev32, pos_post, arc_post, pos_cov, arc_cov};
-  const dim3 grid(lat->n_lattices), block(kPosThreads);
-  const hipStream_t st = (hipStream_t)stream;
-  if (extras_case(lat, scores))
-    return staged ? launch(k_positional_expect<true, true>, grid, block, lds, st, *lat, in, x, w, xw, o)
-                  : launch(k_positional_expect<true, false>, grid, block, lds, st, *lat, in, x, w, xw, o);
-  return staged ? launch(k_positional_expect<false, true>, grid, block, lds, st, *lat, in, x, w, xw, o)
-                : launch(k_positional_expect<false, false>, grid, block, lds, st, *lat, in, x, w, xw, o);
+  return with_pos_flavour(extras_case(lat, scores), staged, [&](auto EX, auto SG) {
+    return launch(k_positional_expect<EX, SG>, dim3(lat->n_lattices), dim3(kPosThreads), lds, (hipStream_t)stream, *lat, in, x, w, xw, o);
+  });
 }
 
 // ------------------------------------------------------------------ k best paths under positional scores (positional_kbest_kernels.h)
@@ -1224,13 +1222,11 @@ int64_t nfst_positional_kbest_ws_bytes(const nfst_batch *lat, int32_t T, int32_t
 int nfst_positional_kbest(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T, int32_t k,
                           void *ws, int64_t ws_bytes, float *best, int32_t *paths, int32_t *path_arcs, int32_t *lengths,
                           int32_t *n_paths, int32_t pad, void *stream) {
-  int rc = check_batch(lat);
+  int rc = pos_check(lat, scores, pos, pos_stride, T);
   if (rc) return rc;
-  if ((rc = check_scores(lat, scores))) return rc;
-  if (T < 1 || (pos && pos_stride != 0 && pos_stride != (int64_t)T * lat->vocab)) return NFST_ERR_ARG;
   if ((rc = kb_check_k(k))) return rc;
   if (!best || !paths || !lengths || !n_paths) return NFST_ERR_ARG;
-  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < pkb_ws_layout(lat, T, k, nullptr, nullptr)) return NFST_ERR_ARG;
+  if ((rc = pos_check_ws(ws, ws_bytes, pkb_ws_layout(lat, T, k, nullptr, nullptr)))) return rc;
   // nfst_kbest's payload: (arc in lattice, rank) in 32 bits
   if (max_lattice_arcs(lat) >= NFST_BATCH_MAX_ARCS_CAP && lat->total_arcs >= ((int64_t)1 << 24)) return NFST_ERR_LIMIT;
   const int64_t lds = (int64_t)kKbSweepWaves * 2 * 64 * 8 + ((int64_t)lat->max_rows + 2 + lat->vocab) * 4;

@@ -7,9 +7,10 @@
 //     v_t(a) = pos_values[b, t, l] + label_values[b, l] + arc_values[a] + coef (s_a + pos[b, t, l])      (l = label_a)
 // in float64.  Backwards in time every (t, s) keeps beta_t(s) and R_t(s) = E[value of the rest of the path | s at t];
 // forwards alpha_t(s) and R^alpha_t(s) = E[value so far | s at t].  A step accumulates sum x and sum x (R(other) + v)
-// under ONE exponent (section 4.5: two numerators under one shared exponent); R is their ratio.  The path mass goes
-// through exactly the operations of PosSum::plus / combine / norm in the order of k_positional, and the numerator never
-// enters it: log Z, pos_post and arc_post are the bits of nfst_positional.
+// under ONE exponent (section 4.5: two numerators under one shared exponent); R is their ratio.
+// The kernel is pos_sum_sweep -- the body of k_positional, step loops included -- with PosExpRider: the path mass goes
+// through the one PosSum::plus / combine / norm of those loops and the rider only follows its exponent, so log Z,
+// pos_post and arc_post are the bits of nfst_positional by construction, not by two copies that agree.
 // The per-arc part of v (arc_values + coef (arc_w + arc_scores)) is a double per arc in the workspace, the per-label part
 // a double per label in the step's table.  A term whose weight mantissa is zero is skipped before its value is read.
 struct PosExpVals {
@@ -33,32 +34,10 @@ struct PosExpOut {
   float *pos_post, *arc_post, *pos_cov, *arc_cov;
 };
 
-// PosSum::plus on the mass, and the numerator N kept under the mass's exponent
-__device__ __forceinline__ void pos_exp_plus(ME64 &acc, double &N, ME64 x, double val) {
-  if (x.e > acc.e) {
-    acc.m = __builtin_amdgcn_ldexp(acc.m, acc.e - x.e);
-    N = __builtin_amdgcn_ldexp(N, acc.e - x.e);
-    acc.e = x.e;
-  }
-  const double xm = __builtin_amdgcn_ldexp(x.m, x.e - acc.e);
-  acc.m += xm;
-  N += xm * val;
-}
-// PosSum::combine on the mass; the numerators are aligned and added the same way (commutative: both partners agree)
-__device__ __forceinline__ void pos_exp_combine(ME64 &acc, double &N, int o) {
-  const double om = __shfl_xor(acc.m, o), oN = __shfl_xor(N, o);
-  const int oe = __shfl_xor(acc.e, o);
-  const int E = max(acc.e, oe);
-  acc.m = __builtin_amdgcn_ldexp(acc.m, acc.e - E) + __builtin_amdgcn_ldexp(om, oe - E);
-  N = __builtin_amdgcn_ldexp(N, acc.e - E) + __builtin_amdgcn_ldexp(oN, oe - E);
-  acc.e = E;
-}
-
-// the label table of position t: the split weights by pos_fill_table<PosSum>, then the per-label part of the value
-// (every thread reads back the entries it wrote itself: no barrier in between)
+// the per-label part of the value beside the label table of position t (every thread reads back the weights it wrote
+// itself in pos_fill_table: no barrier in between)
 __device__ __forceinline__ void pos_exp_fill_table(const PosSum::Rows &tab, double *tv, const float *theta, const float *pos_t,
                                                    const float *lv, const float *pv_t, double coef, int V) {
-  pos_fill_table<PosSum>(tab, theta, pos_t, V);
   for (int l = threadIdx.x; l < V; l += kPosThreads) {
     double v = 0.0;
     if (tab.m[l] != 0.0) {  // (a label of weight zero has no value: coef * s would be -inf or NaN there)
@@ -70,217 +49,95 @@ __device__ __forceinline__ void pos_exp_fill_table(const PosSum::Rows &tab, doub
   }
 }
 
-// LDS: two rows of (float64 mass, float64 R, int32 exponent), the label table (float64 weight, float64 value, int32
-// exponent), two label histograms (64-bit fixed point for p, float64 for p e) and one int per thread:
+// The rider of the expectation sweep (PosNoRider documents the hooks): the numerator N of the lane's running sum, kept
+// under the exponent of the mass `acc` that the loop itself accumulates; R rows `vr` and values `tv` beside the LDS rows
+// and the label table; the R rows of the stored beta rows; a float64 histogram and a per-entry sum for the c_{a,t}.
+struct PosExpRider {
+  const float *pv, *lv;  // of this lattice, or nullptr
+  double coef;
+  const float *av_in;  // arc_values, or nullptr
+  double *av;          // the workspace's value per arc; nullptr: no arc has one
+  double *sbr;         // the stored R rows of this lattice
+  double *acc_c;       // per in-entry of this lattice
+  float *pos_cov, *arc_cov;
+  double *ev64;
+  float *ev32;
+  double *vr, *tv, *hcov;      // LDS
+  double N = 0.0, v = 0.0, rest = 0.0, ev = 0.0;  // v: the value of the term just taken (R(other state) + v_t(a)); rest: R_{t+1}(d) - E[V]
+  __device__ __forceinline__ bool by_step() const { return pv != nullptr; }
+  __device__ __forceinline__ bool arc_val() const { return av != nullptr; }
+  __device__ __forceinline__ bool by_label() const { return pos_cov != nullptr; }
+  __device__ __forceinline__ bool by_arc() const { return arc_cov != nullptr; }
+  __device__ __forceinline__ void arc(int a, double e, bool live) {
+    if (!av) return;
+    double x = (coef != 0.0 && live) ? coef * e : 0.0;
+    if (av_in) x += (double)av_in[a];
+    av[a] = x;
+  }
+  __device__ __forceinline__ void fill(const PosSum::Rows &tab, const float *theta, const float *pos_t, int t, int V) {
+    pos_exp_fill_table(tab, tv, theta, pos_t, lv, pv ? pv + (size_t)t * V : nullptr, coef, V);
+  }
+  __device__ __forceinline__ void start(bool fwd, size_t st_i) {
+    N = 0.0;
+    rest = fwd ? sbr[st_i] - ev : 0.0;
+  }
+  __device__ __forceinline__ void term(const ME64 &was, const ME64 &acc, const ME64 &y, int i, int l, int a) {
+    v = vr[i] + tv[l] + (av ? av[a] : 0.0);
+    if (y.e > was.e) N = __builtin_amdgcn_ldexp(N, was.e - y.e);  // (the move PosSum::plus made: acc.e is y.e now)
+    N += __builtin_amdgcn_ldexp(y.m, y.e - acc.e) * v;
+  }
+  // the partner's numerator comes as it is, beside its mass (no shuffle waits for another), and both are brought under
+  // the common exponent here (commutative: both partners agree)
+  __device__ __forceinline__ void combine(const ME64 &was, const ME64 &acc, int o) {
+    const double oN = __shfl_xor(N, o);
+    const int oe = __shfl_xor(was.e, o);
+    N = __builtin_amdgcn_ldexp(N, was.e - acc.e) + __builtin_amdgcn_ldexp(oN, oe - acc.e);
+  }
+  __device__ __forceinline__ void row(int i, const ME64 &acc, bool live, bool store, size_t st_i) {
+    const double r = (live && acc.m != 0.0) ? N / acc.m : 0.0;
+    vr[i] = r;
+    if (store) sbr[st_i] = r;
+  }
+  __device__ __forceinline__ void beta_done(int b, const ME64 &z) {  // R_0(0) is in row 0 of the pair
+    ev = z.m > 0.0 ? vr[0] : 0.0;
+    if (threadIdx.x == 0) {
+      ev64[b] = ev;
+      if (ev32) ev32[b] = (float)ev;
+    }
+  }
+  __device__ __forceinline__ void post(double p, int j, int l) {
+    const double c = p * (v + rest);
+    if (pos_cov) atomicAdd(&hcov[l], c);  // (float64 LDS atomics: the order of the adds is not fixed)
+    if (arc_cov) acc_c[j] += c;
+  }
+  __device__ __forceinline__ void drain_label(size_t i, int l) {
+    if (pos_cov) pos_cov[i] = (float)hcov[l];
+    hcov[l] = 0.0;
+  }
+  __device__ __forceinline__ void drain_arc(int a, int j) {
+    if (arc_cov) arc_cov[a] = j < 0 ? 0.0f : (float)acc_c[j];
+  }
+};
+
+// LDS: pos_lds_layout with one double beside every row value, table entry and histogram bin:
 // 40 max_rows + 36 vocab + 4 kPosThreads bytes.  STAGED: + 4 (max_rows + 1) + 4 (arcs of the largest lattice) bytes.
 template <bool EXTRA, bool STAGED>
 __global__ __launch_bounds__(kPosThreads) void k_positional_expect(nfst_batch lat, PosIn in, PosExpVals x, PosWs w, PosExpWs xw,
                                                                    PosExpOut o) {
   extern __shared__ double pos_lds[];
-  const int b = blockIdx.x, tid = threadIdx.x;
+  const int b = blockIdx.x;
   const Meta m = load_meta(lat.meta, b);
-  const int R = lat.max_rows, V = lat.vocab, T = in.T, n = m.n_rows;
-  double *vm = pos_lds, *vr = vm + 2 * R, *tm = vr + 2 * R, *tv = tm + V;
-  unsigned long long *hist = (unsigned long long *)(tv + V);
-  double *hcov = (double *)(hist + V);
-  int *ve = (int *)(hcov + V), *te = ve + 2 * R, *scan = te + V;
-  int *rp_l = scan + kPosThreads;
-  uint32_t *recs = (uint32_t *)(rp_l + R + 1);
-  typedef typename std::conditional<STAGED, PosArcsLds, PosArcsGlobal>::type Arcs;
-  const PosSum::Rows val = {vm, ve}, tab = {tm, te};
-  const float *theta = in.sc.theta + (size_t)in.sc.theta_stride * b;
-  const float *pos_b = in.pos ? in.pos + (size_t)in.pos_stride * b : nullptr;
-  const float *pv_b = x.pv ? x.pv + (size_t)x.pv_stride * b : nullptr;
-  const float *lv_b = x.lv ? x.lv + (size_t)x.lv_stride * b : nullptr;
-  const bool by_step = pos_b != nullptr || pv_b != nullptr;  // the table changes from position to position
-  const bool arc_val = x.av != nullptr || (EXTRA && x.coef != 0.0);
-  const int G = pos_group(m);
-  const int slots = kPosThreads / G, slot = tid / G, gl = tid % G;
-
-  // ---- once per launch: the weights and values of the per-arc terms, the arcs by (destination, canonical arc) -----
-  if (EXTRA || arc_val) {
-    for (int a = m.arc_off + tid; a < m.arc_off + m.n_arcs; a += kPosThreads) {
-      double e = 0.0, v = 0.0;
-      if (EXTRA) {
-        if (lat.weighted) e += (double)lat.arc_w[a];
-        if (in.sc.arc_scores) e += (double)in.sc.arc_scores[a];
-        const ME64 ew = exp_split64(e);
-        w.ewm[a] = ew.m;
-        w.ewe[a] = ew.e;
-        if (x.coef != 0.0 && ew.m != 0.0) v = x.coef * e;
-      }
-      if (x.av) v += (double)x.av[a];
-      if (arc_val) xw.av[a] = v;
-    }
-  }
+  const PosLds L = pos_lds_layout(pos_lds, lat.max_rows, lat.vocab, 1);
   // without any of the four optional outputs there is no forward pass: no by-destination order, no stored rows
   const bool need_alpha = o.pos_post || o.arc_post || o.pos_cov || o.arc_cov;
-  int *in_ptr = w.in_ptr + m.row_off + b;
-  if (need_alpha) {
-    pos_in_order(lat, m, (int *)vm, scan, in_ptr, w);
-    for (int i = tid; i < m.n_arcs; i += kPosThreads) xw.acc2[m.arc_off + i] = 0.0;
+  const bool arc_val = x.av != nullptr || (EXTRA && x.coef != 0.0);
+  PosExpRider rd = {x.pv ? x.pv + (size_t)x.pv_stride * b : nullptr, x.lv ? x.lv + (size_t)x.lv_stride * b : nullptr, x.coef, x.av,
+                    arc_val ? xw.av : nullptr, xw.br + (size_t)(in.T + 1) * m.row_off, xw.acc2 + m.arc_off, o.pos_cov, o.arc_cov,
+                    o.ev64, o.ev32, L.xr, L.xt, L.xh};
+  if (need_alpha) {  // (barriers follow before either is added to)
+    for (int l = threadIdx.x; l < lat.vocab; l += kPosThreads) rd.hcov[l] = 0.0;
+    for (int i = threadIdx.x; i < m.n_arcs; i += kPosThreads) rd.acc_c[i] = 0.0;
   }
-
-  // ---- backwards in time ----------------------------------------------------------------------------------------
-  const size_t ro = (size_t)(T + 1) * m.row_off;
-  double *sbm = w.bm + ro, *sbr = xw.br + ro;
-  int *sbe = w.be + ro;
-  auto ext = [&](int a, ME64 y) -> ME64 {
-    if (EXTRA) { y.m *= w.ewm[a]; y.e += w.ewe[a]; }
-    return y;
-  };
-  Arcs out_arcs;
-  if constexpr (STAGED) {
-    pos_stage_out(lat, m, b, rp_l, recs);  // (the pass begins with a barrier)
-    out_arcs = {rp_l, recs, m.arc_off};
-  } else {
-    out_arcs = {lat.row_ptr + m.row_off + b, lat.arc_dst, lat.arc_label, m.arc_off, m.arc_off + m.n_arcs};
-  }
-  for (int i = tid; i < n; i += kPosThreads) {
-    const ME64 v = i == m.sink ? PosSum::one() : PosSum::zero();
-    val.set((T & 1) * R + i, v);
-    vr[(T & 1) * R + i] = 0.0;
-    if (need_alpha) {
-      sbm[(size_t)T * n + i] = v.m;
-      sbe[(size_t)T * n + i] = v.e;
-      sbr[(size_t)T * n + i] = 0.0;
-    }
-  }
-  if (!by_step) pos_exp_fill_table(tab, tv, theta, nullptr, lv_b, nullptr, x.coef, V);
-  for (int t = T - 1; t >= 0; --t) {
-    if (by_step)
-      pos_exp_fill_table(tab, tv, theta, pos_b ? pos_b + (size_t)t * V : nullptr, lv_b, pv_b ? pv_b + (size_t)t * V : nullptr, x.coef, V);
-    __syncthreads();  // the table and the row of position t + 1 are complete
-    const int nxt = ((t + 1) & 1) * R, cur = (t & 1) * R;
-    for (int base = 0; base < n; base += slots) {
-      const int s = base + slot;
-      const bool act = s < n && s != m.sink;
-      const int a0 = act ? out_arcs.lo(s) : 0, a1 = act ? out_arcs.hi(s) : 0;
-      ME64 acc = PosSum::zero();
-      double N = 0.0;
-      for (int a = a0 + gl; a < a1; a += G) {
-        const uint32_t rec = out_arcs.rec(a);
-        const int d = (int)(rec & 0xffffu), l = (int)(rec >> 16);
-        if (d == s) continue;  // self loops are on no path
-        const ME64 y = ext(a, PosSum::times(tab.get(l), val.get(nxt + d)));
-        if (y.m != 0.0) pos_exp_plus(acc, N, y, vr[nxt + d] + tv[l] + (arc_val ? xw.av[a] : 0.0));
-      }
-      for (int og = 1; og < G; og <<= 1) pos_exp_combine(acc, N, og);
-      if (gl == 0 && s < n) {
-        const bool sink = s == m.sink;
-        const ME64 v = sink ? PosSum::one() : PosSum::norm(acc);
-        const double r = (!sink && acc.m != 0.0) ? N / acc.m : 0.0;
-        val.set(cur + s, v);
-        vr[cur + s] = r;
-        if (need_alpha) {
-          sbm[(size_t)t * n + s] = v.m;
-          sbe[(size_t)t * n + s] = v.e;
-          sbr[(size_t)t * n + s] = r;
-        }
-      }
-    }
-    __syncthreads();  // (the next step overwrites the table and the row of position t + 1)
-  }
-  const ME64 z = val.get(0);  // beta_0(0) is in row 0 of the pair (position 0)
-  const double ev = z.m > 0.0 ? vr[0] : 0.0;
-  const double logz = z.m > 0.0 ? log(z.m) + (double)z.e * 0.693147180559945309417232 : -__builtin_huge_val();
-  if (tid == 0) {
-    o.logz64[b] = logz;
-    if (o.logz32) o.logz32[b] = (float)logz;
-    o.ev64[b] = ev;
-    if (o.ev32) o.ev32[b] = (float)ev;
-  }
-  if (!need_alpha) return;
-  __syncthreads();  // (everyone has read beta_0(0) and R_0(0))
-
-  // ---- forwards in time -------------------------------------------------------------------------------------------
-  const double rz = z.m > 0.0 ? 1.0 / z.m : 0.0;
-  const bool want_p = o.pos_post != nullptr || o.arc_post != nullptr, want_c = o.pos_cov != nullptr || o.arc_cov != nullptr;
-  for (int i = tid; i < n; i += kPosThreads) {
-    val.set(i, i == 0 ? PosSum::one() : PosSum::zero());
-    vr[i] = 0.0;
-  }
-  for (int l = tid; l < V; l += kPosThreads) {
-    hist[l] = 0ull;
-    hcov[l] = 0.0;
-  }
-  const int2 *in_rec = w.in_rec + m.arc_off;
-  double *acc_e = w.acc + m.arc_off, *acc_c = xw.acc2 + m.arc_off;
-  if constexpr (STAGED) {  // the same LDS, now by destination: (src | label << 16) of every in-entry
-    const int n_in = in_ptr[n];
-    for (int d = tid; d <= n; d += kPosThreads) rp_l[d] = in_ptr[d];
-    for (int j = tid; j < n_in; j += kPosThreads) recs[j] = (uint32_t)in_rec[j].y;
-  }
-  for (int t = 0; t < T; ++t) {
-    if (by_step)
-      pos_exp_fill_table(tab, tv, theta, pos_b ? pos_b + (size_t)t * V : nullptr, lv_b, pv_b ? pv_b + (size_t)t * V : nullptr, x.coef, V);
-    __syncthreads();
-    const int cur = (t & 1) * R, nxt = ((t + 1) & 1) * R;
-    const double *brm = sbm + (size_t)(t + 1) * n, *brr = sbr + (size_t)(t + 1) * n;
-    const int *bre = sbe + (size_t)(t + 1) * n;
-    for (int base = 0; base < n; base += slots) {
-      const int d = base + slot;
-      const bool act = d < n;
-      const int j0 = act ? (STAGED ? rp_l[d] : in_ptr[d]) : 0, j1 = act ? (STAGED ? rp_l[d + 1] : in_ptr[d + 1]) : 0;
-      const double bmd = act ? brm[d] * rz : 0.0;
-      const int bed = act ? bre[d] - z.e : 0;
-      const double rest = act ? brr[d] - ev : 0.0;  // R_{t+1}(d) - E[V]
-      ME64 acc = PosSum::zero();
-      double N = 0.0;
-      for (int j = j0 + gl; j < j1; j += G) {
-        int2 rec;
-        if (STAGED) {
-          rec.y = (int)recs[j];
-          rec.x = (EXTRA || arc_val) ? in_rec[j].x : 0;
-        } else {
-          rec = in_rec[j];
-        }
-        const int l = rec.y >> 16, s = rec.y & 0xffff;
-        const ME64 y = ext(m.arc_off + rec.x, PosSum::times(tab.get(l), val.get(cur + s)));
-        if (y.m == 0.0) continue;  // (PosSum::plus adds nothing either; the value is not read)
-        const double sofar = vr[cur + s] + tv[l] + (arc_val ? xw.av[m.arc_off + rec.x] : 0.0);  // R^alpha_t(src) + v_t(a)
-        pos_exp_plus(acc, N, y, sofar);
-        const double pm = y.m * bmd;
-        if (pm != 0.0) {
-          const double p = __builtin_amdgcn_ldexp(pm, y.e + bed);
-          if (want_p) {
-            if (o.pos_post) atomicAdd(&hist[l], (unsigned long long)llrint(__builtin_amdgcn_ldexp(p, kPosPostBits)));
-            if (o.arc_post) acc_e[j] += p;  // (entry j belongs to this lane at every step)
-          }
-          if (want_c) {
-            const double c = p * (sofar + rest);
-            if (o.pos_cov) atomicAdd(&hcov[l], c);  // (float64 LDS atomics: the order of the adds is not fixed)
-            if (o.arc_cov) acc_c[j] += c;
-          }
-        }
-      }
-      for (int og = 1; og < G; og <<= 1) pos_exp_combine(acc, N, og);
-      if (gl == 0 && act) {
-        val.set(nxt + d, PosSum::norm(acc));
-        vr[nxt + d] = acc.m != 0.0 ? N / acc.m : 0.0;
-      }
-    }
-    __syncthreads();
-    if (o.pos_post || o.pos_cov) {
-      const size_t row = ((size_t)b * T + t) * V;
-      for (int l = tid; l < V; l += kPosThreads) {
-        if (o.pos_post) o.pos_post[row + l] = (float)__builtin_amdgcn_ldexp((double)hist[l], -kPosPostBits);
-        if (o.pos_cov) o.pos_cov[row + l] = (float)hcov[l];
-        hist[l] = 0ull;
-        hcov[l] = 0.0;
-      }
-    }
-  }
-  if (o.arc_post || o.arc_cov) {
-    for (int i = tid; i < m.n_arcs; i += kPosThreads)
-      if (lat.arc_src[m.arc_off + i] == lat.arc_dst[m.arc_off + i]) {
-        if (o.arc_post) o.arc_post[m.arc_off + i] = 0.0f;
-        if (o.arc_cov) o.arc_cov[m.arc_off + i] = 0.0f;
-      }
-    const int n_in = in_ptr[n];
-    for (int j = tid; j < n_in; j += kPosThreads) {
-      if (o.arc_post) o.arc_post[m.arc_off + in_rec[j].x] = (float)acc_e[j];
-      if (o.arc_cov) o.arc_cov[m.arc_off + in_rec[j].x] = (float)acc_c[j];
-    }
-  }
+  const PosOut po = {o.logz64, o.logz32, nullptr, o.pos_post, o.arc_post};
+  pos_sum_sweep<EXTRA, STAGED>(lat, in, w, po, need_alpha ? kPosModeAlpha : kPosModeLogz, L, rd);
 }

@@ -14,7 +14,10 @@
 //   k_positional_viterbi  the same backward pass in max-plus (plain float32), then one thread walks the best path
 //   k_positional_walk     exact draws: one wave per walk reads the beta rows that k_positional stored (kPosModeRows: the
 //                         backward pass alone, no forward pass); k_positional_score is the forced walk of given marks
-// The backward pass is ONE function template over the semiring (PosSum / PosMax), not a copy.
+// The backward pass is ONE function template over the semiring (PosSum / PosMax), not a copy, and the forward pass is
+// one function too (pos_alpha_pass).  An op that carries a second quantity beside the semiring's value -- the expectation
+// sweep of positional_expect_kernels.h -- does not copy the loops either: it hands them a rider (PosNoRider below lists
+// the hooks), and k_positional and k_positional_expect are both pos_sum_sweep, with the empty rider and with PosExpRider.
 //
 // Arithmetic of the sum-product kernel: (float64 mantissa, int32 exponent) THROUGHOUT, for every T -- label weights by
 // exp_split64, sums in float64.  float32 mantissas would repeat one rounding error per label at every position
@@ -84,6 +87,7 @@ struct PosSum {  // sum-product in (float64 mantissa, exponent)
   static __device__ __forceinline__ V label(float th) { return exp_split64((double)th); }
   static __device__ __forceinline__ V label(float th, float p) { return exp_split64((double)th + (double)p); }
   static __device__ __forceinline__ V times(V lab, V nxt) { return {lab.m * nxt.m, lab.e + nxt.e}; }
+  static __device__ __forceinline__ bool live(V x) { return x.m != 0.0; }  // (plus adds nothing otherwise)
   static __device__ __forceinline__ void plus(V &acc, V x) {
     if (x.m != 0.0) {
       if (x.e > acc.e) { acc.m = __builtin_amdgcn_ldexp(acc.m, acc.e - x.e); acc.e = x.e; }
@@ -120,6 +124,7 @@ struct PosMax {  // max-plus in plain float32: c = e_a + ((theta[l] + pos[b, t, 
   static __device__ __forceinline__ V label(float th) { return th; }
   static __device__ __forceinline__ V label(float th, float p) { return th + p; }
   static __device__ __forceinline__ V times(V lab, V nxt) { return lab + nxt; }
+  static __device__ __forceinline__ bool live(V) { return true; }
   static __device__ __forceinline__ void plus(V &acc, V x) { acc = x > acc ? x : acc; }
   static __device__ __forceinline__ void combine(V &acc, int o) {
     const float x = __shfl_xor(acc, o);
@@ -165,29 +170,89 @@ __device__ __forceinline__ void pos_stage_out(const nfst_batch &lat, const Meta 
     recs[i] = (uint32_t)lat.arc_dst[a_lo + i] | ((uint32_t)lat.arc_label[a_lo + i] << 16);
 }
 
+template <bool STAGED>
+using PosArcs = typename std::conditional<STAGED, PosArcsLds, PosArcsGlobal>::type;
+// the out-arcs of a lattice for the backward pass (STAGED: staged here, before the barrier the pass begins with)
+template <bool STAGED>
+__device__ __forceinline__ PosArcs<STAGED> pos_out_arcs(const nfst_batch &lat, const Meta &m, int b, int *rp_l, uint32_t *recs) {
+  if constexpr (STAGED) {
+    pos_stage_out(lat, m, b, rp_l, recs);
+    return {rp_l, recs, m.arc_off};
+  } else {
+    return {lat.row_ptr + m.row_off + b, lat.arc_dst, lat.arc_label, m.arc_off, m.arc_off + m.n_arcs};
+  }
+}
+
+// ---- riders -------------------------------------------------------------------------------------------------------
+// The step loops below exist once.  What an op carries through them BESIDE the value of the semiring -- the numerator of
+// the expectation sweep (PosExpRider, positional_expect_kernels.h) -- is a rider: a policy class whose hooks sit where
+// the second quantity needs a line.  The value itself goes through S::plus / combine / norm in the loop, never through a
+// hook, so a rider cannot change a bit of it.  PosNoRider has no state and only empty hooks: with it the loops compile
+// to the plain sum-product and max-plus sweeps.
+struct PosNoRider {
+  // what the loops do for the rider's sake: refill the label table at every position, read the arc of every in-entry,
+  // drain per label and step, drain per arc (either drain: the posterior terms are computed)
+  static constexpr bool by_step() { return false; }
+  static constexpr bool arc_val() { return false; }
+  static constexpr bool by_label() { return false; }
+  static constexpr bool by_arc() { return false; }
+  // once per launch and arc: the sum e of the arc's extras; live: its weight is not zero
+  __device__ __forceinline__ void arc(int, double, bool) {}
+  // the label table of position t is filled (by this thread for the labels of its stride)
+  template <class Rows>
+  __device__ __forceinline__ void fill(const Rows &, const float *, const float *, int, int) {}
+  // a state's sum begins; fwd: in the forward pass, for a state whose stored row is st_i
+  __device__ __forceinline__ void start(bool, size_t) {}
+  // `acc` took the term y from (row i of the other state, label l, arc a); `was` is acc before
+  template <class V>
+  __device__ __forceinline__ void term(const V &, const V &, const V &, int, int, int) {}
+  // `acc` took the partner's sum of butterfly stage o; `was` is acc before
+  template <class V>
+  __device__ __forceinline__ void combine(const V &, const V &, int) {}
+  // the value of LDS row i is acc (live) or a constant (not live); store: it also goes to the stored row st_i
+  template <class V>
+  __device__ __forceinline__ void row(int, const V &, bool, bool, size_t) {}
+  // beta_0(0) = z of lattice b is known
+  template <class V>
+  __device__ __forceinline__ void beta_done(int, const V &) {}
+  // the term just taken has posterior p; it is in-entry j with label l
+  __device__ __forceinline__ void post(double, int, int) {}
+  // after every step: label l goes to output element i; after the last: in-entry j (-1: a self loop) to arc a
+  __device__ __forceinline__ void drain_label(size_t, int) {}
+  __device__ __forceinline__ void drain_arc(int, int) {}
+};
+
 // the label table of position t: one entry per label, shared by every arc of the step
 template <class S>
 __device__ __forceinline__ void pos_fill_table(const typename S::Rows &tab, const float *theta, const float *pos_t, int V) {
   for (int l = threadIdx.x; l < V; l += kPosThreads) tab.set(l, pos_t ? S::label(theta[l], pos_t[l]) : S::label(theta[l]));
 }
+template <class S, class Rd>
+__device__ __forceinline__ void pos_step_table(const typename S::Rows &tab, const float *theta, const float *pos_b, int t, int V, Rd &rd) {
+  const float *pos_t = pos_b ? pos_b + (size_t)t * V : nullptr;
+  pos_fill_table<S>(tab, theta, pos_t, V);
+  rd.fill(tab, theta, pos_t, t, V);
+}
 
 // The backward pass, positions T .. 0: val holds two rows of R values (the row of position t is at (t & 1) * R).
 // ext(a) multiplies (adds, in max-plus) the per-arc extras in.  Row t of the lattice goes to `st` when it is on.
-template <class S, class Arcs, class ExtF>
+template <class S, class Arcs, class ExtF, class Rd>
 __device__ __forceinline__ void pos_beta_pass(const nfst_batch &lat, const Meta &m, const Arcs &arcs, const float *theta,
                                               const float *pos_b, int T, int R, int G, const typename S::Rows &val,
-                                              const typename S::Rows &tab, const typename S::Store &st, ExtF ext) {
+                                              const typename S::Rows &tab, const typename S::Store &st, ExtF ext, Rd &rd) {
   typedef typename S::V Val;
   const int tid = threadIdx.x, n = m.n_rows, V = lat.vocab;
   const int slots = kPosThreads / G, slot = tid / G, gl = tid % G;
+  const bool by_step = pos_b != nullptr || rd.by_step();  // the table changes from position to position
   for (int i = tid; i < n; i += kPosThreads) {
     const Val v = i == m.sink ? S::one() : S::zero();
     val.set((T & 1) * R + i, v);
     if (st.on()) st.set((size_t)T * n + i, v);
+    rd.row((T & 1) * R + i, v, false, st.on(), (size_t)T * n + i);
   }
-  if (!pos_b) pos_fill_table<S>(tab, theta, nullptr, V);
+  if (!by_step) pos_step_table<S>(tab, theta, pos_b, 0, V, rd);
   for (int t = T - 1; t >= 0; --t) {
-    if (pos_b) pos_fill_table<S>(tab, theta, pos_b + (size_t)t * V, V);
+    if (by_step) pos_step_table<S>(tab, theta, pos_b, t, V, rd);
     __syncthreads();  // the table and the row of position t + 1 are complete
     const int nxt = ((t + 1) & 1) * R, cur = (t & 1) * R;
     for (int base = 0; base < n; base += slots) {
@@ -195,17 +260,27 @@ __device__ __forceinline__ void pos_beta_pass(const nfst_batch &lat, const Meta 
       const bool act = s < n && s != m.sink;
       const int a0 = act ? arcs.lo(s) : 0, a1 = act ? arcs.hi(s) : 0;
       Val acc = S::zero();
+      rd.start(false, 0);
       for (int a = a0 + gl; a < a1; a += G) {
         const uint32_t rec = arcs.rec(a);
-        const int d = (int)(rec & 0xffffu);
+        const int d = (int)(rec & 0xffffu), l = (int)(rec >> 16);
         if (d == s) continue;  // self loops are on no path
-        S::plus(acc, ext(a, S::times(tab.get((int)(rec >> 16)), val.get(nxt + d))));
+        const Val y = ext(a, S::times(tab.get(l), val.get(nxt + d))), was = acc;
+        if (!S::live(y)) continue;  // (no hook sees a term of no mass: what lies behind it is never read)
+        S::plus(acc, y);
+        rd.term(was, acc, y, nxt + d, l, a);
       }
-      for (int o = 1; o < G; o <<= 1) S::combine(acc, o);
+      for (int o = 1; o < G; o <<= 1) {
+        const Val was = acc;
+        S::combine(acc, o);
+        rd.combine(was, acc, o);
+      }
       if (gl == 0 && s < n) {
-        const Val v = s == m.sink ? S::one() : S::norm(acc);
+        const bool sink = s == m.sink;
+        const Val v = sink ? S::one() : S::norm(acc);
         val.set(cur + s, v);
         if (st.on()) st.set((size_t)t * n + s, v);
+        rd.row(cur + s, acc, !sink, st.on(), (size_t)t * n + s);
       }
     }
     __syncthreads();  // (the next step overwrites the table and the row of position t + 1)
@@ -265,81 +340,54 @@ __device__ __forceinline__ void pos_in_order(const nfst_batch &lat, const Meta &
   __syncthreads();
 }
 
-// LDS: two rows of (float64, int32) values, the label table (float64, int32), the label histogram (64-bit) and one
-// int per thread for the prefix sums: 24 max_rows + 20 vocab + 4 kPosThreads bytes.
-// STAGED: + 4 (max_rows + 1) + 4 (arcs of the largest lattice) bytes for the arc records.
-template <bool EXTRA, bool STAGED>
-__global__ __launch_bounds__(kPosThreads) void k_positional(nfst_batch lat, PosIn in, PosWs w, PosOut o, int mode) {
-  extern __shared__ double pos_lds[];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const bool need_alpha = mode == kPosModeAlpha, store = mode != kPosModeLogz;
-  const Meta m = load_meta(lat.meta, b);
-  const int R = lat.max_rows, V = lat.vocab, T = in.T, n = m.n_rows;
-  double *vm = pos_lds, *tm = vm + 2 * R;
-  unsigned long long *hist = (unsigned long long *)(tm + V);
-  int *ve = (int *)(hist + V), *te = ve + 2 * R, *scan = te + V;
-  int *rp_l = scan + kPosThreads;
-  uint32_t *recs = (uint32_t *)(rp_l + R + 1);
-  typedef typename std::conditional<STAGED, PosArcsLds, PosArcsGlobal>::type Arcs;
-  const PosSum::Rows val = {vm, ve}, tab = {tm, te};
-  const float *theta = in.sc.theta + (size_t)in.sc.theta_stride * b;
-  const float *pos_b = in.pos ? in.pos + (size_t)in.pos_stride * b : nullptr;
-  const int G = pos_group(m);
-  const int slots = kPosThreads / G, slot = tid / G, gl = tid % G;
-
-  // ---- once per launch: the weights of the extras, and the arcs by (destination, canonical arc) -------------------
-  if (EXTRA) {
-    for (int a = m.arc_off + tid; a < m.arc_off + m.n_arcs; a += kPosThreads) {
-      double e = 0.0;
+// once per launch: the weight of every arc's extras (arc_w + arc_scores) into the workspace
+template <bool EXTRA, class Rd>
+__device__ __forceinline__ void pos_arc_extras(const nfst_batch &lat, const Meta &m, const nfst_scores &sc, const PosWs &w, Rd &rd) {
+  if (!EXTRA && !rd.arc_val()) return;
+  for (int a = m.arc_off + threadIdx.x; a < m.arc_off + m.n_arcs; a += kPosThreads) {
+    double e = 0.0;
+    bool live = false;
+    if (EXTRA) {
       if (lat.weighted) e += (double)lat.arc_w[a];
-      if (in.sc.arc_scores) e += (double)in.sc.arc_scores[a];
+      if (sc.arc_scores) e += (double)sc.arc_scores[a];
       const ME64 x = exp_split64(e);
       w.ewm[a] = x.m;
       w.ewe[a] = x.e;
+      live = x.m != 0.0;
     }
+    rd.arc(a, e, live);
   }
-  int *in_ptr = w.in_ptr + m.row_off + b;
-  if (need_alpha) pos_in_order(lat, m, (int *)vm, scan, in_ptr, w);  // (the value rows are not in use yet: 8 n + 4 <= 16 max_rows bytes)
+}
 
-  // ---- backwards in time ----------------------------------------------------------------------------------------
-  const size_t ro = (size_t)(T + 1) * m.row_off;
-  const PosSum::Store st = {store ? w.bm + ro : nullptr, store ? w.be + ro : nullptr};
-  auto ext = [&](int a, ME64 x) -> ME64 {
-    if (EXTRA) { x.m *= w.ewm[a]; x.e += w.ewe[a]; }
-    return x;
-  };
-  Arcs out_arcs;
-  if constexpr (STAGED) {
-    pos_stage_out(lat, m, b, rp_l, recs);  // (the pass begins with a barrier)
-    out_arcs = {rp_l, recs, m.arc_off};
-  } else {
-    out_arcs = {lat.row_ptr + m.row_off + b, lat.arc_dst, lat.arc_label, m.arc_off, m.arc_off + m.n_arcs};
-  }
-  pos_beta_pass<PosSum>(lat, m, out_arcs, theta, pos_b, T, R, G, val, tab, st, ext);
-  const ME64 z = val.get(0);  // beta_0(0) is in row 0 of the pair (position 0)
-  const double logz = z.m > 0.0 ? log(z.m) + (double)z.e * 0.693147180559945309417232 : -__builtin_huge_val();
-  if (tid == 0) {
-    o.logz64[b] = logz;
-    if (o.logz32) o.logz32[b] = (float)logz;
-    if (o.len_logz) o.len_logz[(size_t)b * (T + 1)] = -__builtin_huge_val();
-  }
-  if (!need_alpha) return;
-  __syncthreads();  // (everyone has read beta_0(0))
-
-  // ---- forwards in time -------------------------------------------------------------------------------------------
+// The forward pass, positions 0 .. T, over the in-entries of pos_in_order and the beta rows `st` that the backward pass
+// stored: alpha_t in `val`, the posterior of every term  p = alpha_t(src) w beta_{t+1}(dst) / z  into the label
+// histogram (fixed point) and the lane-owned per-entry sums, the mass of every path length from the sink's row.
+// STAGED: the LDS of the out-arc records now holds (src | label << 16) of every in-entry.
+template <bool EXTRA, bool STAGED, class ExtF, class Rd>
+__device__ __forceinline__ void pos_alpha_pass(const nfst_batch &lat, const Meta &m, int b, const float *theta, const float *pos_b, int T,
+                                               int R, int G, const PosSum::Rows &val, const PosSum::Rows &tab, const PosSum::Store &st,
+                                               ExtF ext, ME64 z, const PosWs &w, const int *in_ptr, int *rp_l, uint32_t *recs,
+                                               unsigned long long *hist, const PosOut &o, Rd &rd) {
+  const int tid = threadIdx.x, n = m.n_rows, V = lat.vocab;
+  const int slots = kPosThreads / G, slot = tid / G, gl = tid % G;
   const double rz = z.m > 0.0 ? 1.0 / z.m : 0.0;
-  const bool want_p = o.pos_post != nullptr || o.arc_post != nullptr;
-  for (int i = tid; i < n; i += kPosThreads) val.set(i, i == 0 ? PosSum::one() : PosSum::zero());
+  const bool by_step = pos_b != nullptr || rd.by_step();
+  const bool want_p = o.pos_post != nullptr || o.arc_post != nullptr || rd.by_label() || rd.by_arc();
+  for (int i = tid; i < n; i += kPosThreads) {
+    const ME64 v = i == 0 ? PosSum::one() : PosSum::zero();
+    val.set(i, v);
+    rd.row(i, v, false, false, 0);
+  }
   for (int l = tid; l < V; l += kPosThreads) hist[l] = 0ull;
   const int2 *in_rec = w.in_rec + m.arc_off;
   double *acc_e = w.acc + m.arc_off;
-  if constexpr (STAGED) {  // the same LDS, now by destination: (src | label << 16) of every in-entry
+  if constexpr (STAGED) {
     const int n_in = in_ptr[n];
     for (int d = tid; d <= n; d += kPosThreads) rp_l[d] = in_ptr[d];
     for (int j = tid; j < n_in; j += kPosThreads) recs[j] = (uint32_t)in_rec[j].y;
   }
   for (int t = 0; t < T; ++t) {
-    if (pos_b) pos_fill_table<PosSum>(tab, theta, pos_b + (size_t)t * V, V);
+    if (by_step) pos_step_table<PosSum>(tab, theta, pos_b, t, V, rd);
     __syncthreads();
     const int cur = (t & 1) * R, nxt = ((t + 1) & 1) * R;
     const double *brm = st.m + (size_t)(t + 1) * n;
@@ -351,48 +399,128 @@ __global__ __launch_bounds__(kPosThreads) void k_positional(nfst_batch lat, PosI
       const double bmd = act ? brm[d] * rz : 0.0;
       const int bed = act ? bre[d] - z.e : 0;
       ME64 acc = PosSum::zero();
+      rd.start(act, (size_t)(t + 1) * n + d);
       for (int j = j0 + gl; j < j1; j += G) {
         int2 rec;
         if (STAGED) {
           rec.y = (int)recs[j];
-          rec.x = EXTRA ? in_rec[j].x : 0;
+          rec.x = (EXTRA || rd.arc_val()) ? in_rec[j].x : 0;
         } else {
           rec = in_rec[j];
         }
-        const ME64 x = ext(m.arc_off + rec.x, PosSum::times(tab.get(rec.y >> 16), val.get(cur + (rec.y & 0xffff))));
+        const int l = rec.y >> 16, s = rec.y & 0xffff;
+        const ME64 x = ext(m.arc_off + rec.x, PosSum::times(tab.get(l), val.get(cur + s))), was = acc;
+        if (!PosSum::live(x)) continue;
         PosSum::plus(acc, x);
+        rd.term(was, acc, x, cur + s, l, m.arc_off + rec.x);
         if (want_p) {
           const double pm = x.m * bmd;
           if (pm != 0.0) {
             const double p = __builtin_amdgcn_ldexp(pm, x.e + bed);
-            if (o.pos_post) atomicAdd(&hist[rec.y >> 16], (unsigned long long)llrint(__builtin_amdgcn_ldexp(p, kPosPostBits)));
+            if (o.pos_post) atomicAdd(&hist[l], (unsigned long long)llrint(__builtin_amdgcn_ldexp(p, kPosPostBits)));
             if (o.arc_post) acc_e[j] += p;  // (entry j belongs to this lane at every step)
+            rd.post(p, j, l);
           }
         }
       }
-      for (int og = 1; og < G; og <<= 1) PosSum::combine(acc, og);
+      for (int og = 1; og < G; og <<= 1) {
+        const ME64 was = acc;
+        PosSum::combine(acc, og);
+        rd.combine(was, acc, og);
+      }
       if (gl == 0 && act) {
         const ME64 v = PosSum::norm(acc);
         val.set(nxt + d, v);
+        rd.row(nxt + d, acc, true, false, 0);
         if (d == m.sink && o.len_logz)  // the paths of exactly t + 1 arcs
           o.len_logz[(size_t)b * (T + 1) + t + 1] = v.m > 0.0 ? log(v.m) + (double)v.e * 0.693147180559945309417232 : -__builtin_huge_val();
       }
     }
     __syncthreads();
-    if (o.pos_post) {
-      float *out = o.pos_post + ((size_t)b * T + t) * V;
+    if (o.pos_post || rd.by_label()) {
+      const size_t row = ((size_t)b * T + t) * V;
       for (int l = tid; l < V; l += kPosThreads) {
-        out[l] = (float)__builtin_amdgcn_ldexp((double)hist[l], -kPosPostBits);
+        if (o.pos_post) o.pos_post[row + l] = (float)__builtin_amdgcn_ldexp((double)hist[l], -kPosPostBits);
         hist[l] = 0ull;
+        rd.drain_label(row + l, l);
       }
     }
   }
-  if (o.arc_post) {
+  if (o.arc_post || rd.by_arc()) {  // self loops are on no path; every other arc is one in-entry
     for (int i = tid; i < m.n_arcs; i += kPosThreads)
-      if (lat.arc_src[m.arc_off + i] == lat.arc_dst[m.arc_off + i]) o.arc_post[m.arc_off + i] = 0.0f;
+      if (lat.arc_src[m.arc_off + i] == lat.arc_dst[m.arc_off + i]) {
+        if (o.arc_post) o.arc_post[m.arc_off + i] = 0.0f;
+        rd.drain_arc(m.arc_off + i, -1);
+      }
     const int n_in = in_ptr[n];
-    for (int j = tid; j < n_in; j += kPosThreads) o.arc_post[m.arc_off + in_rec[j].x] = (float)acc_e[j];
+    for (int j = tid; j < n_in; j += kPosThreads) {
+      if (o.arc_post) o.arc_post[m.arc_off + in_rec[j].x] = (float)acc_e[j];
+      rd.drain_arc(m.arc_off + in_rec[j].x, j);
+    }
   }
+}
+
+// The LDS of the sum-product sweep: two rows of (float64, int32) values, the label table (float64, int32), the label
+// histogram (64-bit) and one int per thread for the prefix sums; a rider gets X doubles beside every row value, table
+// entry and histogram bin (xr, xt, xh): (24 + 16 X) max_rows + (20 + 16 X) vocab + 4 kPosThreads bytes.
+// STAGED: + 4 (max_rows + 1) + 4 (arcs of the largest lattice) bytes for the arc records.
+struct PosLds {
+  double *vm, *xr, *tm, *xt;
+  unsigned long long *hist;
+  double *xh;
+  int *ve, *te, *scan, *rp_l;
+  uint32_t *recs;
+};
+__device__ __forceinline__ PosLds pos_lds_layout(double *base, int R, int V, int X) {
+  PosLds L;
+  L.vm = base, L.xr = L.vm + 2 * R, L.tm = L.vm + (1 + X) * 2 * R, L.xt = L.tm + V;
+  L.hist = (unsigned long long *)(L.tm + (1 + X) * V), L.xh = (double *)(L.hist + V);
+  L.ve = (int *)(L.hist + (1 + X) * V), L.te = L.ve + 2 * R, L.scan = L.te + V, L.rp_l = L.scan + kPosThreads;
+  L.recs = (uint32_t *)(L.rp_l + R + 1);
+  return L;
+}
+
+// One launch of the sum-product sweep for lattice blockIdx.x: the once-per-launch work, the backward pass, log Z, and in
+// kPosModeAlpha the forward pass.  k_positional and k_positional_expect are this function with their rider.
+template <bool EXTRA, bool STAGED, class Rd>
+__device__ __forceinline__ void pos_sum_sweep(const nfst_batch &lat, const PosIn &in, const PosWs &w, const PosOut &o, int mode,
+                                              const PosLds &L, Rd &rd) {
+  const int b = blockIdx.x;
+  const bool need_alpha = mode == kPosModeAlpha, store = mode != kPosModeLogz;
+  const Meta m = load_meta(lat.meta, b);
+  const int R = lat.max_rows, T = in.T;
+  const PosSum::Rows val = {L.vm, L.ve}, tab = {L.tm, L.te};
+  const float *theta = in.sc.theta + (size_t)in.sc.theta_stride * b;
+  const float *pos_b = in.pos ? in.pos + (size_t)in.pos_stride * b : nullptr;
+  const int G = pos_group(m);
+  pos_arc_extras<EXTRA>(lat, m, in.sc, w, rd);
+  int *in_ptr = w.in_ptr + m.row_off + b;
+  if (need_alpha) pos_in_order(lat, m, (int *)L.vm, L.scan, in_ptr, w);  // (the value rows are not in use yet: 8 n + 4 <= 16 max_rows bytes)
+  const size_t ro = (size_t)(T + 1) * m.row_off;
+  const PosSum::Store st = {store ? w.bm + ro : nullptr, store ? w.be + ro : nullptr};
+  auto ext = [&](int a, ME64 x) -> ME64 {
+    if (EXTRA) { x.m *= w.ewm[a]; x.e += w.ewe[a]; }
+    return x;
+  };
+  pos_beta_pass<PosSum>(lat, m, pos_out_arcs<STAGED>(lat, m, b, L.rp_l, L.recs), theta, pos_b, T, R, G, val, tab, st, ext, rd);
+  const ME64 z = val.get(0);  // beta_0(0) is in row 0 of the pair (position 0)
+  const double logz = z.m > 0.0 ? log(z.m) + (double)z.e * 0.693147180559945309417232 : -__builtin_huge_val();
+  if (threadIdx.x == 0) {
+    o.logz64[b] = logz;
+    if (o.logz32) o.logz32[b] = (float)logz;
+    if (o.len_logz) o.len_logz[(size_t)b * (T + 1)] = -__builtin_huge_val();
+  }
+  rd.beta_done(b, z);
+  if (!need_alpha) return;
+  __syncthreads();  // (everyone has read beta_0(0))
+  pos_alpha_pass<EXTRA, STAGED>(lat, m, b, theta, pos_b, T, R, G, val, tab, st, ext, z, w, in_ptr, L.rp_l, L.recs, L.hist, o, rd);
+}
+
+template <bool EXTRA, bool STAGED>
+__global__ __launch_bounds__(kPosThreads) void k_positional(nfst_batch lat, PosIn in, PosWs w, PosOut o, int mode) {
+  extern __shared__ double pos_lds[];
+  PosNoRider rd;
+  pos_sum_sweep<EXTRA, STAGED>(lat, in, w, o, mode, pos_lds_layout(pos_lds, lat.max_rows, lat.vocab, 0), rd);
 }
 
 // Max-plus: the same backward pass, every row stored; then thread 0 reads the path forwards from state 0: at position
@@ -407,14 +535,6 @@ __global__ __launch_bounds__(kPosThreads) void k_positional_viterbi(nfst_batch l
   float *vv = (float *)pos_lds, *tf = vv + 2 * R;
   int *len_s = (int *)(tf + V), *rp_l = len_s + 4;
   uint32_t *recs = (uint32_t *)(rp_l + R + 1);
-  typedef typename std::conditional<STAGED, PosArcsLds, PosArcsGlobal>::type Arcs;
-  Arcs out_arcs;
-  if constexpr (STAGED) {
-    pos_stage_out(lat, m, b, rp_l, recs);
-    out_arcs = {rp_l, recs, m.arc_off};
-  } else {
-    out_arcs = {lat.row_ptr + m.row_off + b, lat.arc_dst, lat.arc_label, m.arc_off, m.arc_off + m.n_arcs};
-  }
   const PosMax::Rows val = {vv}, tab = {tf};
   const float *theta = in.sc.theta + (size_t)in.sc.theta_stride * b;
   const float *pos_b = in.pos ? in.pos + (size_t)in.pos_stride * b : nullptr;
@@ -422,7 +542,8 @@ __global__ __launch_bounds__(kPosThreads) void k_positional_viterbi(nfst_batch l
   float *rows = w.vb + (size_t)(T + 1) * m.row_off;
   const PosMax::Store st = {rows};
   auto ext = [&](int a, float x) -> float { return ex.at(a) + x; };
-  pos_beta_pass<PosMax>(lat, m, out_arcs, theta, pos_b, T, R, pos_group(m), val, tab, st, ext);
+  PosNoRider rd;
+  pos_beta_pass<PosMax>(lat, m, pos_out_arcs<STAGED>(lat, m, b, rp_l, recs), theta, pos_b, T, R, pos_group(m), val, tab, st, ext, rd);
   int32_t *po = o.paths + (size_t)b * T;
   int32_t *ao = o.path_arcs ? o.path_arcs + (size_t)b * T : nullptr;
   if (tid == 0) {

@@ -628,35 +628,50 @@ class PositionalViterbiResult(NamedTuple):
     lengths: torch.Tensor  # [B] int32 (0 where best is -inf)
 
 
+def _position_tensor(lat: LatticeBatch, t, name: str, T: Optional[int]):
+    """(``t`` as contiguous float32, its stride) of a per-position tensor, checked: a floating-point tensor [T, V] (one
+    table for the batch) or [B, T, V] on the batch's device, with the ``T`` of the call (None: any T >= 1)."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{name} must be a torch.Tensor, not {type(t).__name__}")
+    if t.device != lat.device:
+        raise ValueError(f"{name} is on {t.device}, the lattice batch on {lat.device}")
+    if not t.is_floating_point():
+        raise ValueError(f"{name} must be a floating-point tensor, not {t.dtype}")
+    if t.dim() not in (2, 3) or t.shape[-1] != lat.vocab or (t.shape[-2] < 1 if T is None else t.shape[-2] != T) \
+            or (t.dim() == 3 and t.shape[0] != lat.n_lattices):
+        Ts, more = ("T", " with T >= 1") if T is None else (T, "")
+        raise ValueError(f"{name} must be [{Ts}, {lat.vocab}] or [{lat.n_lattices}, {Ts}, {lat.vocab}]{more}, not {list(t.shape)}")
+    return t.to(torch.float32).contiguous(), (0 if t.dim() == 2 else int(t.shape[-2]) * lat.vocab)
+
+
 def _positions(lat: LatticeBatch, pos_scores, T):
-    """(pos_scores as contiguous float32 or None, its stride, T) of the positional ops, checked: ``pos_scores`` is
-    [T, V] (one table for the batch) or [B, T, V] on the batch's device; ``T`` defaults to its length, and without
-    ``pos_scores`` to the longest path of the batch."""
+    """(pos_scores as contiguous float32 or None, its stride, T) of the positional ops, checked by ``_position_tensor``;
+    ``T`` defaults to the length of ``pos_scores``, and without ``pos_scores`` to the longest path of the batch."""
     if T is not None and (isinstance(T, bool) or not isinstance(T, int) or T < 1):
         raise ValueError(f"T must be an int >= 1, not {T!r}")
     if pos_scores is None:
         return None, 0, int(lat.depth.max()) if T is None else T
-    if not isinstance(pos_scores, torch.Tensor):
-        raise ValueError(f"pos_scores must be a torch.Tensor, not {type(pos_scores).__name__}")
-    if pos_scores.device != lat.device:
-        raise ValueError(f"pos_scores is on {pos_scores.device}, the lattice batch on {lat.device}")
-    if not pos_scores.is_floating_point():
-        raise ValueError(f"pos_scores must be a floating-point tensor, not {pos_scores.dtype}")
-    if pos_scores.dim() not in (2, 3) or pos_scores.shape[-1] != lat.vocab or pos_scores.shape[-2] < 1 \
-            or (pos_scores.dim() == 3 and pos_scores.shape[0] != lat.n_lattices):
-        raise ValueError(f"pos_scores must be [T, {lat.vocab}] or [{lat.n_lattices}, T, {lat.vocab}] with T >= 1, "
-                         f"not {list(pos_scores.shape)}")
-    if T is None:
-        T = int(pos_scores.shape[-2])
-    elif T != pos_scores.shape[-2]:
+    pos, stride = _position_tensor(lat, pos_scores, "pos_scores", None)
+    if T is not None and T != pos_scores.shape[-2]:
         raise ValueError(f"T = {T}, but pos_scores has {pos_scores.shape[-2]} positions")
-    return pos_scores.to(torch.float32).contiguous(), (0 if pos_scores.dim() == 2 else T * lat.vocab), T
+    return pos, stride, int(pos_scores.shape[-2])
+
+
+def _workspace(lat: LatticeBatch, query: str, *args) -> tuple:
+    """(workspace on the batch's device, its size) as the library's ``query(lat, *args)`` sizes it"""
+    ws_bytes = int(getattr(lib, query)(C.byref(lat.c_struct()), *args))
+    check(min(ws_bytes, 0), query)
+    return torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=lat.device), ws_bytes
 
 
 def _positional_ws(lat: LatticeBatch, T: int, flags: int) -> tuple:
-    ws_bytes = int(lib.nfst_positional_ws_bytes(C.byref(lat.c_struct()), T, flags))
-    check(min(ws_bytes, 0), "nfst_positional_ws_bytes")
-    return torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=lat.device), ws_bytes
+    return _workspace(lat, "nfst_positional_ws_bytes", T, flags)
+
+
+def _positional_plan(lat: LatticeBatch, name: str, *args) -> tuple:
+    lds, staged = C.c_int64(0), C.c_int32(0)
+    check(getattr(lib, name)(C.byref(lat.c_struct()), *args, C.byref(lds), C.byref(staged)), name)
+    return int(lds.value), bool(staged.value)
 
 
 def positional_plan(lat: LatticeBatch, viterbi: bool = False) -> tuple:
@@ -665,10 +680,7 @@ def positional_plan(lat: LatticeBatch, viterbi: bool = False) -> tuple:
     dynamic LDS of the kernel, and whether it keeps the arc records of the largest lattice there instead of reading the
     canonical arrays at every step.  Asked on the host: the batch may be host-packed, and no GPU is needed.  A batch
     beyond the op's LDS limit raises ``NfstError`` (-6), as the op would."""
-    lds, staged = C.c_int64(0), C.c_int32(0)
-    check(lib.nfst_positional_plan(C.byref(lat.c_struct()), 1 if viterbi else 0, C.byref(lds), C.byref(staged)),
-          "nfst_positional_plan")
-    return int(lds.value), bool(staged.value)
+    return _positional_plan(lat, "nfst_positional_plan", 1 if viterbi else 0)
 
 
 def positional_forward_backward(lat: LatticeBatch, theta, pos_scores=None, T: Optional[int] = None, arc_scores=None,
@@ -774,29 +786,15 @@ class PositionalExpectationResult(NamedTuple):
 
 
 def _position_values(lat: LatticeBatch, t, T: int, name: str):
-    """(``t`` as contiguous float32 or None, its stride) of a per-position value tensor, checked as ``_positions`` checks
-    ``pos_scores``: [T, V] or [B, T, V] on the batch's device, with the ``T`` of the call."""
-    if t is None:
-        return None, 0
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{name} must be a torch.Tensor, not {type(t).__name__}")
-    if t.device != lat.device:
-        raise ValueError(f"{name} is on {t.device}, the lattice batch on {lat.device}")
-    if not t.is_floating_point():
-        raise ValueError(f"{name} must be a floating-point tensor, not {t.dtype}")
-    if t.dim() not in (2, 3) or t.shape[-1] != lat.vocab or t.shape[-2] != T or (t.dim() == 3 and t.shape[0] != lat.n_lattices):
-        raise ValueError(f"{name} must be [{T}, {lat.vocab}] or [{lat.n_lattices}, {T}, {lat.vocab}], not {list(t.shape)}")
-    return t.to(torch.float32).contiguous(), (0 if t.dim() == 2 else T * lat.vocab)
+    """(``t`` as contiguous float32 or None, its stride) of a per-position value tensor with the ``T`` of the call."""
+    return (None, 0) if t is None else _position_tensor(lat, t, name, T)
 
 
 def positional_expectation_plan(lat: LatticeBatch) -> tuple:
     """(``lds_bytes``, ``staged``) of the launch ``positional_expectation_terms`` makes for this batch
     (``nfst_positional_expectation_plan``, the rule the launcher itself calls), as ``positional_plan``: asked on the host,
     no GPU needed; a batch beyond the op's LDS limit raises ``NfstError`` (-6), as the op would."""
-    lds, staged = C.c_int64(0), C.c_int32(0)
-    check(lib.nfst_positional_expectation_plan(C.byref(lat.c_struct()), C.byref(lds), C.byref(staged)),
-          "nfst_positional_expectation_plan")
-    return int(lds.value), bool(staged.value)
+    return _positional_plan(lat, "nfst_positional_expectation_plan")
 
 
 def positional_expectation_terms(lat: LatticeBatch, theta, pos_scores=None, T: Optional[int] = None, arc_scores=None,
@@ -824,9 +822,7 @@ def positional_expectation_terms(lat: LatticeBatch, theta, pos_scores=None, T: O
     sc, keep = _scores(lat, theta, arc_scores)
     dev = lat.device
     B, A, V = lat.n_lattices, lat.total_arcs, lat.vocab
-    ws_bytes = int(lib.nfst_positional_expectation_ws_bytes(C.byref(lat.c_struct()), T))
-    check(min(ws_bytes, 0), "nfst_positional_expectation_ws_bytes")
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace(lat, "nfst_positional_expectation_ws_bytes", T)
     f32 = dict(dtype=torch.float32, device=dev)
     z64 = torch.empty(B, dtype=torch.float64, device=dev)
     ev64 = torch.empty(B, dtype=torch.float64, device=dev)
@@ -1064,9 +1060,7 @@ def positional_k_best_terms(lat: LatticeBatch, theta, k: int, pos_scores=None, T
         pos = pos.detach()
     dev = lat.device
     B = lat.n_lattices
-    ws_bytes = int(lib.nfst_positional_kbest_ws_bytes(C.byref(lat.c_struct()), T, k))
-    check(min(ws_bytes, 0), "nfst_positional_kbest_ws_bytes")
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace(lat, "nfst_positional_kbest_ws_bytes", T, k)
     best = torch.empty((B, k), dtype=torch.float32, device=dev)
     paths = torch.empty((B, k, T), dtype=torch.int32, device=dev)
     arcs = torch.empty((B, k, T), dtype=torch.int32, device=dev)

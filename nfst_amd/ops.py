@@ -29,6 +29,69 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
+def _det(t):
+    """``t`` outside the autograd graph (None stays None; a tensor that is in none comes back as it is)."""
+    return t if t is None or not t.requires_grad else t.detach()
+
+
+# ----------------------------------------------------------------------------- marshalling (DESIGN.md section 4.14)
+def _call(name: str, lat: Optional[LatticeBatch], *args) -> None:
+    """``check(lib.<name>([batch,] *args, stream), name)`` on torch's current stream: a tensor goes as its
+    ``data_ptr()``, None as a null pointer, a ctypes struct by reference (the declared argument types see to the last
+    two), everything else as it is.  ``lat`` is None for the entry points that take no batch.  A wrapper is 10 to 30 us
+    of host work and this helper adds about 0.3 us to it (``hasattr`` is the cheapest test that takes a Parameter too):
+    ``viterbi``, ``k_best_terms`` and ``expectation_terms``, which showed it in the measurement, write their call out."""
+    argv = [a.data_ptr() if hasattr(a, "data_ptr") else a for a in args]
+    if lat is not None:
+        argv.insert(0, C.byref(lat.c_struct()))
+    rc = getattr(lib, name)(*argv, _stream())
+    if rc:
+        check(rc, name)
+
+
+def _workspace(lat: LatticeBatch, query: str, *args) -> tuple:
+    """(workspace on the batch's device, its size) as the library's ``query(lat, *args)`` sizes it"""
+    ws_bytes = int(getattr(lib, query)(C.byref(lat.c_struct()), *args))
+    if ws_bytes < 0:
+        check(ws_bytes, query)
+    return torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=lat.device), ws_bytes
+
+
+MAX_K = 64  # (nfst_kbest: a back pointer keeps the rank in 6 bits)
+
+
+def _check_k(k, bounded: bool = True) -> None:
+    """``k`` paths or draws per lattice: an int >= 1 (a bool is not a count), for the k-best ops at most ``MAX_K``."""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1 or (bounded and k > MAX_K):
+        raise ValueError(f"k must be an int in [1, {MAX_K}], not {k!r}" if bounded else f"k must be an int >= 1, not {k!r}")
+
+
+def _max_len(lat: LatticeBatch, max_len: Optional[int]) -> int:
+    """The length of a path list: the longest path of the batch + 1 (room for the pad) unless the caller gave one."""
+    return int(lat.depth.max()) + 1 if max_len is None else max_len
+
+
+def _path_outputs(lat: LatticeBatch, lead: tuple, L: int, best=False, arcs=True, n_paths=False, logq=False) -> tuple:
+    """``(best, paths, arcs, lengths, n_paths, logq)`` of a path op, uninitialised on the batch's device: ``paths`` and
+    ``arcs`` int32 ``[*lead, L]``, ``lengths`` int32 and ``best`` / ``logq`` float32 ``[*lead]`` with ``lead`` = (B,) or
+    (B, k), ``n_paths`` int32 [B]; None for whatever is not wanted."""
+    dev, i32, f32 = lat.device, torch.int32, torch.float32
+    return (torch.empty(lead, dtype=f32, device=dev) if best else None,
+            torch.empty((*lead, L), dtype=i32, device=dev),
+            torch.empty((*lead, L), dtype=i32, device=dev) if arcs else None,
+            torch.empty(lead, dtype=i32, device=dev),
+            torch.empty(lead[0], dtype=i32, device=dev) if n_paths else None,
+            torch.empty(lead, dtype=f32, device=dev) if logq else None)
+
+
+def _raise_status(status: torch.Tensor, where: str) -> None:
+    """Reads back the status word (an int32 zero on the device before the launch) that ``where`` wrote -- one
+    synchronisation -- and raises what it reports."""
+    st = int(status.item())
+    if st != 0:
+        raise _lib.NfstError(st, where)
+
+
 def _scores(lat: LatticeBatch, theta: torch.Tensor, arc_scores: Optional[torch.Tensor]):
     """nfst_scores + the tensors that must stay alive during the launch."""
     if theta.dtype != torch.float32 or theta.device != lat.device:
@@ -65,13 +128,12 @@ def backward(lat: LatticeBatch, theta, arc_scores=None, want_logbeta=True, want_
     (/root/reference/src/modules/scorers.py:858-875)."""
     _need_gpu(lat)
     sc, keep = _scores(lat, theta, arc_scores)
-    dev = lat.device
+    dev, B = lat.device, lat.n_lattices
     logbeta = torch.empty(lat.total_rows, dtype=torch.float32, device=dev) if want_logbeta else None
-    z64 = torch.empty(lat.n_lattices, dtype=torch.float64, device=dev)
-    z32 = torch.empty(lat.n_lattices, dtype=torch.float32, device=dev)
+    z64 = torch.empty(B, dtype=torch.float64, device=dev)
+    z32 = torch.empty(B, dtype=torch.float32, device=dev)
     me = torch.empty((lat.total_rows, 2), dtype=torch.float32, device=dev) if want_me else None
-    check(lib.nfst_backward(C.byref(lat.c_struct()), C.byref(sc), _ptr(logbeta), _ptr(z64), _ptr(z32), _ptr(me),
-                            _stream()), "nfst_backward")
+    _call("nfst_backward", lat, sc, logbeta, z64, z32, me)
     return BackwardResult(logbeta, z32, z64, me)
 
 
@@ -113,9 +175,7 @@ def forward_backward(lat: LatticeBatch, theta, arc_scores=None, want_alpha_beta=
         me = torch.empty((lat.total_rows, 2), **f32) if want_me else None
     if total is not None and (total.dtype != torch.float64 or total.numel() != 3 or total.device != z64.device):
         raise ValueError("`total` must be a float64 tensor of 3 elements on the batch's device")
-    check(lib.nfst_forward_backward(C.byref(lat.c_struct()), C.byref(sc), _ptr(la), _ptr(lb), _ptr(z64), _ptr(z32),
-                                    _ptr(post), _ptr(gth), _ptr(me), _ptr(total), int(total_slot), _stream()),
-          "nfst_forward_backward")
+    _call("nfst_forward_backward", lat, sc, la, lb, z64, z32, post, gth, me, total, int(total_slot))
     return ForwardBackwardResult(z32, z64, la, lb, post, gth, me)
 
 
@@ -152,6 +212,71 @@ class ForwardBackwardLaunch:
         return self.out
 
 
+# ----------------------------------------------------------------------------- gradient assembly (DESIGN.md section 4.14)
+# Pure torch arithmetic on whatever device its arguments live on: no entry point of the library and no CUDA call, so
+# the backward passes below are these functions and run on host tensors with a host-packed batch.
+def _per_label(x: torch.Tensor, g: torch.Tensor, shared: bool) -> torch.Tensor:
+    """[B, V] per-label sums times the incoming gradient [B]; summed over the batch for a shared [V] table."""
+    y = x * g[:, None]
+    return y.sum(dim=0) if shared else y
+
+
+def _per_position(x: torch.Tensor, g: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    """[B, T, V] per-position sums times the incoming gradient [B]; summed over the batch for a shared [T, V] tensor."""
+    y = x * g[:, None, None]
+    return (y.sum(dim=0) if like.dim() == 2 else y).to(like.dtype)
+
+
+def _arc_grad(lat: LatticeBatch, g: torch.Tensor) -> torch.Tensor:
+    """[total_arcs]: the incoming gradient [B] of every canonical arc's lattice (one small index upload: a backward
+    that needs it for two gradients takes it once)."""
+    return g[lat.arc_lattice()]
+
+
+def _per_arc(lat: LatticeBatch, x: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """[total_arcs] per-arc quantities times the incoming gradient [B] of the arc's lattice."""
+    return x * _arc_grad(lat, g)
+
+
+def _path_score_grads(lat: LatticeBatch, arcs: torch.Tensor, g: torch.Tensor, theta_like=None, arc_like=None,
+                      pos_like=None) -> tuple:
+    """``(d_theta, d_arc, d_pos)`` of path scores best[b, j] = the sum of the terms of path j of lattice b, given the
+    paths as canonical arc ids ``arcs`` [B, K, T] (-1 padded; position t of a path is entry t) and the incoming gradient
+    ``g`` [B, K]: every arc of a path gets g in ``d_arc`` [total_arcs], its label in ``d_theta`` ([V], or [B, V] per
+    lattice) and its (position, label) in ``d_pos`` ([T, V], or [B, T, V]).  Each is computed only if its "like" tensor
+    -- the input it is the gradient of -- is given, in float32, and returned in that tensor's shape, dtype and device.
+    Entries of ``g`` that are not finite (the -inf scores of missing paths feed back -inf or NaN) count as 0."""
+    B, K, T = arcs.shape
+    V = lat.vocab
+    a = arcs.to(torch.int64)
+    on = a >= 0  # (-inf entries have no arcs)
+    gg = torch.where(torch.isfinite(g), g, torch.zeros_like(g)).to(torch.float32)
+    w = gg[:, :, None].expand(B, K, T)[on]
+    idx = a[on]
+
+    def scatter(n, index, like):
+        return torch.zeros(n, dtype=torch.float32, device=arcs.device).index_add_(0, index, w).view(like.shape) \
+            .to(dtype=like.dtype, device=like.device)
+
+    def along(n, dim):  # (the index along ``dim`` of every path entry that holds an arc)
+        shape = [1, 1, 1]
+        shape[dim] = n
+        return torch.arange(n, device=arcs.device).view(shape).expand(B, K, T)[on]
+
+    d_theta = d_arc = d_pos = None
+    if arc_like is not None:
+        d_arc = scatter(lat.total_arcs, idx, arc_like)
+    if theta_like is not None or pos_like is not None:
+        lab = lat.arc_label.to(torch.int64)[idx]
+    if theta_like is not None:
+        d_theta = scatter(V, lab, theta_like) if theta_like.dim() == 1 else scatter(B * V, along(B, 0) * V + lab, theta_like)
+    if pos_like is not None:
+        t = along(T, 2)
+        d_pos = scatter(T * V, t * V + lab, pos_like) if pos_like.dim() == 2 \
+            else scatter(B * T * V, (along(B, 0) * T + t) * V + lab, pos_like)
+    return d_theta, d_arc, d_pos
+
+
 class _LogZ(torch.autograd.Function):
     """log Z with d log Z / d score = arc posterior."""
 
@@ -159,8 +284,7 @@ class _LogZ(torch.autograd.Function):
     def forward(ctx, lat, theta, arc_scores):
         need_t = theta.requires_grad
         need_a = arc_scores is not None and arc_scores.requires_grad
-        r = forward_backward(lat, theta.detach(), None if arc_scores is None else arc_scores.detach(),
-                             want_alpha_beta=False, want_posterior=need_a, want_grad_theta=need_t)
+        r = forward_backward(lat, theta.detach(), _det(arc_scores), want_alpha_beta=False, want_posterior=need_a, want_grad_theta=need_t)
         ctx.lat = lat
         ctx.shared_theta = theta.dim() == 1
         ctx.inputs = (theta, arc_scores)  # (read only by a backward that builds a graph, create_graph=True)
@@ -175,14 +299,8 @@ class _LogZ(torch.autograd.Function):
             theta, arc_scores = ctx.inputs
             g_theta, g_arc = _LogZGrad.apply(ctx.lat, ctx.shared_theta, theta, arc_scores, g, post, gth)
             return None, g_theta, g_arc
-        g_theta = g_arc = None
-        if gth is not None:
-            g_theta = gth * g[:, None]
-            if ctx.shared_theta:
-                g_theta = g_theta.sum(dim=0)
-        if post is not None:
-            g_arc = post * g[ctx.lat.arc_lattice()]
-        return None, g_theta, g_arc
+        return (None, None if gth is None else _per_label(gth, g, ctx.shared_theta),
+                None if post is None else _per_arc(ctx.lat, post, g))
 
 
 def log_z(lat: LatticeBatch, theta: torch.Tensor, arc_scores: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -234,30 +352,23 @@ def expectation_terms(lat: LatticeBatch, theta, arc_scores=None, label_values=No
     if coef != coef or coef in (float("inf"), float("-inf")):
         raise ValueError(f"score_coef must be finite, not {score_coef}")
     sc, keep = _scores(lat, theta, arc_scores)
-    dev = lat.device
-    f32 = dict(dtype=torch.float32, device=dev)
+    dev, f32, f64 = lat.device, torch.float32, torch.float64
     B, A = lat.n_lattices, lat.total_arcs
-    ws_bytes = int(lib.nfst_expectation_ws_bytes(C.byref(lat.c_struct())))
-    check(min(ws_bytes, 0), "nfst_expectation_ws_bytes")
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-    z64 = torch.empty(B, dtype=torch.float64, device=dev)
-    ev64 = torch.empty(B, dtype=torch.float64, device=dev)
-    ev32 = torch.empty(B, **f32)
-    post = torch.empty(A, **f32) if want_posterior else None
-    cov = torch.empty(A, **f32) if want_cov else None
-    lc = torch.empty((B, lat.vocab), **f32) if want_label_cov else None
-    lp = torch.empty((B, lat.vocab), **f32) if want_label_post else None
+    ws, ws_bytes = _workspace(lat, "nfst_expectation_ws_bytes")
+    z64 = torch.empty(B, dtype=f64, device=dev)
+    ev64 = torch.empty(B, dtype=f64, device=dev)
+    ev32 = torch.empty(B, dtype=f32, device=dev)
+    post = torch.empty(A, dtype=f32, device=dev) if want_posterior else None
+    cov = torch.empty(A, dtype=f32, device=dev) if want_cov else None
+    lc = torch.empty((B, lat.vocab), dtype=f32, device=dev) if want_label_cov else None
+    lp = torch.empty((B, lat.vocab), dtype=f32, device=dev) if want_label_post else None
     lv_stride = 0 if label_values is None or label_values.dim() == 1 else lat.vocab
-    check(lib.nfst_expectation(C.byref(lat.c_struct()), C.byref(sc), _ptr(label_values), lv_stride, _ptr(arc_values), coef,
-                               ws.data_ptr(), ws_bytes, _ptr(z64), _ptr(ev64), _ptr(ev32), _ptr(post), _ptr(cov), _ptr(lc),
-                               _ptr(lp), _stream()), "nfst_expectation")
+    rc = lib.nfst_expectation(C.byref(lat.c_struct()), C.byref(sc), _ptr(label_values), lv_stride, _ptr(arc_values), coef,
+                              ws.data_ptr(), ws_bytes, z64.data_ptr(), ev64.data_ptr(), ev32.data_ptr(), _ptr(post), _ptr(cov),
+                              _ptr(lc), _ptr(lp), _stream())  # (written out: see _call)
+    if rc:
+        check(rc, "nfst_expectation")
     return ExpectationResult(z64, ev64, ev32, post, cov, lc, lp)
-
-
-def _per_label(x: torch.Tensor, g: torch.Tensor, shared: bool) -> torch.Tensor:
-    """[B, V] per-label sums times the incoming gradient [B]; summed over the batch for a shared [V] table."""
-    y = x * g[:, None]
-    return y.sum(dim=0) if shared else y
 
 
 class _Expectation(torch.autograd.Function):
@@ -266,9 +377,7 @@ class _Expectation(torch.autograd.Function):
     @staticmethod
     def forward(ctx, lat, theta, arc_scores, label_values, arc_values, coef):
         nt, na, nlv, nav = ctx.needs_input_grad[1:5]
-        r = expectation_terms(lat, theta.detach(), None if arc_scores is None else arc_scores.detach(),
-                              None if label_values is None else label_values.detach(),
-                              None if arc_values is None else arc_values.detach(), coef,
+        r = expectation_terms(lat, theta.detach(), _det(arc_scores), _det(label_values), _det(arc_values), coef,
                               want_posterior=nav or (na and coef != 0.0), want_cov=na, want_label_cov=nt,
                               want_label_post=nlv or (nt and coef != 0.0))
         ctx.lat, ctx.coef = lat, coef
@@ -282,7 +391,7 @@ class _Expectation(torch.autograd.Function):
         post, cov, lc, lp = ctx.saved_tensors
         nt, na, nlv, nav = ctx.needs_input_grad[1:5]
         k = ctx.coef
-        ga = g[ctx.lat.arc_lattice()] if (na or nav) else None
+        ga = _arc_grad(ctx.lat, g) if (na or nav) else None
         d_theta = _per_label(lc if k == 0.0 else lc + k * lp, g, ctx.shared[0]) if nt else None
         d_arc = (cov if k == 0.0 else cov + k * post) * ga if na else None
         d_lv = _per_label(lp, g, ctx.shared[1]) if nlv else None
@@ -306,8 +415,7 @@ class _Entropy(torch.autograd.Function):
     @staticmethod
     def forward(ctx, lat, theta, arc_scores):
         nt, na = ctx.needs_input_grad[1:3]
-        r = expectation_terms(lat, theta.detach(), None if arc_scores is None else arc_scores.detach(), score_coef=1.0,
-                              want_cov=na, want_label_cov=nt)
+        r = expectation_terms(lat, theta.detach(), _det(arc_scores), score_coef=1.0, want_cov=na, want_label_cov=nt)
         ctx.lat, ctx.shared = lat, theta.dim() == 1
         ctx.save_for_backward(r.cov, r.label_cov)
         return (r.logz64 - r.ev64).to(torch.float32)
@@ -318,7 +426,7 @@ class _Entropy(torch.autograd.Function):
         cov, lc = ctx.saved_tensors
         nt, na = ctx.needs_input_grad[1:3]
         d_theta = -_per_label(lc, g, ctx.shared) if nt else None
-        d_arc = -cov * g[ctx.lat.arc_lattice()] if na else None
+        d_arc = _per_arc(ctx.lat, -cov, g) if na else None
         return None, d_theta, d_arc
 
 
@@ -335,9 +443,7 @@ class _KL(torch.autograd.Function):
     @staticmethod
     def forward(ctx, lat, theta_p, theta_q, arc_scores_p, arc_scores_q):
         ntp, ntq, nap, naq = ctx.needs_input_grad[1:5]
-        tp, tq = theta_p.detach(), theta_q.detach()
-        asp = None if arc_scores_p is None else arc_scores_p.detach()
-        asq = None if arc_scores_q is None else arc_scores_q.detach()
+        tp, tq, asp, asq = theta_p.detach(), theta_q.detach(), _det(arc_scores_p), _det(arc_scores_q)
         for name, t in (("theta_p", tp), ("theta_q", tq)):
             _input(lat, t, name, True, False)
         for name, t in (("arc_scores_p", asp), ("arc_scores_q", asq)):
@@ -360,7 +466,7 @@ class _KL(torch.autograd.Function):
     def backward(ctx, g):
         cov_p, lc_p, post_p, lp_p, post_q, lp_q = ctx.saved_tensors
         ntp, ntq, nap, naq = ctx.needs_input_grad[1:5]
-        ga = g[ctx.lat.arc_lattice()] if (nap or naq) else None
+        ga = _arc_grad(ctx.lat, g) if (nap or naq) else None
         return (None, _per_label(lc_p, g, ctx.shared[0]) if ntp else None,
                 _per_label(lp_q - lp_p, g, ctx.shared[1]) if ntq else None,
                 cov_p * ga if nap else None, (post_q - post_p) * ga if naq else None)
@@ -385,12 +491,7 @@ class _LogZGrad(torch.autograd.Function):
     def forward(ctx, lat, shared, theta, arc_scores, g, post, gth):
         ctx.lat, ctx.shared = lat, shared
         ctx.save_for_backward(theta, arc_scores, g)
-        g_theta = g_arc = None
-        if gth is not None:
-            g_theta = _per_label(gth, g, shared)
-        if post is not None:
-            g_arc = post * g[lat.arc_lattice()]
-        return g_theta, g_arc
+        return None if gth is None else _per_label(gth, g, shared), None if post is None else _per_arc(lat, post, g)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -404,7 +505,7 @@ class _LogZGrad(torch.autograd.Function):
         r = expectation_terms(lat, theta.detach().to(**f32), None if arc_scores is None else arc_scores.detach().to(**f32),
                               u_theta, u_arc, want_cov=na, want_label_cov=nt)
         d_theta = _per_label(r.label_cov, g, ctx.shared) if nt else None
-        d_arc = r.cov * g[lat.arc_lattice()] if na else None
+        d_arc = _per_arc(lat, r.cov, g) if na else None
         d_g = r.ev.to(g.dtype) if ng else None
         return None, None, d_theta, d_arc, d_g, None, None
 
@@ -420,15 +521,10 @@ def viterbi(lat: LatticeBatch, theta, arc_scores=None, max_len: Optional[int] = 
     """Best path per lattice (best_sample of JointProb.forward, modules/lightning.py:474-479)."""
     _need_gpu(lat)
     sc, keep = _scores(lat, theta, arc_scores)
-    if max_len is None:
-        max_len = int(lat.depth.max()) + 1
-    dev = lat.device
-    best = torch.empty(lat.n_lattices, dtype=torch.float32, device=dev)
-    paths = torch.empty((lat.n_lattices, max_len), dtype=torch.int32, device=dev)
-    arcs = torch.empty((lat.n_lattices, max_len), dtype=torch.int32, device=dev)
-    lens = torch.empty(lat.n_lattices, dtype=torch.int32, device=dev)
-    check(lib.nfst_viterbi(C.byref(lat.c_struct()), C.byref(sc), _ptr(best), _ptr(paths), _ptr(arcs), _ptr(lens),
-                           int(max_len), int(pad), _stream()), "nfst_viterbi")
+    max_len = _max_len(lat, max_len)
+    best, paths, arcs, lens, _, _ = _path_outputs(lat, (lat.n_lattices,), max_len, best=True)
+    check(lib.nfst_viterbi(C.byref(lat.c_struct()), C.byref(sc), best.data_ptr(), paths.data_ptr(), arcs.data_ptr(),
+                           lens.data_ptr(), int(max_len), int(pad), _stream()), "nfst_viterbi")  # (written out: see _call)
     return ViterbiResult(best, paths, arcs, lens)
 
 
@@ -440,34 +536,28 @@ class KBestResult(NamedTuple):
     n_paths: torch.Tensor  # [B] int32 min(k, paths of score > -inf)
 
 
-MAX_K = 64  # (nfst_kbest: a back pointer keeps the rank in 6 bits)
-
-
 def k_best_terms(lat: LatticeBatch, theta, k: int, arc_scores=None, max_len: Optional[int] = None, pad: int = 0) -> KBestResult:
     """One launch of ``nfst_kbest`` (no autograd); see ``k_best``."""
     _need_gpu(lat)
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
-        raise ValueError(f"k must be an int in [1, {MAX_K}], not {k!r}")
+    _check_k(k)
     sc, keep = _scores(lat, theta, arc_scores)
+    # (length, outputs and call written out: the launch waits for what the host does here and the read-back below waits
+    # for the launch, so this op shows every helper call; with _path_outputs and _call it took 0.9 us more than before)
     if max_len is None:
         max_len = int(lat.depth.max()) + 1
-    dev = lat.device
-    B = lat.n_lattices
-    ws_bytes = int(lib.nfst_kbest_ws_bytes(C.byref(lat.c_struct()), int(k)))
-    check(min(ws_bytes, 0), "nfst_kbest_ws_bytes")
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace(lat, "nfst_kbest_ws_bytes", k)
+    dev, B = lat.device, lat.n_lattices
     best = torch.empty((B, k), dtype=torch.float32, device=dev)
     paths = torch.empty((B, k, max_len), dtype=torch.int32, device=dev)
     arcs = torch.empty((B, k, max_len), dtype=torch.int32, device=dev)
     lens = torch.empty((B, k), dtype=torch.int32, device=dev)
     n_paths = torch.empty(B, dtype=torch.int32, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    check(lib.nfst_kbest(C.byref(lat.c_struct()), C.byref(sc), int(k), ws.data_ptr(), ws_bytes, _ptr(best), _ptr(paths),
-                         _ptr(arcs), _ptr(lens), _ptr(n_paths), int(max_len), int(pad), _ptr(status), _stream()),
-          "nfst_kbest")
-    st = int(status.item())
-    if st != 0:
-        raise _lib.NfstError(st, "nfst_kbest")  # a path longer than max_len
+    rc = lib.nfst_kbest(C.byref(lat.c_struct()), C.byref(sc), k, ws.data_ptr(), ws_bytes, best.data_ptr(), paths.data_ptr(),
+                        arcs.data_ptr(), lens.data_ptr(), n_paths.data_ptr(), int(max_len), int(pad), status.data_ptr(), _stream())
+    if rc:
+        check(rc, "nfst_kbest")
+    _raise_status(status, "nfst_kbest")  # a path longer than max_len
     return KBestResult(best, paths, arcs, lens, n_paths)
 
 
@@ -477,9 +567,9 @@ class _KBest(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, lat, theta, arc_scores, k, max_len, pad):
-        r = k_best_terms(lat, theta.detach(), k, None if arc_scores is None else arc_scores.detach(), max_len, pad)
-        ctx.lat, ctx.theta_like = lat, theta
-        ctx.asc_like = arc_scores
+        r = k_best_terms(lat, theta.detach(), k, _det(arc_scores), max_len, pad)
+        ctx.lat = lat
+        ctx.like = (theta, arc_scores)
         ctx.save_for_backward(r.arcs)
         ctx.mark_non_differentiable(r.paths, r.arcs, r.lengths, r.n_paths)
         return r.best, r.paths, r.arcs, r.lengths, r.n_paths
@@ -489,27 +579,8 @@ class _KBest(torch.autograd.Function):
     def backward(ctx, g, *_):
         (arcs,) = ctx.saved_tensors
         nt, na = ctx.needs_input_grad[1:3]
-        lat = ctx.lat
-        B, K, T = arcs.shape
-        a = arcs.reshape(B, K * T).to(torch.int64)
-        on = a >= 0
-        gg = torch.where(torch.isfinite(g), g, torch.zeros_like(g)).to(torch.float32)
-        w = gg[:, :, None].expand(B, K, T).reshape(B, K * T)[on]  # (-inf entries have no arcs)
-        idx = a[on]
-        f32 = dict(dtype=torch.float32, device=arcs.device)
-        d_arc = d_theta = None
-        if na:
-            d_arc = torch.zeros(lat.total_arcs, **f32).index_add_(0, idx, w)
-            d_arc = d_arc.to(dtype=ctx.asc_like.dtype, device=ctx.asc_like.device)
-        if nt:
-            lab = lat.arc_label.to(torch.int64)[idx]
-            V = lat.vocab
-            if ctx.theta_like.dim() == 1:
-                d_theta = torch.zeros(V, **f32).index_add_(0, lab, w)
-            else:
-                row = torch.arange(B, device=arcs.device)[:, None].expand(B, K * T)[on]
-                d_theta = torch.zeros(B * V, **f32).index_add_(0, row * V + lab, w).view(B, V)
-            d_theta = d_theta.to(dtype=ctx.theta_like.dtype, device=ctx.theta_like.device)
+        theta, arc_scores = ctx.like
+        d_theta, d_arc, _ = _path_score_grads(ctx.lat, arcs, g, theta if nt else None, arc_scores if na else None)
         return None, d_theta, d_arc, None, None, None
 
 
@@ -522,8 +593,7 @@ def k_best(lat: LatticeBatch, theta, k: int, arc_scores=None, max_len: Optional[
     ``pad`` labels and arc -1 (``n_paths`` counts the real ones).  ``max_len`` defaults to the longest path + 1; a
     longer path raises ``NfstError`` (NFST_ERR_LENGTH).  ``best`` is differentiable in theta and arc_scores: the
     gradient of a path's score counts its labels / marks its arcs."""
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
-        raise ValueError(f"k must be an int in [1, {MAX_K}], not {k!r}")
+    _check_k(k)
     if not isinstance(theta, torch.Tensor):
         theta = torch.as_tensor(theta, dtype=torch.float32)
     return KBestResult(*_KBest.apply(lat, theta, arc_scores, k, max_len, pad))
@@ -567,21 +637,18 @@ def arc_slack(lat: LatticeBatch, theta, arc_scores=None, beam=None, want_rows: b
     packing of the same lattices.  Not differentiable: the outputs carry no gradient."""
     _need_gpu(lat)
     sc, alive = _scores(lat, theta.detach() if isinstance(theta, torch.Tensor) else torch.as_tensor(theta, dtype=torch.float32),
-                        None if arc_scores is None else arc_scores.detach())
+                        _det(arc_scores))
     dev = lat.device
     B, A, R = lat.n_lattices, lat.total_arcs, lat.total_rows
     bm = None if beam is None else _beam(lat, beam)
-    ws_bytes = int(lib.nfst_arc_slack_ws_bytes(C.byref(lat.c_struct())))
-    check(min(ws_bytes, 0), "nfst_arc_slack_ws_bytes")
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace(lat, "nfst_arc_slack_ws_bytes")
     best = torch.empty(B, dtype=torch.float32, device=dev)
     slack = torch.empty(A, dtype=torch.float32, device=dev)
     keep = torch.empty(A, dtype=torch.uint8, device=dev) if bm is not None else None
     n_kept = torch.empty(B, dtype=torch.int32, device=dev) if bm is not None else None
     vbeta = torch.empty(R, dtype=torch.float32, device=dev) if want_rows else None
     sslack = torch.empty(R, dtype=torch.float32, device=dev) if want_rows else None
-    check(lib.nfst_arc_slack(C.byref(lat.c_struct()), C.byref(sc), _ptr(bm), ws.data_ptr(), ws_bytes, _ptr(best), _ptr(vbeta),
-                             _ptr(sslack), _ptr(slack), _ptr(keep), _ptr(n_kept), _stream()), "nfst_arc_slack")
+    _call("nfst_arc_slack", lat, sc, bm, ws, ws_bytes, best, vbeta, sslack, slack, keep, n_kept)
     return ArcSlackResult(best, slack, None if keep is None else keep.view(torch.bool), n_kept, vbeta, sslack)
 
 
@@ -657,11 +724,15 @@ def _positions(lat: LatticeBatch, pos_scores, T):
     return pos, stride, int(pos_scores.shape[-2])
 
 
-def _workspace(lat: LatticeBatch, query: str, *args) -> tuple:
-    """(workspace on the batch's device, its size) as the library's ``query(lat, *args)`` sizes it"""
-    ws_bytes = int(getattr(lib, query)(C.byref(lat.c_struct()), *args))
-    check(min(ws_bytes, 0), query)
-    return torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=lat.device), ws_bytes
+def _score_args(lat: LatticeBatch, theta, arc_scores, pos_scores=None, T: Optional[int] = None) -> tuple:
+    """``(nfst_scores, the tensors it points into, pos, stride, T)`` of an op that checks its scores strictly: ``theta``
+    and ``arc_scores`` by ``_input``, then ``pos_scores`` and ``T`` by ``_positions``, in that order; everything
+    detached, since a launch reads values and records nothing."""
+    theta = _input(lat, theta, "theta", True, False)
+    arc_scores = _input(lat, arc_scores, "arc_scores", False, True)
+    pos, stride, T = _positions(lat, pos_scores, T)
+    sc, keep = _scores(lat, _det(theta), _det(arc_scores))
+    return sc, keep, _det(pos), stride, T
 
 
 def _positional_ws(lat: LatticeBatch, T: int, flags: int) -> tuple:
@@ -695,10 +766,7 @@ def positional_forward_backward(lat: LatticeBatch, theta, pos_scores=None, T: Op
     Paths longer than ``T`` are not counted; a lattice without a path of finite score within ``T`` gets -inf and zero
     posteriors.  The workspace stores every beta row of every position: 12 (T + 1) total_rows bytes."""
     _need_gpu(lat)
-    theta = _input(lat, theta, "theta", True, False)
-    arc_scores = _input(lat, arc_scores, "arc_scores", False, True)
-    pos, stride, T = _positions(lat, pos_scores, T)
-    sc, keep = _scores(lat, theta, arc_scores)
+    sc, keep, pos, stride, T = _score_args(lat, theta, arc_scores, pos_scores, T)
     dev = lat.device
     B = lat.n_lattices
     need = want_pos_posterior or want_arc_posterior or want_len
@@ -708,8 +776,7 @@ def positional_forward_backward(lat: LatticeBatch, theta, pos_scores=None, T: Op
     pp = torch.empty((B, T, lat.vocab), dtype=torch.float32, device=dev) if want_pos_posterior else None
     ap = torch.empty(lat.total_arcs, dtype=torch.float32, device=dev) if want_arc_posterior else None
     ll = torch.empty((B, T + 1), dtype=torch.float64, device=dev) if want_len else None
-    check(lib.nfst_positional(C.byref(lat.c_struct()), C.byref(sc), _ptr(pos), stride, T, ws.data_ptr(), ws_bytes, _ptr(z64),
-                              _ptr(z32), _ptr(ll), _ptr(pp), _ptr(ap), _stream()), "nfst_positional")
+    _call("nfst_positional", lat, sc, pos, stride, T, ws, ws_bytes, z64, z32, ll, pp, ap)
     return PositionalResult(z32, z64, pp, ap, ll)
 
 
@@ -720,8 +787,7 @@ class _PositionalLogZ(torch.autograd.Function):
     @staticmethod
     def forward(ctx, lat, theta, pos_scores, arc_scores):
         nt, npos, na = ctx.needs_input_grad[1:4]
-        r = positional_forward_backward(lat, theta.detach(), pos_scores.detach(), None,
-                                        None if arc_scores is None else arc_scores.detach(),
+        r = positional_forward_backward(lat, theta.detach(), pos_scores.detach(), None, _det(arc_scores),
                                         want_pos_posterior=nt or npos, want_arc_posterior=na)
         ctx.lat = lat
         ctx.shared = (theta.dim() == 1, pos_scores.dim() == 2)
@@ -740,10 +806,9 @@ class _PositionalLogZ(torch.autograd.Function):
         if nt:
             d_theta = _per_label(pp.sum(dim=1), g, ctx.shared[0]).to(theta.dtype)
         if npos:
-            d_pos = pp * g[:, None, None]
-            d_pos = (d_pos.sum(dim=0) if ctx.shared[1] else d_pos).to(pos_scores.dtype)
+            d_pos = _per_position(pp, g, pos_scores)
         if na:
-            d_arc = (ap * g[ctx.lat.arc_lattice()]).to(arc_scores.dtype)
+            d_arc = _per_arc(ctx.lat, ap, g).to(arc_scores.dtype)
         return None, d_theta, d_pos, d_arc
 
 
@@ -832,21 +897,9 @@ def positional_expectation_terms(lat: LatticeBatch, theta, pos_scores=None, T: O
     pc = torch.empty((B, T, V), **f32) if want_pos_cov else None
     ac = torch.empty(A, **f32) if want_arc_cov else None
     lv_stride = 0 if label_values is None or label_values.dim() == 1 else V
-    check(lib.nfst_positional_expectation(C.byref(lat.c_struct()), C.byref(sc), _ptr(pos), stride, T, _ptr(pv), pv_stride,
-                                          _ptr(label_values), lv_stride, _ptr(arc_values), coef, ws.data_ptr(), ws_bytes,
-                                          _ptr(z64), _ptr(z32), _ptr(ev64), _ptr(ev32), _ptr(pp), _ptr(ap), _ptr(pc), _ptr(ac),
-                                          _stream()), "nfst_positional_expectation")
+    _call("nfst_positional_expectation", lat, sc, pos, stride, T, pv, pv_stride, label_values, lv_stride, arc_values, coef,
+          ws, ws_bytes, z64, z32, ev64, ev32, pp, ap, pc, ac)
     return PositionalExpectationResult(z64, z32, ev64, ev32, pp, ap, pc, ac)
-
-
-def _det(t):
-    return None if t is None else t.detach()
-
-
-def _per_position(x: torch.Tensor, g: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
-    """[B, T, V] per-position sums times the incoming gradient [B]; summed over the batch for a shared [T, V] tensor."""
-    y = x * g[:, None, None]
-    return (y.sum(dim=0) if like.dim() == 2 else y).to(like.dtype)
 
 
 class _PositionalExpectation(torch.autograd.Function):
@@ -874,7 +927,7 @@ class _PositionalExpectation(torch.autograd.Function):
         theta, pos_scores, arc_scores, pos_values, label_values, arc_values = ctx.like
         k = ctx.coef
         g = g.to(torch.float32)
-        ga = g[ctx.lat.arc_lattice()] if (na or nav) else None
+        ga = _arc_grad(ctx.lat, g) if (na or nav) else None
         d_theta = d_pos = d_arc = d_pv = d_lv = d_av = None
         if nt or npos:
             ds = pc if k == 0.0 else pc + k * pp
@@ -930,7 +983,7 @@ class _PositionalEntropy(torch.autograd.Function):
         g = -g.to(torch.float32)
         d_theta = _per_label(pc.sum(dim=1), g, theta.dim() == 1).to(theta.dtype) if nt else None
         d_pos = _per_position(pc, g, pos_scores) if npos else None
-        d_arc = (ac * g[ctx.lat.arc_lattice()]).to(arc_scores.dtype) if na else None
+        d_arc = _per_arc(ctx.lat, ac, g).to(arc_scores.dtype) if na else None
         return None, d_theta, d_pos, d_arc, None
 
 
@@ -987,7 +1040,7 @@ class _PositionalKL(torch.autograd.Function):
         ntp, npp, ntq, npq, nap, naq = ctx.needs_input_grad[1:7]
         theta_p, pos_p, theta_q, pos_q, asp, asq = ctx.like
         g = g.to(torch.float32)
-        ga = g[ctx.lat.arc_lattice()] if (nap or naq) else None
+        ga = _arc_grad(ctx.lat, g) if (nap or naq) else None
         dq = pp_q - pp_p if (ntq or npq) else None
         return (None,
                 _per_label(pc.sum(dim=1), g, theta_p.dim() == 1).to(theta_p.dtype) if ntp else None,
@@ -1019,22 +1072,10 @@ def positional_viterbi(lat: LatticeBatch, theta, pos_scores=None, T: Optional[in
     longest path it is ``k_best(k=1)`` bit for bit.  A lattice without a path of finite score within ``T`` gets
     ``best`` -inf and length 0.  Not differentiable."""
     _need_gpu(lat)
-    theta = _input(lat, theta, "theta", True, False)
-    arc_scores = _input(lat, arc_scores, "arc_scores", False, True)
-    pos, stride, T = _positions(lat, pos_scores, T)
-    sc, keep = _scores(lat, theta.detach(), None if arc_scores is None else arc_scores.detach())
-    if pos is not None:
-        pos = pos.detach()
-    dev = lat.device
-    B = lat.n_lattices
+    sc, keep, pos, stride, T = _score_args(lat, theta, arc_scores, pos_scores, T)
     ws, ws_bytes = _positional_ws(lat, T, 2)
-    best = torch.empty(B, dtype=torch.float32, device=dev)
-    paths = torch.empty((B, T), dtype=torch.int32, device=dev)
-    arcs = torch.empty((B, T), dtype=torch.int32, device=dev)
-    lens = torch.empty(B, dtype=torch.int32, device=dev)
-    check(lib.nfst_positional_viterbi(C.byref(lat.c_struct()), C.byref(sc), _ptr(pos), stride, T, ws.data_ptr(), ws_bytes,
-                                      _ptr(best), _ptr(paths), _ptr(arcs), _ptr(lens), int(pad), _stream()),
-          "nfst_positional_viterbi")
+    best, paths, arcs, lens, _, _ = _path_outputs(lat, (lat.n_lattices,), T, best=True)
+    _call("nfst_positional_viterbi", lat, sc, pos, stride, T, ws, ws_bytes, best, paths, arcs, lens, int(pad))
     return PositionalViterbiResult(best, paths, arcs, lens)
 
 
@@ -1050,25 +1091,11 @@ def positional_k_best_terms(lat: LatticeBatch, theta, k: int, pos_scores=None, T
                             pad: int = 0) -> PositionalKBestResult:
     """One launch of ``nfst_positional_kbest`` (no autograd); see ``positional_k_best``."""
     _need_gpu(lat)
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
-        raise ValueError(f"k must be an int in [1, {MAX_K}], not {k!r}")
-    theta = _input(lat, theta, "theta", True, False)
-    arc_scores = _input(lat, arc_scores, "arc_scores", False, True)
-    pos, stride, T = _positions(lat, pos_scores, T)
-    sc, keep = _scores(lat, theta.detach(), None if arc_scores is None else arc_scores.detach())
-    if pos is not None:
-        pos = pos.detach()
-    dev = lat.device
-    B = lat.n_lattices
+    _check_k(k)
+    sc, keep, pos, stride, T = _score_args(lat, theta, arc_scores, pos_scores, T)
     ws, ws_bytes = _workspace(lat, "nfst_positional_kbest_ws_bytes", T, k)
-    best = torch.empty((B, k), dtype=torch.float32, device=dev)
-    paths = torch.empty((B, k, T), dtype=torch.int32, device=dev)
-    arcs = torch.empty((B, k, T), dtype=torch.int32, device=dev)
-    lens = torch.empty((B, k), dtype=torch.int32, device=dev)
-    n_paths = torch.empty(B, dtype=torch.int32, device=dev)
-    check(lib.nfst_positional_kbest(C.byref(lat.c_struct()), C.byref(sc), _ptr(pos), stride, T, k, ws.data_ptr(), ws_bytes,
-                                    _ptr(best), _ptr(paths), _ptr(arcs), _ptr(lens), _ptr(n_paths), int(pad), _stream()),
-          "nfst_positional_kbest")
+    best, paths, arcs, lens, n_paths, _ = _path_outputs(lat, (lat.n_lattices, k), T, best=True, n_paths=True)
+    _call("nfst_positional_kbest", lat, sc, pos, stride, T, k, ws, ws_bytes, best, paths, arcs, lens, n_paths, int(pad))
     return PositionalKBestResult(best, paths, arcs, lens, n_paths)
 
 
@@ -1092,34 +1119,8 @@ class _PositionalKBest(torch.autograd.Function):
         (arcs,) = ctx.saved_tensors
         nt, npos, na = ctx.needs_input_grad[1:4]
         theta, pos_scores, arc_scores = ctx.like
-        lat = ctx.lat
-        B, K, T = arcs.shape
-        V = lat.vocab
-        a = arcs.to(torch.int64)
-        on = a >= 0  # (-inf entries have no arcs)
-        gg = torch.where(torch.isfinite(g), g, torch.zeros_like(g)).to(torch.float32)
-        w = gg[:, :, None].expand(B, K, T)[on]
-        idx = a[on]
-        f32 = dict(dtype=torch.float32, device=arcs.device)
-        d_theta = d_pos = d_arc = None
-        if na:
-            d_arc = torch.zeros(lat.total_arcs, **f32).index_add_(0, idx, w).to(arc_scores.dtype)
-        if nt or npos:
-            lab = lat.arc_label.to(torch.int64)[idx]
-            row = torch.arange(B, device=arcs.device)[:, None, None].expand(B, K, T)[on]
-        if nt:
-            if theta.dim() == 1:
-                d_theta = torch.zeros(V, **f32).index_add_(0, lab, w)
-            else:
-                d_theta = torch.zeros(B * V, **f32).index_add_(0, row * V + lab, w).view(B, V)
-            d_theta = d_theta.to(theta.dtype)
-        if npos:
-            t = torch.arange(T, device=arcs.device)[None, None, :].expand(B, K, T)[on]
-            if pos_scores.dim() == 2:
-                d_pos = torch.zeros(T * V, **f32).index_add_(0, t * V + lab, w).view(T, V)
-            else:
-                d_pos = torch.zeros(B * T * V, **f32).index_add_(0, (row * T + t) * V + lab, w).view(B, T, V)
-            d_pos = d_pos.to(pos_scores.dtype)
+        d_theta, d_arc, d_pos = _path_score_grads(ctx.lat, arcs, g, theta if nt else None, arc_scores if na else None,
+                                                  pos_scores if npos else None)
         return None, d_theta, d_pos, d_arc, None, None, None
 
 
@@ -1136,8 +1137,7 @@ def positional_k_best(lat: LatticeBatch, theta, k: int, pos_scores=None, T: Opti
     ``best`` is differentiable in theta, arc_scores and pos_scores (first derivatives only): the gradient of a path's
     score counts its labels, marks its arcs and marks (t, label) of each of its positions."""
     _need_gpu(lat)
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= MAX_K:
-        raise ValueError(f"k must be an int in [1, {MAX_K}], not {k!r}")
+    _check_k(k)
     theta = _input(lat, theta, "theta", True, False)
     arc_scores = _input(lat, arc_scores, "arc_scores", False, True)
     _positions(lat, pos_scores, T)
@@ -1165,14 +1165,8 @@ def positional_sample_paths(lat: LatticeBatch, theta, k: int, pos_scores=None, T
     bytes of workspace) and one wave per walk; the same bits at every launch and for every packing.  Not
     differentiable."""
     _need_gpu(lat)
-    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
-        raise ValueError(f"k must be an int >= 1, not {k!r}")
-    theta = _input(lat, theta, "theta", True, False)
-    arc_scores = _input(lat, arc_scores, "arc_scores", False, True)
-    pos, stride, T = _positions(lat, pos_scores, T)
-    sc, keep = _scores(lat, theta.detach(), None if arc_scores is None else arc_scores.detach())
-    if pos is not None:
-        pos = pos.detach()
+    _check_k(k, bounded=False)
+    sc, keep, pos, stride, T = _score_args(lat, theta, arc_scores, pos_scores, T)
     dev = lat.device
     B = lat.n_lattices
     if uniforms is not None:
@@ -1182,13 +1176,9 @@ def positional_sample_paths(lat: LatticeBatch, theta, k: int, pos_scores=None, T
     ws, ws_bytes = _positional_ws(lat, T, _lib.POS_WS_SAMPLE)
     z64 = torch.empty(B, dtype=torch.float64, device=dev)
     z32 = torch.empty(B, dtype=torch.float32, device=dev)
-    paths = torch.empty((B, k, T), dtype=torch.int32, device=dev)
-    arcs = torch.empty((B, k, T), dtype=torch.int32, device=dev) if want_arcs else None
-    lens = torch.empty((B, k), dtype=torch.int32, device=dev)
-    logq = torch.empty((B, k), dtype=torch.float32, device=dev)
-    check(lib.nfst_positional_sample(C.byref(lat.c_struct()), C.byref(sc), _ptr(pos), stride, T, k, _ptr(uniforms),
-                                     C.c_uint64(seed & (2 ** 64 - 1)), int(pad), ws.data_ptr(), ws_bytes, _ptr(z64), _ptr(z32),
-                                     _ptr(paths), _ptr(arcs), _ptr(lens), _ptr(logq), _stream()), "nfst_positional_sample")
+    _, paths, arcs, lens, _, logq = _path_outputs(lat, (B, k), T, arcs=want_arcs, logq=True)
+    _call("nfst_positional_sample", lat, sc, pos, stride, T, k, uniforms, C.c_uint64(seed & (2 ** 64 - 1)), int(pad), ws, ws_bytes,
+          z64, z32, paths, arcs, lens, logq)
     return PositionalSampleResult(paths, arcs, lens, logq, z32, z64)
 
 
@@ -1210,16 +1200,14 @@ def positional_score_paths(lat: LatticeBatch, theta, marks: torch.Tensor, pos_sc
     pos, stride, T = _positions(lat, pos_scores, T)
     if marks.shape[2] != T:
         raise ValueError(f"marks has {marks.shape[2]} positions, T = {T}")
-    sc, keep = _scores(lat, theta.detach(), None if arc_scores is None else arc_scores.detach())
-    if pos is not None:
-        pos = pos.detach()
+    sc, keep = _scores(lat, theta.detach(), _det(arc_scores))
+    pos = _det(pos)
     marks = marks.to(device=lat.device, dtype=torch.int32).contiguous()
     B, K = int(marks.shape[0]), int(marks.shape[1])
     tot = torch.empty((B, K), dtype=torch.float32, device=lat.device)
     end = torch.empty((B, K), dtype=torch.int32, device=lat.device)
     lens = torch.empty((B, K), dtype=torch.int32, device=lat.device)
-    check(lib.nfst_positional_score_paths(C.byref(lat.c_struct()), C.byref(sc), _ptr(pos), stride, T, _ptr(marks), K, _ptr(tot),
-                                          _ptr(end), _ptr(lens), _stream()), "nfst_positional_score_paths")
+    _call("nfst_positional_score_paths", lat, sc, pos, stride, T, marks, K, tot, end, lens)
     return tot, end, lens
 
 
@@ -1240,8 +1228,7 @@ def sample_paths(lat: LatticeBatch, theta, k: int, arc_scores=None, max_len: Opt
     block, without it a walk computes the probabilities of the arcs it meets)."""
     _need_gpu(lat)
     sc, keep = _scores(lat, theta, arc_scores)
-    if max_len is None:
-        max_len = int(lat.depth.max()) + 1
+    max_len = _max_len(lat, max_len)
     if beta is None or beta.beta_me is None:
         beta = backward(lat, theta, arc_scores, want_logbeta=False, want_me=True)
     dev = lat.device
@@ -1250,17 +1237,11 @@ def sample_paths(lat: LatticeBatch, theta, k: int, arc_scores=None, max_len: Opt
         uniforms = uniforms.to(device=dev, dtype=torch.float32).contiguous()
         if uniforms.shape != (B, k, max_len):
             raise ValueError(f"uniforms must be [{B}, {k}, {max_len}]")
-    paths = torch.empty((B, k, max_len), dtype=torch.int32, device=dev)
-    arcs = torch.empty((B, k, max_len), dtype=torch.int32, device=dev) if want_arcs else None
-    lens = torch.empty((B, k), dtype=torch.int32, device=dev)
-    logq = torch.empty((B, k), dtype=torch.float32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    check(lib.nfst_sample_paths(C.byref(lat.c_struct()), C.byref(sc), _ptr(beta.beta_me), _ptr(beta.logz64), int(k),
-                                int(max_len), _ptr(uniforms), C.c_uint64(seed & (2 ** 64 - 1)), int(pad), _ptr(paths),
-                                _ptr(arcs), _ptr(lens), _ptr(logq), _ptr(status), _stream()), "nfst_sample_paths")
-    st = int(status.item())
-    if st != 0:
-        raise _lib.NfstError(st, "nfst_sample_paths")  # "ran out of length budget" (samplers.py:299-302)
+    _, paths, arcs, lens, _, logq = _path_outputs(lat, (B, k), max_len, arcs=want_arcs, logq=True)
+    status = torch.zeros(1, dtype=torch.int32, device=lat.device)
+    _call("nfst_sample_paths", lat, sc, beta.beta_me, beta.logz64, int(k), int(max_len), uniforms, C.c_uint64(seed & (2 ** 64 - 1)),
+          int(pad), paths, arcs, lens, logq, status)
+    _raise_status(status, "nfst_sample_paths")  # "ran out of length budget" (samplers.py:299-302)
     return SampleResult(paths, arcs, lens, logq, beta.logz)
 
 
@@ -1274,8 +1255,7 @@ def score_paths(lat: LatticeBatch, theta, marks: torch.Tensor, arc_scores=None):
         raise ValueError("marks must be [B, K, T]")
     tot = torch.empty((B, K), dtype=torch.float32, device=lat.device)
     end = torch.empty((B, K), dtype=torch.int32, device=lat.device)
-    check(lib.nfst_score_paths(C.byref(lat.c_struct()), C.byref(sc), _ptr(marks), K, T, _ptr(tot), _ptr(end),
-                               _stream()), "nfst_score_paths")
+    _call("nfst_score_paths", lat, sc, marks, K, T, tot, end)
     return tot, end
 
 
@@ -1291,7 +1271,7 @@ def step(lat: LatticeBatch, state: torch.Tensor, label: torch.Tensor, k: int = 1
     _need_gpu(lat)
     state, label = _walkers(lat, state, k, "state"), _walkers(lat, label, k, "label")
     out = torch.empty_like(state)
-    check(lib.nfst_step(C.byref(lat.c_struct()), _ptr(state), _ptr(label), _ptr(out), int(k), _stream()), "nfst_step")
+    _call("nfst_step", lat, state, label, out, int(k))
     return out
 
 
@@ -1304,8 +1284,7 @@ def emission_mask(lat: LatticeBatch, state: torch.Tensor, k: int = 1, inp: Optio
     if inp is not None:
         inp = _walkers(lat, inp, k, "inp")
     out = torch.empty((state.shape[0], lat.vocab), dtype=torch.float32, device=lat.device)
-    check(lib.nfst_emission_mask(C.byref(lat.c_struct()), _ptr(state), _ptr(inp), int(pad), int(bos), int(eos),
-                                 int(bool(has_to_end)), _ptr(out), int(k), _stream()), "nfst_emission_mask")
+    _call("nfst_emission_mask", lat, state, inp, int(pad), int(bos), int(eos), int(bool(has_to_end)), out, int(k))
     return out
 
 
@@ -1317,8 +1296,7 @@ def beta_logits(lat: LatticeBatch, values: torch.Tensor, state: torch.Tensor, k:
     if values.shape[0] != lat.total_rows:
         raise ValueError("values must be row-indexed [total_rows]")
     out = torch.empty((state.shape[0], lat.vocab), dtype=torch.float32, device=lat.device)
-    check(lib.nfst_beta_logits(C.byref(lat.c_struct()), _ptr(values), _ptr(state), _ptr(out), int(k), _stream()),
-          "nfst_beta_logits")
+    _call("nfst_beta_logits", lat, values, state, out, int(k))
     return out
 
 
@@ -1360,10 +1338,8 @@ class _ProposalStep(torch.autograd.Function):
             logq = torch.empty(N, dtype=torch.float32, device=dev)
             logz = torch.empty(N, dtype=torch.float32, device=dev)
         logits = torch.empty(N, lat.vocab, dtype=torch.float32, device=dev) if need else None
-        check(lib.nfst_proposal_step(C.byref(lat.c_struct()), _ptr(state), _ptr(inp), _ptr(scores), _ptr(values), int(pad),
-                                     int(bos), int(eos), int(bool(has_to_end)), float(temperature), _ptr(uniforms), _ptr(forced),
-                                     None if extras is None else C.byref(extras), _ptr(sym), _ptr(logq), _ptr(logz), _ptr(nxt),
-                                     _ptr(logits), int(k), _stream()), "nfst_proposal_step")
+        _call("nfst_proposal_step", lat, state, inp, scores, values, int(pad), int(bos), int(eos), int(bool(has_to_end)),
+              float(temperature), uniforms, forced, extras, sym, logq, logz, nxt, logits, int(k))
         ctx.lat, ctx.k, ctx.pad, ctx.temperature = lat, k, pad, temperature
         ctx.need_values = values is not None and values.requires_grad
         ctx.n_values = 0 if values is None else values.shape[0]
@@ -1379,9 +1355,8 @@ class _ProposalStep(torch.autograd.Function):
         g_logz = None if g_logz is None else g_logz.to(torch.float32).contiguous()
         grad = torch.empty_like(logits)
         gv = torch.zeros(ctx.n_values, dtype=torch.float32, device=logits.device) if ctx.need_values else None
-        check(lib.nfst_proposal_step_backward(C.byref(lat.c_struct()), _ptr(vstate), _ptr(logits), _ptr(sym), _ptr(logz),
-                                              _ptr(g_logq), _ptr(g_logz), int(ctx.pad), float(ctx.temperature), _ptr(grad),
-                                              _ptr(gv), int(ctx.k), _stream()), "nfst_proposal_step_backward")
+        _call("nfst_proposal_step_backward", lat, vstate, logits, sym, logz, g_logq, g_logz, int(ctx.pad), float(ctx.temperature),
+              grad, gv, int(ctx.k))
         return None, grad, gv, None
 
 
@@ -1502,9 +1477,8 @@ def beam_step(lat: LatticeBatch, state: torch.Tensor, inp: torch.Tensor, beam_sc
                              "n_candidates int32 [B]) on the batch's device")
     else:
         out = tuple(torch.empty(n, dtype=d, device=dev) for d, n in want)
-    check(lib.nfst_beam_step(C.byref(lat.c_struct()), _ptr(state), _ptr(inp), _ptr(beam_score), _ptr(scores), _ptr(lookahead),
-                             int(pad), int(bos), int(eos), int(bool(has_to_end)), int(k), *(_ptr(o) for o in out), _ptr(n_open),
-                             _stream()), "nfst_beam_step")
+    _call("nfst_beam_step", lat, state, inp, beam_score, scores, lookahead, int(pad), int(bos), int(eos), int(bool(has_to_end)),
+          int(k), *out, n_open)
     return BeamStep(*out)
 
 
@@ -1533,8 +1507,7 @@ def beam_backtrack(parent: torch.Tensor, symbol: torch.Tensor, score: torch.Tens
     parent, symbol, score = parent.contiguous(), symbol.contiguous(), score.contiguous()
     paths = torch.empty((n_lattices, k, max_len), dtype=torch.int32, device=dev)
     lengths = torch.empty((n_lattices, k), dtype=torch.int32, device=dev)
-    check(lib.nfst_beam_backtrack(_ptr(parent), _ptr(symbol), _ptr(score), n_steps, int(n_lattices), int(k), max_len, int(pad),
-                                  _ptr(paths), _ptr(lengths), _stream()), "nfst_beam_backtrack")
+    _call("nfst_beam_backtrack", None, parent, symbol, score, n_steps, int(n_lattices), int(k), max_len, int(pad), paths, lengths)
     return paths, lengths
 
 
@@ -1552,12 +1525,10 @@ class _NeuralBeta(torch.autograd.Function):
     def forward(ctx, lat, label_x, wh, w):
         f32 = dict(device=lat.device, dtype=torch.float32)
         H = w.shape[0]
-        s = lat.c_struct()
-        ws = torch.empty(int(lib.nfst_neural_ws_floats(C.byref(s), H)), **f32)
+        ws = torch.empty(int(lib.nfst_neural_ws_floats(C.byref(lat.c_struct()), H)), **f32)
         log_beta = torch.empty(lat.total_rows, **f32)
         beta_hat = torch.empty(lat.total_rows, H, **f32)
-        check(lib.nfst_backward_neural(C.byref(s), label_x.data_ptr(), wh.data_ptr(), w.data_ptr(), H, log_beta.data_ptr(),
-                                       beta_hat.data_ptr(), ws.data_ptr(), _stream()), "nfst_backward_neural")
+        _call("nfst_backward_neural", lat, label_x, wh, w, H, log_beta, beta_hat, ws)
         ctx.lat = lat
         ctx.save_for_backward(label_x, wh, w, beta_hat, ws)
         return log_beta, beta_hat
@@ -1568,7 +1539,6 @@ class _NeuralBeta(torch.autograd.Function):
         label_x, wh, w, beta_hat, ws_fwd = ctx.saved_tensors
         f32 = dict(device=lat.device, dtype=torch.float32)
         H = w.shape[0]
-        s = lat.c_struct()
         g_lb = (torch.zeros(lat.total_rows, **f32) if g_log_beta is None else g_log_beta.to(**f32)).contiguous()
         # rows the sweep never reached carry -inf and no gradient
         g_lb = torch.where(torch.isfinite(g_lb), g_lb, torch.zeros_like(g_lb))
@@ -1576,12 +1546,9 @@ class _NeuralBeta(torch.autograd.Function):
         gamma = torch.zeros(lat.total_rows, H, **f32)
         g_x = torch.zeros_like(label_x)
         g_w = torch.zeros(H, **f32)
-        ws = torch.empty(int(lib.nfst_neural_grad_ws_floats(C.byref(s), H)), **f32)
+        ws = torch.empty(int(lib.nfst_neural_grad_ws_floats(C.byref(lat.c_struct()), H)), **f32)
         wh_t = wh.t().contiguous()
-        check(lib.nfst_backward_neural_grad(C.byref(s), label_x.data_ptr(), wh_t.data_ptr(), w.data_ptr(), H,
-                                            beta_hat.data_ptr(), ws_fwd.data_ptr(), g_lb.data_ptr(),
-                                            0 if g_bh is None else g_bh.data_ptr(), gamma.data_ptr(), g_x.data_ptr(),
-                                            g_w.data_ptr(), ws.data_ptr(), _stream()), "nfst_backward_neural_grad")
+        _call("nfst_backward_neural_grad", lat, label_x, wh_t, w, H, beta_hat, ws_fwd, g_lb, g_bh, gamma, g_x, g_w, ws)
         # dL/dWh[i, j] = sum over states of gamma(s)[i] beta_hat(s)[j]: a library GEMM
         return None, g_x, _gram(gamma, beta_hat), g_w
 
@@ -1624,8 +1591,7 @@ def gather_label_scores(lat: LatticeBatch, theta, arc_scores=None) -> torch.Tens
     _need_gpu(lat)
     sc, keep = _scores(lat, theta, arc_scores)
     out = torch.empty(lat.total_arcs, dtype=torch.float32, device=lat.device)
-    check(lib.nfst_gather_label_scores(C.byref(lat.c_struct()), C.byref(sc), _ptr(out), _stream()),
-          "nfst_gather_label_scores")
+    _call("nfst_gather_label_scores", lat, sc, out)
     return out
 
 
@@ -1645,8 +1611,7 @@ class _PathLogprob(torch.autograd.Function):
     def forward(ctx, scores, marks, cfg):
         N, T, V = scores.shape
         out = torch.empty(N, dtype=torch.float32, device=scores.device)
-        check(lib.nfst_path_logprob(_ptr(scores), _ptr(marks), N, T, V, *_plp_args(*cfg), _ptr(out), _stream()),
-              "nfst_path_logprob")
+        _call("nfst_path_logprob", None, scores, marks, N, T, V, *_plp_args(*cfg), out)
         ctx.cfg = cfg
         ctx.save_for_backward(scores, marks)
         return out
@@ -1657,8 +1622,7 @@ class _PathLogprob(torch.autograd.Function):
         N, T, V = scores.shape
         g = g.to(torch.float32).contiguous()
         grad = torch.empty_like(scores)
-        check(lib.nfst_path_logprob_backward(_ptr(scores), _ptr(marks), _ptr(g), N, T, V, *_plp_args(*ctx.cfg), _ptr(grad),
-                                             _stream()), "nfst_path_logprob_backward")
+        _call("nfst_path_logprob_backward", None, scores, marks, g, N, T, V, *_plp_args(*ctx.cfg), grad)
         return grad, None, None
 
 
@@ -1701,5 +1665,5 @@ def iwae(log_p: torch.Tensor, log_q: torch.Tensor):
     B, K = log_p.shape
     log_w = torch.empty_like(log_p)
     lm = torch.empty(B, dtype=torch.float32, device=log_p.device)
-    check(lib.nfst_iwae(_ptr(log_p), _ptr(log_q), B, K, _ptr(log_w), _ptr(lm), _stream()), "nfst_iwae")
+    _call("nfst_iwae", None, log_p, log_q, B, K, log_w, lm)
     return lm, log_w

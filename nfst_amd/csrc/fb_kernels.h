@@ -131,8 +131,8 @@ __global__ __launch_bounds__(NT) void k_backward(nfst_batch lat, nfst_scores sc,
   } else if constexpr (TW) {
     if (wv == 0) {
       __builtin_amdgcn_s_setprio(3);
-      if constexpr (PREC) tile_sweep2p<kNE>(m.bwd_tiles, ring, R, flags, flags + 4, lane);
-      else if (tw_v2) tile_sweep2<4, kNE>(m.bwd_tiles, ring, R, flags, flags + 4, lane);
+      if constexpr (PREC) tile_sweep2<Sweep64, kNE>(m.bwd_tiles, ring, R, flags, flags + 4, lane);
+      else if (tw_v2) tile_sweep2<Sweep32, kNE>(m.bwd_tiles, ring, R, flags, flags + 4, lane);
       else tile_sweep<4, true, kNE>(m.bwd_tiles, ring, R, flags, flags + 4, lane);
       __builtin_amdgcn_s_setprio(0);
     }
@@ -403,8 +403,8 @@ __global__ __launch_bounds__(NT) void k_forward_backward(
       int *fl = bwd_side ? flags : flags + kSweepFlags;
       __builtin_amdgcn_s_setprio(3);  // (the chain: 45.8 -> 44.3 us at 256 lattices)
       // (every program is compact: four slots per lane)
-      if constexpr (PREC) tile_sweep2p<kNE>(my_tiles, my_ring, R, fl, fl + 4, lane);
-      else if (tw_v2) tile_sweep2<4, kNE>(my_tiles, my_ring, R, fl, fl + 4, lane, bwd_side ? 5 : -1);
+      if constexpr (PREC) tile_sweep2<Sweep64, kNE>(my_tiles, my_ring, R, fl, fl + 4, lane);
+      else if (tw_v2) tile_sweep2<Sweep32, kNE>(my_tiles, my_ring, R, fl, fl + 4, lane, bwd_side ? 5 : -1);
       else tile_sweep<4, true, kNE>(my_tiles, my_ring, R, fl, fl + 4, lane);
       __builtin_amdgcn_s_setprio(0);
       NFST_STAMP(bwd_side ? 2 : 3);

@@ -140,7 +140,7 @@ __device__ __forceinline__ float me_log32(const Rec64 v) { return me_log32(me_f2
 template <bool PREC> struct ValOf { typedef float2 T; };
 template <> struct ValOf<true> { typedef Rec64 T; };
 __device__ __forceinline__ void val_set(float2 &v, float m, int e) { v = make_float2(m, __int_as_float(e)); }
-__device__ __forceinline__ void val_set(Rec64 &v, float m, int e) { v.m = (double)m; v.e = e; v.pad = 0; }
+__device__ __forceinline__ void val_set(Rec64 &v, double m, int e) { v.m = m; v.e = e; v.pad = 0; }
 
 struct Meta {
   int row_off, n_rows, arc_off, n_arcs, fwd_off, fwd_tiles, bwd_off, bwd_tiles, sink, n_reach, depth, n_dp,

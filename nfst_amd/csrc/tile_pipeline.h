@@ -854,7 +854,7 @@ struct WeightWave {
       uint32_t ctl, opoff[U], lab8[U];
       unpack(g.raw, ctl, opoff, lab8);
       if constexpr (PREC) {
-        // the decoded tile of tile_sweep2p: values and label weights are 16-byte records (float64 mantissa, exponent):
+        // the decoded tile of tile_sweep2<Sweep64>: values and label weights are 16-byte records (float64 mantissa, exponent):
         // [store address | g, largest g][3 stage multipliers: the high word of 1.0 or 0][4 operand addresses]
         // [4 weight mantissas, float64][4 weight exponents] = 80 bytes per lane
         double om[U];
@@ -1153,104 +1153,45 @@ __device__ __forceinline__ void run_sweep(int role, int U, bool wide, uint32_t *
 // tile waves (store address incl. the leader select, the stage multipliers, no end-of-program tests: a
 // finished tile wave publishes "infinity"), and the segmented sum is three v_fmac_f32_dpp on terms
 // aligned to a stale wave-uniform exponent (tile_math): ~60 issue slots per tile.
-template <int U>
 struct Dec2 {
   uint32_t dst;
   float k0, k1, k2;
-  uint32_t opa[U];
-  v2f tw[U];
+  uint32_t opa[4];
+  v2f tw[4];
 };
-template <int U>
-__device__ __forceinline__ void dec2_fetch(uint32_t sb, int lane, Dec2<U> &d) {
+__device__ __forceinline__ void dec2_fetch(uint32_t sb, int lane, Dec2 &d) {
   const v4u h = *(const lds_v4u *)(uintptr_t)(sb + lane * 16);
   d.dst = h.x; d.k0 = __uint_as_float(h.y); d.k1 = __uint_as_float(h.z); d.k2 = __uint_as_float(h.w);
-  if (U == 4) {
-    const v4u a = *(const lds_v4u *)(uintptr_t)(sb + 1024 + lane * 16);
-    const v4f p = *(const lds_v4f *)(uintptr_t)(sb + 2048 + lane * 16);
-    const v4f q = *(const lds_v4f *)(uintptr_t)(sb + 3072 + lane * 16);
-    d.opa[0] = a.x; d.opa[1 % U] = a.y; d.opa[2 % U] = a.z; d.opa[3 % U] = a.w;
-    d.tw[0] = v2f{p.x, p.y}; d.tw[1 % U] = v2f{p.z, p.w}; d.tw[2 % U] = v2f{q.x, q.y}; d.tw[3 % U] = v2f{q.z, q.w};
-  } else if (U == 2) {
-    const v2u a = *(const lds_v2u *)(uintptr_t)(sb + 1024 + lane * 8);
-    const v4f p = *(const lds_v4f *)(uintptr_t)(sb + 2048 + lane * 16);
-    d.opa[0] = a.x; d.opa[1 % U] = a.y;
-    d.tw[0] = v2f{p.x, p.y}; d.tw[1 % U] = v2f{p.z, p.w};
-  } else {
-    d.opa[0] = *(const lds_u32 *)(uintptr_t)(sb + 1024 + lane * 4);
-    d.tw[0] = *(const lds_v2f *)(uintptr_t)(sb + 2048 + lane * 8);
-  }
-}
-// tile_math with the per-lane constants precomputed (same arithmetic, same bits)
-template <int U>
-__device__ __forceinline__ void tile_math2(const v2f (&tw)[U], const v2f (&vv)[U], const Dec2<U> &c, int &ref) {
-  const int nref = -ref;
-  float mt[U];
-  int d[U];
-#pragma unroll
-  for (int j = 0; j < U; ++j) {
-    mt[j] = tw[j].x * vv[j].x;
-    d[j] = __float_as_int(tw[j].y) + __float_as_int(vv[j].y) + nref;
-  }
-  int dmax = d[0];
-#pragma unroll
-  for (int j = 1; j < U; ++j) dmax = max(dmax, d[j]);
-  float M = ldexpf(mt[0], d[0]);
-#pragma unroll
-  for (int j = 1; j < U; ++j) M += ldexpf(mt[j], d[j]);
-  constexpr int kZeroish = -(1 << 27);
-  const bool bad = ((uint32_t)(dmax + 64) > 128u) & (dmax > kZeroish);
-  int E = ref;
-  const int e0 = __builtin_amdgcn_readfirstlane(dmax);
-  const int ref_old = ref;
-  ref = (e0 > kZeroish) ? e0 + ref_old : ref_old;
-  if (__builtin_expect(__builtin_amdgcn_ballot_w64(bad) != 0, 0)) {
-    M = ldexpf(mt[0], d[0] - dmax);
-#pragma unroll
-    for (int j = 1; j < U; ++j) M += ldexpf(mt[j], d[j] - dmax);
-    E = dmax + ref_old;
-    const uint64_t m0 = __builtin_amdgcn_ballot_w64(c.k0 != 0.0f), m1 = __builtin_amdgcn_ballot_w64(c.k1 != 0.0f),
-                   m2 = __builtin_amdgcn_ballot_w64(c.k2 != 0.0f);
-    seg_reduce_exec<3>(M, E, m0, m1, m2);
-  } else {
-    asm volatile(
-        "s_nop 1\n\t"  // (a DPP read needs two wait states after the vector write of its source: the compiler does not look into this block)
-        "v_fmac_f32_dpp %[m], %[m], %[k0] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_fmac_f32_dpp %[m], %[m], %[k1] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_fmac_f32_dpp %[m], %[m], %[k2] row_half_mirror row_mask:0xf bank_mask:0xf"
-        : [m] "+v"(M)
-        : [k0] "v"(c.k0), [k1] "v"(c.k1), [k2] "v"(c.k2));
-    E = (M == 0.0f) ? kEZero : E;
-  }
-  const float2 r = me_pack(M, E);
-  *(lds_v2f *)(uintptr_t)c.dst = v2f{r.x, r.y};
+  const v4u a = *(const lds_v4u *)(uintptr_t)(sb + 1024 + lane * 16);
+  const v4f p = *(const lds_v4f *)(uintptr_t)(sb + 2048 + lane * 16);
+  const v4f q = *(const lds_v4f *)(uintptr_t)(sb + 3072 + lane * 16);
+  d.opa[0] = a.x; d.opa[1] = a.y; d.opa[2] = a.z; d.opa[3] = a.w;
+  d.tw[0] = v2f{p.x, p.y}; d.tw[1] = v2f{p.z, p.w}; d.tw[2] = v2f{q.x, q.y}; d.tw[3] = v2f{q.z, q.w};
 }
 
-// One tile of tile_sweep2: tile_math2's arithmetic (same bits) in an order that keeps the scalar uses of
+// One float32 tile of tile_sweep2: tile_math's arithmetic (same bits) in an order that keeps the scalar uses of
 // vector results -- the test for the exact path, the next reference exponent -- away from the instructions that
 // produce them (a scalar use of a fresh vector result costs ~25 cycles): the fast result is computed
 // unconditionally and replaced in the rare tile that needs the exact path.
-template <int U>
-__device__ __forceinline__ int tile_math3(const Dec2<U> &c, const v2f (&vv)[U], const int ref) {  // returns this lane's largest term exponent - ref
+__device__ __forceinline__ int tile_math3(const Dec2 &c, const v2f (&vv)[4], const int ref) {  // returns this lane's largest term exponent - ref
   const int nref = -ref;
-  float mt[U];
-  int d[U];
+  float mt[4];
+  int d[4];
 #pragma unroll
-  for (int j = 0; j < U; ++j) {
+  for (int j = 0; j < 4; ++j) {
     mt[j] = c.tw[j].x * vv[j].x;
     // (one three-operand add with the reference in a scalar register; hipcc splits the C expression in two)
     asm("v_add3_u32 %0, %1, %2, %3" : "=v"(d[j]) : "v"(__float_as_int(c.tw[j].y)), "v"(__float_as_int(vv[j].y)), "s"(nref));
   }
   int dmax = d[0];
 #pragma unroll
-  for (int j = 1; j < U; ++j) dmax = max(dmax, d[j]);
+  for (int j = 1; j < 4; ++j) dmax = max(dmax, d[j]);
   constexpr int kZeroish = -(1 << 27);
   const uint64_t bad = __builtin_amdgcn_ballot_w64(((uint32_t)(dmax + 64) > 128u) & (dmax > kZeroish));
   const int ref_old = ref;
   float M = ldexpf(mt[0], d[0]);
 #pragma unroll
-  for (int j = 1; j < U; ++j) M += ldexpf(mt[j], d[j]);
+  for (int j = 1; j < 4; ++j) M += ldexpf(mt[j], d[j]);
   asm volatile(
       "s_nop 1\n\t"  // (a DPP read needs two wait states after the vector write of its source: the compiler does not look into this block)
       "v_fmac_f32_dpp %[m], %[m], %[k0] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
@@ -1264,7 +1205,7 @@ __device__ __forceinline__ int tile_math3(const Dec2<U> &c, const v2f (&vv)[U], 
   if (__builtin_expect(bad != 0, 0)) {
     M = ldexpf(mt[0], d[0] - dmax);
 #pragma unroll
-    for (int j = 1; j < U; ++j) M += ldexpf(mt[j], d[j] - dmax);
+    for (int j = 1; j < 4; ++j) M += ldexpf(mt[j], d[j] - dmax);
     E = dmax + ref_old;
     const uint64_t m0 = __builtin_amdgcn_ballot_w64(c.k0 != 0.0f), m1 = __builtin_amdgcn_ballot_w64(c.k1 != 0.0f),
                    m2 = __builtin_amdgcn_ballot_w64(c.k2 != 0.0f);
@@ -1278,9 +1219,6 @@ __device__ __forceinline__ int tile_math3(const Dec2<U> &c, const v2f (&vv)[U], 
   return dmax;
 }
 
-// Four tiles per trip (the ring holds a multiple of four slots, so a trip's slots are consecutive and the fetch
-// addresses are one base plus immediates; tile t's wave is t mod 4, so the four flags -- one 16-byte read -- are
-// checked once per trip for the four tiles the trip fetches; `prog` is published every other tile).
 #ifdef NFST_PROF
 constexpr int kProfSlots = 16;  // stamps per workgroup of the profiling build (profiles/tune/stamps.py, tail_stamps.py)
 __device__ unsigned long long fb_prof[4096 * kProfSlots];
@@ -1288,94 +1226,9 @@ __device__ unsigned long long fb_prof[4096 * kProfSlots];
 #else
 #define NFST_STAMP(k) do { } while (0)
 #endif
-template <int U, int NEF>
-__device__ __forceinline__ void tile_sweep2(int n_tiles, const uint32_t *ring, int R, int *prog, const int *land, int lane, int prof_slot = -1) {
-  static_assert(NEF == 4, "four tile waves per sweep");
-  (void)prof_slot;
-  if (n_tiles <= 0) return;
-  constexpr uint32_t SB = kSlotWords2 * 4;
-  const uint32_t ring_base = lds_addr(ring), ring_end = ring_base + (uint32_t)R * SB;
-  const uint32_t land_a = lds_addr(land), prog_a = lds_addr(prog);
-  // the four flags in one read: .x = min over the tiles T+1 .. T+3 of (their wave's flag - their offset): all three are decoded
-  // iff it exceeds T; .y = the same for tile T+4, which the trip's last step fetches (with a ring of four slots that tile can only
-  // be written once the trip has consumed its first tile)
-  // (the raw flag words are kept and the margins evaluated where they are tested, a tile or two later: evaluated at once
-  // they made hipcc wait for the flag read -- the youngest of nine LDS reads in flight -- in front of the tile's arithmetic)
-  auto flags_now = [&]() { return *(const volatile lds_v4u *)(uintptr_t)land_a; };
-  // (every word of a copy is kept alive until the copy is looked at -- the empty asm statements below --: with dead words hipcc
-  // reused their registers at once and put a full wait for the flag read, the youngest of nine LDS reads in flight, in front of
-  // the tile's arithmetic)
-  auto margin_x = [](const v4u f) { return min(min((int)f.y - 1, (int)f.z - 2), (int)f.w - 3); };
-  auto margin_y = [](const v4u f) { return (int)f.x - 4; };
-  auto wait_group = [&](int T, int which) {
-    for (;;) {
-      const v4u f = flags_now();
-      if (__builtin_amdgcn_readfirstlane(which ? margin_y(f) : margin_x(f)) > T) break;
-      __builtin_amdgcn_s_sleep(1);
-    }
-    asm volatile("" ::: "memory");
-  };
-  while (__builtin_amdgcn_readfirstlane((int)*(const volatile lds_u32 *)(uintptr_t)land_a) <= 0) __builtin_amdgcn_s_sleep(1);  // tile 0
-  asm volatile("" ::: "memory");
-#ifdef NFST_PROF
-  if (prof_slot >= 0) NFST_STAMP(prof_slot);
-#endif
-  uint32_t gbase = ring_base;  // slot of the trip's first tile
-  v4u margin = {0u, 0u, 0u, 0u}, margin1 = {0u, 0u, 0u, 0u};  // the flag words as of an earlier tile (per-lane copies): nothing decoded beyond tile 0 is assumed
-  int ref = 0;     // the exponent the terms of a tile are aligned to (wave-uniform, a few tiles old)
-  int dmax0 = 0;
-  Dec2<U> da, db;
-  dec2_fetch<U>(gbase, lane, da);
-  asm volatile("" ::: "memory");
-  // tile T+K: `cur` in registers; fetches tile T+K+1 into `nxt`
-#define NFST_S2_STEP(K, CUR, NXT)                                                                          \
-  {                                                                                                       \
-    v2f vv[U];                                                                                            \
-    _Pragma("unroll") for (int j = 0; j < U; ++j) vv[j] = *(const lds_v2f *)(uintptr_t)CUR.opa[j];         \
-    asm volatile("" ::: "memory");                                                                        \
-    __builtin_amdgcn_sched_barrier(0); /* nothing is scheduled in front of the operand gathers */         \
-    if (K == 3) {                                                                                         \
-      gbase = (gbase + 4 * SB == ring_end) ? ring_base : gbase + 4 * SB;                                  \
-      asm volatile("" ::"v"(margin1));                                                                    \
-      if (__builtin_expect(__builtin_amdgcn_readfirstlane(margin_y(margin1)) <= T, 0)) wait_group(T, 1);     \
-    }                                                                                                     \
-    dec2_fetch<U>(gbase + (K == 3 ? 0u : (K + 1) * SB), lane, NXT);                                       \
-    if (K == 1) margin1 = flags_now();                                                                     \
-    if (K == 3) margin = flags_now();                                                        \
-    asm volatile("" ::: "memory");                                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                                                    \
-    const int dm_ = tile_math3<U>(CUR, vv, ref);                                                          \
-    if (K == 0) dmax0 = dm_;                                                                              \
-    if (K & 1) *(volatile lds_u32 *)(uintptr_t)prog_a = (uint32_t)(T + K + 2); /* tiles 0 .. T+K+1 are consumed */ \
-    asm volatile("" ::: "memory");                                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                                                    \
-  }
-  int T = 0;
-  for (; T + 4 <= n_tiles; T += 4) {  // whole trips: no end-of-program test between the tiles
-    asm volatile("" ::"v"(margin));
-    if (__builtin_expect(__builtin_amdgcn_readfirstlane(margin_x(margin)) <= T, 0)) wait_group(T, 0);
-    NFST_S2_STEP(0, da, db)
-    NFST_S2_STEP(1, db, da)
-    NFST_S2_STEP(2, da, db)
-    NFST_S2_STEP(3, db, da)
-    // the reference exponent follows lane 0 once per trip, from the trip's first tile: by now that vector result is old
-    const int e0 = __builtin_amdgcn_readfirstlane(dmax0);
-    ref = __builtin_amdgcn_readfirstlane((e0 > -(1 << 27)) ? e0 + ref : ref);  // (kept in a scalar register)
-  }
-  if (T < n_tiles) {  // the last one to three tiles
-    asm volatile("" ::"v"(margin));
-    if (__builtin_expect(__builtin_amdgcn_readfirstlane(margin_x(margin)) <= T, 0)) wait_group(T, 0);
-    NFST_S2_STEP(0, da, db)
-    if (T + 1 < n_tiles) {
-      NFST_S2_STEP(1, db, da)
-      if (T + 2 < n_tiles) NFST_S2_STEP(2, da, db)
-    }
-  }
-#undef NFST_S2_STEP
-}
 
-// ---- the precise flavour of tile_sweep2: float64 mantissas (semiring.h) ---------------------------------------
-// Same loop, same hand-shakes, same ring protocol; a value is a 16-byte record (float64 mantissa, exponent), a ring
+// ---- the precise flavour of a tile_sweep2 tile: float64 mantissas (semiring.h) --------------------------------
+// Same loop (tile_sweep2 below is written once for both); a value is a 16-byte record (float64 mantissa, exponent), a ring
 // slot 80 bytes per lane (WeightWave<.., PREC>::process).  The terms of a tile are aligned to the stale wave-uniform
 // exponent as in tile_math3 -- with float64's range the window is 2^+-900 instead of 2^+-64 --, the segmented sum is
 // two v_mov_b32_dpp + one v_fma_f64 per stage.  Tiles with groups wider than 8 lanes (programs the packer marked
@@ -1464,14 +1317,42 @@ __device__ __forceinline__ Rec64 rec64_load(uint32_t a) {
   r.pad = 0;
   return r;
 }
-template <int NEF>
-__device__ __forceinline__ void tile_sweep2p(int n_tiles, const uint32_t *ring, int R, int *prog, const int *land, int lane) {
+
+// What tile_sweep2 needs to know about a value type: the bytes of a ring slot, the decoded tile and its fetch, the
+// gather of one operand and the tile's arithmetic.  Everything else -- the protocol -- is the same text for both.
+struct Sweep32 {  // float32 mantissas
+  static constexpr uint32_t kSlotBytes = kSlotWords2 * 4;
+  typedef Dec2 Dec;
+  typedef v2f Val;
+  static __device__ __forceinline__ void fetch(uint32_t sb, int lane, Dec &d) { dec2_fetch(sb, lane, d); }
+  static __device__ __forceinline__ Val gather(uint32_t a) { return *(const lds_v2f *)(uintptr_t)a; }
+  static __device__ __forceinline__ int math(const Dec &c, const Val (&vv)[4], int ref) { return tile_math3(c, vv, ref); }
+};
+struct Sweep64 {  // float64 mantissas
+  static constexpr uint32_t kSlotBytes = kSlotWordsP * 4;
+  typedef Dec2P Dec;
+  typedef Rec64 Val;
+  static __device__ __forceinline__ void fetch(uint32_t sb, int lane, Dec &d) { dec2p_fetch(sb, lane, d); }
+  static __device__ __forceinline__ Val gather(uint32_t a) { return rec64_load(a); }
+  static __device__ __forceinline__ int math(const Dec &c, const Val (&vv)[4], int ref) { return tile_math3p(c, vv, ref); }
+};
+
+// Four tiles per trip (the ring holds a multiple of four slots, so a trip's slots are consecutive and the fetch
+// addresses are one base plus immediates; tile t's wave is t mod 4, so the four flags -- one 16-byte read -- are
+// checked once per trip for the four tiles the trip fetches; `prog` is published every other tile).
+template <typename P, int NEF>
+__device__ __forceinline__ void tile_sweep2(int n_tiles, const uint32_t *ring, int R, int *prog, const int *land, int lane, int prof_slot = -1) {
   static_assert(NEF == 4, "four tile waves per sweep");
+  (void)prof_slot;
   if (n_tiles <= 0) return;
-  constexpr uint32_t SB = kSlotWordsP * 4;
+  constexpr uint32_t SB = P::kSlotBytes;
   const uint32_t ring_base = lds_addr(ring), ring_end = ring_base + (uint32_t)R * SB;
   const uint32_t land_a = lds_addr(land), prog_a = lds_addr(prog);
-  // (as in tile_sweep2)
+  // the four flags in one read: .x = min over the tiles T+1 .. T+3 of (their wave's flag - their offset): all three are decoded
+  // iff it exceeds T; .y = the same for tile T+4, which the trip's last step fetches (with a ring of four slots that tile can only
+  // be written once the trip has consumed its first tile)
+  // (the raw flag words are kept and the margins evaluated where they are tested, a tile or two later: evaluated at once
+  // they made hipcc wait for the flag read -- the youngest of nine LDS reads in flight -- in front of the tile's arithmetic)
   auto flags_now = [&]() { return *(const volatile lds_v4u *)(uintptr_t)land_a; };
   // (every word of a copy is kept alive until the copy is looked at -- the empty asm statements below --: with dead words hipcc
   // reused their registers at once and put a full wait for the flag read, the youngest of nine LDS reads in flight, in front of
@@ -1488,56 +1369,61 @@ __device__ __forceinline__ void tile_sweep2p(int n_tiles, const uint32_t *ring, 
   };
   while (__builtin_amdgcn_readfirstlane((int)*(const volatile lds_u32 *)(uintptr_t)land_a) <= 0) __builtin_amdgcn_s_sleep(1);  // tile 0
   asm volatile("" ::: "memory");
-  uint32_t gbase = ring_base;
-  v4u margin = {0u, 0u, 0u, 0u}, margin1 = {0u, 0u, 0u, 0u};
-  int ref = 0;
+#ifdef NFST_PROF
+  if (prof_slot >= 0) NFST_STAMP(prof_slot);
+#endif
+  uint32_t gbase = ring_base;  // slot of the trip's first tile
+  v4u margin = {0u, 0u, 0u, 0u}, margin1 = {0u, 0u, 0u, 0u};  // the flag words as of an earlier tile (per-lane copies): nothing decoded beyond tile 0 is assumed
+  int ref = 0;     // the exponent the terms of a tile are aligned to (wave-uniform, a few tiles old)
   int dmax0 = 0;
-  Dec2P da, db;
-  dec2p_fetch(gbase, lane, da);
+  typename P::Dec da, db;
+  P::fetch(gbase, lane, da);
   asm volatile("" ::: "memory");
-#define NFST_S2P_STEP(K, CUR, NXT)                                                                         \
+  // tile T+K: `cur` in registers; fetches tile T+K+1 into `nxt`
+#define NFST_S2_STEP(K, CUR, NXT)                                                                          \
   {                                                                                                       \
-    Rec64 vv[4];                                                                                          \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) vv[j] = rec64_load(CUR.opa[j]);                          \
+    typename P::Val vv[4];                                                                                \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) vv[j] = P::gather(CUR.opa[j]);                           \
     asm volatile("" ::: "memory");                                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                                                    \
+    __builtin_amdgcn_sched_barrier(0); /* nothing is scheduled in front of the operand gathers */         \
     if (K == 3) {                                                                                         \
       gbase = (gbase + 4 * SB == ring_end) ? ring_base : gbase + 4 * SB;                                  \
       asm volatile("" ::"v"(margin1));                                                                    \
       if (__builtin_expect(__builtin_amdgcn_readfirstlane(margin_y(margin1)) <= T, 0)) wait_group(T, 1);     \
     }                                                                                                     \
-    dec2p_fetch(gbase + (K == 3 ? 0u : (K + 1) * SB), lane, NXT);                                         \
+    P::fetch(gbase + (K == 3 ? 0u : (K + 1) * SB), lane, NXT);                                            \
     if (K == 1) margin1 = flags_now();                                                                     \
-    if (K == 3) margin = flags_now();                                                        \
+    if (K == 3) margin = flags_now();                                                                      \
     asm volatile("" ::: "memory");                                                                        \
     __builtin_amdgcn_sched_barrier(0);                                                                    \
-    const int dm_ = tile_math3p(CUR, vv, ref);                                                            \
+    const int dm_ = P::math(CUR, vv, ref);                                                                \
     if (K == 0) dmax0 = dm_;                                                                              \
-    if (K & 1) *(volatile lds_u32 *)(uintptr_t)prog_a = (uint32_t)(T + K + 2);                            \
+    if (K & 1) *(volatile lds_u32 *)(uintptr_t)prog_a = (uint32_t)(T + K + 2); /* tiles 0 .. T+K+1 are consumed */ \
     asm volatile("" ::: "memory");                                                                        \
     __builtin_amdgcn_sched_barrier(0);                                                                    \
   }
   int T = 0;
-  for (; T + 4 <= n_tiles; T += 4) {
+  for (; T + 4 <= n_tiles; T += 4) {  // whole trips: no end-of-program test between the tiles
     asm volatile("" ::"v"(margin));
     if (__builtin_expect(__builtin_amdgcn_readfirstlane(margin_x(margin)) <= T, 0)) wait_group(T, 0);
-    NFST_S2P_STEP(0, da, db)
-    NFST_S2P_STEP(1, db, da)
-    NFST_S2P_STEP(2, da, db)
-    NFST_S2P_STEP(3, db, da)
+    NFST_S2_STEP(0, da, db)
+    NFST_S2_STEP(1, db, da)
+    NFST_S2_STEP(2, da, db)
+    NFST_S2_STEP(3, db, da)
+    // the reference exponent follows lane 0 once per trip, from the trip's first tile: by now that vector result is old
     const int e0 = __builtin_amdgcn_readfirstlane(dmax0);
-    ref = __builtin_amdgcn_readfirstlane((e0 > -(1 << 27)) ? e0 + ref : ref);
+    ref = __builtin_amdgcn_readfirstlane((e0 > -(1 << 27)) ? e0 + ref : ref);  // (kept in a scalar register)
   }
-  if (T < n_tiles) {
+  if (T < n_tiles) {  // the last one to three tiles
     asm volatile("" ::"v"(margin));
     if (__builtin_expect(__builtin_amdgcn_readfirstlane(margin_x(margin)) <= T, 0)) wait_group(T, 0);
-    NFST_S2P_STEP(0, da, db)
+    NFST_S2_STEP(0, da, db)
     if (T + 1 < n_tiles) {
-      NFST_S2P_STEP(1, db, da)
-      if (T + 2 < n_tiles) NFST_S2P_STEP(2, da, db)
+      NFST_S2_STEP(1, db, da)
+      if (T + 2 < n_tiles) NFST_S2_STEP(2, da, db)
     }
   }
-#undef NFST_S2P_STEP
+#undef NFST_S2_STEP
 }
 
 // a weight wave's part of a sweep: compact programs were started at kernel entry (x8), the rarer
@@ -1574,27 +1460,22 @@ __device__ __forceinline__ void run_weights(WeightWave<8, NE, XM, FULL, PREC> &x
 }
 
 // `first` = theta[tid] loaded by the caller at kernel entry (beside the meta record, not behind it)
-__device__ __forceinline__ void load_theta(float2 *th, const float *theta, int64_t stride, int b,
+template <typename VT>  // float2 or Rec64
+__device__ __forceinline__ void load_theta(VT *th, const float *theta, int64_t stride, int b,
                                            int V, int tid, int nt, float first) {
   const float *t = theta + (size_t)stride * b;
   for (int l = tid; l < V; l += nt) {
-    ME x = exp_split(l == tid ? first : t[l]);
-    th[l] = make_float2(x.m, __int_as_float(x.e));
+    const float s = l == tid ? first : t[l];
+    if constexpr (std::is_same<VT, Rec64>::value) {  // (called directly: through an overloaded wrapper hipcc ordered the float32 code differently)
+      const ME64 x = exp_split64((double)s);
+      val_set(th[l], x.m, x.e);
+    } else {
+      const ME x = exp_split(s);
+      val_set(th[l], x.m, x.e);
+    }
   }
   if (tid == 0) {
-    th[V] = make_float2(0.0f, __int_as_float(kEZero));  // the null label of empty slots
-    th[V + 1] = make_float2(0.5f, __int_as_float(1));       // weight one: the carry record of a continuation piece
-  }
-}
-__device__ __forceinline__ void load_theta(Rec64 *th, const float *theta, int64_t stride, int b,
-                                           int V, int tid, int nt, float first) {
-  const float *t = theta + (size_t)stride * b;
-  for (int l = tid; l < V; l += nt) {
-    const ME64 x = exp_split64((double)(l == tid ? first : t[l]));
-    th[l].m = x.m; th[l].e = x.e; th[l].pad = 0;
-  }
-  if (tid == 0) {
-    th[V].m = 0.0; th[V].e = kEZero; th[V].pad = 0;     // the null label of empty slots
-    th[V + 1].m = 0.5; th[V + 1].e = 1; th[V + 1].pad = 0;  // weight one: the carry record of a continuation piece
+    val_set(th[V], 0.0f, kEZero);  // the null label of empty slots
+    val_set(th[V + 1], 0.5f, 1);   // weight one: the carry record of a continuation piece
   }
 }

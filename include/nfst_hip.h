@@ -362,6 +362,10 @@ int nfst_dense_to_arcs_write(const void *emission, int emission_is_float, const 
                              int32_t n_rows, int32_t vocab, const uint8_t *reach, const int32_t *row_cnt,
                              const int64_t *arc_off, int32_t *src, int32_t *label, int32_t *dst, float *arc_w, void *stream);
 int64_t nfst_pack_device_ws_bytes(int32_t n_lattices, int64_t total_rows, int64_t total_arcs);
+/* (host) the sizes at which the packing kernel changes its path: *lds_bytes = dynamic LDS of a workgroup (what does not
+ * fit beside the depths and heights lives in global memory), *max_keys = 64-bit sort keys that fit it (pieces of one sweep
+ * direction beyond that: NFST_ERR_LIMIT), *threads = threads of a workgroup.  For tests that must reach every path. */
+int nfst_pack_device_limits(int64_t *lds_bytes, int32_t *max_keys, int32_t *threads);
 int nfst_pack_device_plan(const nfst_arcs_device *arcs, const nfst_pack_opts *opts, void *ws, int64_t ws_bytes, int32_t *meta,
                           int32_t *status, int32_t *scratch_rows, void *stream);
 int nfst_pack_device_layout(int32_t *meta, const int32_t *status, const int32_t *scratch_rows, int32_t n_lattices,

@@ -113,6 +113,7 @@ def _load():
         "nfst_dense_to_arcs_count": (C.c_int, [vp, C.c_int, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
         "nfst_dense_to_arcs_write": (C.c_int, [vp, C.c_int, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "nfst_pack_device_ws_bytes": (i64, [i32, i64, i64]),
+        "nfst_pack_device_limits": (C.c_int, [C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)]),
         "nfst_pack_device_plan": (C.c_int, [C.POINTER(ArcsDevice), C.POINTER(PackOpts), vp, i64, vp, vp, vp, vp]),
         "nfst_pack_device_layout": (C.c_int, [vp, vp, vp, i32, i32, i32, BP, C.POINTER(i32)]),
         "nfst_pack_device_emit": (C.c_int, [C.POINTER(ArcsDevice), C.POINTER(PackOpts), vp, i64, vp, vp, BP, vp]),

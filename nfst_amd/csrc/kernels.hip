@@ -481,6 +481,12 @@ int64_t nfst_pack_device_ws_bytes(int32_t n_lattices, int64_t total_rows, int64_
   return 4 * pk_ws_words(n_lattices, total_rows, total_arcs);
 }
 
+int nfst_pack_device_limits(int64_t *lds_bytes, int32_t *max_keys, int32_t *threads) {
+  if (!lds_bytes || !max_keys || !threads) return NFST_ERR_ARG;
+  *lds_bytes = kPkLdsBytes; *max_keys = kPkMaxKeys; *threads = kPkThreads;
+  return NFST_OK;
+}
+
 static int pack_device_args(const nfst_arcs_device *arcs, const nfst_pack_opts *opts, void *ws, int64_t ws_bytes, PkArgs *a) {
   if (!arcs || !ws || arcs->n_lattices <= 0 || arcs->vocab <= 0 || !arcs->n_rows || !arcs->row_off || !arcs->arc_off) return NFST_ERR_ARG;
   if (arcs->total_arcs > 0 && (!arcs->src || !arcs->label || !arcs->dst)) return NFST_ERR_ARG;

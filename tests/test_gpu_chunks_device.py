@@ -10,6 +10,7 @@ from nfst_amd import _lib, ops, synth
 from nfst_amd.lattice import ChunkProgram, LatticeBatch
 from nfst_amd.scorers import LatticeScorer
 from oracle import oracle as O
+from tests import pack_cases as PC
 
 pytestmark = pytest.mark.gpu
 
@@ -97,6 +98,21 @@ def test_batches_that_are_not_cut(dev):
     wide = [synth.layered_lattice(5, n_states=300, avg_degree=6.0, vocab=64, width=48, span=1, max_degree=24)]
     lat, ref = _cut_both_ways(dev, wide, "force")
     assert ref is None
+    _assert_identical(lat, ref)
+
+
+_PC = PC.cases()
+
+
+@pytest.mark.parametrize("name", [n for n, c in _PC.items() if c.small and c.branches & {"junk_arcs", "inner_self_loops"}] + ["count_falls_back"])
+def test_branch_corpus_cut_as_the_host_cuts_it(dev, name):
+    """The cutter reads the packer's workspace (depths, heights, arc lists by canonical id).  The entries of
+    tests/pack_cases.py whose workspace differs from the input: unreachable states that own arcs (canonical ids shift,
+    depths of -1 between depths that count), self loops (arcs that are in no list), and the deep, narrow chain whose
+    planning pass counted its tiles by laying them out, which leaves other scans in the workspace than the counting
+    tables do."""
+    lat, ref = _cut_both_ways(dev, _PC[name].lats, "force")
+    assert ref is not None
     _assert_identical(lat, ref)
 
 

@@ -47,6 +47,9 @@
  *                                      K samples" (lightning.py:474-479)
  *   nfst_beam_step, nfst_beam_backtrack  lattice-constrained beam search for path-dependent scorers: the
  *                                      deterministic twin of the proposal sampler's step
+ *   nfst_swor                          k distinct paths per lattice drawn without replacement from the exact
+ *                                      posterior (stochastic beam search): the draws Estimators.iwae and
+ *                                      tune_proposal average over, without the copies of the best path
  *   nfst_positional, nfst_positional_viterbi  exact sweeps under scores that depend on the position of an arc on the
  *                                      path ([B, T, V] logits) and under a length budget: what the sampler side only
  *                                      truncates (emission_mask(has_to_end = length > max_length), NFST_ERR_LENGTH)
@@ -559,6 +562,48 @@ int nfst_beam_step(const nfst_batch *lat, const int64_t *state, const int64_t *i
  */
 int nfst_beam_backtrack(const int32_t *parent, const int64_t *symbol, const float *score, int32_t n_steps, int32_t n_lattices,
                         int32_t k, int32_t max_len, int32_t pad, int32_t *paths, int32_t *lengths, void *stream);
+
+/*
+ * k distinct paths per lattice, drawn without replacement from p(path) = exp S(path) / Z by stochastic beam search
+ * (Gumbel top-k; Kool, van Hoof and Welling 2019; DESIGN.md sections 2 and 4.15), the whole search in one launch.
+ * logbeta [total_rows] and logz64 [B] are what nfst_backward wrote for the same scores.  1 <= k <= 64.  Reads the
+ * canonical arrays only (row_ptr, arc_label, arc_dst, arc_w): any batch, any packing, the same bits.
+ * Per lattice b, all in float64, Z = logz64[b].  If Z is not finite the lattice is empty: n_paths = 0 and every entry
+ * has length 0, marks `pad`, arcs -1, logp = gumbel = -inf; kappa = -inf.
+ * A lattice keeps at most k slots (state s, score S of the prefix, perturbed score G) and starts with one: state 0,
+ * S = 0, G = +inf ("not conditioned").  Step t = 0, 1, ... while some slot is off the sink: the candidates in flat order
+ * are slot j ascending, then the slot's out-arcs in canonical order without self loops; a slot at the sink is one
+ * candidate, itself, unchanged (same S, same G, no noise).  For slot j at state s and arc a of rank r = a - row_ptr[s]:
+ *     e_a = the arc's float32 score: theta[label_a] (+ arc_w[a] if weighted) (+ arc_scores[a] if given), added in this order
+ *     S' = S_j + e_a,   phi = S' + logbeta[dst_a] - Z;   a candidate whose phi is not > -inf (NaN included) is dropped
+ *     g = phi - log(-log x),   x = (double)u + 2^-25
+ *     u = uniforms[b, t, j, r] (uniforms [B, max_len, k, max_degree] float32 in [0, 1); a rank r >= max_degree sets
+ *         *status = NFST_ERR_ARG and drops the candidate), or without uniforms word 0 of the Philox4x32-10 block keyed by
+ *         `seed` with the counter (b, t, j, r) (the block function of nfst_sample_paths)
+ * With M_j the largest g of slot j's kept candidates: G~ = g if G_j = +inf; otherwise the first candidate of the slot
+ * (in flat order) with g = M_j gets G~ = G_j, and every other one
+ *     v = G_j - g + log(1 - exp(g - M_j))   (evaluated as log(-expm1(g - M_j))),
+ *     G~ = G_j - max(v, 0) - log1p(exp(-|v|)).
+ * The k candidates with the largest G~ are kept (-0.0 and +0.0 alike, equal values to the earlier flat index) and take
+ * the new slots in flat order, not ranked: slot order is the lexicographic order of the prefixes.  kappa[b] is the
+ * largest G~ ever dropped, -inf if nothing was.  Every step stores (parent slot, arc) per slot in ws.
+ * If max_len steps pass and some slot is still off the sink, *status = NFST_ERR_LENGTH (status: device, one word,
+ * zeroed by the caller) and the lattice's outputs are those of an empty one.  Otherwise the slots are ranked by
+ * (G desc, slot asc) and entry i < n_paths[b] receives paths [B, k, max_len] marks padded with `pad`, path_arcs
+ * (optional) [B, k, max_len] canonical arc ids padded with -1, lengths [B, k], logp [B, k] = (float)(S - Z) and gumbel
+ * [B, k] = G (float64); entries from n_paths[b] on look like those of an empty lattice.
+ * ws: device workspace of nfst_swor_ws_bytes(lat, k, max_len) bytes (16-byte aligned, overwritten): 8 bytes per
+ * (lattice, step, slot) and, when k * vocab exceeds nfst_beam_lds_candidates(), 8 k vocab bytes per lattice for the keys
+ * of a step that LDS does not hold; both parts rounded up to 256 bytes.  No atomics: the same bits from launch to
+ * launch and, with uniforms, wherever the lattice sits in the batch.
+ * Null required pointers, max_len < 1, k < 1, uniforms with max_degree < 1 or a short workspace: NFST_ERR_ARG; k > 64:
+ * NFST_ERR_LIMIT; all on the host before any launch.
+ */
+int64_t nfst_swor_ws_bytes(const nfst_batch *lat, int32_t k, int32_t max_len);
+int nfst_swor(const nfst_batch *lat, const nfst_scores *scores, const float *logbeta, const double *logz64, int32_t k, int32_t max_len,
+              const float *uniforms, int32_t max_degree, uint64_t seed, int32_t pad, void *ws, int64_t ws_bytes, int32_t *paths,
+              int32_t *path_arcs, int32_t *lengths, float *logp, double *gumbel, double *kappa, int32_t *n_paths, int32_t *status,
+              void *stream);
 
 /*
  * Arc slack, the max-plus counterpart of the arc posteriors, and beam masks (DESIGN.md sections 2 and 4.7).  A path

@@ -80,16 +80,30 @@ struct BeamCand {
   }
 };
 
+// The selection below is shared with k_swor (swor_kernels.h).  Its key source is a parameter: key(e) is the 64-bit key of
+// flat candidate e < total, 0 = none, the same value every time it is asked.
+//
+// FLAT chooses how the candidates go to the threads.  false (k_beam_step, whose winners are ranked by key afterwards): e =
+// base + tid, 256 at a time.  true (k_swor, whose winners keep their order): every wave reads one contiguous share of the
+// flat index, 64 candidates at a time, so "the waves in order, each in the order it reads" is flat order and the
+// compaction keeps it.
+__device__ __forceinline__ int beam_share(int total) { return (total + kBeamThreads - 1) / kBeamThreads * 64; }
+__device__ __forceinline__ int beam_share_end(int total, int wv) {
+  const int e1 = beam_share(total) * (wv + 1);
+  return e1 < total ? e1 : total;
+}
+
 // how many keys are >= t1, t2, t3 (t1 <= t2 <= t3): wave ballots, then the waves' counts through cnt (LDS, [waves][3])
-template <bool IN_LDS>
-__device__ __forceinline__ void beam_count(const BeamCand &cd, const uint64_t *keys, int total, uint64_t t1, uint64_t t2, uint64_t t3,
-                                           int *cnt, int &c1, int &c2, int &c3) {
+template <bool FLAT, class KeyF>
+__device__ __forceinline__ void beam_count(KeyF key, int total, uint64_t t1, uint64_t t2, uint64_t t3, int *cnt, int &c1, int &c2,
+                                           int &c3) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   int a1 = 0, a2 = 0, a3 = 0;
-  for (int base = 0; base < total; base += kBeamThreads) {  // (the same trips in every lane: the ballots see whole waves)
-    const int e = base + tid;
+  const int e1 = FLAT ? beam_share_end(total, wv) : total;
+  for (int base = FLAT ? beam_share(total) * wv : 0; base < e1; base += FLAT ? 64 : kBeamThreads) {  // (the same trips in every lane: the ballots see whole waves)
+    const int e = base + (FLAT ? lane : tid);
     uint64_t k = 0;
-    if (e < total) k = IN_LDS ? keys[e] : cd.key(e);
+    if (e < e1) k = key(e);
     a1 += __popcll(__ballot(k >= t1));
     a2 += __popcll(__ballot(k >= t2));
     a3 += __popcll(__ballot(k >= t3));
@@ -101,14 +115,16 @@ __device__ __forceinline__ void beam_count(const BeamCand &cd, const uint64_t *k
   for (int w = 0; w < kBeamWaves; ++w) { c1 += cnt[w * 3]; c2 += cnt[w * 3 + 1]; c3 += cnt[w * 3 + 2]; }
 }
 
-// phases 3 and 4 up to the compacted winners: returns their number (<= K) and the candidates' number
-template <bool IN_LDS>
-__device__ __forceinline__ int beam_select(const BeamCand &cd, const uint64_t *keys, int total, int K, int (*cnt)[kBeamWaves * 3],
-                                           uint64_t *win, int &n_cand) {
+// phases 3 and 4 up to the compacted winners: the min(K, candidates) largest keys of KEY_BITS bits, of equal keys the
+// first in the order the threads read them (FLAT: the smaller flat index).  keep(pos, e, k) receives winner e with key k
+// and its position among the winners in that order, drop(k) every other candidate's key; returns the winners' number
+// and the candidates' number.  (The keys of k_beam_step are unique: every key >= the threshold wins.)
+template <int KEY_BITS, bool FLAT, class KeyF, class KeepF, class DropF>
+__device__ __forceinline__ int beam_select(KeyF key, int total, int K, int (*cnt)[kBeamWaves * 3], KeepF keep, DropF drop, int &n_cand) {
   const int tid = threadIdx.x, wv = tid >> 6;
   int c1, c2, c3, par = 0;
   // (consecutive passes write alternating count buffers: a buffer is written again only after the barrier of the pass between)
-  beam_count<IN_LDS>(cd, keys, total, 1, 1, 1, cnt[par], c1, c2, c3);
+  beam_count<FLAT>(key, total, 1, 1, 1, cnt[par], c1, c2, c3);
   par ^= 1;
   n_cand = c1;
   const int want = n_cand < K ? n_cand : K;
@@ -116,27 +132,34 @@ __device__ __forceinline__ int beam_select(const BeamCand &cd, const uint64_t *k
   uint64_t thr = 1;  // the largest t with `want` or more keys >= t: the want-th largest key
   if (n_cand > K) {
     thr = 0;
-    for (int sh = kBeamKeyBits - 2; sh >= 0; sh -= 2) {
-      beam_count<IN_LDS>(cd, keys, total, thr | (1ull << sh), thr | (2ull << sh), thr | (3ull << sh), cnt[par], c1, c2, c3);
+    for (int sh = KEY_BITS - 2; sh >= 0; sh -= 2) {
+      beam_count<FLAT>(key, total, thr | (1ull << sh), thr | (2ull << sh), thr | (3ull << sh), cnt[par], c1, c2, c3);
       par ^= 1;
       thr |= (uint64_t)(c3 >= want ? 3 : c2 >= want ? 2 : c1 >= want ? 1 : 0) << sh;
     }
   }
-  // compaction: the waves' totals first, then every wave writes behind the waves before it
-  beam_count<IN_LDS>(cd, keys, total, thr, thr, thr, cnt[par], c1, c2, c3);
-  int at = 0;
-  for (int w = 0; w < wv; ++w) at += cnt[par][w * 3];
-  for (int base = 0; base < total; base += kBeamThreads) {
-    const int e = base + tid;
+  // compaction: the waves' totals first (keys >= thr, keys > thr), then every wave writes behind the waves before it
+  const uint64_t above = thr + 1 ? thr + 1 : thr;  // (a threshold of all ones has nothing above it; no key is all ones)
+  beam_count<FLAT>(key, total, thr, above, above, cnt[par], c1, c2, c3);
+  const int ties = n_cand > K ? want - c2 : c1 - c2;  // keys equal to the threshold that win: the first in flat order
+  int gt = 0, eq = 0;
+  for (int w = 0; w < wv; ++w) { gt += cnt[par][w * 3 + 1]; eq += cnt[par][w * 3] - cnt[par][w * 3 + 1]; }
+  const int e1 = FLAT ? beam_share_end(total, wv) : total;
+  for (int base = FLAT ? beam_share(total) * wv : 0; base < e1; base += FLAT ? 64 : kBeamThreads) {
+    const int e = base + (FLAT ? (tid & 63) : tid);
     uint64_t k = 0;
-    if (e < total) k = IN_LDS ? keys[e] : cd.key(e);
-    const uint64_t m = __ballot(k >= thr);
-    const int pos = at + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    if (k >= thr && pos < kBeamMaxK) win[pos] = k;  // (keys are unique on a valid batch: pos < want)
-    at += __popcll(m);
+    if (e < e1) k = key(e);
+    const uint64_t mg = __ballot(k > thr), me = __ballot(k == thr);
+    const int g = gt + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mg >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mg, 0u));
+    const int q = eq + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(me >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)me, 0u));
+    const int pos = g + (q < ties ? q : ties);
+    if ((k > thr || (k == thr && q < ties)) && pos < kBeamMaxK) keep(pos, e, k);
+    else if (k != 0) drop(k);
+    gt += __popcll(mg);
+    eq += __popcll(me);
   }
   __syncthreads();
-  return c1 < kBeamMaxK ? c1 : kBeamMaxK;
+  return want;
 }
 
 __global__ __launch_bounds__(kBeamThreads) void k_beam_step(nfst_batch lat, BeamIn in, BeamOut out, int cap) {
@@ -175,12 +198,13 @@ __global__ __launch_bounds__(kBeamThreads) void k_beam_step(nfst_batch lat, Beam
   const int total = sl.off[K];
   const BeamCand cd{lat, in, sl, n0, m.row_off, m.n_rows};
   int n_cand = 0, n_win = 0;
+  const auto keep = [&](int pos, int, uint64_t k) { win[pos] = k; };
   if (total <= cap) {  // (the same in every thread of the workgroup)
     for (int e = tid; e < total; e += kBeamThreads) beam_keys[e] = cd.key(e);
     __syncthreads();
-    n_win = beam_select<true>(cd, beam_keys, total, K, cnt, win, n_cand);
+    n_win = beam_select<kBeamKeyBits, false>([&](int e) { return beam_keys[e]; }, total, K, cnt, keep, [](uint64_t) {}, n_cand);
   } else {
-    n_win = beam_select<false>(cd, beam_keys, total, K, cnt, win, n_cand);
+    n_win = beam_select<kBeamKeyBits, false>([&](int e) { return cd.key(e); }, total, K, cnt, keep, [](uint64_t) {}, n_cand);
   }
   if (tid >= 64) return;
   // wave 0: lane i ranks winner i and stores the outputs of its rank; the lanes from n_win to K store the empty ranks

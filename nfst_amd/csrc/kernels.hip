@@ -40,6 +40,7 @@ using namespace nfst_tile;
 #include "expect_kernels.h"
 #include "kbest_kernels.h"
 #include "beam_kernels.h"
+#include "swor_kernels.h"
 #include "slack_kernels.h"
 #include "intersect_kernels.h"
 #include "positional_kernels.h"
@@ -961,6 +962,47 @@ int nfst_beam_backtrack(const int32_t *parent, const int64_t *symbol, const floa
   const int64_t n = (int64_t)n_lattices * k;
   return launch(k_beam_backtrack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, parent, symbol, score,
                 (int)n_steps, (int)n_lattices, (int)k, (int)max_len, (int)pad, paths, lengths);
+}
+
+// ------------------------------------------------------------------ draws without replacement (swor_kernels.h)
+// workspace: the back pointers of every step's slots, then room for the keys of a step that LDS does not hold
+static int64_t swor_ws_layout(const nfst_batch *lat, int k, int max_len, char *base, SworWs *w) {
+  const int64_t B = lat->n_lattices, all = (int64_t)k * lat->vocab;  // a slot has at most one arc per label
+  WsCarve c{base};
+  char *bk = c.take(8 * B * max_len * k), *sp = all > kBeamLdsCand ? c.take(8 * B * all) : nullptr;
+  if (w) *w = {(int2 *)bk, (uint64_t *)sp};
+  return c.size;
+}
+static int swor_check(int32_t k, int32_t max_len) {
+  if (k < 1 || max_len < 1) return NFST_ERR_ARG;
+  return k > kSworMaxK ? NFST_ERR_LIMIT : NFST_OK;
+}
+
+int64_t nfst_swor_ws_bytes(const nfst_batch *lat, int32_t k, int32_t max_len) {
+  int rc = check_batch(lat);
+  if (rc) return rc;
+  if ((rc = swor_check(k, max_len))) return rc;
+  return swor_ws_layout(lat, k, max_len, nullptr, nullptr);
+}
+
+int nfst_swor(const nfst_batch *lat, const nfst_scores *scores, const float *logbeta, const double *logz64, int32_t k, int32_t max_len,
+              const float *uniforms, int32_t max_degree, uint64_t seed, int32_t pad, void *ws, int64_t ws_bytes, int32_t *paths,
+              int32_t *path_arcs, int32_t *lengths, float *logp, double *gumbel, double *kappa, int32_t *n_paths, int32_t *status,
+              void *stream) {
+  int rc = check_batch(lat);
+  if (rc) return rc;
+  if ((rc = check_scores(lat, scores))) return rc;
+  if ((rc = swor_check(k, max_len))) return rc;
+  if (!logbeta || !logz64 || !paths || !lengths || !logp || !gumbel || !kappa || !n_paths || !status) return NFST_ERR_ARG;
+  if (uniforms && max_degree < 1) return NFST_ERR_ARG;
+  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < swor_ws_layout(lat, k, max_len, nullptr, nullptr)) return NFST_ERR_ARG;
+  SworWs w;
+  swor_ws_layout(lat, k, max_len, (char *)ws, &w);
+  const int64_t all = (int64_t)k * lat->vocab;
+  const int cap = (int)(all < kBeamLdsCand ? all : kBeamLdsCand);
+  const SworIn in{logbeta, logz64, uniforms, seed, (int)max_degree, (int)k, (int)max_len, (int)pad};
+  const SworOut out{paths, path_arcs, lengths, logp, gumbel, kappa, n_paths, status};
+  return launch(k_swor, dim3(lat->n_lattices), dim3(kSworThreads), (int64_t)cap * 8, (hipStream_t)stream, *lat, *scores, in, w, out, cap);
 }
 
 // ------------------------------------------------------------------ arc slack and beam masks (slack_kernels.h)

@@ -481,10 +481,9 @@ __device__ __forceinline__ uint32_t mulhilo(uint32_t a, uint32_t b, uint32_t *hi
   *hi = (uint32_t)(p >> 32);
   return (uint32_t)p;
 }
-// Philox4x32-10, counter (walk, step, 0, 0), key from seed; first output word -> [0,1)
-// Philox4x32-10 block keyed by the seed, counter (walk, step / 4): four uniforms, one per step
-__device__ __forceinline__ void philox_uniform4(uint64_t seed, uint32_t walk, uint32_t block, float (&u)[4]) {
-  uint32_t c0 = walk, c1 = block, c2 = 0, c3 = 0;
+// Philox4x32-10 block keyed by the seed, counter (c0, c1, c2, c3): four uniforms in [0, 1)
+// (k_swor counts (lattice, step, slot, arc rank) in the four counter words and takes word 0)
+__device__ __forceinline__ void philox_uniform4(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, float (&u)[4]) {
   uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
   for (int i = 0; i < 10; ++i) {
     uint32_t hi0, hi1;
@@ -497,6 +496,10 @@ __device__ __forceinline__ void philox_uniform4(uint64_t seed, uint32_t walk, ui
   u[1] = (float)(c1 >> 8) * (1.0f / 16777216.0f);
   u[2] = (float)(c2 >> 8) * (1.0f / 16777216.0f);
   u[3] = (float)(c3 >> 8) * (1.0f / 16777216.0f);
+}
+// the walkers' form, counter (walk, step / 4, 0, 0): four uniforms, one per step
+__device__ __forceinline__ void philox_uniform4(uint64_t seed, uint32_t walk, uint32_t block, float (&u)[4]) {
+  philox_uniform4(seed, walk, block, 0u, 0u, u);
 }
 
 __device__ __forceinline__ float arc_score(const float *theta, const float *arc_w,

@@ -69,6 +69,9 @@ __device__ __forceinline__ int read_lane(int v, int l) { return __builtin_amdgcn
 __device__ __forceinline__ float read_lane(float v, int l) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
+__device__ __forceinline__ double read_lane(double v, int l) {
+  return __hiloint2double(read_lane(__double2hiint(v), l), read_lane(__double2loint(v), l));
+}
 
 // All-reduce over rows of L lanes (16, 32 or the whole wave) without LDS traffic: the four DPP stages reduce every row
 // of 16 lanes, v_readlane collects the four row results, combined as op(op(a, b), op(c, d)) -- float sums keep this
@@ -84,6 +87,7 @@ __device__ __forceinline__ T row_reduce(T v, Op op) {
 }
 struct OpMax {
   __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); }
+  __device__ __forceinline__ double operator()(double a, double b) const { return fmax(a, b); }
   __device__ __forceinline__ int operator()(int a, int b) const { return max(a, b); }
 };
 struct OpSum {
@@ -93,4 +97,5 @@ template <int L> __device__ __forceinline__ float row_max(float v) { return row_
 template <int L> __device__ __forceinline__ float row_sum(float v) { return row_reduce<L>(v, OpSum{}); }
 __device__ __forceinline__ float wave_max(float v) { return row_reduce<64>(v, OpMax{}); }
 __device__ __forceinline__ int wave_max(int v) { return row_reduce<64>(v, OpMax{}); }
+__device__ __forceinline__ double wave_max(double v) { return row_reduce<64>(v, OpMax{}); }
 __device__ __forceinline__ float wave_sum(float v) { return row_reduce<64>(v, OpSum{}); }

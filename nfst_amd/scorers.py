@@ -15,7 +15,7 @@ from typing import Any, Dict, Optional
 
 import torch
 
-from . import ops
+from . import ops, swor
 from .lattice import LatticeBatch
 
 
@@ -85,6 +85,13 @@ class LatticeScorer(torch.nn.Module):
         """The k best paths of every lattice with their scores under ``theta`` (``ops.k_best``; ``best`` is
         differentiable in theta)."""
         return ops.k_best(self._lat(), self.theta, k, max_len=max_len, pad=self.__pad__)
+
+    def sample_without_replacement(self, k: int, **kw) -> "swor.SworResult":
+        """``k`` distinct paths per lattice drawn without replacement from the exact posterior under ``theta``, with
+        their perturbed scores and the threshold of the Horvitz-Thompson weights (``swor.sample``; ``kw``: ``max_len``,
+        ``uniforms``, ``seed``, ``beta``, ``want_arcs``)."""
+        kw.setdefault("pad", self.__pad__)
+        return swor.sample(self._lat(), self.theta.detach(), k, **kw)
 
     def positional_log_z(self, pos_scores: torch.Tensor) -> torch.Tensor:
         """Differentiable exact log Z per lattice ``[B]`` when the mark at position t also scores ``pos_scores[(b,) t,

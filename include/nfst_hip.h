@@ -57,6 +57,8 @@
  *                                      budget) with their log-probabilities, and forced scores of given marks
  *   nfst_positional_kbest              the k best paths under those scores and that budget: the reranker's n-best
  *                                      list for a tagger's or encoder's per-position logits
+ *   nfst_positional_swor               k distinct paths drawn without replacement under those scores and that budget:
+ *                                      the weighted path set a sequence-level loss (F1, exact match, edit distance) needs
  *
  * Conventions
  *   - plain C: pointers and sizes only, no C++/torch types.
@@ -840,6 +842,32 @@ int nfst_intersect_write(const nfst_batch *lat, const int8_t *delta_t, int64_t d
  * decision, asked on the host as nfst_positional_plan; the launcher calls it.  Null required pointers, T < 1, a stride
  * that is neither 0 nor the full one, a non-finite score_coef or a short workspace return NFST_ERR_ARG.  All checks run
  * on the host before any launch.
+ *
+ * nfst_positional_swor (draws without replacement).  k distinct paths per lattice drawn without replacement from
+ * p_T(pi) = exp(S_T(pi) - log Z_T) over the paths of at most T arcs; paths, positions, pos, pos_stride, T, -inf entries
+ * and pos = NULL are exactly those of nfst_positional.  The launch runs the backward pass of nfst_positional with every
+ * beta row stored, as nfst_positional_sample does (logz64 / logz32 are the bits nfst_positional writes), then the search
+ * of nfst_swor on the caller's stream, one workgroup per lattice: the same kernel in a second flavour.  Every rule of
+ * nfst_swor holds as written there -- at most k slots in flat order, the conditioning on the parent's perturbed score
+ * with the first-holder rule, ties to the earlier flat index, kappa the largest G~ ever dropped, the final ranking by
+ * (G desc, slot asc), x = u + 2^-25, all arithmetic in float64 -- with max_len = T (uniforms [B, T, k, max_degree], or
+ * Philox with the counter (b, t, j, r)) and two differences.  For slot j at state s and arc a at step t:
+ *     S' = (S_j + (double)e_a) + (double)pos[b, t, label_a]      (e_a: nfst_swor's float32 arc score; without pos: S_j + e_a)
+ *     phi = S' + log beta_{t+1}(dst_a) - Z
+ * where beta_{t+1} is the (float64 mantissa m, int32 exponent e) row the backward pass stored, read as log(m) + e ln 2
+ * (-inf at m = 0), and Z = logz64[b] as the same launch wrote it.  The budget needs no rule of its own: beta_T is 0 off
+ * the sink, so a candidate that cannot finish within T arcs has phi = -inf and is dropped; the search ends within T
+ * steps and there is no NFST_ERR_LENGTH.  *status (device, one word, zeroed by the caller) only reports uniforms narrower
+ * than an out-degree (NFST_ERR_ARG, the candidate is dropped).  Outputs: paths and path_arcs (optional) [B, k, T], lengths,
+ * logp = (float)(S - Z), gumbel [B, k], kappa, n_paths [B], as nfst_swor; a lattice with log Z_T = -inf looks like
+ * nfst_swor's empty lattice and does not disturb its neighbours.  The op reads the canonical arrays only and uses no
+ * atomics: the same bits at every launch, for every packing and, with given uniforms, wherever the lattice sits in the batch.
+ * ws: nfst_positional_swor_ws_bytes(lat, T, k) bytes (16-byte aligned, overwritten): the NFST_POS_WS_SAMPLE parts of
+ * nfst_positional_ws_bytes, then the parts of nfst_swor_ws_bytes(lat, k, T) (back pointers [B, T, k], the key spill when
+ * k * vocab exceeds nfst_beam_lds_candidates()), every part rounded up to 256.  LDS and NFST_ERR_LIMIT: nfst_positional's,
+ * through nfst_positional_plan; k > 64 also returns NFST_ERR_LIMIT.  k < 1, T < 1, a bad stride, uniforms with
+ * max_degree < 1, null required pointers (logz32 and path_arcs are optional) or a short workspace return NFST_ERR_ARG.
+ * All checks run on the host before any launch.
  */
 #define NFST_POS_WS_POSTERIOR 1
 #define NFST_POS_WS_VITERBI 2
@@ -851,6 +879,11 @@ int nfst_positional_sample(const nfst_batch *lat, const nfst_scores *scores, con
 int nfst_positional_score_paths(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T,
                                 const int32_t *marks, int32_t k, float *path_score, int32_t *end_state, int32_t *lengths,
                                 void *stream);
+int64_t nfst_positional_swor_ws_bytes(const nfst_batch *lat, int32_t T, int32_t k);
+int nfst_positional_swor(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T, int32_t k,
+                         const float *uniforms, int32_t max_degree, uint64_t seed, int32_t pad, void *ws, int64_t ws_bytes,
+                         double *logz64, float *logz32, int32_t *paths, int32_t *path_arcs, int32_t *lengths, float *logp,
+                         double *gumbel, double *kappa, int32_t *n_paths, int32_t *status, void *stream);
 int nfst_positional_plan(const nfst_batch *lat, int32_t viterbi, int64_t *lds_bytes, int32_t *staged);
 int nfst_positional(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T, void *ws,
                     int64_t ws_bytes, double *logz64, float *logz32, double *len_logz, float *pos_post, float *arc_post,

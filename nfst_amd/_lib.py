@@ -168,6 +168,9 @@ def _load():
         "nfst_positional_viterbi": (C.c_int, [BP, SP, vp, i64, i32, vp, i64, vp, vp, vp, vp, i32, vp]),
         "nfst_positional_sample": (C.c_int, [BP, SP, vp, i64, i32, i32, vp, u64, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "nfst_positional_score_paths": (C.c_int, [BP, SP, vp, i64, i32, vp, i32, vp, vp, vp, vp]),
+        "nfst_positional_swor_ws_bytes": (i64, [BP, i32, i32]),
+        "nfst_positional_swor": (C.c_int, [BP, SP, vp, i64, i32, i32, vp, i32, u64, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                           vp, vp]),
         "nfst_positional_expectation_ws_bytes": (i64, [BP, i32]),
         "nfst_positional_expectation_plan": (C.c_int, [BP, C.POINTER(i64), C.POINTER(i32)]),
         "nfst_positional_expectation": (C.c_int, [BP, SP, vp, i64, i32, vp, i64, vp, i64, vp, f32, vp, i64, vp, vp, vp, vp, vp, vp,

@@ -1002,7 +1002,7 @@ int nfst_swor(const nfst_batch *lat, const nfst_scores *scores, const float *log
   const int cap = (int)(all < kBeamLdsCand ? all : kBeamLdsCand);
   const SworIn in{logbeta, logz64, uniforms, seed, (int)max_degree, (int)k, (int)max_len, (int)pad};
   const SworOut out{paths, path_arcs, lengths, logp, gumbel, kappa, n_paths, status};
-  return launch(k_swor, dim3(lat->n_lattices), dim3(kSworThreads), (int64_t)cap * 8, (hipStream_t)stream, *lat, *scores, in, w, out, cap);
+  return launch(k_swor<false>, dim3(lat->n_lattices), dim3(kSworThreads), (int64_t)cap * 8, (hipStream_t)stream, *lat, *scores, in, w, out, cap);
 }
 
 // ------------------------------------------------------------------ arc slack and beam masks (slack_kernels.h)
@@ -1166,6 +1166,45 @@ int nfst_positional_sample(const nfst_batch *lat, const nfst_scores *scores, con
   const dim3 grid((unsigned)((walks + kPosWalkWaves - 1) / kPosWalkWaves)), block(kPosWalkWaves * 64);
   if (extras_case(lat, scores)) return launch(k_positional_walk<true>, grid, block, 0, st, *lat, in, w, (int)k, uniforms, seed, wo);
   return launch(k_positional_walk<false>, grid, block, 0, st, *lat, in, w, (int)k, uniforms, seed, wo);
+}
+
+// workspace: the NFST_POS_WS_SAMPLE parts of nfst_positional, then the parts of nfst_swor with max_len = T
+static int64_t pos_swor_ws_layout(const nfst_batch *lat, int64_t T, int k, char *base, PosWs *w, SworWs *sw) {
+  const int64_t first = pos_ws_layout(lat, T, NFST_POS_WS_SAMPLE, base, w);
+  return first + swor_ws_layout(lat, k, (int)T, base ? base + first : nullptr, sw);
+}
+
+int64_t nfst_positional_swor_ws_bytes(const nfst_batch *lat, int32_t T, int32_t k) {
+  int rc = check_batch(lat);
+  if (rc) return rc;
+  if ((rc = swor_check(k, T))) return rc;
+  return pos_swor_ws_layout(lat, T, k, nullptr, nullptr, nullptr);
+}
+
+// the backward pass of nfst_positional alone with every beta row stored, as nfst_positional_sample, then the search of
+// nfst_swor in its positional flavour over those rows, one workgroup per lattice
+int nfst_positional_swor(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T, int32_t k,
+                         const float *uniforms, int32_t max_degree, uint64_t seed, int32_t pad, void *ws, int64_t ws_bytes,
+                         double *logz64, float *logz32, int32_t *paths, int32_t *path_arcs, int32_t *lengths, float *logp,
+                         double *gumbel, double *kappa, int32_t *n_paths, int32_t *status, void *stream) {
+  int rc = pos_check(lat, scores, pos, pos_stride, T);
+  if (rc) return rc;
+  if ((rc = swor_check(k, T))) return rc;
+  if (!logz64 || !paths || !lengths || !logp || !gumbel || !kappa || !n_paths || !status) return NFST_ERR_ARG;
+  if (uniforms && max_degree < 1) return NFST_ERR_ARG;
+  if ((rc = pos_check_ws(ws, ws_bytes, pos_swor_ws_layout(lat, T, k, nullptr, nullptr, nullptr)))) return rc;
+  PosWs w;
+  SworWs sw;
+  pos_swor_ws_layout(lat, T, k, (char *)ws, &w, &sw);
+  const PosIn pin = {*scores, pos, pos ? pos_stride : 0, (int)T};
+  const PosOut o = {logz64, logz32, nullptr, nullptr, nullptr};
+  const hipStream_t st = (hipStream_t)stream;
+  if ((rc = pos_launch_sum(lat, scores, pin, w, o, kPosModeRows, st))) return rc;
+  const int64_t all = (int64_t)k * lat->vocab;
+  const int cap = (int)(all < kBeamLdsCand ? all : kBeamLdsCand);
+  const SworPosIn in{{nullptr, logz64, uniforms, seed, (int)max_degree, (int)k, (int)T, (int)pad}, pos, pos ? pos_stride : 0, w.bm, w.be};
+  const SworOut out{paths, path_arcs, lengths, logp, gumbel, kappa, n_paths, status};
+  return launch(k_swor<true>, dim3(lat->n_lattices), dim3(kSworThreads), (int64_t)cap * 8, st, *lat, *scores, in, sw, out, cap);
 }
 
 int nfst_positional_score_paths(const nfst_batch *lat, const nfst_scores *scores, const float *pos, int64_t pos_stride, int32_t T,

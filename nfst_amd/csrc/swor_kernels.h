@@ -19,15 +19,31 @@
 //      key that loses goes to kappa
 //   4  wave 0 writes the new slots and their back pointers (parent slot, arc) into the workspace
 // After the last step wave 0 ranks the slots by (G desc, slot asc) and walks the back pointers.  No atomics.
+//
+// The kernel has two flavours, which differ only in where a candidate's score and continuation mass come from
+// (SworFlavour below); the step loop is written once.  k_swor<false> is nfst_swor as above.  k_swor<true> is
+// nfst_positional_swor: the arc at step t also scores pos[b, t, label], S' = (S + e_a) + pos[b, t, label_a], and the
+// continuation is log beta_{t+1}(dst_a) of the rows a launch of k_positional in kPosModeRows stored, read as
+// log(m) + e ln 2 per candidate (-inf at m = 0); Z is log Z_T of that launch and max_len is T.  beta_T is zero off the
+// sink, so a candidate that cannot finish within T arcs has phi = -inf and is dropped like any other: the search ends
+// within T steps by itself and the length check below never fires.
 constexpr int kSworThreads = kBeamThreads, kSworMaxK = kBeamMaxK;
 constexpr int kSworKeyBits = 64;
 
 struct SworIn {
-  const float *logbeta;
+  const float *logbeta;  // k_swor<false>: [total_rows] of nfst_backward (k_swor<true>: unused)
   const double *logz64;
   const float *uniforms;
   uint64_t seed;
   int max_degree, k, max_len, pad;
+};
+// k_swor<true> takes SworIn and, behind it, the position scores of PosIn and the stored beta rows of PosWs
+struct SworPosIn {
+  SworIn in;
+  const float *pos;  // (null: no position term)
+  int64_t pos_stride;
+  const double *bm;
+  const int *be;
 };
 // the caller's workspace (nfst_swor_ws_bytes)
 struct SworWs {
@@ -69,7 +85,46 @@ __device__ __forceinline__ int swor_slot_of(const SworSlots &sl, int e) {
   return lo;
 }
 
-__global__ __launch_bounds__(kSworThreads) void k_swor(nfst_batch lat, nfst_scores sc, SworIn in, SworWs ws, SworOut out, int cap) {
+// Where a candidate's score and its continuation mass come from.  score: the prefix score with arc a (float32 score e,
+// label l) appended at step t; rest: the log of the mass of the continuations of state dst after step t.
+template <bool POS>
+struct SworFlavour;
+template <>
+struct SworFlavour<false> {
+  typedef SworIn Arg;
+  const float *logbeta;
+  int row_off;
+  static __device__ __forceinline__ const SworIn &common(const Arg &a) { return a; }
+  __device__ __forceinline__ SworFlavour(const Arg &a, const Meta &m, int, int) : logbeta(a.logbeta), row_off(m.row_off) {}
+  __device__ __forceinline__ double score(double S, float e, int, int) const { return S + (double)e; }
+  __device__ __forceinline__ double rest(int, int dst) const { return (double)logbeta[row_off + dst]; }
+};
+template <>
+struct SworFlavour<true> {
+  typedef SworPosIn Arg;
+  const float *pos_b;
+  const double *bm;
+  const int *be;
+  int n, V;
+  static __device__ __forceinline__ const SworIn &common(const Arg &a) { return a.in; }
+  __device__ __forceinline__ SworFlavour(const Arg &a, const Meta &m, int b, int vocab)
+      : pos_b(a.pos ? a.pos + (size_t)a.pos_stride * b : nullptr), bm(a.bm + (size_t)(a.in.max_len + 1) * m.row_off),
+        be(a.be + (size_t)(a.in.max_len + 1) * m.row_off), n(m.n_rows), V(vocab) {}
+  __device__ __forceinline__ double score(double S, float e, int t, int l) const {
+    const double x = S + (double)e;
+    return pos_b ? x + (double)pos_b[(size_t)t * V + l] : x;
+  }
+  __device__ __forceinline__ double rest(int t, int dst) const {
+    const size_t i = (size_t)(t + 1) * n + dst;
+    const double mt = bm[i];
+    return mt > 0.0 ? log(mt) + (double)be[i] * 0.693147180559945309417232 : -__builtin_huge_val();
+  }
+};
+
+template <bool POS>
+__global__ __launch_bounds__(kSworThreads) void k_swor(nfst_batch lat, nfst_scores sc, typename SworFlavour<POS>::Arg arg, SworWs ws, SworOut out,
+                                                       int cap) {
+  const SworIn &in = SworFlavour<POS>::common(arg);
   extern __shared__ uint64_t swor_keys[];  // [cap]
   __shared__ SworSlots sl;
   __shared__ int cnt[2][kBeamWaves * 3];
@@ -80,6 +135,7 @@ __global__ __launch_bounds__(kSworThreads) void k_swor(nfst_batch lat, nfst_scor
   const Meta m = load_meta(lat.meta, b);
   const double kInf = __builtin_huge_val();
   const double Z = in.logz64[b];
+  const SworFlavour<POS> fl(arg, m, b, lat.vocab);
   const float *theta = sc.theta + (size_t)sc.theta_stride * b;
   const float *arc_w = lat.weighted ? lat.arc_w : nullptr;
   const int32_t *rp = lat.row_ptr + m.row_off + b;
@@ -104,7 +160,7 @@ __global__ __launch_bounds__(kSworThreads) void k_swor(nfst_batch lat, nfst_scor
         } else {
           const int a = sl.r0[j] + r, l = lat.arc_label[a], dst = lat.arc_dst[a];
           if (dst != s && l >= 0 && l < lat.vocab && dst >= 0 && dst < m.n_rows) {
-            const double phi = (sl.S[j] + (double)arc_score(theta, arc_w, sc.arc_scores, l, a)) + (double)in.logbeta[m.row_off + dst] - Z;
+            const double phi = fl.score(sl.S[j], arc_score(theta, arc_w, sc.arc_scores, l, a), t, l) + fl.rest(t, dst) - Z;
             if (phi > -kInf) {
               float u4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
               bool have = true;
@@ -166,7 +222,8 @@ __global__ __launch_bounds__(kSworThreads) void k_swor(nfst_batch lat, nfst_scor
           ns = sl.st[pj]; nS = sl.S[pj]; nG = sl.G[pj]; nl = sl.len[pj];
           if (ns != m.sink) {
             pa = sl.r0[pj] + (e - sl.off[pj]);
-            nS += (double)arc_score(theta, arc_w, sc.arc_scores, lat.arc_label[pa], pa);
+            const int l = lat.arc_label[pa];
+            nS = fl.score(nS, arc_score(theta, arc_w, sc.arc_scores, l, pa), t, l);
             ns = lat.arc_dst[pa];
             nG = swor_unord(win_k[tid]);
             ++nl;

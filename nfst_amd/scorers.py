@@ -145,6 +145,13 @@ class LatticeScorer(torch.nn.Module):
         kw.setdefault("pad", self.__pad__)
         return ops.positional_sample_paths(self._lat(), self.theta.detach(), k, pos_scores, **kw)
 
+    def positional_sample_without_replacement(self, pos_scores: torch.Tensor, k: int, **kw) -> "swor.SworResult":
+        """``k`` distinct paths per lattice drawn without replacement under ``theta`` plus per-position scores, with
+        their perturbed scores and the threshold of the Horvitz-Thompson weights (``swor.positional_sample``; ``kw``:
+        ``T``, ``uniforms``, ``seed``, ``want_arcs``)."""
+        kw.setdefault("pad", self.__pad__)
+        return swor.positional_sample(self._lat(), self.theta.detach(), k, pos_scores, **kw)
+
     def positional_score(self, pos_scores: torch.Tensor, marks: torch.Tensor):
         """``(path_score, end_state, lengths)`` of the forced walk of ``marks`` [B, K, T] under the same scores
         (``ops.positional_score_paths``)."""

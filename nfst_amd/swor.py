@@ -2,8 +2,9 @@
 (Gumbel top-k; Kool, van Hoof and Welling 2019), the Horvitz-Thompson weights that turn the drawn set into an unbiased
 estimate of any expectation, and the differentiable log-probabilities of the drawn paths (DESIGN.md sections 2 and 4.15).
 
-``sample`` is one launch of ``nfst_swor`` (include/nfst_hip.h) behind the beta sweep; everything else is torch
-arithmetic on its result.  There is no CPU implementation of the search.
+``sample`` is one launch of ``nfst_swor`` (include/nfst_hip.h) behind the beta sweep, ``positional_sample`` its twin
+under per-position scores and a length budget (``nfst_positional_swor``); everything else is
+torch arithmetic on their result.  There is no CPU implementation of the search.
 """
 from __future__ import annotations
 
@@ -67,6 +68,41 @@ def sample(lat: LatticeBatch, theta, k: int, arc_scores=None, max_len: Optional[
     return SworResult(paths, arcs, lens, logp, gumbel, kappa, n_paths, beta.logz)
 
 
+def positional_sample(lat: LatticeBatch, theta, k: int, pos_scores=None, T: Optional[int] = None, arc_scores=None,
+                      uniforms: Optional[torch.Tensor] = None, seed: int = 0, pad: int = 0, want_arcs: bool = True) -> SworResult:
+    """``sample`` under the scores of ``ops.positional_forward_backward``: k distinct paths per lattice drawn without
+    replacement from p_T(path) = exp(S_T(path)) / Z_T over the paths of at most ``T`` arcs, where the arc at position t
+    also scores ``pos_scores[(b,) t, label]`` (``nfst_positional_swor``; DESIGN.md sections 2 and 4.16).  What
+    ``ops.positional_sample_paths`` draws with replacement, without the copies of ``positional_viterbi``'s path: the
+    weighted path set that a sequence-level loss needs.  1 <= k <= 64.  ``T`` defaults as in ``ops.positional_k_best``: to
+    ``pos_scores.shape[-2]``, without ``pos_scores`` to the longest path of the batch.  ``uniforms`` [B, T, k, D] as in
+    ``sample``.  No draw overruns ``T`` and there is no length error: a prefix that cannot finish within ``T`` has no
+    mass.  ``paths`` / ``arcs`` are [B, k, T] and ``logz`` is log Z_T; ``log_weights`` and ``expectation`` work on the
+    result unchanged.  One backward pass with every beta row stored (12 (T + 1) total_rows bytes of workspace), then
+    the search."""
+    ops._need_gpu(lat)
+    _check_k(k)
+    sc, keep, pos, stride, T = ops._score_args(lat, theta, arc_scores, pos_scores, T)
+    dev, B = lat.device, lat.n_lattices
+    degree = 0
+    if uniforms is not None:
+        if not isinstance(uniforms, torch.Tensor) or uniforms.dim() != 4 or uniforms.shape[:3] != (B, T, k) or uniforms.shape[3] < 1:
+            raise ValueError(f"uniforms must be a tensor of shape [{B}, {T}, {k}, largest out-degree]")
+        uniforms = uniforms.detach().to(device=dev, dtype=torch.float32).contiguous()
+        degree = int(uniforms.shape[3])
+    ws, ws_bytes = _workspace(lat, "nfst_positional_swor_ws_bytes", T, int(k))
+    z64 = torch.empty(B, dtype=torch.float64, device=dev)
+    z32 = torch.empty(B, dtype=torch.float32, device=dev)
+    _, paths, arcs, lens, n_paths, logp = _path_outputs(lat, (B, k), T, arcs=want_arcs, n_paths=True, logq=True)
+    gumbel = torch.empty((B, k), dtype=torch.float64, device=dev)
+    kappa = torch.empty(B, dtype=torch.float64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    _call("nfst_positional_swor", lat, sc, pos, stride, T, int(k), uniforms, degree, C.c_uint64(seed & (2 ** 64 - 1)), int(pad),
+          ws, ws_bytes, z64, z32, paths, arcs, lens, logp, gumbel, kappa, n_paths, status)
+    _raise_status(status, "nfst_positional_swor")  # uniforms narrower than a state's out-arcs
+    return SworResult(paths, arcs, lens, logp, gumbel, kappa, n_paths, z32)
+
+
 def log_weights(r: SworResult) -> torch.Tensor:
     """log w [B, k] float64 of the Horvitz-Thompson weights w_i = p_i / q_i, q_i = 1 - exp(-exp(log p_i - kappa)) the
     probability that path i's perturbed score exceeds the threshold kappa: log w = logp - log(-expm1(-exp(logp - kappa))).
@@ -111,6 +147,51 @@ class _PathScore(torch.autograd.Function):
         theta, arc_scores = ctx.like
         d_theta, d_arc, _ = _path_score_grads(ctx.lat, arcs, g, theta if nt else None, arc_scores if na else None)
         return None, d_theta, d_arc, None, None
+
+
+class _PositionalPathScore(torch.autograd.Function):
+    """``_PathScore`` under positional scores (``ops.positional_score_paths``): the arc at position t of a path also marks
+    (t, label) in d / d pos_scores."""
+
+    @staticmethod
+    def forward(ctx, lat, theta, pos_scores, arc_scores, paths, arcs, T):
+        tot, _, _ = ops.positional_score_paths(lat, theta.detach(), paths, ops._det(pos_scores), T, ops._det(arc_scores))
+        ctx.lat = lat
+        ctx.like = (theta, pos_scores, arc_scores)
+        ctx.save_for_backward(arcs)
+        return tot
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (arcs,) = ctx.saved_tensors
+        nt, npos, na = ctx.needs_input_grad[1:4]
+        theta, pos_scores, arc_scores = ctx.like
+        d_theta, d_arc, d_pos = _path_score_grads(ctx.lat, arcs, g, theta if nt else None, arc_scores if na else None,
+                                                  pos_like=pos_scores if npos else None)
+        return None, d_theta, d_pos, d_arc, None, None, None
+
+
+def positional_log_prob(lat: LatticeBatch, theta: torch.Tensor, r: SworResult, pos_scores: Optional[torch.Tensor] = None,
+                        T: Optional[int] = None, arc_scores: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``log_prob`` for a result of ``positional_sample`` under the same scores and ``T``: the path's score
+    (``ops.positional_score_paths``) minus ``ops.positional_log_z``, float32 [B, k], the numbers of ``r.logp``,
+    differentiable in ``theta``, ``arc_scores`` and ``pos_scores``: the gradient is the path's label / arc / (position,
+    label) counts minus the posteriors of ``ops.positional_forward_backward``.  -inf beyond ``n_paths`` (no gradient
+    there)."""
+    if r.arcs is None:
+        raise ValueError("positional_log_prob needs the paths' arcs: positional_sample(..., want_arcs=True)")
+    if pos_scores is None and T is None:
+        T = int(r.paths.shape[2])
+    _, _, T = ops._positions(lat, pos_scores, T)
+    if r.paths.shape[2] != T:
+        raise ValueError(f"the paths have {r.paths.shape[2]} positions, T = {T}")
+    score = _PositionalPathScore.apply(lat, theta, pos_scores, arc_scores, r.paths, r.arcs, T)
+    # (log Z_T without pos_scores: a table of zeros adds +0.0 to every label score)
+    table = pos_scores if pos_scores is not None else torch.zeros((T, lat.vocab), dtype=torch.float32, device=lat.device)
+    logz = ops.positional_log_z(lat, theta, table, arc_scores)
+    ok = torch.arange(score.shape[1], device=score.device)[None, :] < r.n_paths[:, None]
+    return torch.where(ok, score - logz[:, None], torch.full_like(score, float("-inf")))
 
 
 def log_prob(lat: LatticeBatch, theta: torch.Tensor, r: SworResult, arc_scores: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -59,6 +59,9 @@
  *                                      list for a tagger's or encoder's per-position logits
  *   nfst_positional_swor               k distinct paths drawn without replacement under those scores and that budget:
  *                                      the weighted path set a sequence-level loss (F1, exact match, edit distance) needs
+ *   nfst_edit_distance                 that loss: the edit distance of every path of a set to a gold row, or between the
+ *                                      paths of a set (the k x k table of minimum-Bayes-risk selection from an n-best
+ *                                      list), in one launch instead of one host-side dynamic program per pair
  *
  * Conventions
  *   - plain C: pointers and sizes only, no C++/torch types.
@@ -606,6 +609,29 @@ int nfst_swor(const nfst_batch *lat, const nfst_scores *scores, const float *log
               const float *uniforms, int32_t max_degree, uint64_t seed, int32_t pad, void *ws, int64_t ws_bytes, int32_t *paths,
               int32_t *path_arcs, int32_t *lengths, float *logp, double *gumbel, double *kappa, int32_t *n_paths, int32_t *status,
               void *stream);
+
+/*
+ * Unit-cost edit distance (Levenshtein: insertion, deletion and substitution cost 1 each) between the rows of two path
+ * sets, the sequence-level loss the draws above exist for and the k x k table minimum-Bayes-risk selection needs
+ * (DESIGN.md sections 2 and 4.17).  All pointers are device memory:
+ *   a [n_sets, ka, La], b [n_sets, kb, Lb]   contiguous int32 token rows (the paths of nfst_kbest, nfst_swor, ...)
+ *   a_len [n_sets, ka], b_len [n_sets, kb]   the rows' lengths
+ *   out [n_sets, ka, kb]                     out[s, i, j] = distance of a[s, i, :a_len[s, i]] and b[s, j, :b_len[s, j]]
+ *   status                                   one word, zeroed by the caller
+ * Tokens are compared as plain integers and nothing beyond a row's length is read: the pad labels and -1 fills behind
+ * a path do not matter.  A length outside [0, La] (or [0, Lb]) is found on the device: *status = NFST_ERR_LENGTH, every
+ * pair of that row gets -1, no token of the pair is read, and every other pair of the launch is computed as usual.
+ * symmetric != 0 is the pairwise table of one set: it requires b == a, b_len == a_len, kb == ka and Lb == La
+ * (NFST_ERR_ARG otherwise), computes only i < j, writes both [i, j] and [j, i] and 0 on the diagonal, and gives the
+ * bits of the general mode called with b = a.
+ * La and Lb are at most NFST_EDIT_MAX_LEN: a longer row returns NFST_ERR_LIMIT, as do more than 4 (2^31 - 1) pairs.
+ * Null pointers, negative n_sets, ka or kb, La < 1 or Lb < 1 return NFST_ERR_ARG; all on the host before any launch.
+ * n_sets * ka * kb == 0 is a successful no-op (the data pointers may then be null).  One wave64 per pair, integer
+ * arithmetic only and no atomics: the same bits at every launch.
+ */
+#define NFST_EDIT_MAX_LEN 1024
+int nfst_edit_distance(const int32_t *a, const int32_t *a_len, int32_t ka, int32_t La, const int32_t *b, const int32_t *b_len,
+                       int32_t kb, int32_t Lb, int32_t n_sets, int32_t symmetric, int32_t *out, int32_t *status, void *stream);
 
 /*
  * Arc slack, the max-plus counterpart of the arc posteriors, and beam masks (DESIGN.md sections 2 and 4.7).  A path

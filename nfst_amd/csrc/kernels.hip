@@ -41,6 +41,7 @@ using namespace nfst_tile;
 #include "kbest_kernels.h"
 #include "beam_kernels.h"
 #include "swor_kernels.h"
+#include "edit_kernels.h"
 #include "slack_kernels.h"
 #include "intersect_kernels.h"
 #include "positional_kernels.h"
@@ -1003,6 +1004,22 @@ int nfst_swor(const nfst_batch *lat, const nfst_scores *scores, const float *log
   const SworIn in{logbeta, logz64, uniforms, seed, (int)max_degree, (int)k, (int)max_len, (int)pad};
   const SworOut out{paths, path_arcs, lengths, logp, gumbel, kappa, n_paths, status};
   return launch(k_swor<false>, dim3(lat->n_lattices), dim3(kSworThreads), (int64_t)cap * 8, (hipStream_t)stream, *lat, *scores, in, w, out, cap);
+}
+
+// ------------------------------------------------------------------ edit distance between path sets (edit_kernels.h)
+int nfst_edit_distance(const int32_t *a, const int32_t *a_len, int32_t ka, int32_t La, const int32_t *b, const int32_t *b_len, int32_t kb,
+                       int32_t Lb, int32_t n_sets, int32_t symmetric, int32_t *out, int32_t *status, void *stream) {
+  if (n_sets < 0 || ka < 0 || kb < 0 || La < 1 || Lb < 1) return NFST_ERR_ARG;
+  if (La > kEditMaxLen || Lb > kEditMaxLen) return NFST_ERR_LIMIT;
+  if (symmetric && (b != a || b_len != a_len || kb != ka || Lb != La)) return NFST_ERR_ARG;
+  if (!status) return NFST_ERR_ARG;
+  const int64_t n_pairs = (int64_t)n_sets * ka * kb;
+  if (n_pairs == 0) return NFST_OK;
+  if (!a || !a_len || !b || !b_len || !out) return NFST_ERR_ARG;
+  const int64_t blocks = (n_pairs + kEditWaves - 1) / kEditWaves;
+  if (blocks > INT32_MAX) return NFST_ERR_LIMIT;
+  const EditIn in{a, a_len, b, b_len, n_pairs, (int)ka, (int)La, (int)kb, (int)Lb, symmetric ? 1 : 0};
+  return launch(k_edit_distance, dim3((unsigned)blocks), dim3(kEditThreads), 0, (hipStream_t)stream, in, out, status);
 }
 
 // ------------------------------------------------------------------ arc slack and beam masks (slack_kernels.h)

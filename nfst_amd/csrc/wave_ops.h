@@ -73,6 +73,15 @@ __device__ __forceinline__ double read_lane(double v, int l) {
   return __hiloint2double(read_lane(__double2hiint(v), l), read_lane(__double2loint(v), l));
 }
 
+// The value of lane - 1, one DPP move across the whole wave (wave_shr:1, no LDS traffic); lane 0, which has no such
+// neighbour, takes `first`: without bound_ctrl the move does not write a lane whose source is out of range, so lane 0
+// keeps the old value of the destination, which is `first`.  The move reads the neighbour's register whatever the
+// neighbour is doing: call it with every lane of the wave active (wave-uniform trip counts; mask values, not control flow).
+constexpr int kDppWaveShr1 = 0x138;
+__device__ __forceinline__ int wave_shr1(int v, int first) {
+  return __builtin_amdgcn_update_dpp(first, v, kDppWaveShr1, 0xf, 0xf, false);
+}
+
 // All-reduce over rows of L lanes (16, 32 or the whole wave) without LDS traffic: the four DPP stages reduce every row
 // of 16 lanes, v_readlane collects the four row results, combined as op(op(a, b), op(c, d)) -- float sums keep this
 // order, (a + b) + (c + d).

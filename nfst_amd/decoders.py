@@ -12,7 +12,7 @@ from typing import NamedTuple, Optional, Union
 
 import torch
 
-from . import ops
+from . import ops, swor
 from .scorers import LatticeScorer
 
 
@@ -110,3 +110,54 @@ class BeamDecoder:
         final = score_all[n_steps - 1]
         paths, lengths = ops.beam_backtrack(parent_all, sym_all, final, B, k, n_steps=n_steps, max_len=T, pad=m.__pad__)
         return BeamResult(paths, lengths, final.reshape(B, k).clone(), n_steps)
+
+
+# ----------------------------------------------------------------------------- minimum-Bayes-risk selection
+def mbr_select(distances: torch.Tensor, log_weights: torch.Tensor, n_paths: Optional[torch.Tensor] = None):
+    """``(index [B] int64, risk [B, K] float64)``: the candidate of least expected distance to the weighted list it
+    stands in.  ``distances`` [B, K, K] (``ops.pairwise_edit_distance``), ``log_weights`` [B, K] unnormalised;
+    risk[b, i] = sum_j w[b, j] distances[b, i, j] with w the float64 softmax of ``log_weights`` over the valid entries.
+    Entry j is valid when j < ``n_paths[b]``; without ``n_paths``, when its weight is finite.  An invalid candidate has
+    risk +inf; ``index`` is the first valid candidate of least risk, -1 for a lattice with no valid entry (or whose
+    valid entries all weigh -inf: there is no mass to take an expectation under).  Pure torch: works on CPU tensors too."""
+    if distances.dim() != 3 or log_weights.dim() != 2 or distances.shape != (*log_weights.shape, log_weights.shape[1]):
+        raise ValueError("distances must be [B, K, K] and log_weights [B, K]")
+    lw = log_weights.detach().to(torch.float64)
+    D = distances.to(device=lw.device, dtype=torch.float64)
+    B, K = lw.shape
+    inf = float("inf")
+    if n_paths is None:
+        valid = torch.isfinite(lw)
+    else:
+        valid = torch.arange(K, device=lw.device)[None, :] < n_paths.to(lw.device).reshape(B, 1)
+    lw = torch.where(valid, lw, torch.full_like(lw, -inf))
+    top = lw.max(dim=1, keepdim=True).values if K > 0 else lw.new_full((B, 1), -inf)
+    some = (top > -inf) & (top < inf)
+    w = torch.where(some, torch.exp(lw - torch.where(some, top, torch.zeros_like(top))), torch.zeros_like(lw))
+    w = w / torch.where(some, w.sum(dim=1, keepdim=True), torch.ones_like(top))
+    # (an invalid column weighs 0 whatever its distance: 0 * D is only taken of the finite D of valid columns)
+    risk = (torch.where(valid[:, None, :], D, torch.zeros_like(D)) * w[:, None, :]).sum(dim=2)
+    risk = torch.where(valid & some, risk, torch.full_like(risk, inf))
+    if K == 0:
+        return torch.full((B,), -1, dtype=torch.int64, device=lw.device), risk
+    least = risk.min(dim=1, keepdim=True).values
+    first = ((risk == least) & valid & some).to(torch.int8).argmax(dim=1)  # (argmax of a 0/1 row: its first 1)
+    return torch.where(some[:, 0], first, torch.full_like(first, -1)), risk
+
+
+def mbr_decode(result):
+    """``(index [B] int64, risk [B, K] float64, distances [B, K, K] int32)`` of a drawn or enumerated path set under
+    edit distance: the pairwise table of ``ops.pairwise_edit_distance`` on the set's paths, then ``mbr_select``.
+    ``result`` is an ``ops.KBestResult`` or ``ops.PositionalKBestResult``, weighed by ``best`` (the path scores: log Z
+    cancels in the softmax), or a ``swor.SworResult``, weighed by its Horvitz-Thompson weights (``swor.log_weights``),
+    under which ``risk`` is the self-normalised estimate of every candidate's expected distance to a path of the
+    posterior."""
+    if isinstance(result, swor.SworResult):
+        logw = swor.log_weights(result)
+    elif isinstance(result, (ops.KBestResult, ops.PositionalKBestResult)):
+        logw = result.best.detach()
+    else:
+        raise TypeError("mbr_decode takes a KBestResult, a PositionalKBestResult or a SworResult")
+    D = ops.pairwise_edit_distance(result.paths, result.lengths)
+    index, risk = mbr_select(D, logw, result.n_paths)
+    return index, risk, D

@@ -1667,3 +1667,8 @@ def iwae(log_p: torch.Tensor, log_q: torch.Tensor):
     lm = torch.empty(B, dtype=torch.float32, device=log_p.device)
     _call("nfst_iwae", None, log_p, log_q, B, K, log_w, lm)
     return lm, log_w
+
+
+# ----------------------------------------------------------------------------- edit distance
+# (at the end: edit.py takes the marshalling helpers above)
+from .edit import EDIT_MAX_LEN, edit_distance, pairwise_edit_distance  # noqa: E402,F401

@@ -139,6 +139,44 @@ class LatticeScorer(torch.nn.Module):
         paths, lens, n = r.paths.cpu().numpy(), r.lengths.cpu().numpy(), r.n_paths.cpu().numpy()
         return [[(float(logp[b, j]), paths[b, j, :lens[b, j]].tolist()) for j in range(int(n[b]))] for b in range(lat.n_lattices)]
 
+    @staticmethod
+    def _mbr_entries(r) -> list:
+        from .decoders import mbr_decode
+
+        index, risk, _ = mbr_decode(r)
+        pick = index.clamp(min=0)
+        rows = torch.arange(index.shape[0], device=index.device)
+        marks, lens = r.paths[rows, pick].cpu().numpy(), r.lengths[rows, pick].cpu().numpy()
+        index, risk = index.cpu().numpy(), risk[rows, pick].cpu().numpy()
+        return [(float(risk[b]), marks[b, :lens[b]].tolist()) if index[b] >= 0 else (float("inf"), [])
+                for b in range(len(index))]
+
+    def mbr(self, k: int, draws: str = "k_best", **kw) -> list:
+        """Minimum-Bayes-risk decoding under edit distance: per lattice ``(risk, marks)``, the mark sequence among ``k``
+        candidates whose expected edit distance to the candidates, weighed by their probabilities, is least, and that
+        expectation (``decoders.mbr_decode``).  ``draws="k_best"``: the k best paths under ``theta``, weighed by their
+        scores; ``"swor"``: k paths drawn without replacement (``kw``: ``seed``, ``uniforms``, ...), weighed by their
+        Horvitz-Thompson weights.  ``kw`` goes to the draw (``max_len`` for both).  A lattice without a path gives
+        ``(inf, [])``."""
+        if draws == "k_best":
+            r = ops.k_best_terms(self._lat(), self.theta.detach(), k, pad=self.__pad__, **kw)
+        elif draws == "swor":
+            r = self.sample_without_replacement(k, **kw)
+        else:
+            raise ValueError(f"draws must be 'k_best' or 'swor', not {draws!r}")
+        return self._mbr_entries(r)
+
+    def positional_mbr(self, pos_scores: torch.Tensor, k: int, draws: str = "k_best", **kw) -> list:
+        """``mbr`` under ``theta`` plus per-position scores and their length budget (``positional_k_best`` or
+        ``positional_sample_without_replacement`` give the candidates)."""
+        if draws == "k_best":
+            r = ops.positional_k_best_terms(self._lat(), self.theta.detach(), k, pos_scores, pad=self.__pad__, **kw)
+        elif draws == "swor":
+            r = self.positional_sample_without_replacement(pos_scores, k, **kw)
+        else:
+            raise ValueError(f"draws must be 'k_best' or 'swor', not {draws!r}")
+        return self._mbr_entries(r)
+
     def positional_sample(self, pos_scores: torch.Tensor, k: int, **kw) -> "ops.PositionalSampleResult":
         """``k`` exact draws per lattice under ``theta`` plus per-position scores, each with its log-probability
         (``ops.positional_sample_paths``; ``kw``: ``T``, ``uniforms``, ``seed``, ``want_arcs``)."""

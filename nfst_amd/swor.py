@@ -120,7 +120,12 @@ def log_weights(r: SworResult) -> torch.Tensor:
 def expectation(r: SworResult, values: torch.Tensor, normalize: bool = False) -> torch.Tensor:
     """sum_i w_i values[b, i] per lattice, float64 [B]: an unbiased estimate of E_p[value], exact once k reaches the
     lattice's number of paths.  ``normalize=True`` divides by sum_i w_i (biased, lower variance).  Entries beyond
-    ``n_paths`` do not count, whatever their values."""
+    ``n_paths`` do not count, whatever their values.  The expected edit distance to a gold sequence ``gold`` [B, L] of
+    lengths ``gold_len`` [B], a sequence-level risk, is::
+
+        cost = ops.edit_distance(r.paths, r.lengths, gold, gold_len).double()
+        risk = swor.expectation(r, cost, normalize=True)
+    """
     w = torch.exp(log_weights(r))
     v = torch.where(w > 0, values.to(device=w.device, dtype=torch.float64), torch.zeros_like(w))
     tot = (w * v).sum(dim=1)

@@ -1068,6 +1068,11 @@ int nfst_proposal_step_backward(const nfst_batch *lat, const int64_t *value_stat
  * hid (in)] row-major; w: [hid]; hid <= 512.  Outputs: log_beta [total_rows] (natural log;
  * the reference returns exp of it), beta_hat [total_rows, hid].  ws: device
  * workspace of nfst_neural_ws_floats() floats, contents irrelevant.
+ * LDS: 8 bytes per row (max_rows rounded up to even), two staged tiles, 32 rows of beta_hat and three bfloat16 planes of
+ * 16 rows: with S = ((hid + 15) & ~15) + 4,  8 max_rows + 5152 + 128 S + 96 (hid + 8) bytes (the part in front of the
+ * planes rounded up to 16), whatever kernel hid selects.  More than 160 KiB returns NFST_ERR_LIMIT before any launch
+ * but the packing of Wh (hid a multiple of 64 from 256 on): max_rows <= 5340 at hid = 512, 7132 at 448; up to
+ * hid = 402 every batch (8191 rows) fits.
  */
 int64_t nfst_neural_ws_floats(const nfst_batch *lat, int32_t hid);
 int nfst_backward_neural(const nfst_batch *lat, const float *label_x, const float *wh, const float *w,
@@ -1084,6 +1089,12 @@ int nfst_backward_neural(const nfst_batch *lat, const float *label_x, const floa
  * dL / d (Wh . beta_hat(s)) per state, so that dL/dWh = gamma^T . beta_hat is one library GEMM on
  * the caller's side.  dL/dWx, dL/dbias and dL/d embeddings follow from grad_label_x through
  * label_x = emb . Wx^T + bias.  ws: nfst_neural_grad_ws_floats() floats, contents irrelevant.
+ * LDS, hid > 32: the forward call's rows and planes, 4 more bytes per row (max_rows rounded up to a multiple of 4) and
+ * wider staged tiles:  8 max_rows + 4 max_rows + 7216 + 128 S + 96 (hid + 8) bytes.  hid <= 32:  8 max_rows +
+ * 4 max_rows + 7216 bytes, and for hid <= 8 a [vocab, hid] float table of dL/dx beside them while it fits (global
+ * atomics otherwise).  More than 160 KiB returns NFST_ERR_LIMIT before any launch but the packing of wh_t.  The limit
+ * is lower than the forward call's -- max_rows <= 3388 against 5340 at hid = 512, 5776 at 384, every batch only up
+ * to hid = 252 -- so a batch between the two runs nfst_backward_neural and is refused here.
  */
 int64_t nfst_neural_grad_ws_floats(const nfst_batch *lat, int32_t hid);
 int nfst_backward_neural_grad(const nfst_batch *lat, const float *label_x, const float *wh_t, const float *w,

@@ -1574,7 +1574,9 @@ def backward_neural(lat: LatticeBatch, emb: torch.Tensor, Wx: torch.Tensor, Wh: 
     one [V, H] x [H, H] product made here (a plain library GEMM); everything that depends on the
     lattice runs in the kernel.  Differentiable in all five parameters (the reference's
     ``tune_proposal`` trains them through ``compute_beta``, lightning.py:339-406): the gradient is
-    ``nfst_backward_neural_grad`` plus two library GEMMs."""
+    ``nfst_backward_neural_grad`` plus two library GEMMs.  Both calls raise ``NfstError`` (NFST_ERR_LIMIT) before any
+    launch when their rows do not fit the 160 KiB of LDS; the gradient's limit is the lower one (3388 against 5340 rows
+    at H = 512, ``include/nfst_hip.h``), so a batch between the two runs forward and raises in ``backward()``."""
     _need_gpu(lat)
     f32 = dict(device=lat.device, dtype=torch.float32)
     emb, Wx, Wh, bias = emb.to(**f32), Wx.to(**f32), Wh.to(**f32), bias.to(**f32)

@@ -214,7 +214,8 @@ def beta_neural(n_rows: int, src, label, dst, emb, Wx, Wh, W, bias, arc_w=None):
     from beta(sink) = 1, beta_hat(sink) = 0 (:699-701, 720).  Parallel arcs count once each, as in
     the per-sample loop.  ``arc_w`` (float emission tables, scorers.py:1011-1027; not used by the
     reference's beta) adds a log weight per arc to W . t.  Returns (log beta [n_rows], beta_hat
-    [n_rows, H]); states that do not reach the sink get -inf / 0."""
+    [n_rows, H]); states that do not reach the sink get -inf / 0, and so does a state whose every
+    arc weighs -inf (it counts for nothing in its sources' sums)."""
     src = np.asarray(src, np.int64); label = np.asarray(label, np.int64); dst = np.asarray(dst, np.int64)
     emb = np.asarray(emb, np.float64); Wx = np.asarray(Wx, np.float64); Wh = np.asarray(Wh, np.float64)
     W = np.asarray(W, np.float64).reshape(-1); bias = np.asarray(bias, np.float64)
@@ -247,11 +248,11 @@ def beta_neural(n_rows: int, src, label, dst, emb, Wx, Wh, W, bias, arc_w=None):
                 t = np.tanh(x[label[arcs]] + bhat[dst[arcs]] @ Wh.T)  # [n, H]
                 lm = t @ W + aw[arcs] + logb[dst[arcs]]
                 mx = lm.max()
+                ready.append(s)  # (a state whose every arc weighs -inf stays at -inf / 0 and still releases its sources)
                 if np.isneginf(mx):
                     continue
                 logb[s] = mx + np.log(np.exp(lm - mx).sum())
                 bhat[s] = np.exp(lm - logb[s]) @ t
-                ready.append(s)
     return logb, bhat
 
 

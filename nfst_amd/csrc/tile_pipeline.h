@@ -1187,34 +1187,59 @@ __device__ __forceinline__ int tile_math3(const Dec2 &c, const v2f (&vv)[4], con
 #pragma unroll
   for (int j = 1; j < 4; ++j) dmax = max(dmax, d[j]);
   constexpr int kZeroish = -(1 << 27);
-  const uint64_t bad = __builtin_amdgcn_ballot_w64(((uint32_t)(dmax + 64) > 128u) & (dmax > kZeroish));
-  const int ref_old = ref;
   float M = ldexpf(mt[0], d[0]);
 #pragma unroll
   for (int j = 1; j < 4; ++j) M += ldexpf(mt[j], d[j]);
+  // The three stages of the segmented sum, with the test for the exact path -- ((uint32_t)(dmax + 64) > 128u) & (dmax > kZeroish),
+  // which needs nothing of the sum -- in the wait states of the first two: a DPP read needs two wait states after the
+  // vector write of its source, and the compiler does not look into this block (it used to put the test in front of it
+  // and the block held one s_nop 1 per stage).  The mask leaves as a scalar pair; the branch stays behind the last stage.
+  uint64_t bad;
+  int tt;
   asm volatile(
-      "s_nop 1\n\t"  // (a DPP read needs two wait states after the vector write of its source: the compiler does not look into this block)
+      "v_add_u32_e32 %[t], 64, %[dm]\n\t"
+      "v_cmp_lt_u32_e32 vcc, 0x80, %[t]\n\t"
       "v_fmac_f32_dpp %[m], %[m], %[k0] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
+      "v_cmp_gt_i32_e64 %[bad], %[dm], %[kz]\n\t"
+      "s_and_b64 %[bad], %[bad], vcc\n\t"
       "v_fmac_f32_dpp %[m], %[m], %[k1] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-      "s_nop 1\n\t"
+      "s_nop 1\n\t"  // the last stage waits for the second one's sum: nothing of this tile is left that does not depend on it
       "v_fmac_f32_dpp %[m], %[m], %[k2] row_half_mirror row_mask:0xf bank_mask:0xf"
-      : [m] "+v"(M)
-      : [k0] "v"(c.k0), [k1] "v"(c.k1), [k2] "v"(c.k2));
-  int E = ref_old;
+      : [m] "+v"(M), [bad] "=&s"(bad), [t] "=&v"(tt)
+      : [k0] "v"(c.k0), [k1] "v"(c.k1), [k2] "v"(c.k2), [dm] "v"(dmax), [kz] "s"(kZeroish)
+      : "vcc");
+  // (mantissa, exponent): mant = frexp(M, &ex), eo = M != 0 ? max(E + ex, kEZero) : kEZero -- an exact zero keeps the exponent
+  // that never wins a maximum.  On the fast path E is the wave-uniform reference: a scalar operand of the add behind frexp.
+  // The fast pack is computed unconditionally, like the fast sum, and the rare exact path packs for itself and replaces it:
+  // merged in one vector register in front of a common pack, E cost a scalar-to-vector copy per tile.  (Written in C++ the
+  // pack came out with no-ops between the compare and the select that reads vcc, two wait states later; in this order
+  // its own instructions fill them.  volatile: not to be sunk into the fast side of the branch, which hipcc then guards by
+  // three more scalar instructions.)
+  static_assert((uint32_t)kEZero == 0xf0000000u, "the literal of the pack below");
+  float mant;
+  int eo;
+  asm volatile(
+      "v_frexp_exp_i32_f32_e32 %[e], %[m]\n\t"
+      "v_cmp_neq_f32_e32 vcc, 0, %[m]\n\t"
+      "v_frexp_mant_f32_e32 %[mant], %[m]\n\t"
+      "v_add_u32_e32 %[e], %[ref], %[e]\n\t"
+      "v_max_i32_e32 %[e], 0xf0000000, %[e]\n\t"
+      "v_cndmask_b32_e32 %[e], %[ez], %[e], vcc"
+      : [mant] "=&v"(mant), [e] "=&v"(eo)
+      : [m] "v"(M), [ref] "s"(ref), [ez] "v"(kEZero)
+      : "vcc");
   if (__builtin_expect(bad != 0, 0)) {
     M = ldexpf(mt[0], d[0] - dmax);
 #pragma unroll
     for (int j = 1; j < 4; ++j) M += ldexpf(mt[j], d[j] - dmax);
-    E = dmax + ref_old;
+    int E = dmax + ref;
     const uint64_t m0 = __builtin_amdgcn_ballot_w64(c.k0 != 0.0f), m1 = __builtin_amdgcn_ballot_w64(c.k1 != 0.0f),
                    m2 = __builtin_amdgcn_ballot_w64(c.k2 != 0.0f);
     seg_reduce_exec<3>(M, E, m0, m1, m2);
+    int ex;
+    mant = frexpf(M, &ex);
+    eo = (M != 0.0f) ? max(E + ex, kEZero) : kEZero;
   }
-  // (mantissa, exponent): an exact zero keeps the exponent that never wins a maximum
-  int ex;
-  const float mant = frexpf(M, &ex);
-  const int eo = (M != 0.0f) ? max(E + ex, kEZero) : kEZero;
   *(lds_v2f *)(uintptr_t)c.dst = v2f{mant, __int_as_float(eo)};
   return dmax;
 }
@@ -1271,27 +1296,35 @@ __device__ __forceinline__ int tile_math3p(const Dec2P &c, const Rec64 (&vv)[4],
 #pragma unroll
   for (int j = 1; j < 4; ++j) dmax = max(dmax, d[j]);
   constexpr int kZeroish = -(1 << 27);
+  static_assert((uint32_t)kZeroish == 0xf8000000u, "the literal of the window test below");
   const uint32_t wide = (c.dst >> 25) & 1u;  // the tile's largest group exceeds 8 lanes (same in every lane)
-  const uint64_t bad = __builtin_amdgcn_ballot_w64((((uint32_t)(dmax + 900) > 1800u) & (dmax > kZeroish)) | (wide != 0));
+  const uint64_t bad_wide = __builtin_amdgcn_ballot_w64(wide != 0);
   // (v_ldexp_f64 takes any int32 exponent: an exact zero's exponent, about -2^28, gives zero)
   double M = ldexp(mt[0], d[0]);
 #pragma unroll
   for (int j = 1; j < 4; ++j) M += ldexp(mt[j], d[j]);
   // the three stages: partner's value by two v_mov_b32_dpp (every lane has a partner: the destination needs no initial
-  // value), times the 0 / 1 multiplier whose high word the tile wave left in the slot
+  // value), times the 0 / 1 multiplier whose high word the tile wave left in the slot.  The two wait states between the
+  // write of a stage's sum and its DPP reads hold the window test -- ((uint32_t)(dmax + 900) > 1800u) & (dmax > kZeroish),
+  // which needs nothing of the sum -- in the first two stages, as in tile_math3.
+  uint64_t bad_range;
   {
-    int plo, phi;
-#define NFST_DPP_PAIR(CTRL)                                                                                              \
-    asm volatile("s_nop 1\n\tv_mov_b32_dpp %0, %2 " CTRL " row_mask:0xf bank_mask:0xf\n\tv_mov_b32_dpp %1, %3 " CTRL      \
-                 " row_mask:0xf bank_mask:0xf" : "=&v"(plo), "=&v"(phi) : "v"(__double2loint(M)), "v"(__double2hiint(M)))
-    NFST_DPP_PAIR("quad_perm:[1,0,3,2]");
+    int plo, phi, tt;
+#define NFST_DPP_PAIR(FILL, ...)                                                                                         \
+    asm volatile(FILL "\n\tv_mov_b32_dpp %[plo], %[mlo] " __VA_ARGS__ " row_mask:0xf bank_mask:0xf\n\tv_mov_b32_dpp %[phi], %[mhi] " __VA_ARGS__ \
+                 " row_mask:0xf bank_mask:0xf" : [plo] "=&v"(plo), [phi] "=&v"(phi), [bad] "+s"(bad_range), [t] "+v"(tt)  \
+                 : [mlo] "v"(__double2loint(M)), [mhi] "v"(__double2hiint(M)), [dm] "v"(dmax), [lim] "s"(1800) : "vcc")
+    asm volatile("" : [bad] "=s"(bad_range), [t] "=v"(tt));  // (written by the first block)
+    // (the first block's result goes to the scalar pair, not to vcc: the compiler's own code lies between the blocks)
+    NFST_DPP_PAIR("v_add_u32_e32 %[t], 0x384, %[dm]\n\tv_cmp_gt_u32_e64 %[bad], %[t], %[lim]", "quad_perm:[1,0,3,2]");
     M = fma(__hiloint2double(phi, plo), __hiloint2double((int)c.k0, 0), M);
-    NFST_DPP_PAIR("quad_perm:[2,3,0,1]");
+    NFST_DPP_PAIR("v_cmp_lt_i32_e32 vcc, 0xf8000000, %[dm]\n\ts_and_b64 %[bad], %[bad], vcc", "quad_perm:[2,3,0,1]");
     M = fma(__hiloint2double(phi, plo), __hiloint2double((int)c.k1, 0), M);
-    NFST_DPP_PAIR("row_half_mirror");
+    NFST_DPP_PAIR("s_nop 1", "row_half_mirror");  // the last stage waits for the second one's sum: nothing independent of it is left
     M = fma(__hiloint2double(phi, plo), __hiloint2double((int)c.k2, 0), M);
 #undef NFST_DPP_PAIR
   }
+  const uint64_t bad = bad_range | bad_wide;
   int E = ref;
   if (__builtin_expect(bad != 0, 0)) {
     const int g = (int)ctl_g(c.dst);
@@ -1347,7 +1380,11 @@ __device__ __forceinline__ void tile_sweep2(int n_tiles, const uint32_t *ring, i
   if (n_tiles <= 0) return;
   constexpr uint32_t SB = P::kSlotBytes;
   const uint32_t ring_base = lds_addr(ring), ring_end = ring_base + (uint32_t)R * SB;
-  const uint32_t land_a = lds_addr(land), prog_a = lds_addr(prog);
+  // (the two addresses stay in vector registers over the loop -- the empty asm hides that they are wave-uniform --: from
+  // scalar registers hipcc copied them into a vector register in front of every flag read and every publication, four
+  // times per trip)
+  uint32_t land_a = lds_addr(land), prog_a = lds_addr(prog);
+  asm volatile("" : "+v"(land_a), "+v"(prog_a));
   // the four flags in one read: .x = min over the tiles T+1 .. T+3 of (their wave's flag - their offset): all three are decoded
   // iff it exceeds T; .y = the same for tile T+4, which the trip's last step fetches (with a ring of four slots that tile can only
   // be written once the trip has consumed its first tile)

@@ -62,6 +62,8 @@
  *   nfst_edit_distance                 that loss: the edit distance of every path of a set to a gold row, or between the
  *                                      paths of a set (the k x k table of minimum-Bayes-risk selection from an n-best
  *                                      list), in one launch instead of one host-side dynamic program per pair
+ *   nfst_lattice_edit                  the distance between a gold row and a whole lattice with the path that attains
+ *                                      it: the oracle error rate of a lattice and the closest reachable string
  *
  * Conventions
  *   - plain C: pointers and sizes only, no C++/torch types.
@@ -632,6 +634,47 @@ int nfst_swor(const nfst_batch *lat, const nfst_scores *scores, const float *log
 #define NFST_EDIT_MAX_LEN 1024
 int nfst_edit_distance(const int32_t *a, const int32_t *a_len, int32_t ka, int32_t La, const int32_t *b, const int32_t *b_len,
                        int32_t kb, int32_t Lb, int32_t n_sets, int32_t symmetric, int32_t *out, int32_t *status, void *stream);
+
+/*
+ * The edit distance between a reference string and a whole lattice, with the path that attains it: the oracle path
+ * (DESIGN.md sections 2 and 4.18).  For lattice b the reference is r = ref[b * R .. b * R + n), n = ref_len[b], int32
+ * tokens compared as plain integers; nothing beyond n is read.  A path runs from state 0 to the sink (self loops are on
+ * no path), its string is the labels of its arcs, bos to eos, as nfst_kbest writes them.  d(path) is the unit-cost
+ * Levenshtein distance of that string and r (nfst_edit_distance's).  The path score is nfst_kbest's float32 sum: the
+ * sink holds 0.0f and arc a extends value v to c = e_a + (theta[label_a] + v), e_a = 0.0f (+ arc_w[a] if weighted)
+ * (+ arc_scores[a] if given); a path of score -inf or NaN is no candidate.  scores == NULL: every term is 0.0f (arc_w
+ * is not read either) and every path counts.
+ * Result: the lexicographic optimum, least distance, then greatest score (scores are ordered by their bits, so +0.0
+ * ranks above -0.0), from cells E[s][j] = (dist, score), j tokens of r consumed:
+ *     E[sink][j] = (n - j, 0.0f)
+ *     E[s][j]    = the best of, over the out-arcs a: s -> d, d != s, label l:
+ *                      insertion           (E[d][j].dist + 1, c(E[d][j].score))
+ *                      match/substitution  (E[d][j + 1].dist + [l != r[j]], c(E[d][j + 1].score))      for j < n
+ *                  and then of the deletion (E[s][j + 1].dist + 1, E[s][j + 1].score), j from n - 1 down to 0.
+ * The answer is E[0][0].  The walk from (0, 0) takes at every cell the first candidate whose (dist, score bits) equal
+ * the cell's: arcs in canonical order, per arc match/substitution before insertion, the deletion last; at the sink the
+ * remaining tokens of r are deletions.
+ * Outputs (device): distance [B]; score [B] (optional); paths [B, max_len] labels padded with `pad`; path_arcs
+ * (optional) [B, max_len] canonical arc ids padded with -1; align (optional) [B, max_len]: for every arc of the path the
+ * index in r of the token it was matched or substituted with, -1 for an insertion, padded with -1; lengths [B]; counts
+ * (optional) [B, 3] = (substitutions, insertions, deletions), which sum to distance[b].  A lattice without a candidate
+ * path gets distance -1, score -inf, length 0, pads and counts 0.
+ * A ref_len[b] outside [0, R] is found on the device: *status = NFST_ERR_LENGTH (status: device, one word, zeroed by the
+ * caller), that lattice gets the outputs of one without a path and none of its tokens is read; the other lattices are
+ * computed as usual.  An oracle path longer than max_len is cut there (length max_len; distance, score and counts are
+ * those of the whole path) and sets *status = NFST_ERR_LENGTH.
+ * ws: device workspace of nfst_lattice_edit_ws_bytes(lat, R) bytes (16-byte aligned, overwritten): (R + 1) cells of 8
+ * bytes per row of the batch plus 12 bytes per row.  Reads the canonical arrays only: any batch, any packing, the same
+ * bits; no atomics on values: the same bits at every launch.
+ * Null required pointers, R < 1, max_len < 1 or a short workspace: NFST_ERR_ARG; R > NFST_EDIT_MAX_LEN: NFST_ERR_LIMIT;
+ * all on the host before any launch.  n_lattices == 0 is a successful no-op (nfst_lattice_edit_ws_bytes: 0).
+ */
+int64_t nfst_lattice_edit_ws_bytes(const nfst_batch *lat, int32_t R);
+int nfst_lattice_edit(const nfst_batch *lat, const nfst_scores *scores /* or NULL */, const int32_t *ref, const int32_t *ref_len,
+                      int32_t R /* row stride of ref */, void *ws, int64_t ws_bytes, int32_t *distance /* [B] */,
+                      float *score /* [B] or NULL */, int32_t *paths, int32_t *path_arcs /* or NULL */, int32_t *align /* or NULL */,
+                      int32_t *lengths /* [B] */, int32_t *counts /* [B,3] or NULL */, int32_t max_len, int32_t pad,
+                      int32_t *status, void *stream);
 
 /*
  * Arc slack, the max-plus counterpart of the arc posteriors, and beam masks (DESIGN.md sections 2 and 4.7).  A path

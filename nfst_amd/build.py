@@ -90,7 +90,9 @@ def check_resources(res: dict) -> list:
     * no sweep kernel may spill vector registers: the tile / sweep loops are latency chains.  The pattern
       ``k_positional`` is a prefix on purpose: it covers ``k_positional<..>``, ``k_positional_viterbi<..>`` and the
       kernels of the draws, ``k_positional_walk<..>`` (a chain of dependent loads and scan stages per position) and
-      ``k_positional_score``.
+      ``k_positional_score``;
+    * the kernels of ``nfst_lattice_edit`` (``k_lattice_edit_sweep``, ``k_lattice_edit_walk``) use no scratch memory
+      (DESIGN.md section 4.18).
     """
     bad = []
     for name, r in res.items():
@@ -101,6 +103,8 @@ def check_resources(res: dict) -> list:
         if (re.search(r"k_(forward_backward|backward|viterbi_tw)<", name) or re.search(r"k_(expect|kbest)_sweep\b|k_arc_slack\b|k_beam_step\b|k_positional", name)) \
                 and r.get("vgpr_spill", 0) != 0:
             bad.append(f"{name}: VGPR spill {r.get('vgpr_spill')} in a sweep kernel")
+        if re.search(r"k_lattice_edit_", name) and (r.get("vgpr_spill", 0) != 0 or r.get("scratch", 0) != 0):
+            bad.append(f"{name}: VGPR spill {r.get('vgpr_spill')}, scratch {r.get('scratch')} in a kernel that must use no scratch")
         if not fused and re.search(r"k_(forward_backward|backward)<", name) and r.get("agprs", 0) != 0:
             bad.append(f"{name}: {r.get('agprs')} AGPRs in a kernel that stages nothing in them")
     return bad

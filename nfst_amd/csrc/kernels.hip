@@ -42,6 +42,7 @@ using namespace nfst_tile;
 #include "beam_kernels.h"
 #include "swor_kernels.h"
 #include "edit_kernels.h"
+#include "lattice_edit_kernels.h"
 #include "slack_kernels.h"
 #include "intersect_kernels.h"
 #include "positional_kernels.h"
@@ -1020,6 +1021,56 @@ int nfst_edit_distance(const int32_t *a, const int32_t *a_len, int32_t ka, int32
   if (blocks > INT32_MAX) return NFST_ERR_LIMIT;
   const EditIn in{a, a_len, b, b_len, n_pairs, (int)ka, (int)La, (int)kb, (int)Lb, symmetric ? 1 : 0};
   return launch(k_edit_distance, dim3((unsigned)blocks), dim3(kEditThreads), 0, (hipStream_t)stream, in, out, status);
+}
+
+// ------------------------------------------------------------------ edit distance to a whole lattice (lattice_edit_kernels.h)
+// workspace: R + 1 cells of 8 bytes for every row of the batch, then the level arrays of k_kbest_levels
+static int64_t le_ws_layout(const nfst_batch *lat, int R, char *base, LeWs *w) {
+  const int64_t TR = lat->total_rows, B = lat->n_lattices;
+  WsCarve c{base};
+  char *ce = c.take(8 * TR * ((int64_t)R + 1)), *od = c.take(4 * TR), *lv = c.take(4 * (TR + B)), *nl = c.take(4 * B);
+  if (w) *w = {(int2 *)ce, (int *)od, (int *)lv, (int *)nl, R + 1};
+  return c.size;
+}
+static int le_check_R(int32_t R) { return R < 1 ? NFST_ERR_ARG : (R > kEditMaxLen ? NFST_ERR_LIMIT : NFST_OK); }
+
+int64_t nfst_lattice_edit_ws_bytes(const nfst_batch *lat, int32_t R) {
+  if (!lat) return NFST_ERR_ARG;
+  int rc = le_check_R(R);
+  if (rc) return rc;
+  if (lat->n_lattices == 0) return 0;
+  if ((rc = check_batch(lat))) return rc;
+  return le_ws_layout(lat, R, nullptr, nullptr);
+}
+
+int nfst_lattice_edit(const nfst_batch *lat, const nfst_scores *scores, const int32_t *ref, const int32_t *ref_len, int32_t R, void *ws,
+                      int64_t ws_bytes, int32_t *distance, float *score, int32_t *paths, int32_t *path_arcs, int32_t *align,
+                      int32_t *lengths, int32_t *counts, int32_t max_len, int32_t pad, int32_t *status, void *stream) {
+  if (!lat || !status || max_len < 1) return NFST_ERR_ARG;
+  int rc = le_check_R(R);
+  if (rc) return rc;
+  if (lat->n_lattices == 0) return NFST_OK;
+  if ((rc = check_batch(lat))) return rc;
+  if (scores && (rc = check_scores(lat, scores))) return rc;
+  if (!ref || !ref_len || !distance || !paths || !lengths) return NFST_ERR_ARG;
+  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < le_ws_layout(lat, R, nullptr, nullptr)) return NFST_ERR_ARG;
+  const int64_t lds_lev = (int64_t)lat->max_rows * 12 + 16;
+  const int64_t lds_sweep = 8 * (int64_t)kLeItems + ((int64_t)lat->max_rows * 2 + 1) * 4;
+  LeWs w;
+  le_ws_layout(lat, R, (char *)ws, &w);
+  const KbWs lw{nullptr, w.order, w.lev, w.n_lev};  // (k_kbest_levels writes the level arrays only)
+  const LeIn in{ref, ref_len, (int)R};
+  const LeOut out{distance, score, paths, path_arcs, align, lengths, counts, (int)max_len, (int)pad, status};
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 grid(lat->n_lattices);
+  if ((rc = launch(k_kbest_levels, grid, dim3(kKbLevelThreads), lds_lev, st, *lat, lw))) return rc;
+  if (scores) {
+    if ((rc = launch(k_lattice_edit_sweep<true>, grid, dim3(kLeThreads), lds_sweep, st, *lat, *scores, in, w, status))) return rc;
+    return launch(k_lattice_edit_walk<true>, grid, dim3(64), 0, st, *lat, *scores, in, w, out);
+  }
+  const nfst_scores none{};
+  if ((rc = launch(k_lattice_edit_sweep<false>, grid, dim3(kLeThreads), lds_sweep, st, *lat, none, in, w, status))) return rc;
+  return launch(k_lattice_edit_walk<false>, grid, dim3(64), 0, st, *lat, none, in, w, out);
 }
 
 // ------------------------------------------------------------------ arc slack and beam masks (slack_kernels.h)

@@ -82,6 +82,12 @@ __device__ __forceinline__ int wave_shr1(int v, int first) {
   return __builtin_amdgcn_update_dpp(first, v, kDppWaveShr1, 0xf, 0xf, false);
 }
 
+// The value of lane + 1, the mirror image of wave_shr1 (wave_shl:1); lane 63 takes `last`.  The same rules apply.
+constexpr int kDppWaveShl1 = 0x130;
+__device__ __forceinline__ int wave_shl1(int v, int last) {
+  return __builtin_amdgcn_update_dpp(last, v, kDppWaveShl1, 0xf, 0xf, false);
+}
+
 // All-reduce over rows of L lanes (16, 32 or the whole wave) without LDS traffic: the four DPP stages reduce every row
 // of 16 lanes, v_readlane collects the four row results, combined as op(op(a, b), op(c, d)) -- float sums keep this
 // order, (a + b) + (c + d).

@@ -1673,4 +1673,4 @@ def iwae(log_p: torch.Tensor, log_q: torch.Tensor):
 
 # ----------------------------------------------------------------------------- edit distance
 # (at the end: edit.py takes the marshalling helpers above)
-from .edit import EDIT_MAX_LEN, edit_distance, pairwise_edit_distance  # noqa: E402,F401
+from .edit import EDIT_MAX_LEN, LatticeEditResult, edit_distance, lattice_edit_distance, pairwise_edit_distance  # noqa: E402,F401

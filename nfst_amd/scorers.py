@@ -166,6 +166,36 @@ class LatticeScorer(torch.nn.Module):
             raise ValueError(f"draws must be 'k_best' or 'swor', not {draws!r}")
         return self._mbr_entries(r)
 
+    def _oracle(self, ref: torch.Tensor, ref_lengths: Optional[torch.Tensor]) -> tuple:
+        """``(ops.LatticeEditResult, ref_lengths)`` of the oracle path under ``theta``; without ``ref_lengths`` the trailing
+        entries of a row equal to the scorer's pad do not count."""
+        ref = torch.as_tensor(ref)
+        if ref_lengths is None:
+            keep = ref != self.__pad__
+            last = torch.arange(1, ref.shape[1] + 1, device=ref.device) * keep
+            ref_lengths = last.max(dim=1).values if ref.shape[1] else torch.zeros(ref.shape[0], dtype=torch.int64, device=ref.device)
+        ref_lengths = torch.as_tensor(ref_lengths)
+        return ops.lattice_edit_distance(self._lat(), ref, ref_lengths, self.theta.detach(), pad=self.__pad__), ref_lengths
+
+    def oracle(self, ref: torch.Tensor, ref_lengths: Optional[torch.Tensor] = None) -> list:
+        """The oracle path of every lattice against the gold marks ``ref`` [B, R]: per lattice ``(distance, marks)``, the
+        least edit distance of any path to ``ref[b, :ref_lengths[b]]`` and the mark sequence that attains it, the one of
+        the greatest score under ``theta`` among equals (``ops.lattice_edit_distance``).  With ``ref_lengths=None``
+        trailing entries equal to the scorer's pad do not count.  A lattice without a path gives ``(-1, [])``."""
+        r, _ = self._oracle(ref, ref_lengths)
+        dist, marks, lens = r.distance.cpu().numpy(), r.paths.cpu().numpy(), r.lengths.cpu().numpy()
+        return [(int(dist[b]), marks[b, :lens[b]].tolist()) for b in range(len(dist))]
+
+    def oracle_error_rate(self, ref: torch.Tensor, ref_lengths: Optional[torch.Tensor] = None) -> float:
+        """The lattices' oracle error rate: the summed oracle distances over the summed reference lengths, over the
+        lattices that have a path (NaN when no reference token is left to count)."""
+        r, n = self._oracle(ref, ref_lengths)
+        dist = r.distance.cpu().to(torch.int64)
+        n = n.reshape(-1).cpu().to(torch.int64)
+        has = dist >= 0
+        total = int(n[has].sum())
+        return float(dist[has].sum()) / total if total else float("nan")
+
     def positional_mbr(self, pos_scores: torch.Tensor, k: int, draws: str = "k_best", **kw) -> list:
         """``mbr`` under ``theta`` plus per-position scores and their length budget (``positional_k_best`` or
         ``positional_sample_without_replacement`` give the candidates)."""

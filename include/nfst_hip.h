@@ -753,6 +753,48 @@ int nfst_intersect_write(const nfst_batch *lat, const int8_t *delta_t, int64_t d
                          int32_t *dst, int64_t *arc_map, int32_t *arc_q, int32_t *row_state, int32_t *row_q, void *stream);
 
 /*
+ * The same product with a sparse automaton of up to 4096 states (DESIGN.md sections 2 and 4.19): the wide route beside
+ * the trio above, which stays as it is.  Semantics, rows, arcs and outputs are exactly those described above with 64
+ * replaced by 4096: reading rules, fwd / bwd / live, row order (s ascending, q ascending), the sink's pairs as one row
+ * carrying its smallest live q, arcs in canonical order per row, self loops once per row, a trim product, arc_q = 0 on
+ * the sink row's loop, and the same determinism: integers written once at positions fixed by prefix sums, from the
+ * canonical arrays only.
+ * Automata: n_dfa = 1 (one for the batch) or n_dfa = n_lattices (one per lattice, ragged), concatenated, device memory:
+ *     q_off     [n_dfa + 1] int32  first state of every automaton in dflt / exc_off / final; Q_i = q_off[i+1] - q_off[i],
+ *                                  1 <= Q_i <= max_q <= 4096; start state 0
+ *     dflt      [sum Q]     int32  default target of every state
+ *     exc_off   [sum Q + 1] int32  first exception of every state in exc_label / exc_dst (one ascending array over all
+ *                                  automata)
+ *     exc_label [E]         int32  strictly ascending inside a state, < vocab
+ *     exc_dst   [E]         int32
+ *     final     [sum Q]     uint8  non-zero: final
+ * delta(q, l) = exc_dst[k] if some k in [exc_off[q], exc_off[q + 1]) has exc_label[k] == l, else dflt[q].  A target is
+ * relative to its own automaton; -1 (in either place) = no transition.  exc_label and exc_dst must be valid pointers
+ * even when E = 0.
+ *   nfst_intersect_wide_count / _write  as nfst_intersect_count / _write: counts [B, 2], status [B] (a product of more
+ *                         than NFST_MAX_ROWS rows: NFST_ERR_LIMIT with counts (rows, 0); an empty product: counts (0, 0),
+ *                         status 0), one read-back, then the write call with the prefix sums and the same lat, automata,
+ *                         max_q and ws.  arc_q, row_q, row_state, src, label, dst int32; arc_map int64.
+ * ws: device workspace of nfst_intersect_wide_ws_bytes(lat, max_q) bytes (16-byte aligned, overwritten): with
+ * W = ceil(max_q / 64), 16 W + 12 bytes per row of the batch and 8 * NFST_MAX_ROWS + 12 per lattice, every array rounded
+ * up to 256 bytes.  No LDS beyond 256 bytes.  max_q > 4096: NFST_ERR_LIMIT; max_q < 1, a null pointer, n_dfa other than 1
+ * or n_lattices, or a short workspace: NFST_ERR_ARG; all on the host before any launch.  The automaton's entries are not
+ * read on the host: the caller validates them (offsets ascending and inside the arrays, targets in -1 .. Q_i - 1,
+ * labels ascending and < vocab, Q_i <= max_q; the Python wrapper does).  As a last line of defence the kernels treat a
+ * target outside 0 .. Q_i - 1 as "no transition" and give a lattice whose Q_i lies outside 1 .. 64 W the status
+ * NFST_ERR_ARG with counts (0, 0).
+ */
+int64_t nfst_intersect_wide_ws_bytes(const nfst_batch *lat, int32_t max_q);
+int nfst_intersect_wide_count(const nfst_batch *lat, const int32_t *q_off, const int32_t *dflt, const int32_t *exc_off,
+                              const int32_t *exc_label, const int32_t *exc_dst, const uint8_t *final, int32_t n_dfa, int32_t max_q,
+                              void *ws, int64_t ws_bytes, int32_t *counts, int32_t *status, void *stream);
+int nfst_intersect_wide_write(const nfst_batch *lat, const int32_t *q_off, const int32_t *dflt, const int32_t *exc_off,
+                              const int32_t *exc_label, const int32_t *exc_dst, const uint8_t *final, int32_t n_dfa, int32_t max_q,
+                              void *ws, int64_t ws_bytes, const int64_t *out_row_off, const int64_t *out_arc_off, int32_t *src,
+                              int32_t *label, int32_t *dst, int64_t *arc_map, int32_t *arc_q, int32_t *row_state, int32_t *row_q,
+                              void *stream);
+
+/*
  * Position-dependent scores: time-synchronous sweeps (DESIGN.md sections 2 and 4.10).  A path pi = a_0 .. a_{L-1} runs
  * from state 0 to the sink over canonical arcs; self loops (the sink's pad loop) are on no path.  Arc a_t is "at
  * position t": the bos arc at position 0, the eos arc at L - 1.  The caller gives T >= 1 positions and optionally pos

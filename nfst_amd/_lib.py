@@ -165,6 +165,10 @@ def _load():
         "nfst_intersect_ws_bytes": (i64, [BP, i32]),
         "nfst_intersect_count": (C.c_int, [BP, vp, i64, vp, i64, i32, vp, i64, vp, vp, vp]),
         "nfst_intersect_write": (C.c_int, [BP, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "nfst_intersect_wide_ws_bytes": (i64, [BP, i32]),
+        "nfst_intersect_wide_count": (C.c_int, [BP, vp, vp, vp, vp, vp, vp, i32, i32, vp, i64, vp, vp, vp]),
+        "nfst_intersect_wide_write": (C.c_int, [BP, vp, vp, vp, vp, vp, vp, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                vp]),
         "nfst_positional_ws_bytes": (i64, [BP, i32, i32]),
         "nfst_positional_plan": (C.c_int, [BP, i32, C.POINTER(i64), C.POINTER(i32)]),
         "nfst_positional": (C.c_int, [BP, SP, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp]),

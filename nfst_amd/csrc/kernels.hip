@@ -45,6 +45,7 @@ using namespace nfst_tile;
 #include "lattice_edit_kernels.h"
 #include "slack_kernels.h"
 #include "intersect_kernels.h"
+#include "intersect_wide_kernels.h"
 #include "positional_kernels.h"
 #include "positional_expect_kernels.h"
 #include "positional_kbest_kernels.h"
@@ -1451,6 +1452,65 @@ int nfst_intersect_write(const nfst_batch *lat, const int8_t *delta, int64_t del
   const IsDfa d = {delta, delta_stride, nullptr, 0};
   const IsOut o = {out_row_off, out_arc_off, src, label, dst, arc_map, arc_q, row_state, row_q};
   return launch(k_intersect_write, dim3(lat->n_lattices), dim3(kIsThreads), 0, (hipStream_t)stream, *lat, d, w, o);
+}
+
+// ------------------------------------------------------------------ product with a sparse automaton of up to 4096 states (intersect_wide_kernels.h)
+// workspace: as is_ws_layout, with fwd and live as W = ceil(max_q / 64) words per row of the batch
+static int64_t iw_ws_layout(const nfst_batch *lat, int32_t max_q, char *base, IwWs *w) {
+  const int64_t TR = lat->total_rows, B = lat->n_lattices, W = (max_q + 63) / 64;
+  WsCarve c{base};
+  char *od = c.take(4 * TR), *lv = c.take(4 * (TR + B)), *nl = c.take(4 * B), *fw = c.take(8 * W * TR), *li = c.take(8 * W * TR);
+  char *fi = c.take(4 * TR), *pa = c.take(4 * B * NFST_MAX_ROWS), *ao = c.take(4 * B * NFST_MAX_ROWS), *no = c.take(4 * B);
+  if (w) *w = {(int *)od, (int *)lv, (int *)nl, (is_mask *)fw, (is_mask *)li, (int *)fi, (int *)pa, (int *)ao, (int *)no, (int)W};
+  return c.size;
+}
+static int iw_check_q(int32_t max_q) { return max_q < 1 ? NFST_ERR_ARG : (max_q > kIwMaxQ ? NFST_ERR_LIMIT : NFST_OK); }
+static int iw_check(const nfst_batch *lat, const int32_t *q_off, const int32_t *dflt, const int32_t *exc_off, const int32_t *exc_label,
+                    const int32_t *exc_dst, const uint8_t *final, int32_t n_dfa, int32_t max_q, const void *ws, int64_t ws_bytes) {
+  int rc = check_batch(lat);
+  if (rc) return rc;
+  if ((rc = iw_check_q(max_q))) return rc;
+  if (!q_off || !dflt || !exc_off || !exc_label || !exc_dst || !final || (n_dfa != 1 && n_dfa != lat->n_lattices)) return NFST_ERR_ARG;
+  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < iw_ws_layout(lat, max_q, nullptr, nullptr)) return NFST_ERR_ARG;
+  return NFST_OK;
+}
+
+int64_t nfst_intersect_wide_ws_bytes(const nfst_batch *lat, int32_t max_q) {
+  int rc = check_batch(lat);
+  if (rc) return rc;
+  if ((rc = iw_check_q(max_q))) return rc;
+  return iw_ws_layout(lat, max_q, nullptr, nullptr);
+}
+
+int nfst_intersect_wide_count(const nfst_batch *lat, const int32_t *q_off, const int32_t *dflt, const int32_t *exc_off,
+                              const int32_t *exc_label, const int32_t *exc_dst, const uint8_t *final, int32_t n_dfa, int32_t max_q,
+                              void *ws, int64_t ws_bytes, int32_t *counts, int32_t *status, void *stream) {
+  int rc = iw_check(lat, q_off, dflt, exc_off, exc_label, exc_dst, final, n_dfa, max_q, ws, ws_bytes);
+  if (rc) return rc;
+  if (!counts || !status) return NFST_ERR_ARG;
+  const int64_t lds_lev = (int64_t)lat->max_rows * 12 + 16;
+  IwWs w;
+  iw_ws_layout(lat, max_q, (char *)ws, &w);
+  const KbWs kw = {nullptr, w.order, w.lev, w.n_lev};
+  const IwDfa d = {q_off, dflt, exc_off, exc_label, exc_dst, final, n_dfa == 1 ? 0 : 1};
+  const hipStream_t st = (hipStream_t)stream;
+  if ((rc = launch(k_kbest_levels, dim3(lat->n_lattices), dim3(kKbLevelThreads), lds_lev, st, *lat, kw))) return rc;
+  return launch(k_intersect_wide_count, dim3(lat->n_lattices), dim3(kIwThreads), 0, st, *lat, d, w, counts, status);
+}
+
+int nfst_intersect_wide_write(const nfst_batch *lat, const int32_t *q_off, const int32_t *dflt, const int32_t *exc_off,
+                              const int32_t *exc_label, const int32_t *exc_dst, const uint8_t *final, int32_t n_dfa, int32_t max_q,
+                              void *ws, int64_t ws_bytes, const int64_t *out_row_off, const int64_t *out_arc_off, int32_t *src,
+                              int32_t *label, int32_t *dst, int64_t *arc_map, int32_t *arc_q, int32_t *row_state, int32_t *row_q,
+                              void *stream) {
+  const int rc = iw_check(lat, q_off, dflt, exc_off, exc_label, exc_dst, final, n_dfa, max_q, ws, ws_bytes);
+  if (rc) return rc;
+  if (!out_row_off || !out_arc_off || !src || !label || !dst || !arc_map || !arc_q || !row_state || !row_q) return NFST_ERR_ARG;
+  IwWs w;
+  iw_ws_layout(lat, max_q, (char *)ws, &w);
+  const IwDfa d = {q_off, dflt, exc_off, exc_label, exc_dst, final, n_dfa == 1 ? 0 : 1};
+  const IsOut o = {out_row_off, out_arc_off, src, label, dst, arc_map, arc_q, row_state, row_q};
+  return launch(k_intersect_wide_write, dim3(lat->n_lattices), dim3(kIwThreads), 0, (hipStream_t)stream, *lat, d, w, o);
 }
 
 // shared argument checks and the variant table of the 16-byte streaming kernels: a row lies on a

@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from ._lib import lib, check
+from .constraints import WideDFA
 
 
 _warned_d2h = False
@@ -166,6 +167,25 @@ class ChunkProgram:
         return self._struct
 
 
+def _narrow_route(bs, dfa, dev, B, vocab):
+    """``(name, ws_bytes(), count(*rest), write(*rest))`` of the 64-state entry points with the automaton's arguments bound
+    (``rest``: everything from the workspace on)."""
+    delta_t, fin = dfa.to(dev)
+    d_stride, f_stride = (vocab * 64, 1) if dfa.n_lattices is not None else (0, 0)
+    d, f, q = delta_t.data_ptr(), fin.data_ptr(), dfa.n_states
+    return ("nfst_intersect", lambda: lib.nfst_intersect_ws_bytes(bs, q),
+            lambda *rest: lib.nfst_intersect_count(bs, d, d_stride, f, f_stride, q, *rest),
+            lambda *rest: lib.nfst_intersect_write(bs, d, d_stride, q, *rest))
+
+
+def _wide_route(bs, dfa, dev, B, vocab):
+    """The same of the entry points for a ``WideDFA`` (its six arrays, the number of automata, the largest Q)."""
+    auto = [t.data_ptr() for t in dfa.to(dev)] + [1 if dfa.n_lattices is None else B, dfa.n_states]
+    return ("nfst_intersect_wide", lambda: lib.nfst_intersect_wide_ws_bytes(bs, dfa.n_states),
+            lambda *rest: lib.nfst_intersect_wide_count(bs, *auto, *rest),
+            lambda *rest: lib.nfst_intersect_wide_write(bs, *auto, *rest))
+
+
 class IntersectResult:
     """What ``LatticeBatch.intersect`` returns; unpacks as ``(lattice, arc_map, arc_q, row_state, row_q)``."""
     __slots__ = ("lattice", "arc_map", "arc_q", "row_state", "row_q", "dfa")
@@ -183,13 +203,17 @@ class IntersectResult:
 
     def scores(self, arc_scores: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``[A']`` float32 per-arc scores of the product: ``arc_scores[arc_map]`` (per-arc scores of the input batch, if
-        given) plus ``dfa.weight[(b,) arc_q, label]`` (if the automaton is weighted); autograd flows through both
-        gathers.  Self loops lie on no path: their value does not matter (it is the gathered one)."""
+        given) plus ``dfa.weight[(b,) arc_q, label]`` (if the automaton is weighted; for a ``WideDFA`` the matching
+        entry of ``weight_exc``, else ``weight_dflt`` of the state); autograd flows through both gathers.  Self loops
+        lie on no path: their value does not matter (it is the gathered one)."""
         lat = self.lattice
         out = torch.zeros(lat.total_arcs, dtype=torch.float32, device=lat.device)
         if arc_scores is not None:
             out = out + arc_scores.to(device=lat.device, dtype=torch.float32)[self.arc_map]
-        if self.dfa.weight is not None:
+        if isinstance(self.dfa, WideDFA):
+            if self.dfa.weighted:  # the sparse automaton's weights: a sorted-key lookup in torch (WideDFA.arc_weights)
+                out = out + self.dfa.arc_weights(self.arc_q, lat.arc_label, lat.vocab, lat.arc_lattice() if self.dfa.per_lattice else None)
+        elif self.dfa.weight is not None:
             w = self.dfa.weight.to(device=lat.device, dtype=torch.float32)
             q, l = self.arc_q.to(torch.int64), lat.arc_label.to(torch.int64)
             out = out + (w[q, l] if w.dim() == 2 else w[lat.arc_lattice(), q, l])
@@ -735,9 +759,11 @@ class LatticeBatch:
 
     # ---------------------------------------------------------------- product with a constraint automaton
     def intersect(self, dfa, chunks=False, chunk_opts: Optional[dict] = None, **pack_opts) -> "IntersectResult":
-        """The product of every lattice with a ``constraints.ConstraintDFA`` (one for the batch or one per lattice), packed
-        into a new batch: its paths are exactly the paths of this batch whose label sequences the automaton accepts
-        (``nfst_intersect_count`` / ``_write``, DESIGN.md sections 2 and 4.8).  Returns ``IntersectResult(lattice,
+        """The product of every lattice with a ``constraints.ConstraintDFA`` (up to 64 states) or a ``constraints.WideDFA``
+        (sparse, up to 4096 states), one for the batch or one per lattice, packed into a new batch: its paths are exactly
+        the paths of this batch whose label sequences the automaton accepts (``nfst_intersect_count`` / ``_write``,
+        DESIGN.md sections 2 and 4.8; for a ``WideDFA`` ``nfst_intersect_wide_count`` / ``_write``, section 4.19).
+        Returns ``IntersectResult(lattice,
         arc_map, arc_q, row_state, row_q)``; every op runs on ``lattice`` unchanged, ``arc_scores[arc_map]`` (or
         ``result.scores(arc_scores)``) scores it, ``arc_w`` is carried over.  Two launches around one small read-back,
         then the device packer (``from_arcs_device`` with ``chunks`` / ``chunk_opts`` / ``pack_opts``); what only the
@@ -750,21 +776,18 @@ class LatticeBatch:
         _check_chunks_arg(chunks)
         dfa.check(self.vocab, self.n_lattices)
         dev, B = self.device, self.n_lattices
-        delta_t, fin = dfa.to(dev)
-        per = dfa.n_lattices is not None
-        d_stride, f_stride = (self.vocab * 64, 1) if per else (0, 0)
         bs = C.byref(self.c_struct())
-        ws_bytes = int(lib.nfst_intersect_ws_bytes(bs, dfa.n_states))
-        check(min(ws_bytes, 0), "nfst_intersect_ws_bytes")
+        name, ws_fn, count_fn, write_fn = (_wide_route if isinstance(dfa, WideDFA) else _narrow_route)(bs, dfa, dev, B, self.vocab)
+        ws_bytes = int(ws_fn())
+        check(min(ws_bytes, 0), name + "_ws_bytes")
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
         cs = torch.zeros(3 * B, dtype=torch.int32, device=dev)  # counts [B, 2] | status [B]
-        check(lib.nfst_intersect_count(bs, delta_t.data_ptr(), d_stride, fin.data_ptr(), f_stride, dfa.n_states, ws.data_ptr(),
-                                       ws_bytes, cs.data_ptr(), cs[2 * B:].data_ptr(), _stream()), "nfst_intersect_count")
+        check(count_fn(ws.data_ptr(), ws_bytes, cs.data_ptr(), cs[2 * B:].data_ptr(), _stream()), name + "_count")
         cs_h = cs.cpu().numpy()  # the one read-back
         cnt, status = cs_h[:2 * B].reshape(B, 2).astype(np.int64), cs_h[2 * B:]
         if status.any():
             bad = int(np.nonzero(status)[0][0])
-            raise _lib.NfstError(int(status[bad]), f"nfst_intersect_count (a product of {int(cnt[bad, 0])} rows)", bad)
+            raise _lib.NfstError(int(status[bad]), f"{name}_count (a product of {int(cnt[bad, 0])} rows)", bad)
         if (cnt[:, 0] == 0).any():
             raise ValueError(f"lattice {int(np.nonzero(cnt[:, 0] == 0)[0][0])}: the automaton accepts none of its paths (empty product)")
         off = np.zeros((2, B + 1), dtype=np.int64)
@@ -777,9 +800,8 @@ class LatticeBatch:
         arc_map = torch.empty(A, dtype=torch.int64, device=dev)
         rows = torch.empty(2 * R, dtype=torch.int32, device=dev)
         row_state, row_q = rows[:R], rows[R:]
-        check(lib.nfst_intersect_write(bs, delta_t.data_ptr(), d_stride, dfa.n_states, ws.data_ptr(), ws_bytes, off_d[0].data_ptr(),
-                                       off_d[1].data_ptr(), src.data_ptr(), label.data_ptr(), dst.data_ptr(), arc_map.data_ptr(),
-                                       arc_q.data_ptr(), row_state.data_ptr(), row_q.data_ptr(), _stream()), "nfst_intersect_write")
+        check(write_fn(ws.data_ptr(), ws_bytes, off_d[0].data_ptr(), off_d[1].data_ptr(), src.data_ptr(), label.data_ptr(), dst.data_ptr(),
+                       arc_map.data_ptr(), arc_q.data_ptr(), row_state.data_ptr(), row_q.data_ptr(), _stream()), name + "_write")
         n_rows, arc_off = cnt[:, 0].astype(np.int32), off[1]
         w = self.arc_w[arc_map] if self.weighted else None
         out = None

@@ -671,10 +671,11 @@ def prune(lat: LatticeBatch, theta, beam, arc_scores=None, **pack_opts) -> Prune
 
 
 def intersect(lat: LatticeBatch, dfa, **pack_opts) -> IntersectResult:
-    """The product of every lattice with a constraint automaton (``constraints.ConstraintDFA``), packed into a new
-    batch whose paths are exactly the accepted paths of ``lat``: ``LatticeBatch.intersect`` (``nfst_intersect_count`` /
-    ``_write``, DESIGN.md sections 2 and 4.8).  ``(lattice, arc_map, arc_q, row_state, row_q)``; ``pack_opts`` go to
-    the packer, ``chunks=`` / ``chunk_opts=`` included."""
+    """The product of every lattice with a constraint automaton (``constraints.ConstraintDFA``, or the sparse
+    ``constraints.WideDFA`` of up to 4096 states), packed into a new batch whose paths are exactly the accepted paths of
+    ``lat``: ``LatticeBatch.intersect`` (``nfst_intersect_count`` / ``_write``, DESIGN.md sections 2 and 4.8; for a
+    ``WideDFA`` ``nfst_intersect_wide_count`` / ``_write``, section 4.19).  ``(lattice, arc_map, arc_q, row_state,
+    row_q)``; ``pack_opts`` go to the packer, ``chunks=`` / ``chunk_opts=`` included."""
     _need_gpu(lat)
     return lat.intersect(dfa, **pack_opts)
 
@@ -1674,3 +1675,4 @@ def iwae(log_p: torch.Tensor, log_q: torch.Tensor):
 # ----------------------------------------------------------------------------- edit distance
 # (at the end: edit.py takes the marshalling helpers above)
 from .edit import EDIT_MAX_LEN, LatticeEditResult, edit_distance, lattice_edit_distance, pairwise_edit_distance  # noqa: E402,F401
+from .constraints import constraint_log_prob  # noqa: E402,F401

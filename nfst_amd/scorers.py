@@ -244,6 +244,11 @@ class LatticeScorer(torch.nn.Module):
         constraint."""
         return ops.intersect(self._lat(), dfa, **pack_opts)
 
+    def constraint_log_prob(self, dfa, **pack_opts) -> torch.Tensor:
+        """log Z of the scorer's lattice under ``dfa`` minus its log Z, per lattice, under ``theta``
+        (``ops.constraint_log_prob``)."""
+        return ops.constraint_log_prob(self._lat(), self.theta, dfa, **pack_opts)
+
     # ------------------------------------------------------------ per-step gathers
     def update_fsa_state(self, updated: torch.Tensor, prev_states: torch.Tensor) -> torch.Tensor:
         """scorers.py:683-690."""

@@ -137,6 +137,29 @@ extern "C" {
  * reachable from state 0 in (state asc, label asc) order; values bit-exact with
  * nonzero(emission) / transition.  The sink's pad self loop is included.
  * Tile programs (engine-private): the level-scheduled sweeps, DESIGN.md section 3.
+ *
+ * What structure a lattice may have ("Lattice structure"; tests/structure_cases.py holds every
+ * statement).  Rows that state 0 does not reach may sit anywhere, below, between and above the reachable ones; the
+ * packers drop their arcs, so canonical arc ids are positions in the list of the REACHABLE states' arcs, not in the
+ * caller's list.  The sink (NFST_META_SINK) is the one reachable state without an out-arc other than self loops,
+ * whatever its row id: every entry point compares against it, none against n_rows - 1.  Self loops may sit at any
+ * reachable state, state 0 included; for every path-side entry point (all but the walkers nfst_step,
+ * nfst_emission_mask, nfst_beta_logits, nfst_proposal_step and nfst_beam_step) a self loop lies on no path: its
+ * posterior, covariance and gradient are exactly 0, its label is not counted, no best path, draw or oracle path takes
+ * it, and its slack is its state's.  Row outputs (log alpha, log beta, vbeta, state slack) hold -inf / +inf at rows
+ * that state 0 does not reach.
+ * A lattice whose state 0 is the sink (one row, or rows and no reachable arc) has exactly one path, the empty one:
+ * length 0, no arc, score 0.0f.  Viterbi, k best, the samplers and the draws without replacement return it (n_paths 1,
+ * labels all pad, arcs all -1; the perturbed score of the one draw is the root's, +inf, and kappa -inf); log Z is 0
+ * within the entry point's tolerance (the sweeps take the logarithm of a (mantissa, exponent) pair), log q and log p
+ * of the empty path likewise; the positional sums give log Z_T = 0 exactly and len_logz entry 0 = 0, every other entry
+ * -inf; E[V], the entropy and every per-label sum are 0; nfst_lattice_edit gives distance n, counts (0, 0, n), length 0
+ * and score 0.0f for a reference of n tokens; nfst_arc_slack gives best 0.0f and keeps nothing, and
+ * LatticeBatch.restrict leaves such a member as it is; the product with an automaton is one row without arcs if state
+ * 0 of the automaton is final, else empty.  The forced walks (nfst_score_paths, nfst_positional_score_paths) follow
+ * marks: on the empty path's marks, all pad, they look for a pad arc at state 0 and, as for any mark without an arc,
+ * return -inf and end state 0.  Such members may stand anywhere in a batch, and a batch may consist of them alone
+ * (total_arcs = 0); an entry point then still wants non-null pointers for its required per-arc outputs.
  */
 /* nfst_batch.reserved0 bit: every tile program of the batch is in the compact format (code 8): the
  * fused sweep kernels apply (set by the packer; LatticeBatch.concat keeps it if all parts have it) */
@@ -809,7 +832,8 @@ int nfst_intersect_wide_write(const nfst_batch *lat, const int32_t *q_off, const
  * nfst_positional (sum-product).  Outputs on the device, optional unless stated, every element written exactly once
  * (no zeroing by the caller):
  *     logz64 [B] (required), logz32 [B]   log Z_T
- *     len_logz [B, T + 1] float64         entry L = log of the total weight of the paths of exactly L arcs, entry 0 = -inf;
+ *     len_logz [B, T + 1] float64         entry L = log of the total weight of the paths of exactly L arcs; entry 0 = -inf
+ *                                         (0.0 for a lattice whose state 0 is the sink: its one path is the empty one);
  *                                         logsumexp over L = logz64, len_logz - logz64 = the length distribution under
  *                                         truncation at T
  *     pos_post [B, T, V] float32          sum over the arcs with label l of P(that arc is at position t)

@@ -508,7 +508,7 @@ __device__ __forceinline__ void pos_sum_sweep(const nfst_batch &lat, const PosIn
   if (threadIdx.x == 0) {
     o.logz64[b] = logz;
     if (o.logz32) o.logz32[b] = (float)logz;
-    if (o.len_logz) o.len_logz[(size_t)b * (T + 1)] = -__builtin_huge_val();
+    if (o.len_logz) o.len_logz[(size_t)b * (T + 1)] = m.sink == 0 ? 0.0 : -__builtin_huge_val();  // (the empty path, where state 0 is the sink)
   }
   rd.beta_done(b, z);
   if (!need_alpha) return;

@@ -711,7 +711,7 @@ class LatticeBatch:
         A batch on the GPU is packed there (``from_arcs_device``, with ``chunks`` / ``chunk_opts``; one small read-back of
         ``n_kept`` -- pass the ``[B]`` counts if they are at hand); what only the host packer takes falls back to
         ``from_arcs`` with a warning.  A host batch goes through ``from_arcs``.  Raises ``ValueError`` naming the lattice
-        if a lattice keeps no arc."""
+        if a lattice keeps no arc (a lattice that has none -- state 0 is its sink -- stays as it is)."""
         dev = self.device
         A, B = self.total_arcs, self.n_lattices
         keep_t = keep if isinstance(keep, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(keep))
@@ -727,8 +727,9 @@ class LatticeBatch:
             cnt = (n_kept.detach().cpu().numpy() if isinstance(n_kept, torch.Tensor) else np.asarray(n_kept)).astype(np.int64).reshape(-1)
             if cnt.shape[0] != B:
                 raise ValueError(f"n_kept must have {B} entries")
-        if (cnt <= 0).any():
-            raise ValueError(f"lattice {int(np.nonzero(cnt <= 0)[0][0])} keeps no arc")
+        empty = (cnt <= 0) & (self.n_arcs > 0)  # (a lattice without arcs -- state 0 is its sink -- has none to keep)
+        if empty.any():
+            raise ValueError(f"lattice {int(np.nonzero(empty)[0][0])} keeps no arc")
         if int(arc_map.numel()) != int(cnt.sum()):
             raise ValueError("n_kept does not count the arcs that keep marks")
         arc_off = np.zeros(B + 1, dtype=np.int64)
@@ -795,13 +796,15 @@ class LatticeBatch:
         np.cumsum(cnt[:, 1], out=off[1, 1:])
         R, A = int(off[0, -1]), int(off[1, -1])
         off_d = torch.from_numpy(off).to(dev)
-        arcs = torch.empty(4 * A, dtype=torch.int32, device=dev)
-        src, label, dst, arc_q = arcs[:A], arcs[A:2 * A], arcs[2 * A:3 * A], arcs[3 * A:]
-        arc_map = torch.empty(A, dtype=torch.int64, device=dev)
+        A1 = max(A, 1)  # (one element at least: a product without any arc still hands the library pointers)
+        arcs = torch.empty(4 * A1, dtype=torch.int32, device=dev)
+        src, label, dst, arc_q = arcs[:A1], arcs[A1:2 * A1], arcs[2 * A1:3 * A1], arcs[3 * A1:]
+        arc_map = torch.empty(A1, dtype=torch.int64, device=dev)
         rows = torch.empty(2 * R, dtype=torch.int32, device=dev)
         row_state, row_q = rows[:R], rows[R:]
         check(write_fn(ws.data_ptr(), ws_bytes, off_d[0].data_ptr(), off_d[1].data_ptr(), src.data_ptr(), label.data_ptr(), dst.data_ptr(),
                        arc_map.data_ptr(), arc_q.data_ptr(), row_state.data_ptr(), row_q.data_ptr(), _stream()), name + "_write")
+        src, label, dst, arc_q, arc_map = src[:A], label[:A], dst[:A], arc_q[:A], arc_map[:A]
         n_rows, arc_off = cnt[:, 0].astype(np.int32), off[1]
         w = self.arc_w[arc_map] if self.weighted else None
         out = None

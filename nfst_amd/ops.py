@@ -643,12 +643,15 @@ def arc_slack(lat: LatticeBatch, theta, arc_scores=None, beam=None, want_rows: b
     bm = None if beam is None else _beam(lat, beam)
     ws, ws_bytes = _workspace(lat, "nfst_arc_slack_ws_bytes")
     best = torch.empty(B, dtype=torch.float32, device=dev)
-    slack = torch.empty(A, dtype=torch.float32, device=dev)
-    keep = torch.empty(A, dtype=torch.uint8, device=dev) if bm is not None else None
+    # (one element at least: a batch without any arc still hands the library pointers)
+    slack = torch.empty(max(A, 1), dtype=torch.float32, device=dev)
+    keep = torch.empty(max(A, 1), dtype=torch.uint8, device=dev) if bm is not None else None
     n_kept = torch.empty(B, dtype=torch.int32, device=dev) if bm is not None else None
     vbeta = torch.empty(R, dtype=torch.float32, device=dev) if want_rows else None
     sslack = torch.empty(R, dtype=torch.float32, device=dev) if want_rows else None
     _call("nfst_arc_slack", lat, sc, bm, ws, ws_bytes, best, vbeta, sslack, slack, keep, n_kept)
+    if A == 0:
+        slack, keep = slack[:0], None if keep is None else keep[:0]
     return ArcSlackResult(best, slack, None if keep is None else keep.view(torch.bool), n_kept, vbeta, sslack)
 
 
@@ -686,7 +689,7 @@ class PositionalResult(NamedTuple):
     logz64: torch.Tensor  # [B] float64
     pos_posterior: Optional[torch.Tensor]  # [B, T, V] float32: P(the mark at position t is l) = d log Z_T / d pos_scores
     arc_posterior: Optional[torch.Tensor]  # [total_arcs] float32: sum over t of P(arc a is at position t)
-    len_logz: Optional[torch.Tensor]  # [B, T + 1] float64: log weight of the paths of exactly L arcs (entry 0: -inf)
+    len_logz: Optional[torch.Tensor]  # [B, T + 1] float64: log weight of the paths of exactly L arcs (entry 0: -inf; 0 where state 0 is the sink)
 
 
 class PositionalViterbiResult(NamedTuple):

@@ -13,6 +13,7 @@ from __future__ import annotations
 import numpy as np
 
 from nfst_amd import synth
+from tests.expectation_ref import sink_of
 
 F32 = np.float32
 NEG = F32(-np.inf)
@@ -152,9 +153,10 @@ def vbeta(l, theta_b):
     depth = levels(l.n_rows, l.src, l.dst)
     rp = row_ptr(l)
     v = np.full(l.n_rows, NEG, F32)
-    v[l.n_rows - 1] = 0.0
+    sink = sink_of(l.n_rows, l.src, l.dst)
+    v[sink] = 0.0
     th = np.asarray(theta_b, F32)
-    for s in sorted((r for r in range(l.n_rows - 1) if depth[r] >= 0), key=lambda r: -depth[r]):
+    for s in sorted((r for r in range(l.n_rows) if depth[r] >= 0 and r != sink), key=lambda r: -depth[r]):
         for a in range(rp[s], rp[s + 1]):
             if l.dst[a] != s:
                 e = F32(l.weight[a]) if l.weight is not None else F32(0.0)
@@ -172,11 +174,12 @@ def step_case(lats, K, seed, lookahead=False, quarter=False):
     N = B * K
     state, inp = np.zeros(N, np.int64), np.zeros(N, np.int64)
     for b, l in enumerate(lats):
+        sink = sink_of(l.n_rows, l.src, l.dst)
         for i in range(K):
             n = b * K + i
             u = rng.random()
             if u < 0.2:
-                state[n], inp[n] = l.n_rows - 1, (EOS if u < 0.1 else PAD)
+                state[n], inp[n] = sink, (EOS if u < 0.1 else PAD)
             else:
                 state[n], inp[n] = rng.integers(0, l.n_rows), rng.integers(synth.N_SPECIAL, V)
     beam_score = rng.normal(-5.0, 2.0, size=N).astype(F32)
@@ -215,7 +218,7 @@ def tie_case(lats, K, seed=5):
     scores = np.zeros((N, V), F32)
     for b, l in enumerate(lats):
         deg = np.diff(row_ptr(l))
-        deg[l.n_rows - 1] = 0
+        deg[sink_of(l.n_rows, l.src, l.dst)] = 0
         state[b * K:(b + 1) * K] = int(np.argmax(deg))
         for i in range(K):
             if i % 3 == 0:

@@ -48,6 +48,28 @@ def levels(n_rows: int, src, dst) -> np.ndarray:
     return depth
 
 
+def sink_of(n_rows: int, src, dst) -> int:
+    """The sink as the packers take it from the arcs: the one state that state 0 reaches and that has no out-arc other
+    than self loops (asserted: exactly one).  Arcs of states that state 0 does not reach are ignored, cycles among them
+    included; on every ``nfst_amd.synth`` lattice this is ``n_rows - 1``."""
+    src, dst = np.asarray(src, np.int64), np.asarray(dst, np.int64)
+    keep = src != dst
+    s, d = src[keep], dst[keep]
+    order = np.argsort(s, kind="stable")
+    s, d = s[order], d[order]
+    start = np.searchsorted(s, np.arange(n_rows + 1))
+    reach = np.zeros(n_rows, bool)
+    reach[0] = True
+    frontier = np.zeros(1, np.int64)
+    while frontier.size:  # breadth first from state 0, a level per trip
+        nxt = np.unique(np.concatenate([d[start[r]:start[r + 1]] for r in frontier]))
+        frontier = nxt[~reach[nxt]]
+        reach[frontier] = True
+    sinks = np.nonzero(reach & (np.diff(start) == 0))[0]
+    assert len(sinks) == 1, f"{len(sinks)} reachable states without an out-arc: {sinks.tolist()[:8]}"
+    return int(sinks[0])
+
+
 def expectation(n_rows: int, src, dst, score, value) -> dict:
     """{"logZ", "ev" (E[V]), "posterior" p_a, "cov" c_a = p_a (E[V | a] - E[V]), "r_alpha", "r_beta"}."""
     src, dst = np.asarray(src, np.int64), np.asarray(dst, np.int64)

@@ -2,14 +2,14 @@
 the semantics of ``nfst_intersect_count`` / ``_write`` (include/nfst_hip.h) on one ``SynthLattice``,
 with Python integers as the masks of automaton states.
 
-A path runs from state 0 to the sink (the last row) over canonical arcs; self loops lie on no path and the automaton
+A path runs from state 0 to the sink (``expectation_ref.sink_of``) over canonical arcs; self loops lie on no path and the automaton
 never reads them.  ``delta`` is ``[Q, V]`` (-1: no transition), ``final`` ``[Q]``.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from tests.expectation_ref import levels
+from tests.expectation_ref import levels, sink_of
 
 
 def _bits(m: int):
@@ -24,7 +24,7 @@ def _bits(m: int):
 def masks(l, delta, final):
     """(fwd, bwd, live): one Python-int mask per row."""
     delta = np.asarray(delta, np.int64)
-    n, sink = l.n_rows, l.n_rows - 1
+    n, sink = l.n_rows, sink_of(l.n_rows, l.src, l.dst)
     depth = levels(n, l.src, l.dst)
     order = sorted((s for s in range(n) if depth[s] >= 0), key=lambda s: depth[s])
     out = [[] for _ in range(n)]
@@ -56,7 +56,7 @@ def intersect(l, delta, final) -> dict:
     """{"n_rows", "n_arcs", "src", "label", "dst", "arc_map" (positions among the lattice's arcs), "arc_q", "row_state",
     "row_q"}; an empty product has n_rows = n_arcs = 0."""
     delta = np.asarray(delta, np.int64)
-    n, sink = l.n_rows, l.n_rows - 1
+    n, sink = l.n_rows, sink_of(l.n_rows, l.src, l.dst)
     _, _, live = masks(l, delta, final)
     row_state, row_q, row_of = [], [], {}
     for s in range(n):

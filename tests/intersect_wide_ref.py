@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from tests.expectation_ref import levels
+from tests.expectation_ref import levels, sink_of
 
 
 def edit_denominator(x, symbols, max_out: int, vocab: int, input_mark: int = 3, output_mark: int = 4, insertion_mark: int = 5):
@@ -67,7 +67,7 @@ def live_sets(l, delta, final) -> np.ndarray:
     """bool ``[rows, Q]``: the pairs (s, q) that lie on an accepted path."""
     delta = np.asarray(delta, np.int64)
     Q = delta.shape[0]
-    n, sink = l.n_rows, l.n_rows - 1
+    n, sink = l.n_rows, sink_of(l.n_rows, l.src, l.dst)
     depth = levels(n, l.src, l.dst)
     order = sorted((s for s in range(n) if depth[s] >= 0), key=lambda s: depth[s])
     first_arc = np.searchsorted(l.src, np.arange(n + 1))
@@ -104,7 +104,7 @@ def live_sets(l, delta, final) -> np.ndarray:
 def intersect(l, delta, final) -> dict:
     """The dictionary of ``intersect_ref.intersect``."""
     delta = np.asarray(delta, np.int64)
-    n, sink = l.n_rows, l.n_rows - 1
+    n, sink = l.n_rows, sink_of(l.n_rows, l.src, l.dst)
     live = live_sets(l, delta, final)
     i32 = lambda x: np.asarray(x, np.int32)
     if not live[0, 0]:

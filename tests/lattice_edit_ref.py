@@ -11,7 +11,7 @@ from __future__ import annotations
 import numpy as np
 
 from tests import edge_cases, edit_ref, kbest_ref
-from tests.expectation_ref import levels
+from tests.expectation_ref import levels, sink_of
 
 F32 = np.float32
 NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -130,7 +130,7 @@ def of_lattice(l, ref, theta_b=None, arc_scores=None) -> dict:
     th = e = None
     if theta_b is not None:
         th, e = kbest_ref.arc_terms(l, theta_b, arc_scores)
-    return lattice_edit(l.n_rows, l.src, l.dst, l.label, th, e, ref, l.n_rows - 1)
+    return lattice_edit(l.n_rows, l.src, l.dst, l.label, th, e, ref, sink_of(l.n_rows, l.src, l.dst))
 
 
 def of_batch(lats, refs, theta=None, asc=None) -> list:
@@ -148,7 +148,7 @@ def brute_force(l, ref, score64=None) -> dict:
     float64 score among the paths at that distance, "best_arcs": that path, "ties": the distinct float64 scores at that
     distance, "n": paths}."""
     s64 = np.zeros(l.n_arcs) if score64 is None else np.asarray(score64, np.float64)
-    paths = kbest_ref.enumerate_paths(l.n_rows, l.src, l.dst, s64, l.n_rows - 1)
+    paths = kbest_ref.enumerate_paths(l.n_rows, l.src, l.dst, s64, sink_of(l.n_rows, l.src, l.dst))
     if not paths:
         return {"distance": -1, "best": -np.inf, "best_arcs": [], "ties": [], "n": 0}
     # every path against ref in one table (edit_ref.distance_table, held to edit_ref.levenshtein in test_edit_cpu.py)
@@ -175,7 +175,7 @@ def dead_label_case():
     refs = []
     for l in lats:
         th, e = kbest_ref.arc_terms(l, alive)
-        y = l.label[kbest_ref.k_best(l.n_rows, l.src, l.dst, th, e, 1, l.n_rows - 1)["arcs"][0]].astype(np.int64)
+        y = l.label[kbest_ref.k_best(l.n_rows, l.src, l.dst, th, e, 1, sink_of(l.n_rows, l.src, l.dst))["arcs"][0]].astype(np.int64)
         y[1::3] = edge_cases.DEAD[np.arange(len(y[1::3])) % len(edge_cases.DEAD)]
         refs.append(y)
     return lats, theta, refs

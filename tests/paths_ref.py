@@ -4,7 +4,7 @@ only), and the inputs that tests/test_gpu_paths.py and tests/test_paths_ref_cpu.
 walks and walkers with the oracle only where the uniform stays clear of every CDF boundary (``margin > 1e-5``), and
 the CPU file proves on the oracle alone that every such case keeps more than 90 % of them.
 
-A path runs from state 0 to the sink (the last row); self loops (the sink's pad loop) lie on no path.  Arcs are the
+A path runs from state 0 to the sink (``expectation_ref.sink_of``: taken from the arcs); self loops lie on no path.  Arcs are the
 canonical arcs of a lattice, sorted by (source, label).
 """
 from __future__ import annotations
@@ -13,7 +13,7 @@ import numpy as np
 
 from nfst_amd import synth
 from oracle import oracle as O
-from tests.expectation_ref import levels
+from tests.expectation_ref import levels, sink_of
 from tests.kbest_ref import enumerate_paths
 
 F32 = np.float32
@@ -48,7 +48,7 @@ def viterbi_ref(l, theta, arc_w=None, arc_scores=None, order="general") -> dict:
         e = (w + s) if (w is not None and s is not None) else (w if w is not None else s)
     else:
         raise ValueError(order)
-    sink = l.n_rows - 1
+    sink = sink_of(l.n_rows, l.src, l.dst)
     depth = levels(l.n_rows, src, dst)
     rp = _row_ptr(l.n_rows, src)
     v = np.full(l.n_rows, -np.inf, F32)
@@ -82,7 +82,7 @@ def viterbi_f64(l, score64) -> dict:
     """The optimum in float64: {"best", "arcs"} (ties: the smaller arc; -inf and no arcs without a finite path)."""
     src, dst = np.asarray(l.src, np.int64), np.asarray(l.dst, np.int64)
     sc = np.asarray(score64, np.float64)
-    sink = l.n_rows - 1
+    sink = sink_of(l.n_rows, l.src, l.dst)
     depth = levels(l.n_rows, src, dst)
     rp = _row_ptr(l.n_rows, src)
     v = np.full(l.n_rows, -np.inf)
@@ -107,7 +107,7 @@ def viterbi_f64(l, score64) -> dict:
 def brute_force_best(l, score64):
     """(best float64 score, number of paths of finite score) by enumerating every path: lattices of a few hundred
     paths at most."""
-    paths = enumerate_paths(l.n_rows, l.src, l.dst, score64, l.n_rows - 1)
+    paths = enumerate_paths(l.n_rows, l.src, l.dst, score64, sink_of(l.n_rows, l.src, l.dst))
     return (paths[0][0] if paths else -np.inf), len(paths)
 
 
@@ -226,7 +226,7 @@ def walker_positions(lats, k: int, seed: int):
         if j == 0:
             vstate[n], inp[n], state[n] = 0, BOS, 1
         elif j == 2:
-            sink = l.n_rows - 1
+            sink = sink_of(l.n_rows, l.src, l.dst)
             if (n // k) % 2 == 0:
                 vstate[n], inp[n], state[n] = sink - 1, EOS, sink
             else:

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from tests.expectation_ref import sink_of
 from tests.positional_ref import NEG, enumerate_paths
 
 KEYS = ("logz", "ev", "M", "pos_post", "arc_post", "pos_cov", "arc_cov")
@@ -51,7 +52,7 @@ def expectation(l, score, pos, T: int, pos_values=None, label_values=None, arc_v
     """{"logz", "ev", "M" = sum_{t,a} P(a at t) |v_t(a)|, "pos_post" [T, V], "arc_post" [A], "pos_cov" [T, V], "arc_cov"
     [A]} in float64.  ``score`` [A] float64 (``positional_ref.arc_score64``), ``pos`` / ``pos_values`` [T, V] or None,
     ``label_values`` [V] or None, ``arc_values`` [A] or None."""
-    n, sink = l.n_rows, l.n_rows - 1
+    n, sink = l.n_rows, sink_of(l.n_rows, l.src, l.dst)
     s, d, lab = l.src.astype(np.int64), l.dst.astype(np.int64), l.label.astype(np.int64)
     W, Vt = tables(l, score, pos, T, pos_values, label_values, arc_values, coef)
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):

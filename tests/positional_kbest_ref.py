@@ -13,6 +13,7 @@ from __future__ import annotations
 import numpy as np
 
 from tests import kbest_ref as K
+from tests.expectation_ref import sink_of
 
 F32 = np.float32
 NEG = -np.inf
@@ -41,7 +42,7 @@ def k_best(l, theta_b, pos, T: int, k: int, arc_scores=None, every_list: bool = 
     "n_paths"}.  ``pos`` [T, V] or None.  Only the lists of the (t, s) that state 0 reaches in exactly t arcs are
     computed -- no other list is ever read on the way to (0, state 0) -- unless ``every_list`` is set
     (tests/test_positional_kbest_cpu.py: the result is the same)."""
-    n, sink = l.n_rows, l.n_rows - 1
+    n, sink = l.n_rows, sink_of(l.n_rows, l.src, l.dst)
     need = np.ones((T + 1, n), bool) if every_list else reached(l, T)
     th, e = K.arc_terms(l, theta_b, arc_scores)
     P = None if pos is None else np.asarray(pos, F32)

@@ -14,6 +14,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from tests.expectation_ref import sink_of
+
 F32 = np.float32
 NEG = -np.inf
 
@@ -30,7 +32,9 @@ def arc_score64(l, theta_b, arc_scores=None) -> np.ndarray:
 
 def min_max_len(l):
     """(shortest, longest) path from state 0 to the sink, in arcs."""
-    sink = l.n_rows - 1
+    sink = sink_of(l.n_rows, l.src, l.dst)
+    if sink == 0:  # state 0 is the sink: the one path is the empty one
+        return 0, 0
     keep = l.src != l.dst
     s, d = l.src[keep].astype(np.int64), l.dst[keep].astype(np.int64)
     reach = np.zeros(l.n_rows, bool)
@@ -51,7 +55,7 @@ def min_max_len(l):
 def sum_product(l, score, pos, T: int) -> dict:
     """{"logz", "len_logz" [T + 1], "pos_post" [T, V], "arc_post" [A]} in float64.  ``score`` [A] float64, ``pos`` [T, V]
     or None."""
-    n, sink, V = l.n_rows, l.n_rows - 1, l.vocab
+    n, sink, V = l.n_rows, sink_of(l.n_rows, l.src, l.dst), l.vocab
     live = np.nonzero(l.src != l.dst)[0]
     s, d, lab = l.src[live].astype(np.int64), l.dst[live].astype(np.int64), l.label[live].astype(np.int64)
     sc = np.asarray(score, np.float64)[live]
@@ -73,6 +77,8 @@ def sum_product(l, score, pos, T: int) -> dict:
         alpha = np.full(n, NEG)
         alpha[0] = 0.0
         len_logz = np.full(T + 1, NEG)
+        if sink == 0:  # the empty path
+            len_logz[0] = 0.0
         pos_post = np.zeros((T, V))
         arc_post = np.zeros(l.n_arcs)
         for t in range(T):
@@ -95,7 +101,7 @@ def max_plus(l, theta_b, pos, T: int, arc_scores=None) -> dict:
     """{"best" float32, "arcs" list (relative to the lattice), "labels", "vb" [T + 1, n] float32, "ties"}: plain float32
     in the engine's order, from position T backwards; the walk takes the smallest canonical arc whose candidate has the
     bits of vb_t(state).  ``ties[t]`` is the number of live arcs of the walked state that attain it at step t."""
-    n, sink = l.n_rows, l.n_rows - 1
+    n, sink = l.n_rows, sink_of(l.n_rows, l.src, l.dst)
     th = np.asarray(theta_b, F32)
     e = np.zeros(l.n_arcs, F32)
     if l.weight is not None:
@@ -163,7 +169,7 @@ def batch_groups(lat) -> list:
 
 def enumerate_paths(l, cap: int = 10000):
     """Every path from state 0 to the sink as a list of arcs; asserts that there are at most ``cap``."""
-    sink = l.n_rows - 1
+    sink = sink_of(l.n_rows, l.src, l.dst)
     out = {r: [] for r in range(l.n_rows)}
     for a in range(l.n_arcs):
         if l.src[a] != l.dst[a]:

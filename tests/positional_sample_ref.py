@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from tests.expectation_ref import sink_of
 from tests.positional_ref import NEG
 
 DECIDED = 1e-6  # a walk is decided when its margin exceeds this (float64 engine, float32 uniforms)
@@ -35,7 +36,7 @@ def small_uniforms(i: int, T: int, K: int = K_SMALL) -> np.ndarray:
 
 def beta_rows(l, score, pos, T: int) -> np.ndarray:
     """log beta_t(s) [T + 1, n] in float64, as ``positional_ref.sum_product`` computes them."""
-    n, sink = l.n_rows, l.n_rows - 1
+    n, sink = l.n_rows, sink_of(l.n_rows, l.src, l.dst)
     live = np.nonzero(l.src != l.dst)[0]
     s, d, lab = l.src[live].astype(np.int64), l.dst[live].astype(np.int64), l.label[live].astype(np.int64)
     sc = np.asarray(score, np.float64)[live]
@@ -61,7 +62,7 @@ class Sampler:
         self.P = None if pos is None else np.asarray(pos, np.float64)
         self.beta = beta_rows(l, score, pos, T)
         self.logz = float(self.beta[0, 0])
-        self.sink = l.n_rows - 1
+        self.sink = sink_of(l.n_rows, l.src, l.dst)
         order = np.nonzero(l.src != l.dst)[0]
         self.out = [order[l.src[order] == s] for s in range(l.n_rows)]  # canonical order within a state
 

@@ -19,6 +19,7 @@ from tests import edge_cases as E
 from tests import positional_ref as P
 from tests import positional_sample_ref as PS
 from tests import swor_ref as R
+from tests.expectation_ref import sink_of
 
 F32 = np.float32
 NEG = -np.inf
@@ -48,7 +49,7 @@ def search(l, e, pos, logbeta, Z, k: int, T: int, uniforms) -> dict:
     if not np.isfinite(Z):
         return empty
     rp = R.out_arcs(l)
-    sink = l.n_rows - 1
+    sink = sink_of(l.n_rows, l.src, l.dst)
     D = uniforms.shape[2]
     st, S, G = np.array([0]), np.array([0.0]), np.array([np.inf])
     hist = [[]]  # arcs of every slot's prefix

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from tests.expectation_ref import levels
+from tests.expectation_ref import levels, sink_of
 from tests.kbest_ref import arc_terms, enumerate_paths
 
 F32 = np.float32
@@ -23,7 +23,7 @@ def arc_slack(l, theta_b, arc_scores=None, beam=None) -> dict:
     """{"best", "vbeta" [n_rows], "state_slack" [n_rows], "slack" [A], "keep", "n_kept" (with a beam), "depth"}; vbeta
     and state_slack are -inf / +inf for the rows that lie on no path of finite score."""
     th, e = arc_terms(l, theta_b, arc_scores)
-    n, sink = l.n_rows, l.n_rows - 1
+    n, sink = l.n_rows, sink_of(l.n_rows, l.src, l.dst)
     src, dst = np.asarray(l.src, np.int64), np.asarray(l.dst, np.int64)
     depth = levels(n, src, dst)
     loop = src == dst
@@ -70,7 +70,7 @@ def is_trim(l, keep) -> bool:
     has_in[dst[k]] = True
     has_out[src[k]] = True
     has_in[0] = True
-    has_out[l.n_rows - 1] = True
+    has_out[sink_of(l.n_rows, l.src, l.dst)] = True
     return bool(np.all(has_in[src[k]]) and np.all(has_out[dst[k]]))
 
 
@@ -80,6 +80,6 @@ def max_marginals64(l, theta_b, arc_scores=None) -> np.ndarray:
     th, e = arc_terms(l, theta_b, arc_scores)
     score = th.astype(np.float64) + e.astype(np.float64)
     mm = np.full(l.n_arcs, -np.inf)
-    for s, p in enumerate_paths(l.n_rows, l.src, l.dst, score, l.n_rows - 1):
+    for s, p in enumerate_paths(l.n_rows, l.src, l.dst, score, sink_of(l.n_rows, l.src, l.dst)):
         mm[p] = np.maximum(mm[p], s)
     return mm

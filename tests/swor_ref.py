@@ -16,7 +16,7 @@ import numpy as np
 
 from nfst_amd import synth
 from tests import edge_cases as E
-from tests.expectation_ref import levels
+from tests.expectation_ref import levels, sink_of
 
 F32 = np.float32
 NEG = -np.inf
@@ -50,7 +50,7 @@ def backward64(l, e) -> tuple:
     e = np.asarray(e, np.float64)
     depth = levels(l.n_rows, l.src, l.dst)
     rp = out_arcs(l)
-    sink = l.n_rows - 1
+    sink = sink_of(l.n_rows, l.src, l.dst)
     lb = np.full(l.n_rows, NEG)
     lb[sink] = 0.0
     for s in sorted((r for r in range(l.n_rows) if depth[r] >= 0 and r != sink), key=lambda r: -depth[r]):
@@ -85,7 +85,7 @@ def search(l, e, logbeta, Z, k: int, max_len: int, uniforms) -> dict:
     if not np.isfinite(Z):
         return empty
     rp = out_arcs(l)
-    sink = l.n_rows - 1
+    sink = sink_of(l.n_rows, l.src, l.dst)
     D = uniforms.shape[2]
     st, S, G = np.array([0]), np.array([0.0]), np.array([np.inf])
     hist = [[]]  # arcs of every slot's prefix
@@ -173,7 +173,7 @@ def enumerate_paths(l, e):
     """[(arcs, score)] of every path of finite score, in the lexicographic order of the arcs."""
     e = np.asarray(e, np.float64)
     rp = out_arcs(l)
-    sink = l.n_rows - 1
+    sink = sink_of(l.n_rows, l.src, l.dst)
     out = []
 
     def walk(s, arcs, tot):

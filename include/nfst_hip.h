@@ -64,6 +64,10 @@
  *                                      list), in one launch instead of one host-side dynamic program per pair
  *   nfst_lattice_edit                  the distance between a gold row and a whole lattice with the path that attains
  *                                      it: the oracle error rate of a lattice and the closest reachable string
+ *   nfst_merge_paths                   the rows of a path set merged by the output string they spell, weights summed:
+ *                                      an n-best list of alignments becomes an n-best list of strings
+ *   nfst_string_logprob                exact log p(y | x) of candidate strings from the lattice alone: the reranker's
+ *                                      score of its hypotheses, without one product lattice per hypothesis
  *
  * Conventions
  *   - plain C: pointers and sizes only, no C++/torch types.
@@ -698,6 +702,83 @@ int nfst_lattice_edit(const nfst_batch *lat, const nfst_scores *scores /* or NUL
                       float *score /* [B] or NULL */, int32_t *paths, int32_t *path_arcs /* or NULL */, int32_t *align /* or NULL */,
                       int32_t *lengths /* [B] */, int32_t *counts /* [B,3] or NULL */, int32_t max_len, int32_t pad,
                       int32_t *status, void *stream);
+
+/*
+ * Output strings (DESIGN.md sections 2, 4.20 and 4.21).  The path-side ops answer in mark paths; the string of a path
+ * is its projection onto the output tape, given in one of two ways (device pointer, host integer):
+ *   keep [vocab] uint8    the labels of the path whose entry is non-zero, in order (WideDFA.projected_sequence's meaning)
+ *   marker                the labels that directly follow an arc labelled marker (marked_sequence's meaning): a label
+ *                         that follows the marker is a symbol even if it is the marker itself, and it does not then act
+ *                         as a marker; a marker with nothing behind it yields no symbol
+ * keep == NULL means "no mask" and marker == -1 "no marker".  Both given, a marker below -1 or not below vocab:
+ * NFST_ERR_ARG.  Neither given: NFST_ERR_ARG for nfst_string_logprob; the identity for nfst_merge_paths.
+ *
+ * nfst_merge_paths merges the rows of path sets that spell the same string ("crunching" an n-best list).  All pointers
+ * but keep's meaning above are device memory:
+ *   paths [n_sets, K, L] int32, lengths [n_sets, K], log_weights [n_sets, K] float64, n_paths [n_sets] or NULL
+ * Row k of set b is valid when k < n_paths[b] (always without n_paths) and its weight is neither -inf nor NaN (a
+ * weight of +inf is not supported).  Only paths[b, k, :lengths[b, k]] is read, and projected; a token outside
+ * [0, vocab) is on no keep mask.  Outputs, one entry per distinct projected string of the valid rows:
+ *   strings [n_sets, K, L]     the strings, every row filled up with `pad`; rows beyond n_strings[b] all pad
+ *   out_lengths [n_sets, K]    their lengths; 0 beyond n_strings[b]
+ *   out_log_weights            float64: max + log(sum_k exp(w_k - max)) over the members k in ascending row order, max
+ *                              their greatest weight; -inf beyond n_strings[b].  exp and log are evaluated in IEEE
+ *                              products, sums and one division, none of them fused (string_merge_kernels.h: exp by
+ *                              ln 2 reduction and the Taylor series to degree 13, log by 2 atanh((m - 1) / (m + 1)) to
+ *                              z^23), so the bits do not depend on a math library and a restatement reproduces them
+ *   n_strings [n_sets]
+ *   group [n_sets, K]          the entry input row k went to; -1 for an invalid row
+ *   first [n_sets, K]          per entry the lowest input row among its members of greatest weight; -1 beyond n_strings
+ * Entries are ordered by merged weight, descending; equal weights by their lowest member row.  Rows are equal when their
+ * projected lengths are, a 64-bit hash of the projected rows agrees in its low hash_bits bits (1 .. 64) and a comparison
+ * token by token confirms it: hash_bits changes the work, never the outputs.  scratch [n_sets, K, L] int32 is
+ * overwritten (the projected rows).  One workgroup per set, no atomics: the same bits at every launch.
+ * A length outside [0, L] is found on the device: *status = NFST_ERR_LENGTH (status: device, one word, zeroed by the
+ * caller), the row counts as invalid, none of its tokens is read and the rest is computed as usual.
+ * K > 1024 or L > NFST_EDIT_MAX_LEN: NFST_ERR_LIMIT.  Negative n_sets or K, L < 1, hash_bits outside 1 .. 64, a bad
+ * tape, a null status or (when n_sets * K > 0) any other null required pointer: NFST_ERR_ARG; all on the host before
+ * any launch.  n_sets * K == 0 is a successful no-op (the data pointers may then be null).
+ */
+int nfst_merge_paths(const int32_t *paths, const int32_t *lengths, const double *log_weights, const int32_t *n_paths /* or NULL */,
+                     int32_t n_sets, int32_t K, int32_t L, const uint8_t *keep /* [vocab] or NULL */, int32_t vocab,
+                     int32_t marker /* -1: none */, int32_t hash_bits, int32_t pad, int32_t *scratch, int32_t *strings,
+                     int32_t *out_lengths, double *out_log_weights, int32_t *n_strings, int32_t *group, int32_t *first,
+                     int32_t *status, void *stream);
+
+/*
+ * nfst_string_logprob: for lattice b and candidate m, y = strings[b, m, :lengths[b, m]] (strings [B, M, N] int32,
+ * lengths [B, M]; nothing beyond a length is read),
+ *   log_num [B, M] float64   the log of the sum of exp(path score) over the paths whose projection onto the tape is y;
+ *                            -inf (never NaN, and no error) when no path spells y
+ *   logz [B] float64         the same sum over all paths of the lattice, from the same sweep
+ * so that log_num - logz is log p(y | x) exactly, for any number of paths and without a product lattice.  A path runs
+ * from state 0 to the sink, self loops are on no path, and an arc contributes theta[label] + arc_w[a] (if weighted) +
+ * arc_scores[a] (if given), each taken as float64 and added in this order.  Acceptance is that of
+ * WideDFA.projected_sequence(vocab, keep, y) or WideDFA.marked_sequence(vocab, marker, y): a path that ends on a marker
+ * with nothing behind it spells no string (in marker mode the strings' probabilities add up to 1 less those paths'
+ * share).  Cells are float64 log weights, n = len(y), j tokens of y spelled so far:
+ *   keep:    G[sink][j] = [j == n];  G[s][j] = sum over the out-arcs a: s -> d, d != s, label l of
+ *                w_a (l not kept ? G[d][j] : (j < n and y[j] == l) ? G[d][j + 1] : 0)
+ *   marker:  two rows per state, G0 (the arc into s was no active marker) and G1 (it was one): under G1 the label must
+ *            equal y[j] and leads to G0[d][j + 1]; under G0 a marker arc leads to G1[d][j], any other to G0[d][j];
+ *            G0[sink][j] = [j == n], G1[sink][j] = 0
+ * and the answer is G[0][0] (G0).  A state's sum runs over its arcs in canonical order as a running log-sum around the
+ * greatest term so far; only the canonical arrays are read and there are no atomics: the same bits at every launch and
+ * under every packing.  A lattice whose state 0 is the sink gives 0 for the empty string, -inf otherwise, and logz 0.
+ * A lengths[b, m] outside [0, N] is found on the device: *status = NFST_ERR_LENGTH (status: device, one word, zeroed by
+ * the caller), that candidate gets -inf and none of its tokens is read; the others are computed as usual.
+ * ws: device workspace of nfst_string_logprob_ws_bytes(lat, M, N, marker >= 0) bytes (16-byte aligned, overwritten):
+ * 8 (N + 1) M bytes per row of the batch, twice that in marker mode, plus 20 bytes per row; every part rounded up to
+ * 256.  LDS: 12 max_rows + 16 bytes (the level pass); more than 160 KiB returns NFST_ERR_LIMIT.
+ * M < 0, N < 1, a bad tape, null required pointers (strings, lengths and log_num may be null when M == 0: logz alone is
+ * computed) or a short workspace: NFST_ERR_ARG; N > NFST_EDIT_MAX_LEN: NFST_ERR_LIMIT; all on the host before any
+ * launch.  n_lattices == 0 is a successful no-op (nfst_string_logprob_ws_bytes: 0).
+ */
+int64_t nfst_string_logprob_ws_bytes(const nfst_batch *lat, int32_t M, int32_t N, int32_t marker_mode);
+int nfst_string_logprob(const nfst_batch *lat, const nfst_scores *scores, const int32_t *strings, const int32_t *lengths, int32_t M,
+                        int32_t N /* row stride of strings */, const uint8_t *keep /* [vocab] or NULL */, int32_t marker /* -1: none */,
+                        void *ws, int64_t ws_bytes, double *log_num /* [B,M] */, double *logz /* [B] */, int32_t *status,
+                        void *stream);
 
 /*
  * Arc slack, the max-plus counterpart of the arc posteriors, and beam masks (DESIGN.md sections 2 and 4.7).  A path

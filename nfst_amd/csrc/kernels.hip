@@ -43,6 +43,8 @@ using namespace nfst_tile;
 #include "swor_kernels.h"
 #include "edit_kernels.h"
 #include "lattice_edit_kernels.h"
+#include "string_merge_kernels.h"
+#include "string_logprob_kernels.h"
 #include "slack_kernels.h"
 #include "intersect_kernels.h"
 #include "intersect_wide_kernels.h"
@@ -1072,6 +1074,83 @@ int nfst_lattice_edit(const nfst_batch *lat, const nfst_scores *scores, const in
   const nfst_scores none{};
   if ((rc = launch(k_lattice_edit_sweep<false>, grid, dim3(kLeThreads), lds_sweep, st, *lat, none, in, w, status))) return rc;
   return launch(k_lattice_edit_walk<false>, grid, dim3(64), 0, st, *lat, none, in, w, out);
+}
+
+// ------------------------------------------------------------------ path sets merged by their output strings (string_merge_kernels.h)
+// the tape of nfst_merge_paths and nfst_string_logprob: a keep mask, a marker, or (need_one == false) neither
+static int tape_check(const uint8_t *keep, int32_t marker, int32_t vocab, bool need_one) {
+  if (marker < -1 || (keep && marker >= 0) || (need_one && !keep && marker < 0)) return NFST_ERR_ARG;
+  if ((keep || marker >= 0) && (vocab < 1 || marker >= vocab)) return NFST_ERR_ARG;
+  return NFST_OK;
+}
+
+int nfst_merge_paths(const int32_t *paths, const int32_t *lengths, const double *log_weights, const int32_t *n_paths, int32_t n_sets,
+                     int32_t K, int32_t L, const uint8_t *keep, int32_t vocab, int32_t marker, int32_t hash_bits, int32_t pad,
+                     int32_t *scratch, int32_t *strings, int32_t *out_lengths, double *out_log_weights, int32_t *n_strings,
+                     int32_t *group, int32_t *first, int32_t *status, void *stream) {
+  if (n_sets < 0 || K < 0 || L < 1 || hash_bits < 1 || hash_bits > 64 || !status) return NFST_ERR_ARG;
+  if (int rc = tape_check(keep, marker, vocab, false)) return rc;
+  if (K > kSmMaxK || L > kEditMaxLen) return NFST_ERR_LIMIT;
+  if ((int64_t)n_sets * K == 0) return NFST_OK;
+  if (!paths || !lengths || !log_weights || !scratch || !strings || !out_lengths || !out_log_weights || !n_strings || !group || !first)
+    return NFST_ERR_ARG;
+  const SmIn in{paths, lengths, log_weights, n_paths, keep, (int)K, (int)L, (int)vocab, (int)marker, (int)pad,
+                hash_bits == 64 ? ~0ull : ((1ull << hash_bits) - 1)};
+  const SmOut out{scratch, strings, out_lengths, out_log_weights, n_strings, group, first, status};
+  return launch(k_merge_paths, dim3(n_sets), dim3(kSmThreads), 0, (hipStream_t)stream, in, out);
+}
+
+// ------------------------------------------------------------------ exact string weights (string_logprob_kernels.h)
+// workspace: N + 1 cells of 8 bytes per row, candidate and plane, log Z of every row, then the level arrays of k_kbest_levels
+static int64_t sl_ws_layout(const nfst_batch *lat, int M, int N, int planes, char *base, SlWs *w) {
+  const int64_t TR = lat->total_rows, B = lat->n_lattices, sm = (int64_t)planes * (N + 1), sr = sm * M;
+  WsCarve c{base};
+  char *ce = c.take(8 * TR * sr), *zz = c.take(8 * TR), *od = c.take(4 * TR), *lv = c.take(4 * (TR + B)), *nl = c.take(4 * B);
+  if (w) *w = {(double *)ce, (double *)zz, (int *)od, (int *)lv, (int *)nl, sm, sr};
+  return c.size;
+}
+static int sl_check_sizes(int32_t M, int32_t N) {
+  if (M < 0 || N < 1) return NFST_ERR_ARG;
+  return N > kEditMaxLen ? NFST_ERR_LIMIT : NFST_OK;
+}
+
+int64_t nfst_string_logprob_ws_bytes(const nfst_batch *lat, int32_t M, int32_t N, int32_t marker_mode) {
+  if (!lat) return NFST_ERR_ARG;
+  int rc = sl_check_sizes(M, N);
+  if (rc) return rc;
+  if (lat->n_lattices == 0) return 0;
+  if ((rc = check_batch(lat))) return rc;
+  return sl_ws_layout(lat, M, N, marker_mode ? 2 : 1, nullptr, nullptr);
+}
+
+int nfst_string_logprob(const nfst_batch *lat, const nfst_scores *scores, const int32_t *strings, const int32_t *lengths, int32_t M,
+                        int32_t N, const uint8_t *keep, int32_t marker, void *ws, int64_t ws_bytes, double *log_num, double *logz,
+                        int32_t *status, void *stream) {
+  if (!lat || !status) return NFST_ERR_ARG;
+  int rc = sl_check_sizes(M, N);
+  if (rc) return rc;
+  if ((rc = tape_check(keep, marker, lat->vocab, true))) return rc;
+  if (lat->n_lattices == 0) return NFST_OK;
+  if ((rc = check_batch(lat))) return rc;
+  if ((rc = check_scores(lat, scores))) return rc;
+  if (!logz || (M > 0 && (!strings || !lengths || !log_num))) return NFST_ERR_ARG;
+  const int planes = marker >= 0 ? 2 : 1;
+  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < sl_ws_layout(lat, M, N, planes, nullptr, nullptr)) return NFST_ERR_ARG;
+  const int64_t lds_lev = (int64_t)lat->max_rows * 12 + 16;
+  const int64_t lds_sweep = ((int64_t)lat->max_rows * 2 + 1) * 4;
+  if (lds_lev > kMaxLds || lds_sweep > kMaxLds) return NFST_ERR_LIMIT;
+  SlWs w;
+  sl_ws_layout(lat, M, N, planes, (char *)ws, &w);
+  const KbWs lw{nullptr, w.order, w.lev, w.n_lev};  // (k_kbest_levels writes the level arrays only)
+  const SlIn in{strings, lengths, (int)M, (int)N, keep, (int)marker};
+  const hipStream_t st = (hipStream_t)stream;
+  // the candidates of a lattice are dealt to as many workgroups as fill the device about twice (any number gives the same bits)
+  const int64_t want = (2 * (int64_t)cu_count() + lat->n_lattices - 1) / lat->n_lattices;
+  const int Y = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(M, want), 65535));
+  if ((rc = launch(k_kbest_levels, dim3(lat->n_lattices), dim3(kKbLevelThreads), lds_lev, st, *lat, lw))) return rc;
+  const dim3 grid(lat->n_lattices, Y);
+  if (marker >= 0) return launch(k_string_logprob<true>, grid, dim3(kSlThreads), lds_sweep, st, *lat, *scores, in, w, log_num, logz, status);
+  return launch(k_string_logprob<false>, grid, dim3(kSlThreads), lds_sweep, st, *lat, *scores, in, w, log_num, logz, status);
 }
 
 // ------------------------------------------------------------------ arc slack and beam masks (slack_kernels.h)

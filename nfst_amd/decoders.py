@@ -161,3 +161,75 @@ def mbr_decode(result):
     D = ops.pairwise_edit_distance(result.paths, result.lengths)
     index, risk = mbr_select(D, logw, result.n_paths)
     return index, risk, D
+
+
+# ----------------------------------------------------------------------------- output strings
+class StringDecodeResult(NamedTuple):
+    strings: torch.Tensor     # [B, k, L] int32: the distinct output strings of the path set, best first, pad-filled
+    lengths: torch.Tensor     # [B, k] int32 (0 beyond n_strings)
+    log_prob: torch.Tensor    # [B, k] float64: exact log p(y | x) (rescore=False: path_mass); -inf beyond n_strings
+    n_strings: torch.Tensor   # [B] int32
+    path_mass: torch.Tensor   # [B, k] float64: the merged weight of the string's paths in the set, less log Z
+    first_path: torch.Tensor  # [B, k] int32: the row of the path set that represents the string (its heaviest alignment); -1 beyond n_strings
+
+
+def path_scores64(lat, theta: torch.Tensor, r, arc_scores=None) -> torch.Tensor:
+    """The scores [B, k] of the paths of a ``KBestResult`` summed again in float64 from their arcs (``best`` is the
+    kernel's float32 sum): theta[label] + the table's weight + arc_scores per arc, as ``ops.string_log_prob`` takes them,
+    so that a string's share of its paths compares with its exact weight at float64 round-off; -inf beyond ``n_paths``."""
+    B, k, L = r.paths.shape
+    dev = r.paths.device
+    live = torch.arange(L, device=dev)[None, None, :] < r.lengths[:, :, None]
+    labels, arcs = r.paths.to(torch.int64).clamp(min=0), r.arcs.to(torch.int64).clamp(min=0)
+    th = theta.detach().to(device=dev, dtype=torch.float64)
+    t = th[labels] if th.dim() == 1 else th.gather(1, labels.reshape(B, -1)).reshape(B, k, L)
+    if lat.weighted:
+        t = t + lat.arc_w.to(torch.float64)[arcs]
+    if arc_scores is not None:
+        t = t + arc_scores.detach().to(device=dev, dtype=torch.float64)[arcs]
+    s = torch.where(live, t, torch.zeros_like(t)).sum(dim=2)
+    return torch.where(torch.arange(k, device=dev)[None, :] < r.n_paths[:, None], s, torch.full_like(s, float("-inf")))
+
+
+def decode_strings(lat, theta, k: int, *, keep=None, marker: Optional[int] = None, method: str = "k_best", rescore: bool = True,
+                   arc_scores=None, seed: int = 0, pad: int = 0) -> StringDecodeResult:
+    """The best output strings of every lattice with their exact probabilities.  The ``k`` best paths (``method="k_best"``,
+    weighed by their scores ``best``, summed again in float64: ``path_scores64``) or ``k`` paths drawn without replacement (``"swor"``, weighed by ``swor.log_weights``) are
+    merged by the string they spell on the tape ``keep`` or ``marker`` (``ops.merge_paths``): one alignment's score is
+    not a string's, and the heaviest string need not own the best path.  ``rescore=True`` then computes log p(y | x) of
+    every distinct string exactly (``ops.string_log_prob``) and ranks by it, ties keeping the merged order;
+    ``path_mass`` keeps what the path set saw of each string, its merged weight minus log Z -- for ``k_best`` a lower
+    bound of ``log_prob``.  ``rescore=False`` returns the merged order with ``log_prob`` = ``path_mass``."""
+    if (keep is None) == (marker is None):
+        raise ValueError("give keep (a set of labels) or marker (a label)")
+    theta = torch.as_tensor(theta, dtype=torch.float32).detach()
+    if method == "k_best":
+        r = ops.k_best_terms(lat, theta, k, arc_scores, pad=pad)
+        logw = path_scores64(lat, theta, r, arc_scores)  # (``best``, in float64)
+    elif method == "swor":
+        r = swor.sample(lat, theta, k, arc_scores, seed=seed, pad=pad)
+        logw = swor.log_weights(r)  # (of probabilities: log Z is in them already)
+    else:
+        raise ValueError(f"method must be 'k_best' or 'swor', not {method!r}")
+    s = ops.merge_paths(r.paths, r.lengths, logw, r.n_paths, keep=keep, marker=marker, vocab=lat.vocab, pad=pad)
+    live = torch.arange(s.strings.shape[1], device=s.strings.device)[None, :] < s.n_strings[:, None]
+    n_max = max(1, int(s.lengths.max())) if s.lengths.numel() else 1  # (the workspace grows with the candidates' row stride)
+    cand = (s.strings[:, :, :n_max], s.lengths) if rescore else (s.strings[:, :0], s.lengths[:, :0])  # (no candidate: log Z alone)
+    sc = ops.string_log_prob(lat, theta, *cand, keep=keep, marker=marker, arc_scores=arc_scores)
+    mass = torch.where(live, s.log_weights - sc.logz[:, None], s.log_weights) if method == "k_best" else s.log_weights
+    if not rescore:
+        return StringDecodeResult(s.strings, s.lengths, mass, s.n_strings, mass, s.first)
+    logp = torch.where(live, sc.log_prob, torch.full_like(sc.log_prob, float("-inf")))
+    # exact log p descending, ties and the dead entries in the merged order (a stable sort; NaN cannot occur)
+    order = torch.sort(torch.where(live, -logp, torch.full_like(logp, float("inf"))), dim=1, stable=True).indices
+    take = lambda x: x.gather(1, order)
+    return StringDecodeResult(s.strings.gather(1, order[:, :, None].expand_as(s.strings)), take(s.lengths), take(logp), s.n_strings,
+                              take(mass), take(s.first))
+
+
+def mbr_decode_strings(string_set):
+    """``mbr_decode`` on output strings: ``(index [B] int64, risk [B, K] float64, distances [B, K, K] int32)`` of a
+    ``ops.StringSet`` under edit distance between the strings, weighed by the merged weights."""
+    D = ops.pairwise_edit_distance(string_set.strings, string_set.lengths)
+    index, risk = mbr_select(D, string_set.log_weights.detach(), string_set.n_strings)
+    return index, risk, D

@@ -166,6 +166,23 @@ class LatticeScorer(torch.nn.Module):
             raise ValueError(f"draws must be 'k_best' or 'swor', not {draws!r}")
         return self._mbr_entries(r)
 
+    def decode_strings(self, k: int, **kw) -> list:
+        """The best output strings of every lattice: per lattice ``[(log p, symbols), ...]``, best first, the distinct
+        strings that the ``k`` best (``method="swor"``: drawn) paths spell on the tape ``keep`` or ``marker``, each with
+        its exact log p(y | x) under ``theta`` (``decoders.decode_strings``; ``kw``: ``keep``, ``marker``, ``method``,
+        ``rescore``, ``seed``)."""
+        from .decoders import decode_strings
+
+        r = decode_strings(self._lat(), self.theta.detach(), k, pad=self.__pad__, **kw)
+        logp, rows, lens, n = (x.cpu().numpy() for x in (r.log_prob, r.strings, r.lengths, r.n_strings))
+        return [[(float(logp[b, j]), rows[b, j, :lens[b, j]].tolist()) for j in range(int(n[b]))] for b in range(len(n))]
+
+    def string_log_prob(self, strings: torch.Tensor, lengths: torch.Tensor, **kw) -> torch.Tensor:
+        """The reranker's call: exact log p(y | x) float64 [B, M] of the candidate strings ``strings[b, m, :lengths[b,
+        m]]`` under ``theta`` (``ops.string_log_prob``; ``kw``: ``keep`` or ``marker``); -inf for a string that no path
+        spells."""
+        return ops.string_log_prob(self._lat(), self.theta.detach(), strings, lengths, **kw).log_prob
+
     def _oracle(self, ref: torch.Tensor, ref_lengths: Optional[torch.Tensor]) -> tuple:
         """``(ops.LatticeEditResult, ref_lengths)`` of the oracle path under ``theta``; without ``ref_lengths`` the trailing
         entries of a row equal to the scorer's pad do not count."""

@@ -1,0 +1,187 @@
+"""Output strings: the wrappers of ``nfst_merge_paths`` and ``nfst_string_logprob`` (include/nfst_hip.h; DESIGN.md sections
+2, 4.20 and 4.21).  The path-side ops answer in mark paths; the string of a path is its projection onto the output tape,
+given as ``keep`` (a set of labels: the path's labels that belong to it, ``WideDFA.projected_sequence``'s meaning) or as
+``marker`` (the labels that directly follow an arc labelled ``marker``, ``WideDFA.marked_sequence``'s meaning).
+``ops.merge_paths`` and ``ops.string_log_prob`` are these functions; ``decoders.decode_strings`` puts them together.
+There is no CPU implementation.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from .edit import _edit_side
+
+MERGE_MAX_K = 1024  # nfst_merge_paths: the rows of one set
+
+
+class StringSet(NamedTuple):
+    strings: torch.Tensor      # [B, K, L] int32: one row per distinct string, pad-filled
+    lengths: torch.Tensor      # [B, K] int32 (0 beyond n_strings)
+    log_weights: torch.Tensor  # [B, K] float64: the logsumexp of the members' weights, descending (-inf beyond n_strings)
+    n_strings: torch.Tensor    # [B] int32 distinct strings
+    group: torch.Tensor        # [B, K] int32: the entry that input row k went to (-1: an invalid row)
+    first: torch.Tensor        # [B, K] int32: per entry the lowest input row among its members of greatest weight (-1 beyond n_strings)
+
+
+class StringScores(NamedTuple):
+    log_num: torch.Tensor   # [B, M] float64: log of the summed weight of the paths that spell the string (-inf: none does)
+    logz: torch.Tensor      # [B] float64: the same over all paths
+    log_prob: torch.Tensor  # [B, M] float64 = log_num - logz
+
+
+def _tape(keep, marker, vocab: Optional[int], device, need_one: bool) -> tuple:
+    """``(keep mask [vocab] uint8 on the device or None, marker or -1, vocab)`` of the two ways to give the tape."""
+    if keep is not None and marker is not None:
+        raise ValueError("give keep or marker, not both")
+    if keep is None and marker is None:
+        if need_one:
+            raise ValueError("give keep (a set of labels) or marker (a label)")
+        return None, -1, 0
+    labels = np.asarray([marker] if keep is None else sorted(set(int(x) for x in keep)), np.int64).reshape(-1)
+    if vocab is None:
+        vocab = int(labels.max()) + 1 if labels.size else 1
+    if vocab < 1 or (labels.size and (labels.min() < 0 or labels.max() >= vocab)):
+        raise ValueError(f"the labels of keep / marker must lie in 0 .. {vocab - 1}")
+    if keep is None:
+        return None, int(marker), int(vocab)
+    mask = np.zeros(vocab, np.uint8)
+    mask[labels] = 1
+    return torch.from_numpy(mask).to(device), -1, int(vocab)
+
+
+def _merge_launch(paths, lengths, logw, n_paths, keep_mask, marker: int, vocab: int, pad: int, hash_bits: int = 64):
+    """One launch of ``nfst_merge_paths`` on marshalled inputs: ``(StringSet, status word on the device)``."""
+    from .ops import _call
+
+    B, K, L = paths.shape
+    dev, i32 = paths.device, torch.int32
+    strings = torch.empty((B, K, L), dtype=i32, device=dev)
+    out_len = torch.empty((B, K), dtype=i32, device=dev)
+    out_w = torch.empty((B, K), dtype=torch.float64, device=dev)
+    n_strings = torch.zeros(B, dtype=i32, device=dev)
+    group = torch.empty((B, K), dtype=i32, device=dev)
+    first = torch.empty((B, K), dtype=i32, device=dev)
+    status = torch.zeros(1, dtype=i32, device=dev)
+    scratch = torch.empty((B, K, L), dtype=i32, device=dev)
+    _call("nfst_merge_paths", None, paths, lengths, logw, n_paths, B, K, L, keep_mask, vocab, marker, hash_bits, int(pad), scratch,
+          strings, out_len, out_w, n_strings, group, first, status)  # (K > MERGE_MAX_K, L > EDIT_MAX_LEN: NFST_ERR_LIMIT)
+    return StringSet(strings, out_len, out_w, n_strings, group, first), status
+
+
+class _MergedWeight(torch.autograd.Function):
+    """merged[b, g] = logsumexp of the weights of group g's members: d merged[g] / d w[k] = exp(w[k] - merged[g]) for the
+    members k of g, from ``group``."""
+
+    @staticmethod
+    def forward(ctx, log_weights, merged, group):
+        ctx.save_for_backward(log_weights, merged, group)
+        return merged.clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        w, merged, group = ctx.saved_tensors
+        ok = group >= 0
+        idx = group.clamp(min=0).to(torch.int64)
+        share = torch.exp(w.to(torch.float64) - merged.gather(1, idx))
+        grad = torch.where(ok, share * g.gather(1, idx), torch.zeros_like(share))
+        return grad.to(w.dtype), None, None
+
+
+def merge_paths(paths: torch.Tensor, lengths: torch.Tensor, log_weights: torch.Tensor, n_paths: Optional[torch.Tensor] = None, *,
+                keep=None, marker: Optional[int] = None, vocab: Optional[int] = None, pad: int = 0) -> StringSet:
+    """The rows of every path set merged by the string they spell ("crunching", ``nfst_merge_paths``): ``paths``
+    [B, K, L] int32 or int64 with ``lengths`` [B, K], as ``k_best``, ``swor.sample`` or ``sample_paths`` return them, and
+    ``log_weights`` [B, K] float32 or float64 (taken as float64).  Row k counts when k < ``n_paths[b]`` (always without
+    ``n_paths``) and its weight is neither -inf nor NaN; only ``paths[b, k, :lengths[b, k]]`` is read.  The string of a
+    row is its projection onto the tape ``keep`` or ``marker`` (module docstring; ``vocab`` bounds their labels and
+    defaults to the largest of them + 1); with neither it is the row itself, and the op merges plain duplicates.  The
+    result has one entry per distinct string, its weight the float64 logsumexp of its members' weights (summed in
+    ascending row order around their maximum), ordered by that weight, descending, ties by the lowest member row; the same
+    bits at every launch.  K <= 1024, L <= ``EDIT_MAX_LEN``.  A length outside [0, L] raises ``NfstError``
+    (NFST_ERR_LENGTH) after the launch.  The weights carry the gradient into ``log_weights``."""
+    from .ops import _raise_status
+
+    if not isinstance(paths, torch.Tensor) or paths.device.type != "cuda":
+        raise RuntimeError("nfst_amd: merge_paths runs on the MI355X only (no CPU fallback)")
+    if paths.dim() != 3:
+        raise ValueError("paths must be [B, K, L]")
+    rows, lens, _ = _edit_side(paths, lengths, "paths")
+    B, K, L = rows.shape
+    if not isinstance(log_weights, torch.Tensor) or log_weights.device != rows.device or tuple(log_weights.shape) != (B, K) \
+            or log_weights.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"log_weights must be a float32 or float64 tensor [{B}, {K}] on paths' device")
+    if n_paths is not None:
+        if not isinstance(n_paths, torch.Tensor) or n_paths.numel() != B or n_paths.dtype not in (torch.int32, torch.int64):
+            raise ValueError("n_paths must hold one integer per set")
+        n_paths = n_paths.reshape(B).to(device=rows.device, dtype=torch.int32).contiguous()
+    keep_mask, mk, V = _tape(keep, marker, vocab, rows.device, need_one=False)
+    logw = log_weights.detach().to(torch.float64).contiguous()
+    out, status = _merge_launch(rows, lens, logw, n_paths, keep_mask, mk, V, pad)
+    if B * K:
+        _raise_status(status, "nfst_merge_paths")  # a length outside its row
+    if log_weights.requires_grad:
+        out = out._replace(log_weights=_MergedWeight.apply(log_weights, out.log_weights, out.group))
+    return out
+
+
+def string_log_prob(lat, theta, strings: torch.Tensor, lengths: torch.Tensor, *, keep=None, marker: Optional[int] = None,
+                    arc_scores=None, max_workspace_bytes: int = 1 << 30) -> StringScores:
+    """Exact log p(y | x) of candidate strings from the lattice alone (``nfst_string_logprob``): for lattice b and
+    candidate m, y = ``strings[b, m, :lengths[b, m]]`` (``strings`` [B, M, N] int32 or int64, N <= ``EDIT_MAX_LEN``),
+    ``log_num`` is the log of the summed weight exp(score) of the paths whose projection onto the tape ``keep`` or
+    ``marker`` is y, ``logz`` that of all paths and ``log_prob`` their difference, all float64; a string that no path
+    spells gets -inf, which is no error.  Scores are those of the other path-side ops (``theta`` [V] or [B, V],
+    ``arc_scores`` [total_arcs], the table's weights), acceptance that of ``WideDFA.projected_sequence`` /
+    ``marked_sequence``; unlike ``ops.constraint_log_prob`` on those automata, nothing is intersected or packed, the
+    arithmetic is float64 and no product has to fit ``NFST_MAX_ROWS``.  The candidates are swept in slices whose workspace
+    stays under ``max_workspace_bytes`` (ValueError if one candidate does not fit); the bits do not depend on the
+    slicing.  A length outside [0, N] raises ``NfstError`` (NFST_ERR_LENGTH) after the launch.  Forward only: for
+    gradients use ``ops.constraint_log_prob``."""
+    from .ops import _call, _need_gpu, _raise_status, _scores
+
+    _need_gpu(lat)
+    B = lat.n_lattices
+    if not isinstance(strings, torch.Tensor) or strings.dim() != 3 or strings.shape[0] != B:
+        raise ValueError(f"strings must be an int32 or int64 tensor [{B}, M, N]")
+    if not isinstance(theta, torch.Tensor):
+        theta = torch.as_tensor(theta, dtype=torch.float32)
+    rows, lens, _ = _edit_side(strings.to(lat.device), lengths.to(lat.device) if isinstance(lengths, torch.Tensor) else lengths, "strings")
+    M, N = rows.shape[1], rows.shape[2]
+    keep_mask, mk, _ = _tape(keep, marker, lat.vocab, lat.device, need_one=True)
+    sc, alive = _scores(lat, theta.detach(), None if arc_scores is None else arc_scores.detach())
+    dev = lat.device
+    log_num = torch.empty((B, M), dtype=torch.float64, device=dev)
+    logz = torch.empty(B, dtype=torch.float64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    bs = C.byref(lat.c_struct())
+
+    def ws_bytes(m):
+        n = int(_lib.lib.nfst_string_logprob_ws_bytes(bs, m, N, int(mk >= 0)))
+        if n < 0:
+            _lib.check(n, "nfst_string_logprob_ws_bytes")  # (N > EDIT_MAX_LEN: NFST_ERR_LIMIT)
+        return n
+
+    fixed = ws_bytes(0)
+    per = max(ws_bytes(1) - fixed, 1)
+    if fixed + per > max_workspace_bytes and M > 0:
+        raise ValueError(f"one candidate needs a workspace of {fixed + per} bytes, max_workspace_bytes is {max_workspace_bytes}")
+    step = max(1, min(M, (max_workspace_bytes - fixed) // per)) if M else 0
+    ws = torch.empty(max(ws_bytes(step), 16), dtype=torch.uint8, device=dev)
+    for m0 in range(0, max(M, 1), max(step, 1)):
+        m1 = min(M, m0 + step)
+        part_rows = rows[:, m0:m1].contiguous()
+        part_lens = lens[:, m0:m1].contiguous()
+        part_num = log_num if (m0, m1) == (0, M) else torch.empty((B, m1 - m0), dtype=torch.float64, device=dev)
+        _call("nfst_string_logprob", lat, sc, part_rows, part_lens, m1 - m0, N, keep_mask, mk, ws, ws.numel(), part_num, logz, status)
+        if part_num is not log_num:
+            log_num[:, m0:m1] = part_num
+    _raise_status(status, "nfst_string_logprob")  # a candidate's length outside its row
+    del alive
+    neg = torch.full_like(log_num, float("-inf"))
+    return StringScores(log_num, logz, torch.where(torch.isneginf(log_num), neg, log_num - logz[:, None]))

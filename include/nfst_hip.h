@@ -68,6 +68,8 @@
  *                                      an n-best list of alignments becomes an n-best list of strings
  *   nfst_string_logprob                exact log p(y | x) of candidate strings from the lattice alone: the reranker's
  *                                      score of its hypotheses, without one product lattice per hypothesis
+ *   nfst_string_logprob_grad           its exact gradient in every arc's score: maximum likelihood and risk on strings,
+ *                                      and the arc posteriors given a string
  *
  * Conventions
  *   - plain C: pointers and sizes only, no C++/torch types.
@@ -779,6 +781,54 @@ int nfst_string_logprob(const nfst_batch *lat, const nfst_scores *scores, const 
                         int32_t N /* row stride of strings */, const uint8_t *keep /* [vocab] or NULL */, int32_t marker /* -1: none */,
                         void *ws, int64_t ws_bytes, double *log_num /* [B,M] */, double *logz /* [B] */, int32_t *status,
                         void *stream);
+
+/*
+ * nfst_string_logprob_grad: the derivative of sum_{b,m} g_num[b, m] log_num[b, m] + sum_b g_z[b] logz[b] in every arc's
+ * score, the one float64 value theta[label] + arc_w + arc_scores that nfst_string_logprob forms.
+ * Inputs as nfst_string_logprob's, plus g_num [B, M] and g_z [B] float64 (device) and the host integer accumulate;
+ * output grad_arc [total_arcs] float64 in canonical arc order.  The entry point recomputes G, G0, G1 and z (the sweep of
+ * nfst_string_logprob, bit for bit) and sweeps the matching prefix tables in ascending level order: F[s][j], the log
+ * weight of the path prefixes from state 0 to s that have spelled y[:j], and az[s], that of all prefixes; w_a is the score
+ * of arc a: s -> d with label l, s != d:
+ *   keep:    F[0][j] = [j == 0];  a non-kept arc carries F[s][j] to F[d][j], a kept one F[s][j] to F[d][j + 1] when
+ *            j < n and y[j] == l
+ *            post_m(a) = sum_j exp(F[s][j] + w_a + G[d][j] - log_num)                         (l not kept)
+ *                        sum_{j < n, y[j] == l} exp(F[s][j] + w_a + G[d][j + 1] - log_num)    (l kept)
+ *   marker:  F0[0][j] = [j == 0], F1[0][j] = 0;  from F0[s][j] a marker arc goes to F1[d][j], any other to F0[d][j];
+ *            from F1[s][j] every arc goes to F0[d][j + 1] when j < n and y[j] == l
+ *            post_m(a) = sum_j (exp(F0[s][j] + w_a + (l == marker ? G1 : G0)[d][j] - log_num)
+ *                               + [j < n and y[j] == l] exp(F1[s][j] + w_a + G0[d][j + 1] - log_num))
+ *   log Z:   az[0] = 0;  post_z(a) = exp(az[s] + w_a + z[d] - z[0])
+ *   grad_arc[a] = (((start + t_0) + t_1) + ...) + t_{M-1},  t_m = g_num[b, m] post_m(a), added in ascending m;
+ *            start = g_z[b] post_z(a) with accumulate == 0; with accumulate != 0 start is the value already in
+ *            grad_arc[a] and the g_z term is not added again (g_z may then be NULL), so that a caller who slices the
+ *            candidates -- the first slice with accumulate == 0, the others in ascending order with accumulate != 0 --
+ *            gets the bits of one launch.
+ * Order of the sums (float64, none fused across terms): a cell of F is a running log-sum around the greatest term so far
+ * (as G's) over the in-arcs of its state in ascending canonical arc id, a term being w_a + F[s][.]; in marker mode an
+ * in-arc adds to F0[d][j] first its F0 term, then its F1 term.  An exponent of post is evaluated as ((F + w_a) + G) -
+ * log_num.  Inside t_m the columns j are taken in strips of 64, j = 64 p + lane; lane j's term of a strip is 0 outside
+ * the row and in marker mode the F0 term plus the F1 term in this order; the 64 terms of a strip are added in the tree
+ * x_i += x_(i^1), x_(i^2), x_(i^7), x_(i^15) (four stages inside every 16 lanes), then (r_0 + r_16) + (r_32 + r_48); the
+ * strips' sums are added to 0.0 in ascending p; t_m is g_num[b, m] times that sum.
+ * Exactly 0 (never NaN, and no error): a self loop, an arc whose source state 0 does not reach or that reaches no sink,
+ * a candidate whose log_num is -inf, a candidate with g_num[b, m] == 0, a candidate with a length outside [0, N]
+ * (*status = NFST_ERR_LENGTH as in nfst_string_logprob, none of its tokens is read), a lattice whose state 0 is the sink.
+ * Only the canonical arrays are read and there are no atomics on values: the same bits at every launch, for every grid,
+ * under every packing and for every such slicing.
+ * ws: device workspace of nfst_string_logprob_grad_ws_bytes(lat, M, N, marker >= 0) bytes (16-byte aligned, overwritten):
+ * that of nfst_string_logprob, a second cell table of the same size, 8 bytes per row, 8 (M + 1) per lattice, and the
+ * in-arc lists (4 bytes per row and lattice, 8 per arc); every part rounded up to 256.  LDS: 12 max_rows + 4100 bytes.
+ * Checks and their codes are those of nfst_string_logprob (g_num may be null when M == 0: the log Z term alone; a null
+ * g_z without accumulate, a null grad_arc with arcs: NFST_ERR_ARG), all on the host before any launch, outputs untouched.
+ * n_lattices == 0 is a successful no-op (nfst_string_logprob_grad_ws_bytes: 0).
+ */
+int64_t nfst_string_logprob_grad_ws_bytes(const nfst_batch *lat, int32_t M, int32_t N, int32_t marker_mode);
+int nfst_string_logprob_grad(const nfst_batch *lat, const nfst_scores *scores, const int32_t *strings, const int32_t *lengths, int32_t M,
+                             int32_t N /* row stride of strings */, const uint8_t *keep /* [vocab] or NULL */,
+                             int32_t marker /* -1: none */, const double *g_num /* [B,M] */, const double *g_z /* [B] */,
+                             int32_t accumulate, void *ws, int64_t ws_bytes, double *grad_arc /* [total_arcs] */, int32_t *status,
+                             void *stream);
 
 /*
  * Arc slack, the max-plus counterpart of the arc posteriors, and beam masks (DESIGN.md sections 2 and 4.7).  A path

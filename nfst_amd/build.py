@@ -92,7 +92,8 @@ def check_resources(res: dict) -> list:
       kernels of the draws, ``k_positional_walk<..>`` (a chain of dependent loads and scan stages per position) and
       ``k_positional_score``;
     * the kernels of ``nfst_lattice_edit`` (``k_lattice_edit_sweep``, ``k_lattice_edit_walk``) use no scratch memory
-      (DESIGN.md section 4.18), and neither do ``k_merge_paths`` and ``k_string_logprob`` (sections 4.20 and 4.21).
+      (DESIGN.md section 4.18), and neither do ``k_merge_paths`` and ``k_string_logprob`` (sections 4.20 and 4.21) nor the
+      gradient's ``k_string_logprob_index``, ``k_string_logprob_fwd`` and ``k_string_logprob_arcs`` (section 4.22).
     """
     bad = []
     for name, r in res.items():
@@ -105,7 +106,7 @@ def check_resources(res: dict) -> list:
             bad.append(f"{name}: VGPR spill {r.get('vgpr_spill')} in a sweep kernel")
         if re.search(r"k_lattice_edit_", name) and (r.get("vgpr_spill", 0) != 0 or r.get("scratch", 0) != 0):
             bad.append(f"{name}: VGPR spill {r.get('vgpr_spill')}, scratch {r.get('scratch')} in a kernel that must use no scratch")
-        if re.search(r"k_(merge_paths|string_logprob)\b", name) and (r.get("vgpr_spill", 0) != 0 or r.get("scratch", 0) != 0):
+        if re.search(r"k_(merge_paths|string_logprob(_index|_fwd|_arcs)?)\b", name) and (r.get("vgpr_spill", 0) != 0 or r.get("scratch", 0) != 0):
             bad.append(f"{name}: VGPR spill {r.get('vgpr_spill')}, scratch {r.get('scratch')} in a kernel that must use no scratch")
         if not fused and re.search(r"k_(forward_backward|backward)<", name) and r.get("agprs", 0) != 0:
             bad.append(f"{name}: {r.get('agprs')} AGPRs in a kernel that stages nothing in them")

@@ -45,6 +45,7 @@ using namespace nfst_tile;
 #include "lattice_edit_kernels.h"
 #include "string_merge_kernels.h"
 #include "string_logprob_kernels.h"
+#include "string_logprob_grad_kernels.h"
 #include "slack_kernels.h"
 #include "intersect_kernels.h"
 #include "intersect_wide_kernels.h"
@@ -1151,6 +1152,73 @@ int nfst_string_logprob(const nfst_batch *lat, const nfst_scores *scores, const 
   const dim3 grid(lat->n_lattices, Y);
   if (marker >= 0) return launch(k_string_logprob<true>, grid, dim3(kSlThreads), lds_sweep, st, *lat, *scores, in, w, log_num, logz, status);
   return launch(k_string_logprob<false>, grid, dim3(kSlThreads), lds_sweep, st, *lat, *scores, in, w, log_num, logz, status);
+}
+
+// ------------------------------------------------------------------ gradients of the string weights (string_logprob_grad_kernels.h)
+// workspace: that of nfst_string_logprob, then the prefix table F (as large as G), az of every row, the forward's log_num
+// and logz, and the in-arc lists (4 bytes per row and lattice, 8 per arc: the list and its unordered draft)
+static int64_t slg_ws_layout(const nfst_batch *lat, int M, int N, int planes, char *base, SlWs *w, SlgWs *g) {
+  const int64_t TR = lat->total_rows, TA = lat->total_arcs, B = lat->n_lattices, sr = (int64_t)planes * (N + 1) * M;
+  const int64_t fwd = sl_ws_layout(lat, M, N, planes, base, w);
+  WsCarve c{base ? base + fwd : nullptr};
+  char *fc = c.take(8 * TR * sr), *az = c.take(8 * TR), *ln = c.take(8 * B * (int64_t)M), *lz = c.take(8 * B);
+  char *ip = c.take(4 * (TR + B)), *il = c.take(4 * TA), *it = c.take(4 * TA);
+  if (g) *g = {(double *)fc, (double *)az, (double *)ln, (double *)lz, (int *)ip, (int *)il, (int *)it};
+  return fwd + c.size;
+}
+
+int64_t nfst_string_logprob_grad_ws_bytes(const nfst_batch *lat, int32_t M, int32_t N, int32_t marker_mode) {
+  if (!lat) return NFST_ERR_ARG;
+  int rc = sl_check_sizes(M, N);
+  if (rc) return rc;
+  if (lat->n_lattices == 0) return 0;
+  if ((rc = check_batch(lat))) return rc;
+  return slg_ws_layout(lat, M, N, marker_mode ? 2 : 1, nullptr, nullptr, nullptr);
+}
+
+int nfst_string_logprob_grad(const nfst_batch *lat, const nfst_scores *scores, const int32_t *strings, const int32_t *lengths, int32_t M,
+                             int32_t N, const uint8_t *keep, int32_t marker, const double *g_num, const double *g_z,
+                             int32_t accumulate, void *ws, int64_t ws_bytes, double *grad_arc, int32_t *status, void *stream) {
+  if (!lat || !status) return NFST_ERR_ARG;
+  int rc = sl_check_sizes(M, N);
+  if (rc) return rc;
+  if ((rc = tape_check(keep, marker, lat->vocab, true))) return rc;
+  if (lat->n_lattices == 0) return NFST_OK;
+  if ((rc = check_batch(lat))) return rc;
+  if ((rc = check_scores(lat, scores))) return rc;
+  if ((M > 0 && (!strings || !lengths || !g_num)) || (!accumulate && !g_z) || (lat->total_arcs > 0 && !grad_arc)) return NFST_ERR_ARG;
+  const int planes = marker >= 0 ? 2 : 1;
+  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < slg_ws_layout(lat, M, N, planes, nullptr, nullptr, nullptr)) return NFST_ERR_ARG;
+  const int64_t lds_lev = (int64_t)lat->max_rows * 12 + 16;
+  const int64_t lds_sweep = ((int64_t)lat->max_rows * 2 + 1) * 4;
+  const int64_t lds_index = ((int64_t)lat->max_rows * 3 + 1 + kSlgIndexThreads) * 4;
+  if (lds_lev > kMaxLds || lds_sweep > kMaxLds || lds_index > kMaxLds) return NFST_ERR_LIMIT;
+  if (lat->total_arcs == 0) return NFST_OK;  // (no arc, no gradient)
+  SlWs w;
+  SlgWs g;
+  slg_ws_layout(lat, M, N, planes, (char *)ws, &w, &g);
+  const KbWs lw{nullptr, w.order, w.lev, w.n_lev};  // (k_kbest_levels writes the level arrays only)
+  const SlIn in{strings, lengths, (int)M, (int)N, keep, (int)marker};
+  const hipStream_t st = (hipStream_t)stream;
+  // the grid of nfst_string_logprob for both sweeps (any number of workgroups per lattice gives the same bits)
+  const int64_t want = (2 * (int64_t)cu_count() + lat->n_lattices - 1) / lat->n_lattices;
+  const int Y = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(M, want), 65535));
+  const dim3 lattices(lat->n_lattices), grid(lat->n_lattices, Y);
+  // the arc pass: one wave per arc of the largest lattice where the batch records that count, a share of all arcs otherwise
+  int64_t per_lat = max_lattice_arcs(lat);
+  if (per_lat <= 0 || per_lat >= NFST_BATCH_MAX_ARCS_CAP) per_lat = lat->total_arcs;
+  const dim3 arc_grid(lat->n_lattices, (unsigned)std::min<int64_t>((per_lat + kSlgArcWaves - 1) / kSlgArcWaves, 65535));
+  if ((rc = launch(k_kbest_levels, lattices, dim3(kKbLevelThreads), lds_lev, st, *lat, lw))) return rc;
+  auto run = [&](auto MK) {
+    constexpr bool mk = decltype(MK)::value;
+    int r = launch(k_string_logprob<mk>, grid, dim3(kSlThreads), lds_sweep, st, *lat, *scores, in, w, g.log_num, g.logz, status);
+    if (!r) r = launch(k_string_logprob_index, lattices, dim3(kSlgIndexThreads), lds_index, st, *lat, w, g);
+    if (!r) r = launch(k_string_logprob_fwd<mk>, grid, dim3(kSlThreads), lds_sweep, st, *lat, *scores, in, w, g);
+    if (!r) r = launch(k_string_logprob_arcs<mk>, arc_grid, dim3(kSlgArcThreads), 0, st, *lat, *scores, in, w, g, g_num, g_z,
+                       accumulate ? 1 : 0, grad_arc);
+    return r;
+  };
+  return marker >= 0 ? run(std::true_type{}) : run(std::false_type{});
 }
 
 // ------------------------------------------------------------------ arc slack and beam masks (slack_kernels.h)

@@ -215,7 +215,7 @@ def decode_strings(lat, theta, k: int, *, keep=None, marker: Optional[int] = Non
     live = torch.arange(s.strings.shape[1], device=s.strings.device)[None, :] < s.n_strings[:, None]
     n_max = max(1, int(s.lengths.max())) if s.lengths.numel() else 1  # (the workspace grows with the candidates' row stride)
     cand = (s.strings[:, :, :n_max], s.lengths) if rescore else (s.strings[:, :0], s.lengths[:, :0])  # (no candidate: log Z alone)
-    sc = ops.string_log_prob(lat, theta, *cand, keep=keep, marker=marker, arc_scores=arc_scores)
+    sc = ops.string_log_prob(lat, theta, *cand, keep=keep, marker=marker, arc_scores=ops._det(arc_scores))  # (the ranking carries no gradient)
     mass = torch.where(live, s.log_weights - sc.logz[:, None], s.log_weights) if method == "k_best" else s.log_weights
     if not rescore:
         return StringDecodeResult(s.strings, s.lengths, mass, s.n_strings, mass, s.first)

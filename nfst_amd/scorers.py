@@ -180,8 +180,19 @@ class LatticeScorer(torch.nn.Module):
     def string_log_prob(self, strings: torch.Tensor, lengths: torch.Tensor, **kw) -> torch.Tensor:
         """The reranker's call: exact log p(y | x) float64 [B, M] of the candidate strings ``strings[b, m, :lengths[b,
         m]]`` under ``theta`` (``ops.string_log_prob``; ``kw``: ``keep`` or ``marker``); -inf for a string that no path
-        spells."""
-        return ops.string_log_prob(self._lat(), self.theta.detach(), strings, lengths, **kw).log_prob
+        spells.  Differentiable in ``theta``."""
+        return ops.string_log_prob(self._lat(), self.theta, strings, lengths, **kw).log_prob
+
+    def string_nll(self, strings: torch.Tensor, lengths: torch.Tensor, **kw) -> torch.Tensor:
+        """The maximum-likelihood loss on strings: the mean over the batch of -log p(y | x), y = ``strings[b, 0,
+        :lengths[b, 0]]`` the one reference string of lattice b (``strings`` [B, 1, N]; ``kw``: ``keep`` or ``marker``),
+        float64 and differentiable in ``theta``.  ValueError if a lattice has no path that spells its string."""
+        if strings.dim() != 3 or strings.shape[1] != 1:
+            raise ValueError("strings must hold one reference string per lattice, [B, 1, N]")
+        lp = self.string_log_prob(strings, lengths, **kw)
+        if bool(torch.isneginf(lp).any()):
+            raise ValueError("string_nll: a string has probability 0 (no path of its lattice spells it)")
+        return -lp.mean()
 
     def _oracle(self, ref: torch.Tensor, ref_lengths: Optional[torch.Tensor]) -> tuple:
         """``(ops.LatticeEditResult, ref_lengths)`` of the oracle path under ``theta``; without ``ref_lengths`` the trailing

@@ -1,8 +1,9 @@
-"""Output strings: the wrappers of ``nfst_merge_paths`` and ``nfst_string_logprob`` (include/nfst_hip.h; DESIGN.md sections
-2, 4.20 and 4.21).  The path-side ops answer in mark paths; the string of a path is its projection onto the output tape,
+"""Output strings: the wrappers of ``nfst_merge_paths``, ``nfst_string_logprob`` and ``nfst_string_logprob_grad``
+(include/nfst_hip.h; DESIGN.md sections 2 and 4.20 to 4.22).  The path-side ops answer in mark paths; the string of a path is its projection onto the output tape,
 given as ``keep`` (a set of labels: the path's labels that belong to it, ``WideDFA.projected_sequence``'s meaning) or as
 ``marker`` (the labels that directly follow an arc labelled ``marker``, ``WideDFA.marked_sequence``'s meaning).
-``ops.merge_paths`` and ``ops.string_log_prob`` are these functions; ``decoders.decode_strings`` puts them together.
+``ops.merge_paths``, ``ops.string_log_prob`` and ``ops.string_arc_posteriors`` are these functions;
+``decoders.decode_strings`` puts the first two together.
 There is no CPU implementation.
 """
 from __future__ import annotations
@@ -32,6 +33,11 @@ class StringScores(NamedTuple):
     log_num: torch.Tensor   # [B, M] float64: log of the summed weight of the paths that spell the string (-inf: none does)
     logz: torch.Tensor      # [B] float64: the same over all paths
     log_prob: torch.Tensor  # [B, M] float64 = log_num - logz
+
+
+class _StringScoresWithOffsets(StringScores):
+    """``StringScores`` of a call with ``want_arc_grad=True``: ``arc_offsets`` is the float64 zero leaf [total_arcs] whose
+    ``.grad`` receives the gradient of the arcs' scores."""
 
 
 def _tape(keep, marker, vocab: Optional[int], device, need_one: bool) -> tuple:
@@ -130,35 +136,39 @@ def merge_paths(paths: torch.Tensor, lengths: torch.Tensor, log_weights: torch.T
     return out
 
 
-def string_log_prob(lat, theta, strings: torch.Tensor, lengths: torch.Tensor, *, keep=None, marker: Optional[int] = None,
-                    arc_scores=None, max_workspace_bytes: int = 1 << 30) -> StringScores:
-    """Exact log p(y | x) of candidate strings from the lattice alone (``nfst_string_logprob``): for lattice b and
-    candidate m, y = ``strings[b, m, :lengths[b, m]]`` (``strings`` [B, M, N] int32 or int64, N <= ``EDIT_MAX_LEN``),
-    ``log_num`` is the log of the summed weight exp(score) of the paths whose projection onto the tape ``keep`` or
-    ``marker`` is y, ``logz`` that of all paths and ``log_prob`` their difference, all float64; a string that no path
-    spells gets -inf, which is no error.  Scores are those of the other path-side ops (``theta`` [V] or [B, V],
-    ``arc_scores`` [total_arcs], the table's weights), acceptance that of ``WideDFA.projected_sequence`` /
-    ``marked_sequence``; unlike ``ops.constraint_log_prob`` on those automata, nothing is intersected or packed, the
-    arithmetic is float64 and no product has to fit ``NFST_MAX_ROWS``.  The candidates are swept in slices whose workspace
-    stays under ``max_workspace_bytes`` (ValueError if one candidate does not fit); the bits do not depend on the
-    slicing.  A length outside [0, N] raises ``NfstError`` (NFST_ERR_LENGTH) after the launch.  Forward only: for
-    gradients use ``ops.constraint_log_prob``."""
-    from .ops import _call, _need_gpu, _raise_status, _scores
+class _Candidates(NamedTuple):
+    """The marshalled side of one ``string_log_prob`` call: what both entry points take besides the scores."""
+    lat: object
+    rows: torch.Tensor       # [B, M, N] int32
+    lens: torch.Tensor       # [B, M] int32
+    keep_mask: Optional[torch.Tensor]
+    marker: int
+    step: int                # candidates per slice (0: there are none)
+
+    def slices(self):
+        M = self.rows.shape[1]
+        return [(m0, min(M, m0 + self.step)) for m0 in range(0, max(M, 1), max(self.step, 1))]
+
+    def workspace(self, query: str) -> torch.Tensor:
+        """Room for the largest slice as the library's ``query`` sizes it"""
+        n = int(getattr(_lib.lib, query)(C.byref(self.lat.c_struct()), self.step, self.rows.shape[2], int(self.marker >= 0)))
+        if n < 0:
+            _lib.check(n, query)
+        return torch.empty(max(n, 16), dtype=torch.uint8, device=self.lat.device)
+
+
+def _candidates(lat, strings, lengths, keep, marker, max_workspace_bytes: int) -> _Candidates:
+    """Checks and marshals the candidates and the tape, and cuts the candidates into slices whose forward workspace
+    stays under ``max_workspace_bytes``."""
+    from .ops import _need_gpu
 
     _need_gpu(lat)
     B = lat.n_lattices
     if not isinstance(strings, torch.Tensor) or strings.dim() != 3 or strings.shape[0] != B:
         raise ValueError(f"strings must be an int32 or int64 tensor [{B}, M, N]")
-    if not isinstance(theta, torch.Tensor):
-        theta = torch.as_tensor(theta, dtype=torch.float32)
     rows, lens, _ = _edit_side(strings.to(lat.device), lengths.to(lat.device) if isinstance(lengths, torch.Tensor) else lengths, "strings")
     M, N = rows.shape[1], rows.shape[2]
     keep_mask, mk, _ = _tape(keep, marker, lat.vocab, lat.device, need_one=True)
-    sc, alive = _scores(lat, theta.detach(), None if arc_scores is None else arc_scores.detach())
-    dev = lat.device
-    log_num = torch.empty((B, M), dtype=torch.float64, device=dev)
-    logz = torch.empty(B, dtype=torch.float64, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
     bs = C.byref(lat.c_struct())
 
     def ws_bytes(m):
@@ -172,16 +182,152 @@ def string_log_prob(lat, theta, strings: torch.Tensor, lengths: torch.Tensor, *,
     if fixed + per > max_workspace_bytes and M > 0:
         raise ValueError(f"one candidate needs a workspace of {fixed + per} bytes, max_workspace_bytes is {max_workspace_bytes}")
     step = max(1, min(M, (max_workspace_bytes - fixed) // per)) if M else 0
-    ws = torch.empty(max(ws_bytes(step), 16), dtype=torch.uint8, device=dev)
-    for m0 in range(0, max(M, 1), max(step, 1)):
-        m1 = min(M, m0 + step)
-        part_rows = rows[:, m0:m1].contiguous()
-        part_lens = lens[:, m0:m1].contiguous()
+    return _Candidates(lat, rows, lens, keep_mask, mk, step)
+
+
+def _weights_launches(c: _Candidates, sc) -> tuple:
+    """``nfst_string_logprob`` slice by slice: ``(log_num [B, M], logz [B], status word on the device)``"""
+    from .ops import _call
+
+    lat, dev = c.lat, c.lat.device
+    B, M, N = c.rows.shape
+    log_num = torch.empty((B, M), dtype=torch.float64, device=dev)
+    logz = torch.empty(B, dtype=torch.float64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = c.workspace("nfst_string_logprob_ws_bytes")
+    for m0, m1 in c.slices():
+        part_rows = c.rows[:, m0:m1].contiguous()
+        part_lens = c.lens[:, m0:m1].contiguous()
         part_num = log_num if (m0, m1) == (0, M) else torch.empty((B, m1 - m0), dtype=torch.float64, device=dev)
-        _call("nfst_string_logprob", lat, sc, part_rows, part_lens, m1 - m0, N, keep_mask, mk, ws, ws.numel(), part_num, logz, status)
+        _call("nfst_string_logprob", lat, sc, part_rows, part_lens, m1 - m0, N, c.keep_mask, c.marker, ws, ws.numel(), part_num, logz, status)
         if part_num is not log_num:
             log_num[:, m0:m1] = part_num
-    _raise_status(status, "nfst_string_logprob")  # a candidate's length outside its row
+    return log_num, logz, status
+
+
+def _grad_launches(c: _Candidates, sc, g_num: torch.Tensor, g_z: torch.Tensor) -> tuple:
+    """``nfst_string_logprob_grad`` over the forward's slices in ascending order, the first with ``accumulate=0`` and the
+    rest with ``accumulate=1`` (the bits of one launch): ``(grad_arc [total_arcs] float64, status word on the device)``.
+    The workspace is about twice the forward's."""
+    from .ops import _call
+
+    lat, dev = c.lat, c.lat.device
+    B, M, N = c.rows.shape
+    g_num = g_num.to(device=dev, dtype=torch.float64)
+    g_z = g_z.to(device=dev, dtype=torch.float64).contiguous()
+    grad_arc = torch.zeros(lat.total_arcs, dtype=torch.float64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = c.workspace("nfst_string_logprob_grad_ws_bytes")
+    for i, (m0, m1) in enumerate(c.slices()):
+        _call("nfst_string_logprob_grad", lat, sc, c.rows[:, m0:m1].contiguous(), c.lens[:, m0:m1].contiguous(), m1 - m0, N, c.keep_mask,
+              c.marker, g_num[:, m0:m1].contiguous(), g_z, int(i > 0), ws, ws.numel(), grad_arc, status)
+    return grad_arc, status
+
+
+def _label_sums(lat, grad_arc: torch.Tensor, theta: torch.Tensor) -> torch.Tensor:
+    """The gradient of ``theta`` ([V], or [B, V] per lattice) from that of the arcs' scores: summed per label, in
+    float64.  ``bincount`` and not ``index_add_``: millions of arcs land on a few hundred labels, and ``index_add_`` sends
+    every one of them to global memory as a float64 atomic (270 ms on 5.1 M arcs and 256 labels)."""
+    lab = lat.arc_label.to(torch.int64)
+    if theta.dim() == 2:
+        n_arcs = torch.as_tensor(lat.n_arcs.astype("int64"), device=grad_arc.device)
+        lab = lab + torch.repeat_interleave(torch.arange(lat.n_lattices, device=grad_arc.device), n_arcs, output_size=lab.numel()) * lat.vocab
+    out = torch.bincount(lab, weights=grad_arc, minlength=theta.numel())
+    return out.view(theta.shape).to(dtype=theta.dtype, device=theta.device)
+
+
+class _StringWeights(torch.autograd.Function):
+    """``(log_num, logz)`` of ``nfst_string_logprob`` with the gradient of ``nfst_string_logprob_grad``: d log_num[b, m] /
+    d score = the arc's posterior among the paths that spell candidate m, d logz[b] / d score = its posterior among all
+    paths.  The backward pass sweeps G again: nothing but the inputs survives between the two."""
+
+    @staticmethod
+    def forward(ctx, c, theta, arc_scores):
+        from .ops import _det, _raise_status, _scores
+
+        sc, alive = _scores(c.lat, theta.detach(), _det(arc_scores))
+        log_num, logz, status = _weights_launches(c, sc)
+        _raise_status(status, "nfst_string_logprob")  # a candidate's length outside its row
+        del alive
+        ctx.c = c
+        ctx.save_for_backward(theta, arc_scores)
+        return log_num, logz
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_num, g_z):
+        from .ops import _det, _scores
+
+        c = ctx.c
+        theta, arc_scores = ctx.saved_tensors
+        sc, alive = _scores(c.lat, theta.detach(), _det(arc_scores))
+        grad_arc, _ = _grad_launches(c, sc, g_num, g_z)  # (the forward has raised on a bad length)
+        del alive
+        g_theta = _label_sums(c.lat, grad_arc, theta) if ctx.needs_input_grad[1] else None
+        g_arc = grad_arc.to(dtype=arc_scores.dtype, device=arc_scores.device).view(arc_scores.shape) if ctx.needs_input_grad[2] else None
+        return None, g_theta, g_arc
+
+
+def string_arc_posteriors(lat, theta, strings: torch.Tensor, lengths: torch.Tensor, *, keep=None, marker: Optional[int] = None,
+                          arc_scores=None) -> torch.Tensor:
+    """p(arc | x, y) float64 [total_arcs] in canonical arc order, y = ``strings[b, 0, :lengths[b, 0]]`` the one candidate
+    of lattice b (``strings`` [B, 1, N]): the share of the weight of the paths that spell y which passes through the arc
+    -- the alignment posteriors given the string (``nfst_string_logprob_grad`` with g_num = 1 and g_z = 0, the gradient
+    of ``string_log_prob(...).log_num`` in the arc's score).  The out-arcs of state 0 add up to 1; all arcs of a lattice
+    that has no path for its y get 0.  A length outside [0, N] raises ``NfstError`` (NFST_ERR_LENGTH) after the launch."""
+    from .ops import _raise_status, _scores
+
+    c = _candidates(lat, strings, lengths, keep, marker, 1 << 62)
+    if c.rows.shape[1] != 1:
+        raise ValueError(f"strings must hold one candidate per lattice, [{lat.n_lattices}, 1, N]")
+    if not isinstance(theta, torch.Tensor):
+        theta = torch.as_tensor(theta, dtype=torch.float32)
+    sc, alive = _scores(lat, theta.detach(), None if arc_scores is None else arc_scores.detach())
+    B = lat.n_lattices
+    grad_arc, status = _grad_launches(c, sc, torch.ones((B, 1), dtype=torch.float64), torch.zeros(B, dtype=torch.float64))
+    _raise_status(status, "nfst_string_logprob_grad")
     del alive
+    return grad_arc
+
+
+def string_log_prob(lat, theta, strings: torch.Tensor, lengths: torch.Tensor, *, keep=None, marker: Optional[int] = None,
+                    arc_scores=None, max_workspace_bytes: int = 1 << 30, want_arc_grad: bool = False) -> StringScores:
+    """Exact log p(y | x) of candidate strings from the lattice alone (``nfst_string_logprob``): for lattice b and
+    candidate m, y = ``strings[b, m, :lengths[b, m]]`` (``strings`` [B, M, N] int32 or int64, N <= ``EDIT_MAX_LEN``),
+    ``log_num`` is the log of the summed weight exp(score) of the paths whose projection onto the tape ``keep`` or
+    ``marker`` is y, ``logz`` that of all paths and ``log_prob`` their difference, all float64; a string that no path
+    spells gets -inf, which is no error.  Scores are those of the other path-side ops (``theta`` [V] or [B, V],
+    ``arc_scores`` [total_arcs], the table's weights), acceptance that of ``WideDFA.projected_sequence`` /
+    ``marked_sequence``; unlike ``ops.constraint_log_prob`` on those automata, nothing is intersected or packed, the
+    arithmetic is float64 and no product has to fit ``NFST_MAX_ROWS``.  The candidates are swept in slices whose workspace
+    stays under ``max_workspace_bytes`` (ValueError if one candidate does not fit); the bits do not depend on the
+    slicing.  A length outside [0, N] raises ``NfstError`` (NFST_ERR_LENGTH) after the launch.  All three results carry
+    exact float64 gradients (``nfst_string_logprob_grad``, once differentiable) into ``theta`` and ``arc_scores`` when
+    either requires grad: the gradient of ``arc_scores`` is that of the arcs' scores cast to its dtype, the gradient of
+    ``theta`` its sum per label; a candidate of probability 0 passes back zeros through ``log_prob``.  The backward pass
+    sweeps the forward's slices again, in a workspace about twice as large.  ``want_arc_grad=True`` asks for the float64
+    gradient of every arc's score without a cast and whether or not ``arc_scores`` was given: the result (still a
+    ``StringScores``) has one more attribute, ``arc_offsets``, a float64 leaf of zeros [total_arcs] that was added to the
+    arcs' scores, and ``arc_offsets.grad`` holds that gradient after a backward pass; the values do not change."""
+    from .ops import _raise_status, _scores
+
+    c = _candidates(lat, strings, lengths, keep, marker, max_workspace_bytes)
+    if not isinstance(theta, torch.Tensor):
+        theta = torch.as_tensor(theta, dtype=torch.float32)
+    arc_offsets = None
+    if want_arc_grad:
+        arc_offsets = torch.zeros(lat.total_arcs, dtype=torch.float64, device=lat.device, requires_grad=True)
+        arc_scores = arc_offsets if arc_scores is None else arc_scores.to(device=lat.device, dtype=torch.float64) + arc_offsets
+    if torch.is_grad_enabled() and (theta.requires_grad or (isinstance(arc_scores, torch.Tensor) and arc_scores.requires_grad)):
+        log_num, logz = _StringWeights.apply(c, theta, arc_scores)
+    else:
+        sc, alive = _scores(lat, theta.detach(), None if arc_scores is None else arc_scores.detach())
+        log_num, logz, status = _weights_launches(c, sc)
+        _raise_status(status, "nfst_string_logprob")  # a candidate's length outside its row
+        del alive
     neg = torch.full_like(log_num, float("-inf"))
-    return StringScores(log_num, logz, torch.where(torch.isneginf(log_num), neg, log_num - logz[:, None]))
+    out = StringScores(log_num, logz, torch.where(torch.isneginf(log_num), neg, log_num - logz[:, None]))
+    if arc_offsets is not None:
+        out = _StringScoresWithOffsets(*out)
+        out.arc_offsets = arc_offsets
+    return out

@@ -70,6 +70,8 @@
  *                                      score of its hypotheses, without one product lattice per hypothesis
  *   nfst_string_logprob_grad           its exact gradient in every arc's score: maximum likelihood and risk on strings,
  *                                      and the arc posteriors given a string
+ *   nfst_string_prefix / _next         the exact weight of all strings that start with a prefix, and of its extensions
+ *                                      by every next symbol: prefix beam search with a bound on every completion
  *
  * Conventions
  *   - plain C: pointers and sizes only, no C++/torch types.
@@ -829,6 +831,66 @@ int nfst_string_logprob_grad(const nfst_batch *lat, const nfst_scores *scores, c
                              int32_t marker /* -1: none */, const double *g_num /* [B,M] */, const double *g_z /* [B] */,
                              int32_t accumulate, void *ws, int64_t ws_bytes, double *grad_arc /* [total_arcs] */, int32_t *status,
                              void *stream);
+
+/*
+ * Prefix weights and next symbols (DESIGN.md sections 2 and 4.23).  Tape, scores, paths and the canonical order of the
+ * arcs are nfst_string_logprob's; for lattice b and prefix y = prefixes[b, m, :lengths[b, m]] (prefixes [B, M, N] int32,
+ * lengths [B, M]; nothing beyond a length is read), n = len(y), all outputs float64 log weights on the device:
+ *   log_prefix [B, M]      the sum of exp(path score) over the paths whose string starts with y; a path that ends on a
+ *                          marker with nothing behind it spells no string and counts nowhere.  The empty prefix gives
+ *                          log Z in keep mode and log Z less those paths' share in marker mode
+ *   eos [B, M]             the same over the paths that spell exactly y (nfst_string_logprob's log_num)
+ *   next [B, M, vocab]     log_prefix of y followed by the label v, for every v; -inf for a label that is never on the
+ *                          tape (keep mode: v not kept)
+ *   logz [B]               nfst_string_logprob's logz, bit for bit (the same items in the same order)
+ * so that exp(log_prefix) = exp(eos) + sum_v exp(next[v]) as real numbers.  A prefix that no path spells gives -inf
+ * everywhere, never NaN, and no error.
+ *
+ * nfst_string_prefix (log_prefix and logz) sweeps H, which is G of nfst_string_logprob with "anything may follow" at
+ * column n, in descending level order; columns j < n follow G's recurrence, and at j = n
+ *   keep:    H[sink][n] = 1;  every out-arc a: s -> d, d != s, kept or not, carries w_a H[d][n]
+ *   marker:  H0[sink][n] = 1, H1[sink][n] = 0;  H0[s][n] = sum_a w_a (l == marker ? H1 : H0)[d][n];
+ *            H1[s][n] = sum_a w_a H0[d][n]
+ * and log_prefix = H0[0][0].  A cell is a running log-sum around the greatest term so far over the out-arcs of its
+ * state in ascending canonical arc id, as G's.
+ *
+ * nfst_string_next (all four outputs) sweeps no H over the candidates.  It runs nfst_string_prefix's sweep once per
+ * lattice on the empty prefix (one column), which leaves z[s] (log Z of the rest of the lattice behind s) and zn0[s],
+ * zn1[s] (the same without the paths that end on a marker, the arc into s being no active marker / one), then the
+ * prefix tables F, F0, F1 and az of nfst_string_logprob_grad (same kernels, same order), and forms
+ *   keep:    next[v] = sum over the arcs a: s -> d, d != s, of label v (v kept) of exp((F[s][n] + w_a) + z[d])
+ *   marker:  next[v] = sum over the arcs of label v of exp((F1[s][n] + w_a) + zn0[d])
+ *   eos = F0[sink][n];  log_prefix = the sum of eos and next[0 .. vocab - 1]
+ * Order of these sums (float64, none fused across terms): the terms of a sum are numbered i = 0, 1, ... -- for next[v]
+ * the arcs of label v whose source state 0 reaches in ascending canonical arc id, for log_prefix eos first and then
+ * next[v] in ascending v.  The greatest term t* is found first (exact in any order).  Term i belongs to strip i / 64 and
+ * lane i mod 64; the 64 values exp(t_i - t*) of a strip (0 beyond the last term and for a term of -inf) are added in
+ * the tree of nfst_string_logprob_grad (x_i += x_(i^1), x_(i^2), x_(i^7), x_(i^15), then (r_0 + r_16) + (r_32 + r_48));
+ * the strips' sums are added to 0.0 in ascending order, and the result is t* + log(sum), or -inf without a term above
+ * -inf.  Only the canonical arrays are read and there are no atomics on values: the same bits at every launch, for every
+ * grid, under every packing and for every slicing of the candidates.
+ * A lattice whose state 0 is the sink gives log_prefix = eos = 0 for the empty prefix, -inf otherwise, and next = -inf.
+ * A lengths[b, m] outside [0, N] is found on the device: *status = NFST_ERR_LENGTH (status: device, one word, zeroed by
+ * the caller), every output of that candidate is -inf and none of its tokens is read; the others are computed as usual.
+ * ws: device workspace (16-byte aligned, overwritten), every part rounded up to 256.  nfst_string_prefix_ws_bytes is
+ * nfst_string_logprob_ws_bytes.  nfst_string_next_ws_bytes(lat, M, N, marker >= 0): 8 (N + 1) M bytes per row of the
+ * batch (F), twice that in marker mode, 8 (planes + 2) + 12 bytes per row, 12 bytes per arc and 4 vocab + 24 bytes per
+ * lattice.  LDS: 12 max_rows + 4100 bytes (the in-arc lists), and for nfst_string_next 4 (max_rows + vocab) + 4100 bytes
+ * (the label lists); more than 160 KiB returns NFST_ERR_LIMIT.
+ * M < 0, N < 1, a bad tape, null required pointers (all but lat, scores, ws, logz and status may be null when M == 0)
+ * or a short workspace: NFST_ERR_ARG; N > NFST_EDIT_MAX_LEN: NFST_ERR_LIMIT; all on the host before any launch, outputs
+ * untouched.  n_lattices == 0 and M == 0 are successful no-ops (n_lattices == 0: the ws_bytes queries return 0).
+ */
+int64_t nfst_string_prefix_ws_bytes(const nfst_batch *lat, int32_t M, int32_t N, int32_t marker_mode);
+int nfst_string_prefix(const nfst_batch *lat, const nfst_scores *scores, const int32_t *prefixes, const int32_t *lengths, int32_t M,
+                       int32_t N /* row stride of prefixes */, const uint8_t *keep /* [vocab] or NULL */, int32_t marker /* -1: none */,
+                       void *ws, int64_t ws_bytes, double *log_prefix /* [B,M] */, double *logz /* [B] */, int32_t *status,
+                       void *stream);
+int64_t nfst_string_next_ws_bytes(const nfst_batch *lat, int32_t M, int32_t N, int32_t marker_mode);
+int nfst_string_next(const nfst_batch *lat, const nfst_scores *scores, const int32_t *prefixes, const int32_t *lengths, int32_t M,
+                     int32_t N /* row stride of prefixes */, const uint8_t *keep /* [vocab] or NULL */, int32_t marker /* -1: none */,
+                     void *ws, int64_t ws_bytes, double *next /* [B,M,vocab] */, double *eos /* [B,M] */,
+                     double *log_prefix /* [B,M] */, double *logz /* [B] */, int32_t *status, void *stream);
 
 /*
  * Arc slack, the max-plus counterpart of the arc posteriors, and beam masks (DESIGN.md sections 2 and 4.7).  A path

@@ -165,6 +165,10 @@ def _load():
         "nfst_string_logprob": (C.c_int, [BP, SP, vp, vp, i32, i32, vp, i32, vp, i64, vp, vp, vp, vp]),
         "nfst_string_logprob_grad_ws_bytes": (i64, [BP, i32, i32, i32]),
         "nfst_string_logprob_grad": (C.c_int, [BP, SP, vp, vp, i32, i32, vp, i32, vp, vp, i32, vp, i64, vp, vp, vp]),
+        "nfst_string_prefix_ws_bytes": (i64, [BP, i32, i32, i32]),
+        "nfst_string_prefix": (C.c_int, [BP, SP, vp, vp, i32, i32, vp, i32, vp, i64, vp, vp, vp, vp]),
+        "nfst_string_next_ws_bytes": (i64, [BP, i32, i32, i32]),
+        "nfst_string_next": (C.c_int, [BP, SP, vp, vp, i32, i32, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp]),
         "nfst_arc_slack_ws_bytes": (i64, [BP]),
         "nfst_arc_slack": (C.c_int, [BP, SP, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "nfst_intersect_ws_bytes": (i64, [BP, i32]),

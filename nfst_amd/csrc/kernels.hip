@@ -46,6 +46,7 @@ using namespace nfst_tile;
 #include "string_merge_kernels.h"
 #include "string_logprob_kernels.h"
 #include "string_logprob_grad_kernels.h"
+#include "string_prefix_kernels.h"
 #include "slack_kernels.h"
 #include "intersect_kernels.h"
 #include "intersect_wide_kernels.h"
@@ -1216,6 +1217,113 @@ int nfst_string_logprob_grad(const nfst_batch *lat, const nfst_scores *scores, c
     if (!r) r = launch(k_string_logprob_fwd<mk>, grid, dim3(kSlThreads), lds_sweep, st, *lat, *scores, in, w, g);
     if (!r) r = launch(k_string_logprob_arcs<mk>, arc_grid, dim3(kSlgArcThreads), 0, st, *lat, *scores, in, w, g, g_num, g_z,
                        accumulate ? 1 : 0, grad_arc);
+    return r;
+  };
+  return marker >= 0 ? run(std::true_type{}) : run(std::false_type{});
+}
+
+// ------------------------------------------------------------------ prefix weights and next symbols (string_prefix_kernels.h)
+// nfst_string_prefix sweeps H in the workspace of nfst_string_logprob.  nfst_string_next's workspace: the prefix table F
+// (N + 1 cells of 8 bytes per row, candidate and plane), zn (8 bytes per row and plane), z and az of every row, the level
+// arrays, the in-arc lists of k_string_logprob_index and the label lists (4 bytes per row and lattice, 12 per arc, 4
+// (vocab + 1) + 8 per lattice)
+static int64_t sp_ws_layout(const nfst_batch *lat, int M, int N, int planes, char *base, SlWs *w, SlWs *wz, SlgWs *g, SpWs *p) {
+  const int64_t TR = lat->total_rows, TA = lat->total_arcs, B = lat->n_lattices, sm = (int64_t)planes * (N + 1), sr = sm * M;
+  WsCarve c{base};
+  char *fc = c.take(8 * TR * sr), *zn = c.take(8 * TR * planes), *zz = c.take(8 * TR), *az = c.take(8 * TR);
+  char *od = c.take(4 * TR), *lv = c.take(4 * (TR + B)), *nl = c.take(4 * B);
+  char *ip = c.take(4 * (TR + B)), *il = c.take(4 * TA), *it = c.take(4 * TA);
+  char *lp = c.take(4 * B * ((int64_t)lat->vocab + 1)), *ll = c.take(4 * TA), *z0 = c.take(8 * B);
+  if (w) *w = {nullptr, (double *)zz, (int *)od, (int *)lv, (int *)nl, sm, sr};  // (the forward sweep writes g->fcells)
+  if (wz) *wz = {(double *)zn, (double *)zz, (int *)od, (int *)lv, (int *)nl, planes, planes};  // M = 1, N = 0
+  if (g) *g = {(double *)fc, (double *)az, nullptr, nullptr, (int *)ip, (int *)il, (int *)it};
+  if (p) *p = {(double *)zn, (double *)z0, (int *)lp, (int *)ll};
+  return c.size;
+}
+
+int64_t nfst_string_prefix_ws_bytes(const nfst_batch *lat, int32_t M, int32_t N, int32_t marker_mode) {
+  return nfst_string_logprob_ws_bytes(lat, M, N, marker_mode);
+}
+
+int nfst_string_prefix(const nfst_batch *lat, const nfst_scores *scores, const int32_t *prefixes, const int32_t *lengths, int32_t M,
+                       int32_t N, const uint8_t *keep, int32_t marker, void *ws, int64_t ws_bytes, double *log_prefix, double *logz,
+                       int32_t *status, void *stream) {
+  if (!lat || !status) return NFST_ERR_ARG;
+  int rc = sl_check_sizes(M, N);
+  if (rc) return rc;
+  if ((rc = tape_check(keep, marker, lat->vocab, true))) return rc;
+  if (lat->n_lattices == 0) return NFST_OK;
+  if ((rc = check_batch(lat))) return rc;
+  if ((rc = check_scores(lat, scores))) return rc;
+  if (!logz || (M > 0 && (!prefixes || !lengths || !log_prefix))) return NFST_ERR_ARG;
+  const int planes = marker >= 0 ? 2 : 1;
+  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < sl_ws_layout(lat, M, N, planes, nullptr, nullptr)) return NFST_ERR_ARG;
+  const int64_t lds_lev = (int64_t)lat->max_rows * 12 + 16;
+  const int64_t lds_sweep = ((int64_t)lat->max_rows * 2 + 1) * 4;
+  if (lds_lev > kMaxLds || lds_sweep > kMaxLds) return NFST_ERR_LIMIT;
+  if (M == 0) return NFST_OK;
+  SlWs w;
+  sl_ws_layout(lat, M, N, planes, (char *)ws, &w);
+  const KbWs lw{nullptr, w.order, w.lev, w.n_lev};  // (k_kbest_levels writes the level arrays only)
+  const SlIn in{prefixes, lengths, (int)M, (int)N, keep, (int)marker};
+  const hipStream_t st = (hipStream_t)stream;
+  // the grid of nfst_string_logprob (any number of workgroups per lattice gives the same bits)
+  const int64_t want = (2 * (int64_t)cu_count() + lat->n_lattices - 1) / lat->n_lattices;
+  const int Y = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(M, want), 65535));
+  if ((rc = launch(k_kbest_levels, dim3(lat->n_lattices), dim3(kKbLevelThreads), lds_lev, st, *lat, lw))) return rc;
+  const dim3 grid(lat->n_lattices, Y);
+  if (marker >= 0) return launch(k_string_prefix<true>, grid, dim3(kSlThreads), lds_sweep, st, *lat, *scores, in, w, log_prefix, logz, status);
+  return launch(k_string_prefix<false>, grid, dim3(kSlThreads), lds_sweep, st, *lat, *scores, in, w, log_prefix, logz, status);
+}
+
+int64_t nfst_string_next_ws_bytes(const nfst_batch *lat, int32_t M, int32_t N, int32_t marker_mode) {
+  if (!lat) return NFST_ERR_ARG;
+  int rc = sl_check_sizes(M, N);
+  if (rc) return rc;
+  if (lat->n_lattices == 0) return 0;
+  if ((rc = check_batch(lat))) return rc;
+  return sp_ws_layout(lat, M, N, marker_mode ? 2 : 1, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+int nfst_string_next(const nfst_batch *lat, const nfst_scores *scores, const int32_t *prefixes, const int32_t *lengths, int32_t M,
+                     int32_t N, const uint8_t *keep, int32_t marker, void *ws, int64_t ws_bytes, double *next, double *eos,
+                     double *log_prefix, double *logz, int32_t *status, void *stream) {
+  if (!lat || !status) return NFST_ERR_ARG;
+  int rc = sl_check_sizes(M, N);
+  if (rc) return rc;
+  if ((rc = tape_check(keep, marker, lat->vocab, true))) return rc;
+  if (lat->n_lattices == 0) return NFST_OK;
+  if ((rc = check_batch(lat))) return rc;
+  if ((rc = check_scores(lat, scores))) return rc;
+  if (!logz || (M > 0 && (!prefixes || !lengths || !next || !eos || !log_prefix))) return NFST_ERR_ARG;
+  const int planes = marker >= 0 ? 2 : 1;
+  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < sp_ws_layout(lat, M, N, planes, nullptr, nullptr, nullptr, nullptr, nullptr))
+    return NFST_ERR_ARG;
+  const int64_t lds_lev = (int64_t)lat->max_rows * 12 + 16;
+  const int64_t lds_sweep = ((int64_t)lat->max_rows * 2 + 1) * 4;
+  const int64_t lds_index = ((int64_t)lat->max_rows * 3 + 1 + kSlgIndexThreads) * 4;
+  const int64_t lds_label = ((int64_t)lat->max_rows + lat->vocab + 1 + kSpIndexThreads) * 4;
+  if (lds_lev > kMaxLds || lds_sweep > kMaxLds || lds_index > kMaxLds || lds_label > kMaxLds) return NFST_ERR_LIMIT;
+  if (M == 0) return NFST_OK;
+  SlWs w, wz;
+  SlgWs g;
+  SpWs p;
+  sp_ws_layout(lat, M, N, planes, (char *)ws, &w, &wz, &g, &p);
+  const KbWs lw{nullptr, w.order, w.lev, w.n_lev};  // (k_kbest_levels writes the level arrays only)
+  const SlIn in{prefixes, lengths, (int)M, (int)N, keep, (int)marker};
+  const SlIn empty{nullptr, nullptr, 1, 0, keep, (int)marker};  // the empty prefix once per lattice: zn, z and logz
+  const hipStream_t st = (hipStream_t)stream;
+  const int64_t want = (2 * (int64_t)cu_count() + lat->n_lattices - 1) / lat->n_lattices;
+  const int Y = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(M, want), 65535));
+  const dim3 lattices(lat->n_lattices), grid(lat->n_lattices, Y), cands(lat->n_lattices, (unsigned)std::min<int64_t>(M, 65535));
+  if ((rc = launch(k_kbest_levels, lattices, dim3(kKbLevelThreads), lds_lev, st, *lat, lw))) return rc;
+  auto run = [&](auto MK) {
+    constexpr bool mk = decltype(MK)::value;
+    int r = launch(k_string_prefix<mk>, lattices, dim3(kSlThreads), lds_sweep, st, *lat, *scores, empty, wz, p.zn_lp, logz, status);
+    if (!r) r = launch(k_string_logprob_index, lattices, dim3(kSlgIndexThreads), lds_index, st, *lat, w, g);
+    if (!r) r = launch(k_string_label_index, lattices, dim3(kSpIndexThreads), lds_label, st, *lat, w, p);
+    if (!r) r = launch(k_string_logprob_fwd<mk>, grid, dim3(kSlThreads), lds_sweep, st, *lat, *scores, in, w, g);
+    if (!r) r = launch(k_string_next<mk>, cands, dim3(kSpNextThreads), 0, st, *lat, *scores, in, w, g, p, next, eos, log_prefix, status);
     return r;
   };
   return marker >= 0 ? run(std::true_type{}) : run(std::false_type{});

@@ -227,6 +227,145 @@ def decode_strings(lat, theta, k: int, *, keep=None, marker: Optional[int] = Non
                               take(mass), take(s.first))
 
 
+class PrefixSearchResult(NamedTuple):
+    strings: torch.Tensor    # [B, k, L] int32: complete output strings, the most probable first, pad-filled
+    lengths: torch.Tensor    # [B, k] int32 (0 beyond n_strings)
+    log_prob: torch.Tensor   # [B, k] float64: exact log p(y | x); -inf beyond n_strings
+    n_strings: torch.Tensor  # [B] int32
+    bound: torch.Tensor      # [B] float64: log of the largest share of probability that the search set aside unexplored (-inf: none)
+    exact: torch.Tensor      # [B] bool: the first entry is provably the most probable string of the lattice
+
+
+def prefix_search(lat, theta, k: int = 8, max_len: Optional[int] = None, *, keep=None, marker: Optional[int] = None, arc_scores=None,
+                  pad: int = 0, reserve: int = 64, refine_steps: int = 32) -> PrefixSearchResult:
+    """Prefix beam search for the most probable output strings with exact prefix probabilities
+    (``ops.string_next_log_probs``), in two phases.  The first is length-synchronous: step t holds at most ``k`` open
+    prefixes of length t per lattice and asks for their ``eos`` and ``next`` in one call (M = k, N = t).  Every ``eos`` is the
+    exact weight of a complete string and enters the list of the k best complete strings.  The k V extensions are ranked
+    by ``next``, the exact mass of all strings that start with them (ties go to the lower prefix slot, then to the lower
+    label: a stable sort on the device), and the k heaviest stay open.  No string that starts with a pruned extension
+    weighs more than the extension, so what is pruned bounds what was missed: the pruned extensions are set aside in a
+    reserve of the ``reserve`` heaviest per lattice, and the heaviest one that the reserve drops raises ``bound[b]``.  A
+    prefix of ``max_len`` symbols (default: the longest path of the batch) is not extended; its mass beyond its own ``eos``
+    raises the bound.  A lattice leaves this phase when no open prefix outweighs its k-th complete string.  The second
+    phase comes back to what was set aside: per step the k heaviest prefixes of the reserve, whatever their lengths, are
+    scored in one call and all their extensions set aside, until the reserve holds nothing heavier than the lattice's
+    first complete string or ``refine_steps`` steps have passed; what is then left in the reserve joins the bound.
+    ``exact[b]`` is set when the first entry weighs at least ``bound[b]`` and at least every prefix that was open when the
+    first phase stopped: it is then the most probable string of lattice b, which no list of paths can certify.
+    ``reserve=0, refine_steps=0`` is the first phase alone, ``bound`` the heaviest mass ever pruned.  ``log_prob`` and
+    ``bound`` are less log Z.  Every step sweeps the prefix table of the whole prefix again.  No gradient."""
+    ops._check_k(k, bounded=False)
+    if (keep is None) == (marker is None):
+        raise ValueError("give keep (a set of labels) or marker (a label)")
+    for name, x in (("reserve", reserve), ("refine_steps", refine_steps)):
+        if isinstance(x, bool) or not isinstance(x, int) or x < 0:
+            raise ValueError(f"{name} must be an int >= 0")
+    ops._need_gpu(lat)
+    theta = torch.as_tensor(theta, dtype=torch.float32).detach()
+    arc_scores = ops._det(arc_scores)
+    if max_len is None:
+        max_len = min(int(lat.depth.max()), ops.EDIT_MAX_LEN)
+    if isinstance(max_len, bool) or not isinstance(max_len, int) or not 0 <= max_len <= ops.EDIT_MAX_LEN:
+        raise ValueError(f"max_len must be an int in [0, {ops.EDIT_MAX_LEN}]")
+    B, V, dev, L, R = lat.n_lattices, lat.vocab, lat.device, max(max_len, 1), reserve
+    f64, i32, ninf = torch.float64, torch.int32, float("-inf")
+    new_rows = lambda n: torch.full((B, n, L), pad, dtype=i32, device=dev)
+    new_mass = lambda n: torch.full((B, n), ninf, dtype=f64, device=dev)
+    st = dict(comp_rows=new_rows(k), comp_len=torch.zeros((B, k), dtype=i32, device=dev), comp_w=new_mass(k), bound=new_mass(1)[:, 0],
+              res_rows=new_rows(R), res_len=torch.zeros((B, R), dtype=i32, device=dev), res_mass=new_mass(R),
+              logz=torch.zeros(B, dtype=f64, device=dev))
+
+    def expand(rows, lens, live, N):
+        """One call on the open prefixes: their eos into the complete lists, their extensions' masses [B, k V] (-inf for a
+        dead slot and for a prefix of max_len symbols, whose mass beyond its eos raises the bound)"""
+        ns = ops.string_next_log_probs(lat, theta, rows[:, :, :max(N, 1)], lens, keep=keep, marker=marker, arc_scores=arc_scores)
+        st["logz"] = ns.logz
+        eos = torch.where(live, ns.eos, torch.full_like(ns.eos, ninf))
+        nxt = torch.where(live[:, :, None], ns.next, torch.full_like(ns.next, ninf))
+        # the complete strings: the k best of the list so far and this step's, the earlier entry first among equals
+        w = torch.cat([st["comp_w"], eos], dim=1)
+        order = torch.sort(-w, dim=1, stable=True).indices[:, :k]
+        st["comp_w"] = w.gather(1, order)
+        st["comp_len"] = torch.cat([st["comp_len"], torch.where(eos > ninf, lens, torch.zeros_like(lens))], dim=1).gather(1, order)
+        st["comp_rows"] = torch.cat([st["comp_rows"], rows], dim=1).gather(1, order[:, :, None].expand(B, k, L))
+        capped = (lens >= max_len)[:, :, None]
+        rest = torch.logsumexp(torch.where(capped, nxt, torch.full_like(nxt, ninf)), dim=2).max(dim=1).values
+        st["bound"] = torch.maximum(st["bound"], torch.where(rest.isnan(), torch.full_like(rest, ninf), rest))
+        return torch.where(capped, torch.full_like(nxt, ninf), nxt).reshape(B, k * V)
+
+    def extended(rows, lens, picked):
+        """The prefixes of the extensions ``picked`` [B, n] (slot * V + label) of the open prefixes: (rows, lengths)"""
+        slot, label = picked // V, picked % V
+        at = lens.gather(1, slot).to(torch.int64)
+        out = rows.gather(1, slot[:, :, None].expand(B, picked.shape[1], L)).clone()
+        out.scatter_(2, at.clamp(max=L - 1)[:, :, None], label[:, :, None].to(i32))
+        return out, (at + 1).to(i32)
+
+    def set_aside(rows, lens, flat):
+        """The extensions of mass ``flat`` [B, k V] into the reserve, which keeps its R heaviest entries in descending
+        order (among equals its own entries first, then the lower slot and label); the heaviest dropped raises the bound"""
+        both = torch.cat([st["res_mass"], flat], dim=1)
+        order = torch.sort(-both, dim=1, stable=True).indices[:, :R + 1]
+        if order.shape[1] > R:
+            st["bound"] = torch.maximum(st["bound"], both.gather(1, order[:, R:]).squeeze(1))
+        if R == 0:
+            return
+        order = order[:, :R]
+        old = order < R
+        e_rows, e_len = extended(rows, lens, (order - R).clamp(min=0))
+        o = order.clamp(max=R - 1)
+        mass = both.gather(1, order)
+        st["res_rows"] = torch.where(old[:, :, None], st["res_rows"].gather(1, o[:, :, None].expand(B, R, L)), e_rows)
+        st["res_len"] = torch.where(old, st["res_len"].gather(1, o), e_len)
+        st["res_mass"] = mass
+
+    # the length-synchronous phase
+    open_rows, open_len, open_mass = new_rows(k), torch.zeros((B, k), dtype=i32, device=dev), new_mass(k)
+    open_mass[:, 0] = 0.0  # the empty prefix in slot 0 (its mass is not needed)
+    open_at_stop = new_mass(1)[:, 0]
+    active = torch.ones(B, dtype=torch.bool, device=dev)
+    n_open = min(k, k * V)
+    for t in range(max_len + 1):
+        flat = expand(open_rows, open_len, active[:, None] & (open_mass > ninf), t)
+        order = torch.sort(-flat, dim=1, stable=True).indices[:, :n_open]
+        mass = flat.gather(1, order)
+        rows, lens = extended(open_rows, open_len, order)
+        set_aside(open_rows, open_len, flat.scatter(1, order, ninf))
+        alive = mass > ninf
+        open_rows, open_len, open_mass = new_rows(k), torch.zeros((B, k), dtype=i32, device=dev), new_mass(k)
+        open_rows[:, :n_open] = torch.where(alive[:, :, None], rows, open_rows[:, :n_open])
+        open_len[:, :n_open] = torch.where(alive, lens, open_len[:, :n_open])
+        open_mass[:, :n_open] = mass
+        go_on = active & (open_mass > st["comp_w"][:, k - 1, None]).any(dim=1)
+        open_at_stop = torch.where(active & ~go_on, open_mass.max(dim=1).values, open_at_stop)
+        active = go_on
+        if not bool(active.any()):
+            break
+    # back to the reserve
+    for _ in range(refine_steps if R else 0):
+        active = st["res_mass"][:, 0] > st["comp_w"][:, 0]
+        if not bool(active.any()):
+            break
+        n_pop = min(k, R)
+        open_rows, open_len, open_mass = new_rows(k), torch.zeros((B, k), dtype=i32, device=dev), new_mass(k)
+        taken = active[:, None] & (st["res_mass"][:, :n_pop] > ninf)
+        open_rows[:, :n_pop] = torch.where(taken[:, :, None], st["res_rows"][:, :n_pop], open_rows[:, :n_pop])
+        open_len[:, :n_pop] = torch.where(taken, st["res_len"][:, :n_pop], open_len[:, :n_pop])
+        open_mass[:, :n_pop] = torch.where(taken, st["res_mass"][:, :n_pop], open_mass[:, :n_pop])
+        st["res_mass"] = torch.cat([torch.where(taken, torch.full_like(open_mass[:, :n_pop], ninf), st["res_mass"][:, :n_pop]),
+                                    st["res_mass"][:, n_pop:]], dim=1)
+        set_aside(open_rows, open_len, expand(open_rows, open_len, open_mass > ninf, int(open_len.max())))
+    comp_w, logz = st["comp_w"], st["logz"]
+    bound = torch.maximum(st["bound"], st["res_mass"].max(dim=1).values) if R else st["bound"]
+    found = comp_w > ninf
+    first = comp_w[:, 0]
+    exact = found[:, 0] & (first >= bound) & (first >= open_at_stop)
+    log_prob = torch.where(found, comp_w - logz[:, None], comp_w)
+    comp_rows = torch.where(found[:, :, None], st["comp_rows"], torch.full_like(st["comp_rows"], pad))
+    return PrefixSearchResult(comp_rows, st["comp_len"], log_prob, found.sum(dim=1).to(i32), torch.where(bound > ninf, bound - logz, bound), exact)
+
+
 def mbr_decode_strings(string_set):
     """``mbr_decode`` on output strings: ``(index [B] int64, risk [B, K] float64, distances [B, K, K] int32)`` of a
     ``ops.StringSet`` under edit distance between the strings, weighed by the merged weights."""

@@ -1679,4 +1679,5 @@ def iwae(log_p: torch.Tensor, log_q: torch.Tensor):
 # (at the end: edit.py takes the marshalling helpers above)
 from .edit import EDIT_MAX_LEN, LatticeEditResult, edit_distance, lattice_edit_distance, pairwise_edit_distance  # noqa: E402,F401
 from .constraints import constraint_log_prob  # noqa: E402,F401
-from .strings import MERGE_MAX_K, StringScores, StringSet, merge_paths, string_arc_posteriors, string_log_prob  # noqa: E402,F401
+from .strings import (MERGE_MAX_K, NextSymbols, PrefixScores, StringScores, StringSet, merge_paths, string_arc_posteriors,  # noqa: E402,F401
+                      string_log_prob, string_next_log_probs, string_prefix_log_prob)

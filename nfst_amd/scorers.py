@@ -183,6 +183,23 @@ class LatticeScorer(torch.nn.Module):
         spells.  Differentiable in ``theta``."""
         return ops.string_log_prob(self._lat(), self.theta, strings, lengths, **kw).log_prob
 
+    def string_next_log_probs(self, prefixes: torch.Tensor, lengths: torch.Tensor, marker: Optional[int] = 4, **kw):
+        """Incremental decoding: ``ops.NextSymbols`` of the prefixes ``prefixes[b, m, :lengths[b, m]]`` under ``theta``
+        (``ops.string_next_log_probs``): the exact mass of every one-symbol extension, of the prefix as a complete
+        string and of the prefix itself.  The tape is ``marker`` (default: the output mark 4) or ``keep=`` a set of
+        labels.  No gradient."""
+        tape = dict(keep=kw.pop("keep")) if kw.get("keep") is not None else dict(marker=marker)
+        return ops.string_next_log_probs(self._lat(), self.theta.detach(), prefixes, lengths, **tape, **kw)
+
+    def prefix_search(self, k: int = 8, marker: Optional[int] = 4, **kw):
+        """The most probable output strings of every lattice by exact prefix beam search: ``decoders.PrefixSearchResult``
+        (``decoders.prefix_search``; ``kw``: ``max_len``, ``keep`` in place of ``marker``), whose ``exact`` flags say where
+        the first string is provably the most probable one."""
+        from .decoders import prefix_search
+
+        tape = dict(keep=kw.pop("keep")) if kw.get("keep") is not None else dict(marker=marker)
+        return prefix_search(self._lat(), self.theta.detach(), k, pad=self.__pad__, **tape, **kw)
+
     def string_nll(self, strings: torch.Tensor, lengths: torch.Tensor, **kw) -> torch.Tensor:
         """The maximum-likelihood loss on strings: the mean over the batch of -log p(y | x), y = ``strings[b, 0,
         :lengths[b, 0]]`` the one reference string of lattice b (``strings`` [B, 1, N]; ``kw``: ``keep`` or ``marker``),

@@ -1,9 +1,10 @@
-"""Output strings: the wrappers of ``nfst_merge_paths``, ``nfst_string_logprob`` and ``nfst_string_logprob_grad``
-(include/nfst_hip.h; DESIGN.md sections 2 and 4.20 to 4.22).  The path-side ops answer in mark paths; the string of a path is its projection onto the output tape,
+"""Output strings: the wrappers of ``nfst_merge_paths``, ``nfst_string_logprob``, ``nfst_string_logprob_grad``,
+``nfst_string_prefix`` and ``nfst_string_next`` (include/nfst_hip.h; DESIGN.md sections 2 and 4.20 to 4.23).  The path-side ops answer in mark paths; the string of a path is its projection onto the output tape,
 given as ``keep`` (a set of labels: the path's labels that belong to it, ``WideDFA.projected_sequence``'s meaning) or as
 ``marker`` (the labels that directly follow an arc labelled ``marker``, ``WideDFA.marked_sequence``'s meaning).
-``ops.merge_paths``, ``ops.string_log_prob`` and ``ops.string_arc_posteriors`` are these functions;
-``decoders.decode_strings`` puts the first two together.
+``ops.merge_paths``, ``ops.string_log_prob``, ``ops.string_arc_posteriors``, ``ops.string_prefix_log_prob`` and
+``ops.string_next_log_probs`` are these functions; ``decoders.decode_strings`` puts the first two together and
+``decoders.prefix_search`` searches with the last.
 There is no CPU implementation.
 """
 from __future__ import annotations
@@ -157,9 +158,9 @@ class _Candidates(NamedTuple):
         return torch.empty(max(n, 16), dtype=torch.uint8, device=self.lat.device)
 
 
-def _candidates(lat, strings, lengths, keep, marker, max_workspace_bytes: int) -> _Candidates:
-    """Checks and marshals the candidates and the tape, and cuts the candidates into slices whose forward workspace
-    stays under ``max_workspace_bytes``."""
+def _candidates(lat, strings, lengths, keep, marker, max_workspace_bytes: int, query: str = "nfst_string_logprob_ws_bytes") -> _Candidates:
+    """Checks and marshals the candidates and the tape, and cuts the candidates into slices whose workspace, as the
+    library's ``query`` sizes it (the forward's by default), stays under ``max_workspace_bytes``."""
     from .ops import _need_gpu
 
     _need_gpu(lat)
@@ -172,9 +173,9 @@ def _candidates(lat, strings, lengths, keep, marker, max_workspace_bytes: int) -
     bs = C.byref(lat.c_struct())
 
     def ws_bytes(m):
-        n = int(_lib.lib.nfst_string_logprob_ws_bytes(bs, m, N, int(mk >= 0)))
+        n = int(getattr(_lib.lib, query)(bs, m, N, int(mk >= 0)))
         if n < 0:
-            _lib.check(n, "nfst_string_logprob_ws_bytes")  # (N > EDIT_MAX_LEN: NFST_ERR_LIMIT)
+            _lib.check(n, query)  # (N > EDIT_MAX_LEN: NFST_ERR_LIMIT)
         return n
 
     fixed = ws_bytes(0)
@@ -331,3 +332,77 @@ def string_log_prob(lat, theta, strings: torch.Tensor, lengths: torch.Tensor, *,
         out = _StringScoresWithOffsets(*out)
         out.arc_offsets = arc_offsets
     return out
+
+
+# ----------------------------------------------------------------------------- prefixes
+class PrefixScores(NamedTuple):
+    log_prefix: torch.Tensor  # [B, M] float64: log of the summed weight of the paths whose string starts with the prefix
+    logz: torch.Tensor        # [B] float64: the same over all paths (``string_log_prob``'s, bit for bit)
+    log_prob: torch.Tensor    # [B, M] float64 = log_prefix - logz
+
+
+class NextSymbols(NamedTuple):
+    next: torch.Tensor        # [B, M, V] float64: log_prefix of the prefix followed by label v (-inf: v is never on the tape)
+    eos: torch.Tensor         # [B, M] float64: the log weight of the paths that spell exactly the prefix
+    log_prefix: torch.Tensor  # [B, M] float64: the log-sum of eos and next
+    logz: torch.Tensor        # [B] float64
+
+
+def _prefix_launches(name: str, lat, theta, prefixes, lengths, keep, marker, arc_scores, max_workspace_bytes: int, n_out: int) -> tuple:
+    """``nfst_string_prefix`` (``n_out`` = 1) or ``nfst_string_next`` (3) slice by slice: ``(outputs [B, M(, V)] ...,
+    logz [B])`` after the status word has been read back."""
+    from .ops import _call, _raise_status, _scores
+
+    c = _candidates(lat, prefixes, lengths, keep, marker, max_workspace_bytes, name + "_ws_bytes")
+    if not isinstance(theta, torch.Tensor):
+        theta = torch.as_tensor(theta, dtype=torch.float32)
+    sc, alive = _scores(lat, theta.detach(), None if arc_scores is None else arc_scores.detach())
+    dev, f64 = lat.device, torch.float64
+    B, M, N = c.rows.shape
+    shapes = [(B, M)] if n_out == 1 else [(B, M, lat.vocab), (B, M), (B, M)]
+    outs = [torch.empty(sh, dtype=f64, device=dev) for sh in shapes]
+    logz = torch.empty(B, dtype=f64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    if M == 0:  # no prefix: log Z alone, from the sweep that every slice shares
+        ws = c.workspace("nfst_string_logprob_ws_bytes")
+        _call("nfst_string_logprob", lat, sc, None, None, 0, N, c.keep_mask, c.marker, ws, ws.numel(), None, logz, status)
+    else:
+        ws = c.workspace(name + "_ws_bytes")
+    for m0, m1 in c.slices() if M else ():
+        whole = (m0, m1) == (0, M)
+        part = outs if whole else [torch.empty((B, m1 - m0) + sh[2:], dtype=f64, device=dev) for sh in shapes]
+        _call(name, lat, sc, c.rows[:, m0:m1].contiguous(), c.lens[:, m0:m1].contiguous(), m1 - m0, N, c.keep_mask, c.marker, ws,
+              ws.numel(), *part, logz, status)
+        if not whole:
+            for o, q in zip(outs, part):
+                o[:, m0:m1] = q
+    _raise_status(status, name)  # a prefix's length outside its row
+    del alive
+    return (*outs, logz)
+
+
+def string_prefix_log_prob(lat, theta, prefixes: torch.Tensor, lengths: torch.Tensor, *, keep=None, marker: Optional[int] = None,
+                           arc_scores=None, max_workspace_bytes: int = 1 << 30) -> PrefixScores:
+    """The exact probability that the output string starts with a prefix (``nfst_string_prefix``): for lattice b and
+    y = ``prefixes[b, m, :lengths[b, m]]`` (``prefixes`` [B, M, N] int32 or int64, N <= ``EDIT_MAX_LEN``), ``log_prefix``
+    is the log of the summed weight of the paths whose string on the tape ``keep`` or ``marker`` starts with y, ``logz``
+    that of all paths (``string_log_prob``'s, bit for bit) and ``log_prob`` their difference, all float64; a prefix that
+    no path spells gets -inf.  A path that ends on a marker with nothing behind it spells no string and counts under no
+    prefix: in marker mode the empty prefix has ``log_prob`` = log(1 - those paths' share), in keep mode 0.  The value
+    bounds log p of every string that starts with y from above.  Scores, slicing under ``max_workspace_bytes`` and the
+    length error are ``string_log_prob``'s.  The results carry no gradient: gradients of prefix masses are out of scope."""
+    log_prefix, logz = _prefix_launches("nfst_string_prefix", lat, theta, prefixes, lengths, keep, marker, arc_scores, max_workspace_bytes, 1)
+    neg = torch.full_like(log_prefix, float("-inf"))
+    return PrefixScores(log_prefix, logz, torch.where(torch.isneginf(log_prefix), neg, log_prefix - logz[:, None]))
+
+
+def string_next_log_probs(lat, theta, prefixes: torch.Tensor, lengths: torch.Tensor, *, keep=None, marker: Optional[int] = None,
+                          arc_scores=None, max_workspace_bytes: int = 1 << 30) -> NextSymbols:
+    """The next-symbol masses of prefixes (``nfst_string_next``; arguments as ``string_prefix_log_prob``'s): ``next[b, m,
+    v]`` is ``log_prefix`` of the prefix followed by label v, for every label of the vocabulary (-inf for a label that is
+    never on the tape: one that ``keep`` does not hold), ``eos[b, m]`` the log weight of the paths that spell exactly the
+    prefix (``string_log_prob``'s ``log_num``) and ``log_prefix`` the log-sum of ``eos`` and ``next``, so that
+    exp(log_prefix) = exp(eos) + sum_v exp(next[v]); all float64 log weights, not normalised: subtract ``log_prefix`` for
+    log p(v | y, x) and ``logz`` for probabilities.  The results carry no gradient: gradients of prefix masses are out
+    of scope."""
+    return NextSymbols(*_prefix_launches("nfst_string_next", lat, theta, prefixes, lengths, keep, marker, arc_scores, max_workspace_bytes, 3))

@@ -84,6 +84,7 @@ __global__ __launch_bounds__(NT) void k_backward(nfst_batch lat, nfst_scores sc,
   VT *lds = reinterpret_cast<VT *>(lds_raw);
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   if (lat.only && lat.only[b] != lat.only_tag) return;  // (the chunked flavour ran this lattice: nfst_batch.only)
+  if (tid == 0) NFST_STAMP(0);  // (profiling build; the slots of k_forward_backward: 0 entry, 5 first tile, 2 swept, 11 waits)
   // this thread's label score: requested before anything waits for the meta record
   const float theta_first = tid < lat.vocab ? sc.theta[(size_t)sc.theta_stride * b + tid] : 0.0f;
   const Meta m = load_meta(lat.meta, b);
@@ -132,9 +133,10 @@ __global__ __launch_bounds__(NT) void k_backward(nfst_batch lat, nfst_scores sc,
     if (wv == 0) {
       __builtin_amdgcn_s_setprio(3);
       if constexpr (PREC) tile_sweep2<Sweep64, kNE>(m.bwd_tiles, ring, R, flags, flags + 4, lane);
-      else if (tw_v2) tile_sweep2<Sweep32, kNE>(m.bwd_tiles, ring, R, flags, flags + 4, lane);
+      else if (tw_v2) tile_sweep2<Sweep32, kNE>(m.bwd_tiles, ring, R, flags, flags + 4, lane, 5);
       else tile_sweep<4, true, kNE>(m.bwd_tiles, ring, R, flags, flags + 4, lane);
       __builtin_amdgcn_s_setprio(0);
+      NFST_STAMP(2);
     }
   } else if (wv < (kSelf ? 2 : 3))
     run_sweep<EXTRA, kSelf, kAhead, kNE>(wv, m.bwd_u, m.bwd_wide != 0, raw, RS, lat.bwd_stream + m.bwd_off,
@@ -179,9 +181,11 @@ __device__ __forceinline__ float arc_posterior(const float2 av, const float2 bv,
 // beta, odd ones for alpha (tile_pipeline.h).
 // FUSED: waves 0 / 1 load, decode and sweep by themselves (FusedSweep, tile_pipeline.h): no loader,
 // no decoder, no rings; every program of the batch is compact and there are no per-arc extras.
-// TW (1024 threads): tile waves -- no loader, no staging ring, no decoder: the eight waves 2, 3, 6, 7, 10, 11, 14, 15
-// (the SIMDs the sweep waves are not on) decode every fourth tile of their sweep's program straight from
-// HBM into the decoded ring, label weights and per-arc extras included (WeightWave<.., FULL>).
+// TW (1024 threads): tile waves -- no loader, no staging ring, no decoder: the eight waves 2 .. 9 (two per SIMD, even
+// ones for beta, odd ones for alpha: waves 4, 5, 8 and 9 share the sweep waves' SIMDs) decode every fourth tile of their
+// sweep's program straight from HBM into the decoded ring, label weights and per-arc extras included
+// (WeightWave<.., FULL>::run_tiles).  Alone on its SIMD the beta sweep of k_backward takes 148 ns per tile, here 173
+// (profiles/tile_wave_diet.json): moving the tile waves to the other two SIMDs is not tried yet with the shorter loop.
 // PTH (tile waves, no extras, float32, launches without grad_theta): the helper threads gather the label weights of their
 // preloaded arc groups in front of the barrier and keep them in registers in place of the labels; no label histogram.
 template <int NT, int EXTRA, bool FUSED = false, bool TW = false, bool PREC = false, bool PTH = false>

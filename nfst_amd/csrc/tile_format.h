@@ -92,6 +92,24 @@ NFST_HD inline void unpack24(uint32_t w1, uint32_t w2, uint32_t w3, uint32_t (&r
   r[0] = w1; r[1] = (w1 >> 24) | (w2 << 8); r[2] = (w2 >> 16) | (w3 << 16); r[3] = w3 >> 8;
 #endif
 }
+// state and label of a compact lane's four records, one bit-field extract each: only record 1's state and record 2's label
+// straddle a word.  (Device: the extracts are opaque to the compiler, which otherwise folds the shift that follows -- times
+// 8 or 16, plus an array's base: one shift-and-add -- into a shift, a mask and an add.)
+NFST_HD inline void unpack24_fields(uint32_t w1, uint32_t w2, uint32_t w3, uint32_t (&state)[4], uint32_t (&label)[4]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#define NFST_BFE(D, X, OFF, W) asm("v_bfe_u32 %0, %1, %2, %3" : "=v"(D) : "v"(X), "n"(OFF), "n"(W))
+  const uint32_t r1 = __builtin_amdgcn_alignbit(w2, w1, 24), r2 = __builtin_amdgcn_alignbit(w3, w2, 16);
+  NFST_BFE(state[0], w1, 0, 13);  NFST_BFE(label[0], w1, 13, 11);
+  NFST_BFE(state[1], r1, 0, 13);  NFST_BFE(label[1], w2, 5, 11);
+  NFST_BFE(state[2], w2, 16, 13); NFST_BFE(label[2], r2, 13, 11);
+  NFST_BFE(state[3], w3, 8, 13);  NFST_BFE(label[3], w3, 21, 11);
+#undef NFST_BFE
+#else
+  uint32_t r[4];
+  unpack24(w1, w2, w3, r);
+  for (int j = 0; j < 4; ++j) { state[j] = rec24_state(r[j]); label[j] = rec24_label(r[j]); }
+#endif
+}
 
 // ---- pieces of a state.  cap = records of the largest group; a chain's first piece takes cap records, every
 // continuation piece one less (its carry).  Pass k of a level holds the k-th piece of every state of the level: a chain's

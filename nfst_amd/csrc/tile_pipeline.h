@@ -750,10 +750,13 @@ struct WeightWave {
   int n_mine, last, ei;
 
   __device__ __forceinline__ P ld_tile(int i, int lane) const {
-    P p;
     const int t = ei + min(i, max(n_mine - 1, 0)) * NE;  // past this wave's last tile: that tile again
-    const int32_t *q = perm + (size_t)t * (64 * U) + lane * U;
-    const uint32_t *g = prog_words + (size_t)t * fmt_words(F);
+    return ld_at(prog_words + (size_t)t * fmt_words(F), perm + (size_t)t * (64 * U), lane);
+  }
+  // g, qt: the tile's records and its slot -> arc map (wave-uniform: a lane's part is one offset from a scalar base)
+  __device__ __forceinline__ static P ld_at(const uint32_t *g, const int32_t *qt, int lane) {
+    P p;
+    const int32_t *q = qt + lane * U;
     if (XM == 0) p.a[0] = -1;
     if (U == 4) {
       if (XM != 0) {
@@ -829,83 +832,252 @@ struct WeightWave {
     p0 = ld_tile(0, lane); p1 = ld_tile(1, lane); p2 = ld_tile(2, lane);
   }
   __device__ __forceinline__ void start_gathers(int lane) {
-    if (n_mine <= 0) return;
+    if (n_mine <= 0 || (FULL && XM == 0)) return;  // (tile waves without extras keep three tiles' records: run_tiles)
     g0 = issue(p0);
     p0 = ld_tile(3, lane);
     g1 = issue(p1);
   }
-  // v2 (FULL, four slots per lane, narrow groups): the decoded tile of tile_sweep2 -- per lane the store address
-  // (the state's value for a leader lane, 8 bytes of trash otherwise) and the three 0 / 1 stage multipliers of the
-  // segmented sum instead of the control word.  Tile waves use ring slots of kSlotWords2 words for every format.
+  // float32 weights of a tile's four (U) slots: label weight (tha: its LDS address) x exp(per-arc extras) as (mantissa, exponent)
   // xc_base / xc_first (XM = 3): LDS address of the staged sums of the per-arc extras, and the canonical arc the first one belongs to
-  __device__ __forceinline__ void run(uint32_t *ring, int R, const int *prog, int *xland, const float2 *th_, const float2 *val, bool v2,
-                                      uint32_t trash, uint32_t xc_base, int xc_first, int lane) {
-    const uint32_t xl_a = lds_addr(xland) + (uint32_t)ei * 4;
+  template <class S>  // G, or P in kernels without extras
+  __device__ __forceinline__ static void weights32(const S &g, const uint32_t (&tha)[U], uint32_t xc_base, int xc_first, v2f (&o)[U]) {
+    v2f tw[U];
+#pragma unroll
+    for (int j = 0; j < U; ++j) tw[j] = *(const lds_v2f *)(uintptr_t)tha[j];
+#pragma unroll
+    for (int j = 0; j < U; ++j) {
+      if (XM == 0) { o[j] = tw[j]; continue; }
+      if constexpr (XM != 0) {
+        const float xs = CACHED ? *(const __attribute__((address_space(3))) float *)(uintptr_t)(xc_base + (uint32_t)(g.a[CACHED ? j : 0] - xc_first) * 4)
+                                : (BOTH ? g.w[GATHER ? j : 0] + g.s[BOTH ? j : 0] : g.w[GATHER ? j : 0]);
+        const ME x = exp_split_nb(((g.valid >> j) & 1u) ? xs : 0.0f);
+        o[j] = v2f{tw[j].x * x.m, __int_as_float(__float_as_int(tw[j].y) + x.e)};
+      }
+    }
+  }
+  // ---- the tile waves' loop (FULL: compact programs only, four slots per lane) ------------------------------------
+  // Per tile the wave issues what changes per tile and little else.  Its tile number, its ring slot and its place in the
+  // program are cursors: tiles ei, ei + NE, ... lie NE slots apart in a ring of a multiple of NE slots, so the slot address
+  // advances by NE slots and wraps by one compare (no t % R: a runtime division was 14 scalar instructions per tile), and the
+  // records' pointer advances by NE tiles (no clamp, no 64-bit multiply-add per load).  A lane's part of a slot is one
+  // address, sb + 16 * lane, and immediates; the bases of the value and label-weight arrays go into the shift-and-add that
+  // makes an operand's or a label's address (unpack24_fields).
+  // V2: the ring format is the sweep's choice per program (narrow groups: tile_sweep2), made once in front of the loop:
+  //   V2  the decoded tile of tile_sweep2 -- per lane the store address (the state's value for a leader lane, 8 bytes of
+  //       trash otherwise) and the three 0 / 1 stage multipliers of the segmented sum instead of the control word;
+  //   !V2 control word + value base, operand addresses and weights at the offsets of tile_sweep<4, true>.
+  // Tile waves use ring slots of kSlotWords2 words for both (kSlotWordsP: the precise flavour, always the tile_sweep2 layout).
+  // Without per-arc extras (XM = 0) there is nothing to gather, so the records of the wave's tiles i, i+1, i+2 sit in p0, p1,
+  // p2 and a set is loaded again (tile i+3) as soon as its tile is unpacked: three tiles per trip, no copies between the sets
+  // (through the P -> G stages of the kernels with extras hipcc rotated five sets through three names: ten copies per trip
+  // that waited for the loads just issued).  The trip runs while its three tiles and its three loads all exist, so it clamps
+  // nothing; the last one to five tiles are straight-line code behind it.
+  // With extras: map and records of tile i+4, gathers of tile i+2, tile i; past its last tile the wave writes that tile
+  // again -- same slot, same words: the cursors stand still --, which keeps the trip a single block.
+  template <bool V2>
+  __device__ __forceinline__ void run_tiles(uint32_t *ring, int R, const int *prog, int *xland, const float2 *th_, const float2 *val,
+                                            uint32_t trash, uint32_t xc_base, int xc_first, int lane) {
+    static_assert(FULL && F == 8 && U == 4 && (V2 || !PREC), "tile waves decode compact programs");
+    uint32_t xl_a = lds_addr(xland) + (uint32_t)ei * 4;
+    // (stays in a vector register: from a scalar one hipcc copied it in front of every flag write; the kernels with two
+    // arrays of extras have no register to spare for it)
+    if constexpr (XM == 0) asm volatile("" : "+v"(xl_a));
     if (n_mine <= 0) {
-      if (FULL) *(volatile lds_u32 *)(uintptr_t)xl_a = 0x7fffffffu;  // "every tile of mine is there" (there is none)
+      *(volatile lds_u32 *)(uintptr_t)xl_a = 0x7fffffffu;  // "every tile of mine is there" (there is none)
       return;
     }
-    constexpr uint32_t SB = FULL ? kSlotWords2 * 4 : 64 * (1 + 3 * U) * 4;
-    const uint32_t ring_base = lds_addr(ring), prog_a = lds_addr(prog);
-    const uint32_t th_base = lds_addr(th_), val_base = lds_addr(val);
-    int prog_seen = 0;
-    auto process = [&](int i, const auto &g) {  // g: G, or P in kernels without extras
-      const int t = ei + min(i, n_mine - 1) * NE;
-      uint32_t ctl, opoff[U], lab8[U];
-      unpack(g.raw, ctl, opoff, lab8);
+    constexpr uint32_t SB = (PREC ? kSlotWordsP : kSlotWords2) * 4;
+    constexpr int SH = PREC ? 4 : 3;  // log2 of the bytes of a value / a label weight: 8, precise 16
+    constexpr bool kClamp = XM != 0;  // the cursors stop at the wave's last tile
+    constexpr int kLoadAhead = XM == 0 ? 3 : 4;
+    const uint32_t prog_a = lds_addr(prog), th_base = lds_addr(th_), val_base = lds_addr(val);
+    const uint32_t ring_bytes = (uint32_t)R * SB, ring_end = lds_addr(ring) + ring_bytes;
+    const uint32_t l16 = (uint32_t)lane * 16;
+    // the tile in hand: its number and its slot (ei < NE <= R)
+    const int t_last = ei + (n_mine - 1) * NE;
+    int t = ei;
+    uint32_t sb = lds_addr(ring) + (uint32_t)ei * SB;
+    // the next tile to load (start_maps / start_gathers loaded the wave's first kLoadAhead tiles)
+    constexpr size_t kStep = (size_t)NE * fmt_words(F);
+    const size_t first = (size_t)(ei + (kClamp ? min(kLoadAhead, n_mine - 1) : kLoadAhead) * NE) * fmt_words(F);
+    const uint32_t *gp = prog_words + first, *const gp_last = prog_words + (size_t)t_last * fmt_words(F);
+    const int32_t *qp = perm + first;
+    auto load = [&](P &p) {
+      p = ld_at(gp, qp, lane);
+      const size_t st = !kClamp || gp != gp_last ? kStep : 0;
+      gp += st;
+      qp += st;
+    };
+    // the decoded tile of tile_sweep2<Sweep64>: values and label weights are 16-byte records (float64 mantissa, exponent):
+    // [store address | g, largest g][3 stage multipliers: the high word of 1.0 or 0][4 operand addresses]
+    // [4 weight mantissas, float64][4 weight exponents] = 80 bytes per lane
+    // (everything that needs a word of the tile's records is computed in decode: with the control word still alive in publish,
+    // behind the load that takes the records' registers again, hipcc copied it at the end of the trip -- and waited there
+    // for the loads just issued)
+    struct Dec { v4u h; uint32_t opa[4]; v2f o[PREC ? 1 : 4]; double om[PREC ? 4 : 1]; int oe[PREC ? 4 : 1]; };
+    auto decode = [&](const auto &g) {  // g: G, or P in kernels without extras
+      Dec d;
+      const uint32_t ctl = g.raw[0];
       if constexpr (PREC) {
-        // the decoded tile of tile_sweep2<Sweep64>: values and label weights are 16-byte records (float64 mantissa, exponent):
-        // [store address | g, largest g][3 stage multipliers: the high word of 1.0 or 0][4 operand addresses]
-        // [4 weight mantissas, float64][4 weight exponents] = 80 bytes per lane
-        double om[U];
-        int oe[U];
+        const int gl = (int)((ctl >> 20) & 7u);  // (through the accessors of tile_format.h the compiler schedules this differently)
+        const uint32_t dst = (((int)ctl < 0) ? 2 * (ctl & 0xffffu) + val_base : trash) | (ctl & 0x03f00000u);
+        d.h = v4u{dst, gl > 0 ? 0x3ff00000u : 0u, gl > 1 ? 0x3ff00000u : 0u, gl > 2 ? 0x3ff00000u : 0u};
+      } else if constexpr (V2) {
+        const int gl = (int)ctl_g(ctl);
+        const uint32_t dst = ctl_leader(ctl) ? ctl_off8(ctl) + val_base : trash;
+        d.h = v4u{dst, gl > 0 ? 0x3f800000u : 0u, gl > 1 ? 0x3f800000u : 0u, gl > 2 ? 0x3f800000u : 0u};
+      } else {
+        d.h = v4u{ctl + val_base, 0u, 0u, 0u};
+      }
+      if constexpr (XM != 0) {  // (nothing lies between decode and publish)
+      } else if constexpr (PREC || V2) {
+        asm volatile("" ::"v"(d.h));  // (computed here, not sunk into publish)
+      } else {
+        asm volatile("" ::"v"(d.h.x));
+      }
+      uint32_t st[4], lb[4], tha[4];
+      unpack24_fields(g.raw[1], g.raw[2], g.raw[3], st, lb);
 #pragma unroll
-        for (int j = 0; j < U; ++j) {
-          const v4u tr = *(const lds_v4u *)(uintptr_t)(th_base + 2 * lab8[j]);
+      for (int j = 0; j < 4; ++j) {
+        d.opa[j] = (st[j] << SH) + val_base;
+        tha[j] = (lb[j] << SH) + th_base;
+      }
+      if constexpr (PREC) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const v4u tr = *(const lds_v4u *)(uintptr_t)tha[j];
           const double tm = __hiloint2double((int)tr.y, (int)tr.x);
           if constexpr (XM == 0) {
-            om[j] = tm;
-            oe[j] = (int)tr.z;
+            d.om[j] = tm;
+            d.oe[j] = (int)tr.z;
           } else {
             const double xs = BOTH ? (double)g.w[GATHER ? j : 0] + (double)g.s[BOTH ? j : 0] : (double)g.w[GATHER ? j : 0];
             const ME64 x = exp_split64(((g.valid >> j) & 1u) ? xs : 0.0);
-            om[j] = tm * x.m;
-            oe[j] = (int)tr.z + x.e;
+            d.om[j] = tm * x.m;
+            d.oe[j] = (int)tr.z + x.e;
           }
         }
-        while (__builtin_expect(prog_seen < t - R + 1, 0)) {  // the slot's previous tile is consumed
+      } else {
+        weights32(g, tha, xc_base, xc_first, d.o);
+      }
+      return d;
+    };
+    int prog_seen = 0;
+    auto publish = [&](const Dec &d) {
+      // the slot's previous tile is consumed?  (Only a wave that is R - NE tiles ahead of its sweep gets into the loop: its
+      // tile is ready and the sweep far behind: long naps, few issue slots.)
+      if (__builtin_expect(prog_seen < t - R + 1, 0)) {
+        for (;;) {
           prog_seen = __builtin_amdgcn_readfirstlane(*(const volatile lds_u32 *)(uintptr_t)prog_a);
-          if (prog_seen < t - R + 1) { if (R >= 8) __builtin_amdgcn_s_sleep(kXNap); else __builtin_amdgcn_s_sleep(1); }
+          if (prog_seen >= t - R + 1) break;
+          if (R >= 8) __builtin_amdgcn_s_sleep(kXNap); else __builtin_amdgcn_s_sleep(1);
         }
-        asm volatile("" ::: "memory");
-        const uint32_t sb = ring_base + (uint32_t)(t % R) * (kSlotWordsP * 4);
-        const int gl = (int)((ctl >> 20) & 7u);  // (through the accessors of tile_format.h the compiler schedules this differently)
-        const uint32_t dst = (((int)ctl < 0) ? 2 * (ctl & 0xffffu) + val_base : trash) | (ctl & 0x03f00000u);
-        *(lds_v4u *)(uintptr_t)(sb + lane * 16) = v4u{dst, gl > 0 ? 0x3ff00000u : 0u, gl > 1 ? 0x3ff00000u : 0u, gl > 2 ? 0x3ff00000u : 0u};
-        *(lds_v4u *)(uintptr_t)(sb + 1024 + lane * 16) = v4u{2 * opoff[0] + val_base, 2 * opoff[1 % U] + val_base, 2 * opoff[2 % U] + val_base, 2 * opoff[3 % U] + val_base};
-        *(lds_v4u *)(uintptr_t)(sb + 2048 + lane * 16) = v4u{(uint32_t)__double2loint(om[0]), (uint32_t)__double2hiint(om[0]),
-                                                             (uint32_t)__double2loint(om[1 % U]), (uint32_t)__double2hiint(om[1 % U])};
-        *(lds_v4u *)(uintptr_t)(sb + 3072 + lane * 16) = v4u{(uint32_t)__double2loint(om[2 % U]), (uint32_t)__double2hiint(om[2 % U]),
-                                                             (uint32_t)__double2loint(om[3 % U]), (uint32_t)__double2hiint(om[3 % U])};
-        *(lds_v4u *)(uintptr_t)(sb + 4096 + lane * 16) = v4u{(uint32_t)oe[0], (uint32_t)oe[1 % U], (uint32_t)oe[2 % U], (uint32_t)oe[3 % U]};
-        asm volatile("" ::: "memory");
-        *(volatile lds_u32 *)(uintptr_t)xl_a = (uint32_t)(t + 1);
-        return;
       }
-      v2f tw[U];
+      asm volatile("" ::: "memory");
+      const uint32_t a = sb + l16;
+      if constexpr (PREC) {
+        *(lds_v4u *)(uintptr_t)a = d.h;
+        *(lds_v4u *)(uintptr_t)(a + 1024) = v4u{d.opa[0], d.opa[1], d.opa[2], d.opa[3]};
+        *(lds_v4u *)(uintptr_t)(a + 2048) = v4u{(uint32_t)__double2loint(d.om[0]), (uint32_t)__double2hiint(d.om[0]),
+                                                (uint32_t)__double2loint(d.om[PREC ? 1 : 0]), (uint32_t)__double2hiint(d.om[PREC ? 1 : 0])};
+        *(lds_v4u *)(uintptr_t)(a + 3072) = v4u{(uint32_t)__double2loint(d.om[PREC ? 2 : 0]), (uint32_t)__double2hiint(d.om[PREC ? 2 : 0]),
+                                                (uint32_t)__double2loint(d.om[PREC ? 3 : 0]), (uint32_t)__double2hiint(d.om[PREC ? 3 : 0])};
+        *(lds_v4u *)(uintptr_t)(a + 4096) = v4u{(uint32_t)d.oe[0], (uint32_t)d.oe[PREC ? 1 : 0], (uint32_t)d.oe[PREC ? 2 : 0], (uint32_t)d.oe[PREC ? 3 : 0]};
+      } else {
+        constexpr int J1 = PREC ? 0 : 1, J2 = PREC ? 0 : 2, J3 = PREC ? 0 : 3;
+        const v4f w01 = v4f{d.o[0].x, d.o[0].y, d.o[J1].x, d.o[J1].y}, w23 = v4f{d.o[J2].x, d.o[J2].y, d.o[J3].x, d.o[J3].y};
+        if constexpr (V2) {
+          *(lds_v4u *)(uintptr_t)a = d.h;
+          *(lds_v4u *)(uintptr_t)(a + 1024) = v4u{d.opa[0], d.opa[1], d.opa[2], d.opa[3]};
+          *(lds_v4f *)(uintptr_t)(a + 2048) = w01;
+          *(lds_v4f *)(uintptr_t)(a + 3072) = w23;
+        } else {
+          *(lds_u32 *)(uintptr_t)(sb + (uint32_t)lane * 4) = d.h.x;
+          *(lds_v4u *)(uintptr_t)(a + 256) = v4u{d.opa[0], d.opa[1], d.opa[2], d.opa[3]};
+          *(lds_v4f *)(uintptr_t)(a + 256 + 1024) = w01;
+          *(lds_v4f *)(uintptr_t)(a + 256 + 2048) = w23;
+        }
+      }
+      asm volatile("" ::: "memory");
+      *(volatile lds_u32 *)(uintptr_t)xl_a = (uint32_t)(t + 1);
+      const bool more = !kClamp || t != t_last;
+      t += more ? NE : 0;
+      sb += more ? NE * SB : 0u;
+      sb -= sb >= ring_end ? ring_bytes : 0u;
+    };
+    if constexpr (XM == 0) {
+      // a trip's three loads: one scalar base, advanced once per trip, and three per-lane offsets that stay in registers (the
+      // step of 4096 bytes is one more than a load's immediate offset holds, and from a pointer advanced per load hipcc made
+      // two of the three addresses with 64-bit vector adds; the empty asm makes the offset a 32-bit value of the block that
+      // loads: scalar base + 32-bit vector offset is one addressing mode)
+      uint32_t off[3];
 #pragma unroll
-      for (int j = 0; j < U; ++j) tw[j] = *(const lds_v2f *)(uintptr_t)(th_base + lab8[j]);
+      for (int k = 0; k < 3; ++k) off[k] = l16 + (uint32_t)(k * kStep * 4);
+      auto load0 = [&](P &p, int k) {
+        asm volatile("" : "+v"(off[k]));
+        const uint4 x = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(gp) + off[k]);
+        p.raw[0] = x.x; p.raw[1] = x.y; p.raw[2] = x.z; p.raw[3] = x.w;
+      };
+      // (the fence: whatever reads the records is issued in front of the load that takes their registers again)
+#define NFST_X_STEP(PK, K) { const Dec d_ = decode(PK); __builtin_amdgcn_sched_barrier(0); load0(PK, K); publish(d_); }
+      int i = 0;
+      for (; i + 2 + kLoadAhead < n_mine; i += 3) {  // tiles i .. i+2 and the loads of tiles i+3 .. i+5
+        NFST_X_STEP(p0, 0)
+        NFST_X_STEP(p1, 1)
+        NFST_X_STEP(p2, 2)
+        gp += 3 * kStep;
+      }
+#undef NFST_X_STEP
+      const int left = n_mine - i;  // 1 .. 5 tiles: i, i+1, i+2 are loaded, tiles i+3 and i+4 go into the first sets freed
+      {
+        const Dec d = decode(p0);
+        if (left > 3) load0(p0, 0);
+        publish(d);
+      }
+      if (left > 1) {
+        const Dec d = decode(p1);
+        if (left > 4) load0(p1, 1);
+        publish(d);
+      }
+      if (left > 2) publish(decode(p2));
+      if (left > 3) publish(decode(p0));
+      if (left > 4) publish(decode(p1));
+    } else {
+      // iteration i: the gathers of tile i+2 (its records and map were loaded two iterations ago), the records and map of
+      // tile i+4, then tile i itself; register roles are compile-time: three iterations per trip
+      // (no exit inside a trip: with exits in between hipcc rotated registers through copies that wait for the loads just issued)
+#define NFST_X_STEP(PU, GN, PL, GC)  \
+      GN = issue(PU);                \
+      load(PL);                      \
+      publish(decode(GC));
+      for (int i = 0; i < n_mine; i += 3) {
+        NFST_X_STEP(p2, g2, p1, g0)
+        NFST_X_STEP(p0, g0, p2, g1)
+        NFST_X_STEP(p1, g1, p0, g2)
+      }
+#undef NFST_X_STEP
+    }
+    // every tile of this wave is there: a sweep that looks one tile past the end of its program never waits
+    *(volatile lds_u32 *)(uintptr_t)xl_a = 0x7fffffffu;
+  }
+  // weight waves beside a decoder wave (!FULL: the pipeline flavours with per-arc extras): the weights only
+  __device__ __forceinline__ void run(uint32_t *ring, int R, const int *prog, int *xland, const float2 *th_, uint32_t xc_base, int xc_first,
+                                      int lane) {
+    static_assert(!FULL && !PREC, "tile waves: run_tiles");
+    const uint32_t xl_a = lds_addr(xland) + (uint32_t)ei * 4;
+    if (n_mine <= 0) return;
+    constexpr uint32_t SB = 64 * (1 + 3 * U) * 4;
+    const uint32_t ring_base = lds_addr(ring), prog_a = lds_addr(prog);
+    const uint32_t th_base = lds_addr(th_);
+    int prog_seen = 0;
+    auto process = [&](int i, const G &g) {
+      const int t = ei + min(i, n_mine - 1) * NE;
+      uint32_t ctl, opoff[U], lab8[U], tha[U];
+      unpack(g.raw, ctl, opoff, lab8);
+#pragma unroll
+      for (int j = 0; j < U; ++j) tha[j] = th_base + lab8[j];
       v2f o[U];
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        if (XM == 0) { o[j] = tw[j]; continue; }
-        if constexpr (XM != 0) {
-          const float xs = CACHED ? *(const __attribute__((address_space(3))) float *)(uintptr_t)(xc_base + (uint32_t)(g.a[CACHED ? j : 0] - xc_first) * 4)
-                                  : (BOTH ? g.w[GATHER ? j : 0] + g.s[BOTH ? j : 0] : g.w[GATHER ? j : 0]);
-          const ME x = exp_split_nb(((g.valid >> j) & 1u) ? xs : 0.0f);
-          o[j] = v2f{tw[j].x * x.m, __int_as_float(__float_as_int(tw[j].y) + x.e)};
-        }
-      }
+      weights32(g, tha, xc_base, xc_first, o);
       while (__builtin_expect(prog_seen < t - R + 1, 0)) {  // the slot's previous tile is consumed
         prog_seen = __builtin_amdgcn_readfirstlane(*(const volatile lds_u32 *)(uintptr_t)prog_a);
         // (a blocked wave has its tile ready and the sweep is R - NE tiles behind: long naps, few issue slots)
@@ -913,34 +1085,6 @@ struct WeightWave {
       }
       asm volatile("" ::: "memory");
       const uint32_t sb = ring_base + (uint32_t)(t % R) * SB;
-      if (FULL && v2) {
-        const int gl = (int)ctl_g(ctl);
-        const uint32_t dst = ctl_leader(ctl) ? ctl_off8(ctl) + val_base : trash;
-        *(lds_v4u *)(uintptr_t)(sb + lane * 16) = v4u{dst, gl > 0 ? 0x3f800000u : 0u, gl > 1 ? 0x3f800000u : 0u, gl > 2 ? 0x3f800000u : 0u};
-        if (U == 4) {
-          *(lds_v4u *)(uintptr_t)(sb + 1024 + lane * 16) = v4u{opoff[0] + val_base, opoff[1 % U] + val_base, opoff[2 % U] + val_base, opoff[3 % U] + val_base};
-          *(lds_v4f *)(uintptr_t)(sb + 2048 + lane * 16) = v4f{o[0].x, o[0].y, o[1 % U].x, o[1 % U].y};
-          *(lds_v4f *)(uintptr_t)(sb + 3072 + lane * 16) = v4f{o[2 % U].x, o[2 % U].y, o[3 % U].x, o[3 % U].y};
-        } else if (U == 2) {
-          *(lds_v2u *)(uintptr_t)(sb + 1024 + lane * 8) = v2u{opoff[0] + val_base, opoff[1 % U] + val_base};
-          *(lds_v4f *)(uintptr_t)(sb + 2048 + lane * 16) = v4f{o[0].x, o[0].y, o[1 % U].x, o[1 % U].y};
-        } else {
-          *(lds_u32 *)(uintptr_t)(sb + 1024 + lane * 4) = opoff[0] + val_base;
-          *(lds_v2f *)(uintptr_t)(sb + 2048 + lane * 8) = o[0];
-        }
-        asm volatile("" ::: "memory");
-        *(volatile lds_u32 *)(uintptr_t)xl_a = (uint32_t)(t + 1);
-        return;
-      }
-      if (FULL) {
-        uint32_t oa[U];
-#pragma unroll
-        for (int j = 0; j < U; ++j) oa[j] = opoff[j] + val_base;
-        *(lds_u32 *)(uintptr_t)(sb + lane * 4) = ctl + val_base;
-        if (U == 4) *(lds_v4u *)(uintptr_t)(sb + 256 + lane * 16) = v4u{oa[0], oa[1 % U], oa[2 % U], oa[3 % U]};
-        else if (U == 2) *(lds_v2u *)(uintptr_t)(sb + 256 + lane * 8) = v2u{oa[0], oa[1 % U]};
-        else *(lds_u32 *)(uintptr_t)(sb + 256 + lane * 4) = oa[0];
-      }
       if (U == 4) {
         *(lds_v4f *)(uintptr_t)(sb + 256 + 1024 + lane * 16) = v4f{o[0].x, o[0].y, o[1 % U].x, o[1 % U].y};
         *(lds_v4f *)(uintptr_t)(sb + 256 + 2048 + lane * 16) = v4f{o[2 % U].x, o[2 % U].y, o[3 % U].x, o[3 % U].y};
@@ -968,8 +1112,6 @@ struct WeightWave {
       NFST_X_STEP(p1, g1, p0, g2) i -= 2;
     }
 #undef NFST_X_STEP
-    // every tile of this wave is there: a sweep that looks one tile past the end of its program never waits
-    if (FULL) *(volatile lds_u32 *)(uintptr_t)xl_a = 0x7fffffffu;
   }
 };
 
@@ -1396,7 +1538,13 @@ __device__ __forceinline__ void tile_sweep2(int n_tiles, const uint32_t *ring, i
   // the tile's arithmetic)
   auto margin_x = [](const v4u f) { return min(min((int)f.y - 1, (int)f.z - 2), (int)f.w - 3); };
   auto margin_y = [](const v4u f) { return (int)f.x - 4; };
+#ifdef NFST_PROF
+  int prof_waits = 0;  // times the sweep found a tile of the group not decoded yet (stamp slot prof_slot + 6)
+#endif
   auto wait_group = [&](int T, int which) {
+#ifdef NFST_PROF
+    ++prof_waits;
+#endif
     for (;;) {
       const v4u f = flags_now();
       if (__builtin_amdgcn_readfirstlane(which ? margin_y(f) : margin_x(f)) > T) break;
@@ -1460,6 +1608,9 @@ __device__ __forceinline__ void tile_sweep2(int n_tiles, const uint32_t *ring, i
       if (T + 2 < n_tiles) NFST_S2_STEP(2, da, db)
     }
   }
+#ifdef NFST_PROF
+  if (prof_slot >= 0 && (threadIdx.x & 63) == 0 && blockIdx.x < 4096) fb_prof[blockIdx.x * kProfSlots + prof_slot + 6] = (unsigned long long)prof_waits;
+#endif
 #undef NFST_S2_STEP
 }
 
@@ -1472,27 +1623,27 @@ __device__ __forceinline__ void run_weights(WeightWave<8, NE, XM, FULL, PREC> &x
                                             int lane) {
   const int *prog = flags;
   int *xland = flags + 4;
-  if constexpr (PREC) {
-    x8.run(ring, R, prog, xland, th, val, v2, trash, xc_base, xc_first, lane);
-    return;
-  }
-  if (F == 8 || FULL) {  // (tile waves run all-compact batches only)
-    x8.run(ring, R, prog, xland, th, val, v2, trash, xc_base, xc_first, lane);
+  (void)val; (void)v2; (void)trash;  // (the tile waves')
+  if constexpr (FULL) {  // (tile waves run all-compact batches only; the ring format is chosen here, once, not per tile)
+    if (PREC || v2) x8.template run_tiles<true>(ring, R, prog, xland, th, val, trash, xc_base, xc_first, lane);
+    else x8.template run_tiles<PREC>(ring, R, prog, xland, th, val, trash, xc_base, xc_first, lane);
+  } else if (F == 8) {
+    x8.run(ring, R, prog, xland, th, xc_base, xc_first, lane);
   } else if (F == 4) {
     WeightWave<4, NE, XM, FULL> x;
     x.start_maps(prog_words, perm, n_tiles, ex, ei, lane);
     x.start_gathers(lane);
-    x.run(ring, R, prog, xland, th, val, v2, trash, xc_base, xc_first, lane);
+    x.run(ring, R, prog, xland, th, xc_base, xc_first, lane);
   } else if (F == 2) {
     WeightWave<2, NE, XM, FULL> x;
     x.start_maps(prog_words, perm, n_tiles, ex, ei, lane);
     x.start_gathers(lane);
-    x.run(ring, R, prog, xland, th, val, v2, trash, xc_base, xc_first, lane);
+    x.run(ring, R, prog, xland, th, xc_base, xc_first, lane);
   } else {
     WeightWave<1, NE, XM, FULL> x;
     x.start_maps(prog_words, perm, n_tiles, ex, ei, lane);
     x.start_gathers(lane);
-    x.run(ring, R, prog, xland, th, val, v2, trash, xc_base, xc_first, lane);
+    x.run(ring, R, prog, xland, th, xc_base, xc_first, lane);
   }
 }
 

@@ -72,6 +72,8 @@
  *                                      and the arc posteriors given a string
  *   nfst_string_prefix / _next         the exact weight of all strings that start with a prefix, and of its extensions
  *                                      by every next symbol: prefix beam search with a bound on every completion
+ *   nfst_string_viterbi / _sample      the alignments of given strings: the best path that spells y with the arc that
+ *                                      emitted every symbol (forced alignment), and exact draws from p(path | x, y)
  *
  * Conventions
  *   - plain C: pointers and sizes only, no C++/torch types.
@@ -891,6 +893,62 @@ int nfst_string_next(const nfst_batch *lat, const nfst_scores *scores, const int
                      int32_t N /* row stride of prefixes */, const uint8_t *keep /* [vocab] or NULL */, int32_t marker /* -1: none */,
                      void *ws, int64_t ws_bytes, double *next /* [B,M,vocab] */, double *eos /* [B,M] */,
                      double *log_prefix /* [B,M] */, double *logz /* [B] */, int32_t *status, void *stream);
+
+/*
+ * Alignments to given strings (DESIGN.md sections 2 and 4.24).  Tape, scores, paths, candidates (strings [B, M, N],
+ * lengths [B, M]), the canonical order of the arcs and the workspace are nfst_string_logprob's.  A walk is in a state
+ * (s, j, f): lattice state, tokens of y already spelled, and (marker mode) "the arc into s was an active marker"; it
+ * starts at (0, 0, 0) and an out-arc a: s -> d, d != s, label l leads to the cell its term of G reads:
+ *   keep:    l not kept: (d, j);  l kept, j < n and y[j] == l: (d, j + 1), the arc emits position j;  otherwise nowhere
+ *   marker:  f == 0: (d, j, l == marker);  f == 1, j < n and y[j] == l: (d, j + 1, 0), the arc emits position j;
+ *            f == 1 otherwise nowhere
+ * and it ends at the sink, where the table leaves only j == n, f == 0.
+ *
+ * nfst_string_viterbi: V is G with max for the sum, V[sink][n] = 0, V[s][j] = max over the arcs of fl(w_a + V[cell of
+ * a]), float64, -inf without an arc.  score [B, M] is V0[0][0], -inf where no path of finite score spells y.  From every
+ * state the walk takes the first arc in canonical order whose term equals the state's cell.  Every output is a pure
+ * function of the inputs: the same bits as any restatement that forms w_a as nfst_string_logprob does.
+ *
+ * nfst_string_sample: K draws per (lattice, candidate) from p(path | x, y) = exp(score(path) - log_num) over the paths
+ * that spell y, behind the sweep of nfst_string_logprob as it is (log_num [B, M] and logz [B] have its bits).  At
+ * (s, j, f) arc a has the weight p_a = exp((w_a + G[cell of a]) - G_f[s][j]); the walk takes the first arc of positive
+ * weight whose running sum in canonical order exceeds u, and if rounding leaves none the last arc of positive weight
+ * (the rule of nfst_positional_sample; the running sum is an inclusive scan over 64 arcs at a time carried from chunk
+ * to chunk, so that a draw whose u lies within rounding of a boundary may differ from another order of summation).
+ * u is float32: step t of walk (b, m, k) reads uniforms[b, m, k, t] (uniforms [B, M, K, max_len], device), or without
+ * uniforms word t mod 4 of the Philox4x32-10 block keyed by seed at the counter (b, t / 4, m0 + m, k); m0 is the place
+ * of this call's first candidate among the caller's, so that a caller who slices the candidates gets the draws of one
+ * call.  score [B, M, K] is the float64 sum of the path's arc scores in path order, logq [B, M, K] = score - log_num.
+ *
+ * Both write per walk (one per candidate, or K): paths [.., max_len] int32 labels, pad-terminated; path_arcs the
+ * canonical arc ids, -1 padded; align the position of y that each arc emitted, -1 for none and beyond the path;
+ * out_lengths the arcs of the path.  A candidate that no path spells: length 0, pad, -1, score -inf, logq 0.  A lattice
+ * whose state 0 is the sink: the empty path of score 0 for the empty string, nothing for any other.
+ * A lengths[b, m] outside [0, N] is found on the device: *status = NFST_ERR_LENGTH (status: device, one word, zeroed by
+ * the caller), that candidate gets the empty answer and none of its tokens is read.  A path longer than max_len: the
+ * same status, the path is cut at max_len (a draw's score and logq still cover the whole path).
+ * ws: nfst_string_viterbi_ws_bytes and nfst_string_sample_ws_bytes are nfst_string_logprob_ws_bytes; the walks need no
+ * workspace.  LDS as nfst_string_logprob.
+ * M < 0, N < 1, K < 1, m0 < 0, max_len < 1, a bad tape, a null required pointer (every output is required) or a short
+ * workspace: NFST_ERR_ARG; N > NFST_EDIT_MAX_LEN or more than 2^31 - 1 walks: NFST_ERR_LIMIT; all on the host before
+ * any launch, outputs untouched.  n_lattices == 0 and M == 0 are successful no-ops that launch nothing and write nothing:
+ * with M == 0 nfst_string_sample leaves logz untouched too, unlike nfst_string_logprob, which computes log Z without
+ * candidates -- call that one for log Z alone.  nfst_string_viterbi has no K, m0, uniforms or seed: it walks once per
+ * candidate and reads no uniform.
+ */
+int64_t nfst_string_viterbi_ws_bytes(const nfst_batch *lat, int32_t M, int32_t N, int32_t marker_mode);
+int nfst_string_viterbi(const nfst_batch *lat, const nfst_scores *scores, const int32_t *strings, const int32_t *lengths, int32_t M,
+                        int32_t N /* row stride of strings */, const uint8_t *keep /* [vocab] or NULL */, int32_t marker /* -1: none */,
+                        int32_t max_len, int32_t pad, void *ws, int64_t ws_bytes, double *score /* [B,M] */,
+                        int32_t *paths /* [B,M,max_len] */, int32_t *path_arcs, int32_t *align, int32_t *out_lengths /* [B,M] */,
+                        int32_t *status, void *stream);
+int64_t nfst_string_sample_ws_bytes(const nfst_batch *lat, int32_t M, int32_t N, int32_t marker_mode);
+int nfst_string_sample(const nfst_batch *lat, const nfst_scores *scores, const int32_t *strings, const int32_t *lengths, int32_t M,
+                       int32_t N /* row stride of strings */, const uint8_t *keep /* [vocab] or NULL */, int32_t marker /* -1: none */,
+                       int32_t K, int32_t m0, const float *uniforms /* [B,M,K,max_len] or NULL */, uint64_t seed, int32_t max_len,
+                       int32_t pad, void *ws, int64_t ws_bytes, double *log_num /* [B,M] */, double *logz /* [B] */,
+                       double *score /* [B,M,K] */, double *logq /* [B,M,K] */, int32_t *paths /* [B,M,K,max_len] */,
+                       int32_t *path_arcs, int32_t *align, int32_t *out_lengths /* [B,M,K] */, int32_t *status, void *stream);
 
 /*
  * Arc slack, the max-plus counterpart of the arc posteriors, and beam masks (DESIGN.md sections 2 and 4.7).  A path

@@ -169,6 +169,11 @@ def _load():
         "nfst_string_prefix": (C.c_int, [BP, SP, vp, vp, i32, i32, vp, i32, vp, i64, vp, vp, vp, vp]),
         "nfst_string_next_ws_bytes": (i64, [BP, i32, i32, i32]),
         "nfst_string_next": (C.c_int, [BP, SP, vp, vp, i32, i32, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp]),
+        "nfst_string_viterbi_ws_bytes": (i64, [BP, i32, i32, i32]),
+        "nfst_string_viterbi": (C.c_int, [BP, SP, vp, vp, i32, i32, vp, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "nfst_string_sample_ws_bytes": (i64, [BP, i32, i32, i32]),
+        "nfst_string_sample": (C.c_int, [BP, SP, vp, vp, i32, i32, vp, i32, i32, i32, vp, u64, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp,
+                                         vp, vp, vp, vp]),
         "nfst_arc_slack_ws_bytes": (i64, [BP]),
         "nfst_arc_slack": (C.c_int, [BP, SP, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "nfst_intersect_ws_bytes": (i64, [BP, i32]),

@@ -45,6 +45,7 @@ using namespace nfst_tile;
 #include "lattice_edit_kernels.h"
 #include "string_merge_kernels.h"
 #include "string_logprob_kernels.h"
+#include "string_align_kernels.h"
 #include "string_logprob_grad_kernels.h"
 #include "string_prefix_kernels.h"
 #include "slack_kernels.h"
@@ -1116,6 +1117,19 @@ static int sl_check_sizes(int32_t M, int32_t N) {
   return N > kEditMaxLen ? NFST_ERR_LIMIT : NFST_OK;
 }
 
+// the launch shape that the sum sweep and the max sweep (string_align_kernels.h) share: the LDS of the level pass and of
+// the sweep, and the grid -- the candidates of a lattice are dealt to as many workgroups as fill the device about twice
+// (any number gives the same bits)
+struct SlPlan {
+  int64_t lds_lev, lds_sweep;
+  dim3 grid;
+};
+static SlPlan sl_plan(const nfst_batch *lat, int32_t M) {
+  const int64_t want = (2 * (int64_t)cu_count() + lat->n_lattices - 1) / lat->n_lattices;
+  const int Y = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(M, want), 65535));
+  return {(int64_t)lat->max_rows * 12 + 16, ((int64_t)lat->max_rows * 2 + 1) * 4, dim3(lat->n_lattices, Y)};
+}
+
 int64_t nfst_string_logprob_ws_bytes(const nfst_batch *lat, int32_t M, int32_t N, int32_t marker_mode) {
   if (!lat) return NFST_ERR_ARG;
   int rc = sl_check_sizes(M, N);
@@ -1138,21 +1152,100 @@ int nfst_string_logprob(const nfst_batch *lat, const nfst_scores *scores, const 
   if (!logz || (M > 0 && (!strings || !lengths || !log_num))) return NFST_ERR_ARG;
   const int planes = marker >= 0 ? 2 : 1;
   if (!ws || ((uintptr_t)ws & 15) || ws_bytes < sl_ws_layout(lat, M, N, planes, nullptr, nullptr)) return NFST_ERR_ARG;
-  const int64_t lds_lev = (int64_t)lat->max_rows * 12 + 16;
-  const int64_t lds_sweep = ((int64_t)lat->max_rows * 2 + 1) * 4;
-  if (lds_lev > kMaxLds || lds_sweep > kMaxLds) return NFST_ERR_LIMIT;
+  const SlPlan p = sl_plan(lat, M);
+  if (p.lds_lev > kMaxLds || p.lds_sweep > kMaxLds) return NFST_ERR_LIMIT;
   SlWs w;
   sl_ws_layout(lat, M, N, planes, (char *)ws, &w);
   const KbWs lw{nullptr, w.order, w.lev, w.n_lev};  // (k_kbest_levels writes the level arrays only)
   const SlIn in{strings, lengths, (int)M, (int)N, keep, (int)marker};
   const hipStream_t st = (hipStream_t)stream;
-  // the candidates of a lattice are dealt to as many workgroups as fill the device about twice (any number gives the same bits)
-  const int64_t want = (2 * (int64_t)cu_count() + lat->n_lattices - 1) / lat->n_lattices;
-  const int Y = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(M, want), 65535));
-  if ((rc = launch(k_kbest_levels, dim3(lat->n_lattices), dim3(kKbLevelThreads), lds_lev, st, *lat, lw))) return rc;
-  const dim3 grid(lat->n_lattices, Y);
-  if (marker >= 0) return launch(k_string_logprob<true>, grid, dim3(kSlThreads), lds_sweep, st, *lat, *scores, in, w, log_num, logz, status);
-  return launch(k_string_logprob<false>, grid, dim3(kSlThreads), lds_sweep, st, *lat, *scores, in, w, log_num, logz, status);
+  if ((rc = launch(k_kbest_levels, dim3(lat->n_lattices), dim3(kKbLevelThreads), p.lds_lev, st, *lat, lw))) return rc;
+  if (marker >= 0) return launch(k_string_logprob<true>, p.grid, dim3(kSlThreads), p.lds_sweep, st, *lat, *scores, in, w, log_num, logz, status);
+  return launch(k_string_logprob<false>, p.grid, dim3(kSlThreads), p.lds_sweep, st, *lat, *scores, in, w, log_num, logz, status);
+}
+
+// ------------------------------------------------------------------ alignments to given strings (string_align_kernels.h)
+// both ops sweep in the workspace of nfst_string_logprob; the walk needs none of its own
+int64_t nfst_string_viterbi_ws_bytes(const nfst_batch *lat, int32_t M, int32_t N, int32_t marker_mode) {
+  return nfst_string_logprob_ws_bytes(lat, M, N, marker_mode);
+}
+int64_t nfst_string_sample_ws_bytes(const nfst_batch *lat, int32_t M, int32_t N, int32_t marker_mode) {
+  return nfst_string_logprob_ws_bytes(lat, M, N, marker_mode);
+}
+
+// the host checks of both entry points, in nfst_string_logprob's order; NFST_OK with *noop set: nothing to launch
+static int sa_check(const nfst_batch *lat, const nfst_scores *scores, const int32_t *strings, const int32_t *lengths, int32_t M, int32_t N,
+                    const uint8_t *keep, int32_t marker, int32_t K, int32_t m0, int32_t max_len, const void *ws, int64_t ws_bytes,
+                    const SaOut &o, bool sample, bool *noop) {
+  *noop = true;
+  if (!lat || !o.status || K < 1 || m0 < 0 || max_len < 1) return NFST_ERR_ARG;
+  int rc = sl_check_sizes(M, N);
+  if (rc) return rc;
+  if ((rc = tape_check(keep, marker, lat->vocab, true))) return rc;
+  if (lat->n_lattices == 0 || M == 0) return NFST_OK;
+  if ((rc = check_batch(lat))) return rc;
+  if ((rc = check_scores(lat, scores))) return rc;
+  if (!strings || !lengths || !o.paths || !o.path_arcs || !o.align || !o.lengths || !o.score || (sample && !o.logq)) return NFST_ERR_ARG;
+  if (!ws || ((uintptr_t)ws & 15) || ws_bytes < sl_ws_layout(lat, M, N, marker >= 0 ? 2 : 1, nullptr, nullptr)) return NFST_ERR_ARG;
+  if ((int64_t)lat->n_lattices * M * K > INT32_MAX || (int64_t)m0 + M > INT32_MAX) return NFST_ERR_LIMIT;
+  const SlPlan p = sl_plan(lat, M);
+  if (p.lds_lev > kMaxLds || p.lds_sweep > kMaxLds) return NFST_ERR_LIMIT;
+  *noop = false;
+  return NFST_OK;
+}
+
+static int sa_launch_walk(const nfst_batch *lat, const nfst_scores *scores, const SlIn &in, const SlWs &w, const SaWalk &wk, const SaOut &o,
+                          bool sample, hipStream_t st) {
+  const int64_t walks = (int64_t)lat->n_lattices * in.M * wk.K;
+  const dim3 grid((unsigned)((walks + kSaWalkWaves - 1) / kSaWalkWaves)), block(kSaWalkWaves * 64);
+  if (sample) {
+    if (in.marker >= 0) return launch(k_string_walk<true, true>, grid, block, 0, st, *lat, *scores, in, w, wk, o);
+    return launch(k_string_walk<false, true>, grid, block, 0, st, *lat, *scores, in, w, wk, o);
+  }
+  if (in.marker >= 0) return launch(k_string_walk<true, false>, grid, block, 0, st, *lat, *scores, in, w, wk, o);
+  return launch(k_string_walk<false, false>, grid, block, 0, st, *lat, *scores, in, w, wk, o);
+}
+
+// k_kbest_levels, the max sweep on the grid of nfst_string_logprob, then one wave per candidate
+int nfst_string_viterbi(const nfst_batch *lat, const nfst_scores *scores, const int32_t *strings, const int32_t *lengths, int32_t M,
+                        int32_t N, const uint8_t *keep, int32_t marker, int32_t max_len, int32_t pad, void *ws, int64_t ws_bytes,
+                        double *score, int32_t *paths, int32_t *path_arcs, int32_t *align, int32_t *out_lengths, int32_t *status,
+                        void *stream) {
+  const SaOut o{paths, path_arcs, align, out_lengths, score, nullptr, status};
+  bool noop;
+  int rc = sa_check(lat, scores, strings, lengths, M, N, keep, marker, 1, 0, max_len, ws, ws_bytes, o, false, &noop);
+  if (rc || noop) return rc;
+  const SlPlan p = sl_plan(lat, M);  // (the grid and the LDS of nfst_string_logprob)
+  SlWs w;
+  sl_ws_layout(lat, M, N, marker >= 0 ? 2 : 1, (char *)ws, &w);
+  const KbWs lw{nullptr, w.order, w.lev, w.n_lev};  // (k_kbest_levels writes the level arrays only)
+  const SlIn in{strings, lengths, (int)M, (int)N, keep, (int)marker};
+  const hipStream_t st = (hipStream_t)stream;
+  if ((rc = launch(k_kbest_levels, dim3(lat->n_lattices), dim3(kKbLevelThreads), p.lds_lev, st, *lat, lw))) return rc;
+  rc = marker >= 0 ? launch(k_string_viterbi_sweep<true>, p.grid, dim3(kSlThreads), p.lds_sweep, st, *lat, *scores, in, w)
+                   : launch(k_string_viterbi_sweep<false>, p.grid, dim3(kSlThreads), p.lds_sweep, st, *lat, *scores, in, w);
+  if (rc) return rc;
+  const SaWalk wk{1, 0, nullptr, 0, (int)max_len, (int)pad};
+  return sa_launch_walk(lat, scores, in, w, wk, o, false, st);
+}
+
+// nfst_string_logprob as it is (the table, log_num and logz have its bits), then one wave per draw
+int nfst_string_sample(const nfst_batch *lat, const nfst_scores *scores, const int32_t *strings, const int32_t *lengths, int32_t M,
+                       int32_t N, const uint8_t *keep, int32_t marker, int32_t K, int32_t m0, const float *uniforms, uint64_t seed,
+                       int32_t max_len, int32_t pad, void *ws, int64_t ws_bytes, double *log_num, double *logz, double *score,
+                       double *logq, int32_t *paths, int32_t *path_arcs, int32_t *align, int32_t *out_lengths, int32_t *status,
+                       void *stream) {
+  const SaOut o{paths, path_arcs, align, out_lengths, score, logq, status};
+  bool noop;
+  int rc = sa_check(lat, scores, strings, lengths, M, N, keep, marker, K, m0, max_len, ws, ws_bytes, o, true, &noop);
+  if (rc || noop) return rc;
+  if (!log_num || !logz) return NFST_ERR_ARG;
+  if ((rc = nfst_string_logprob(lat, scores, strings, lengths, M, N, keep, marker, ws, ws_bytes, log_num, logz, status, stream))) return rc;
+  SlWs w;
+  sl_ws_layout(lat, M, N, marker >= 0 ? 2 : 1, (char *)ws, &w);
+  const SlIn in{strings, lengths, (int)M, (int)N, keep, (int)marker};
+  const SaWalk wk{(int)K, (int)m0, uniforms, seed, (int)max_len, (int)pad};
+  return sa_launch_walk(lat, scores, in, w, wk, o, true, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------ gradients of the string weights (string_logprob_grad_kernels.h)

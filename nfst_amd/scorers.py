@@ -200,6 +200,28 @@ class LatticeScorer(torch.nn.Module):
         tape = dict(keep=kw.pop("keep")) if kw.get("keep") is not None else dict(marker=marker)
         return prefix_search(self._lat(), self.theta.detach(), k, pad=self.__pad__, **tape, **kw)
 
+    def align(self, strings: torch.Tensor, lengths: torch.Tensor, marker: Optional[int] = 4, **kw) -> list:
+        """Forced alignment under ``theta``: per lattice a list with one ``(score, marks, align)`` per candidate string
+        ``strings[b, m, :lengths[b, m]]`` -- the score of the best path that spells it, that path's marks and, per mark,
+        the position of the string it emitted or -1 (``ops.string_viterbi``).  The tape is ``marker`` (default: the output
+        mark 4) or ``keep=`` a set of labels; ``kw`` also takes ``max_len``.  A string that no path spells gives
+        ``(-inf, [], [])``."""
+        tape = dict(keep=kw.pop("keep")) if kw.get("keep") is not None else dict(marker=marker)
+        kw.pop("keep", None)
+        r = ops.string_viterbi(self._lat(), self.theta.detach(), strings, lengths, pad=self.__pad__, **tape, **kw)
+        score, marks, al, lens = (x.cpu().numpy() for x in (r.score, r.paths, r.align, r.lengths))
+        return [[(float(score[b, m]), marks[b, m, :lens[b, m]].tolist(), al[b, m, :lens[b, m]].tolist()) for m in range(score.shape[1])]
+                for b in range(score.shape[0])]
+
+    def sample_alignments(self, strings: torch.Tensor, lengths: torch.Tensor, k: int, marker: Optional[int] = 4, **kw):
+        """``k`` exact draws per lattice and candidate string from p(path | x, y) under ``theta``, each with its exact
+        log-probability: ``ops.StringSampleResult`` (``ops.string_sample_paths``; ``kw``: ``keep`` in place of ``marker``,
+        ``uniforms``, ``seed``, ``max_len``).  No gradient."""
+        tape = dict(keep=kw.pop("keep")) if kw.get("keep") is not None else dict(marker=marker)
+        kw.pop("keep", None)
+        kw.setdefault("pad", self.__pad__)
+        return ops.string_sample_paths(self._lat(), self.theta.detach(), strings, lengths, k, **tape, **kw)
+
     def string_nll(self, strings: torch.Tensor, lengths: torch.Tensor, **kw) -> torch.Tensor:
         """The maximum-likelihood loss on strings: the mean over the batch of -log p(y | x), y = ``strings[b, 0,
         :lengths[b, 0]]`` the one reference string of lattice b (``strings`` [B, 1, N]; ``kw``: ``keep`` or ``marker``),

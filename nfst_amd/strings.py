@@ -4,7 +4,9 @@ given as ``keep`` (a set of labels: the path's labels that belong to it, ``WideD
 ``marker`` (the labels that directly follow an arc labelled ``marker``, ``WideDFA.marked_sequence``'s meaning).
 ``ops.merge_paths``, ``ops.string_log_prob``, ``ops.string_arc_posteriors``, ``ops.string_prefix_log_prob`` and
 ``ops.string_next_log_probs`` are these functions; ``decoders.decode_strings`` puts the first two together and
-``decoders.prefix_search`` searches with the last.
+``decoders.prefix_search`` searches with the last.  ``ops.string_viterbi`` and ``ops.string_sample_paths``
+(``nfst_string_viterbi``, ``nfst_string_sample``; section 4.24) hand back the alignments of given strings, the best one and
+exact draws, and ``ops.string_alignment_log_prob`` scores given alignments with a gradient.
 There is no CPU implementation.
 """
 from __future__ import annotations
@@ -332,6 +334,218 @@ def string_log_prob(lat, theta, strings: torch.Tensor, lengths: torch.Tensor, *,
         out = _StringScoresWithOffsets(*out)
         out.arc_offsets = arc_offsets
     return out
+
+
+# ----------------------------------------------------------------------------- alignments
+class StringAlignment(NamedTuple):
+    score: torch.Tensor    # [B, M] float64: the score of the best path that spells the string (-inf: none does)
+    paths: torch.Tensor    # [B, M, L] int32 labels, pad-terminated
+    arcs: torch.Tensor     # [B, M, L] int32 canonical arc ids, -1 padded
+    align: torch.Tensor    # [B, M, L] int32: the position of the string that the arc emitted, -1: none
+    lengths: torch.Tensor  # [B, M] int32 arcs of the path
+
+
+class StringSampleResult(NamedTuple):
+    paths: torch.Tensor    # [B, M, K, L] int32 labels, pad-terminated
+    arcs: torch.Tensor     # [B, M, K, L] int32 canonical arc ids, -1 padded
+    align: torch.Tensor    # [B, M, K, L] int32: the position of the string that the arc emitted, -1: none
+    lengths: torch.Tensor  # [B, M, K] int32
+    score: torch.Tensor    # [B, M, K] float64: the sum of the path's arc scores (-inf: no path spells the string)
+    logq: torch.Tensor     # [B, M, K] float64 = score - log_num: the draw's exact log p(path | x, y) (0 without a path)
+    log_num: torch.Tensor  # [B, M] float64: ``string_log_prob``'s, bit for bit
+    logz: torch.Tensor     # [B] float64: ``string_log_prob``'s, bit for bit
+
+
+def _walk_outputs(dev, lead: tuple, L: int) -> tuple:
+    """``(paths, arcs, align [*lead, L], lengths [*lead])`` int32, uninitialised"""
+    i32 = torch.int32
+    return (torch.empty((*lead, L), dtype=i32, device=dev), torch.empty((*lead, L), dtype=i32, device=dev),
+            torch.empty((*lead, L), dtype=i32, device=dev), torch.empty(lead, dtype=i32, device=dev))
+
+
+def _viterbi_launches(c: _Candidates, sc, max_len: int, pad: int) -> StringAlignment:
+    """``nfst_string_viterbi`` slice by slice, then the status word (no autograd)"""
+    from .ops import _call, _raise_status
+
+    lat, dev = c.lat, c.lat.device
+    B, M, N = c.rows.shape
+    score = torch.empty((B, M), dtype=torch.float64, device=dev)
+    outs = _walk_outputs(dev, (B, M), max_len)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = c.workspace("nfst_string_viterbi_ws_bytes") if M else None
+    for m0, m1 in c.slices() if M else ():
+        whole = (m0, m1) == (0, M)
+        part = (score, *outs) if whole else (torch.empty((B, m1 - m0), dtype=torch.float64, device=dev), *_walk_outputs(dev, (B, m1 - m0), max_len))
+        _call("nfst_string_viterbi", lat, sc, c.rows[:, m0:m1].contiguous(), c.lens[:, m0:m1].contiguous(), m1 - m0, N, c.keep_mask,
+              c.marker, int(max_len), int(pad), ws, ws.numel(), part[0], part[1], part[2], part[3], part[4], status)
+        if not whole:
+            for o, q in zip((score, *outs), part):
+                o[:, m0:m1] = q
+    if B * M:
+        _raise_status(status, "nfst_string_viterbi")  # a candidate's length outside its row, or a path longer than max_len
+    return StringAlignment(score, *outs)
+
+
+class _StringViterbi(torch.autograd.Function):
+    """score[b, m] = the sum of the scores of the best path's arcs: the gradients of ``_LatticeEdit``, one path per candidate."""
+
+    @staticmethod
+    def forward(ctx, c, theta, arc_scores, max_len, pad):
+        from .ops import _det, _scores
+
+        sc, alive = _scores(c.lat, theta.detach(), _det(arc_scores))
+        r = _viterbi_launches(c, sc, max_len, pad)
+        del alive
+        ctx.lat = c.lat
+        ctx.like = (theta, arc_scores)
+        ctx.save_for_backward(r.arcs)
+        ctx.mark_non_differentiable(r.paths, r.arcs, r.align, r.lengths)
+        return tuple(r)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, *_):
+        from .ops import _path_score_grads
+
+        (arcs,) = ctx.saved_tensors
+        nt, na = ctx.needs_input_grad[1:3]
+        theta, arc_scores = ctx.like
+        d_theta, d_arc, _ = _path_score_grads(ctx.lat, arcs, g, theta if nt else None, arc_scores if na else None)
+        return None, d_theta, d_arc, None, None
+
+
+def string_viterbi(lat, theta, strings: torch.Tensor, lengths: torch.Tensor, *, keep=None, marker: Optional[int] = None,
+                   arc_scores=None, max_len: Optional[int] = None, pad: int = 0, max_workspace_bytes: int = 1 << 30) -> StringAlignment:
+    """Forced alignment (``nfst_string_viterbi``; DESIGN.md sections 2 and 4.24): for lattice b and candidate m, the path
+    of the greatest score among those whose projection onto the tape ``keep`` or ``marker`` is y = ``strings[b, m,
+    :lengths[b, m]]``, from the lattice alone -- no product, float64, any number of paths.  Candidates, tape, scores,
+    slicing under ``max_workspace_bytes`` and the length error are ``string_log_prob``'s.  ``score`` [B, M] float64 is
+    that path's score, ``paths`` its labels (``pad``-terminated), ``arcs`` its canonical arc ids (-1 padded), ``align``
+    the position of y that each arc emitted (-1: none) and ``lengths`` its arcs, all [B, M, max_len] / [B, M]; among
+    paths of equal score the one that takes the earlier arc in canonical order at the first difference.  Every output is
+    a pure function of the inputs: the same bits at every launch, packing and slicing.  A string that no path of finite
+    score spells gets score -inf, length 0, ``pad`` labels and ``align`` -1, which is no error.  ``max_len`` defaults to
+    the longest path + 1; a longer path, or a length outside [0, N], raises ``NfstError`` (NFST_ERR_LENGTH) after the
+    launch.  ``score`` is differentiable in ``theta`` and ``arc_scores``: the gradient counts the path's labels / marks
+    its arcs (float32, as ``lattice_edit_distance``'s); candidates of score -inf pass nothing back."""
+    from .ops import _max_len, _scores
+
+    c = _candidates(lat, strings, lengths, keep, marker, max_workspace_bytes, "nfst_string_viterbi_ws_bytes")
+    if not isinstance(theta, torch.Tensor):
+        theta = torch.as_tensor(theta, dtype=torch.float32)
+    max_len = int(_max_len(lat, max_len))
+    if max_len < 1:
+        raise ValueError("max_len must be at least 1")
+    if torch.is_grad_enabled() and (theta.requires_grad or (isinstance(arc_scores, torch.Tensor) and arc_scores.requires_grad)):
+        return StringAlignment(*_StringViterbi.apply(c, theta, arc_scores, max_len, int(pad)))
+    sc, alive = _scores(lat, theta.detach(), None if arc_scores is None else arc_scores.detach())
+    out = _viterbi_launches(c, sc, max_len, int(pad))
+    del alive
+    return out
+
+
+def string_sample_paths(lat, theta, strings: torch.Tensor, lengths: torch.Tensor, k: int, *, keep=None, marker: Optional[int] = None,
+                        arc_scores=None, uniforms: Optional[torch.Tensor] = None, seed: int = 0, max_len: Optional[int] = None,
+                        pad: int = 0, max_workspace_bytes: int = 1 << 30) -> StringSampleResult:
+    """``k`` exact draws per lattice and candidate from p(path | x, y), proportional to exp(score) over the paths whose
+    projection onto the tape is y = ``strings[b, m, :lengths[b, m]]`` (``nfst_string_sample``; DESIGN.md sections 2 and
+    4.24): the proposal over the alignments of a given string, for M candidates at once from the one lattice.
+    Candidates, tape, scores, slicing under ``max_workspace_bytes`` and the length error are ``string_log_prob``'s, and
+    ``log_num`` / ``logz`` are its results, bit for bit.  Per draw: ``paths``, ``arcs``, ``align`` [B, M, k, max_len] and
+    ``lengths`` [B, M, k] as ``string_viterbi``'s, ``score`` the float64 sum of the path's arc scores and ``logq`` =
+    ``score - log_num``, the draw's exact log-probability.  ``uniforms`` [B, M, k, max_len] float32 in [0, 1) decide the
+    walks (walk (b, m, j) reads its own row only; the rule is ``positional_sample_paths``'s); without them Philox4x32-10
+    keyed by ``seed`` and the walk (b, m, j), whatever the slicing.  A string that no path spells gets length 0, ``pad``
+    labels, score -inf and ``logq`` 0.  ``max_len`` defaults to the longest path + 1; a longer path raises ``NfstError``
+    (NFST_ERR_LENGTH) after the launch.  Not differentiable (``string_alignment_log_prob`` scores given draws with a
+    gradient)."""
+    from .ops import _call, _check_k, _max_len, _raise_status, _scores
+
+    _check_k(k, bounded=False)
+    c = _candidates(lat, strings, lengths, keep, marker, max_workspace_bytes, "nfst_string_sample_ws_bytes")
+    if not isinstance(theta, torch.Tensor):
+        theta = torch.as_tensor(theta, dtype=torch.float32)
+    max_len = int(_max_len(lat, max_len))
+    if max_len < 1:
+        raise ValueError("max_len must be at least 1")
+    dev, f64 = lat.device, torch.float64
+    B, M, N = c.rows.shape
+    if uniforms is not None:
+        if not isinstance(uniforms, torch.Tensor) or tuple(uniforms.shape) != (B, M, k, max_len):
+            raise ValueError(f"uniforms must be a tensor of shape [{B}, {M}, {k}, {max_len}]")
+        uniforms = uniforms.detach().to(device=dev, dtype=torch.float32).contiguous()
+    sc, alive = _scores(lat, theta.detach(), None if arc_scores is None else arc_scores.detach())
+    shapes = [((B, M), f64), ((B, M, k), f64), ((B, M, k), f64)]  # log_num, score, logq
+
+    def outputs(m):
+        return [torch.empty((B, m) + sh[2:], dtype=dt, device=dev) for sh, dt in shapes] + list(_walk_outputs(dev, (B, m, k), max_len))
+
+    outs = outputs(M)
+    logz = torch.empty(B, dtype=f64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    seed64 = C.c_uint64(seed & (2 ** 64 - 1))
+    ws = c.workspace("nfst_string_sample_ws_bytes") if M else c.workspace("nfst_string_logprob_ws_bytes")
+    if M == 0:  # no candidate: log Z alone
+        _call("nfst_string_logprob", lat, sc, None, None, 0, N, c.keep_mask, c.marker, ws, ws.numel(), None, logz, status)
+    for m0, m1 in c.slices() if M else ():
+        whole = (m0, m1) == (0, M)
+        part = outs if whole else outputs(m1 - m0)
+        log_num, score, logq, paths, arcs, align, lens = part
+        _call("nfst_string_sample", lat, sc, c.rows[:, m0:m1].contiguous(), c.lens[:, m0:m1].contiguous(), m1 - m0, N, c.keep_mask,
+              c.marker, int(k), m0, None if uniforms is None else uniforms[:, m0:m1].contiguous(), seed64, max_len, int(pad), ws,
+              ws.numel(), log_num, logz, score, logq, paths, arcs, align, lens, status)
+        if not whole:
+            for o, q in zip(outs, part):
+                o[:, m0:m1] = q
+    if B:
+        _raise_status(status, "nfst_string_sample")  # a candidate's length outside its row, or a path longer than max_len
+    del alive
+    log_num, score, logq, paths, arcs, align, lens = outs
+    return StringSampleResult(paths, arcs, align, lens, score, logq, log_num, logz)
+
+
+def string_alignment_log_prob(lat, theta, strings: torch.Tensor, lengths: torch.Tensor, arcs: torch.Tensor, path_lengths: torch.Tensor, *,
+                              keep=None, marker: Optional[int] = None, arc_scores=None) -> torch.Tensor:
+    """log p(path | x, y) float64 [B, M, K] of given alignments, differentiable in ``theta`` and ``arc_scores``: the sum
+    of the float64 scores (theta[label] + the table's weight + ``arc_scores``) of ``arcs[b, m, j, :path_lengths[b, m,
+    j]]`` (canonical arc ids [B, M, K, L], as ``string_sample_paths`` returns them) less ``string_log_prob(...).log_num``
+    of candidate m -- what a score-function estimator over drawn alignments needs, in the role of ``swor.log_prob``.  It
+    equals the draws' ``logq`` up to the order of the sum.  Composed from ``string_log_prob`` and a gather: no kernel of
+    its own.  An entry with ``path_lengths`` 0 under a string that no path spells is 0, as the draws' ``logq``; the
+    caller answers for the paths spelling their strings."""
+    from .ops import _need_gpu
+
+    _need_gpu(lat)
+    B = lat.n_lattices
+    if not isinstance(arcs, torch.Tensor) or arcs.dim() != 4 or arcs.shape[0] != B or arcs.is_floating_point():
+        raise ValueError(f"arcs must be an integer tensor [{B}, M, K, L]")
+    _, M, K, L = arcs.shape
+    if not isinstance(strings, torch.Tensor) or strings.dim() != 3 or strings.shape[1] != M:
+        raise ValueError(f"strings must be [{B}, {M}, N]: one candidate per row of arcs")
+    if not isinstance(path_lengths, torch.Tensor) or tuple(path_lengths.shape) != (B, M, K) or path_lengths.is_floating_point():
+        raise ValueError(f"path_lengths must be an integer tensor [{B}, {M}, {K}]")
+    if not isinstance(theta, torch.Tensor):
+        theta = torch.as_tensor(theta, dtype=torch.float32)
+    dev, f64 = lat.device, torch.float64
+    log_num = string_log_prob(lat, theta, strings, lengths, keep=keep, marker=marker, arc_scores=arc_scores).log_num
+    a = arcs.to(device=dev, dtype=torch.int64)
+    on = (torch.arange(L, device=dev) < path_lengths.to(dev)[..., None]) & (a >= 0)
+    idx = a.clamp(min=0)
+    lab = lat.arc_label.to(torch.int64)[idx]
+    th = theta.to(device=dev, dtype=f64)
+    if th.dim() == 2:
+        b_of = torch.arange(B, device=dev).view(B, 1, 1, 1).expand_as(lab)
+        term = th[b_of, lab]
+    else:
+        term = th[lab]
+    if lat.weighted:
+        term = term + lat.arc_w.to(f64)[idx]
+    if arc_scores is not None:
+        a64 = arc_scores.to(device=dev, dtype=f64)  # (the kernels read float32; the gradient does not pass through the rounding)
+        term = term + (a64 + (a64.detach().to(torch.float32).to(f64) - a64.detach()))[idx]
+    score = torch.where(on, term, torch.zeros_like(term)).sum(dim=-1)
+    has = torch.isfinite(log_num)[..., None]
+    return torch.where(has, score - torch.where(has, log_num[..., None], torch.zeros_like(score)), score)
 
 
 # ----------------------------------------------------------------------------- prefixes

@@ -895,6 +895,65 @@ int nfst_string_next(const nfst_batch *lat, const nfst_scores *scores, const int
                      double *log_prefix /* [B,M] */, double *logz /* [B] */, int32_t *status, void *stream);
 
 /*
+ * Prefix states (DESIGN.md sections 2 and 4.25): nfst_string_next's answers for prefixes that grow by one symbol per call,
+ * at the cost of one column of F per symbol instead of the whole table.  Tape, scores, paths and the canonical order of
+ * the arcs are nfst_string_logprob's.
+ *
+ * nfst_string_prefix_open does once what depends on the lattice and the scores but on no prefix, with the kernels of
+ * nfst_string_next in this order: the level pass, nfst_string_prefix's sweep on the empty prefix (z, zn0 / zn1 and
+ * logz [B], which has nfst_string_logprob's bits), the in-arc lists, az (the prefix sweep without a candidate), the label
+ * lists.  Its workspace is the context that the other calls read (with the same lattice, scores and tape; it must be
+ * opened again when any of them changes): nfst_string_prefix_open_ws_bytes(lat, marker >= 0) is nfst_string_next_ws_bytes
+ * without the table F -- 8 (planes + 2) + 12 bytes per row, 12 bytes per arc and 4 vocab + 24 bytes per lattice, every part
+ * rounded up to 256.  LDS: nfst_string_next's; more than 160 KiB returns NFST_ERR_LIMIT.
+ *
+ * A state holds one column of F (marker mode: of F0 and F1) for M hypotheses of every lattice, float64: the cell of row r
+ * of lattice b (row_off[b] + r in the batch), plane p and hypothesis m lies at ((row_off[b] + r) planes + p) M + m, so
+ * the hypotheses of one state are adjacent.  nfst_string_prefix_state_bytes(lat, M, marker >= 0) = 8 planes M total_rows
+ * rounded up to 256 (planes = 2 in marker mode, else 1).  Rows that state 0 does not reach are never written and never
+ * read.  A state is opaque to the caller, 16-byte aligned, and belongs to the context it was made with.
+ *
+ * nfst_string_prefix_extend forms, for lattice b and child slot m < M_out, the column of the prefix that is one symbol,
+ * symbol[b, m], longer than the prefix of slot parent[b, m] of parent_state (M_in slots):
+ *   parent == -2   the empty prefix (column 0: F0[state 0] = 0, F1 = -inf, and the arcs that are not on the tape / no
+ *                  markers carry it forward); the symbol is not read.  With no parent >= 0 anywhere parent_state may be
+ *                  null and M_in 0
+ *   parent == -1   a dead slot: every cell is -inf
+ * The recurrence and the order of every cell's sum are those of nfst_string_logprob_grad's table F at column n + 1: a
+ * running log-sum around the greatest term so far over the in-arcs of the state (source reached from state 0, no self
+ * loop) in ascending canonical arc id, one term per in-arc, in marker mode the F0 term before the F1 term into F0.  A
+ * child's column therefore has the bits of column n + 1 of that table for the same prefix.  Children are independent of
+ * one another and several may share a parent; the bits do not depend on M_in, M_out, the slots or the launch.  A parent
+ * outside [-2, M_in), or a symbol outside [0, vocab) in a slot with parent >= 0, is found on the device: *status =
+ * NFST_ERR_INDEX (status: device, one word, zeroed by the caller), that slot is dead and the others are computed as usual.
+ * A symbol that is off the tape, or that no path spells after the parent, gives -inf cells, never NaN, and no error.
+ * LDS: 8 max_rows + 4 bytes.
+ *
+ * nfst_string_prefix_state_next gives next [B, M, vocab], eos [B, M] and log_prefix [B, M] of nfst_string_next, formed
+ * from the state's column in place of F[.][n] with the same terms in the same order: bit for bit nfst_string_next's
+ * outputs for the same prefixes.  A dead slot gives -inf everywhere.  logz is nfst_string_prefix_open's.
+ *
+ * On the host before any launch, outputs untouched: a bad tape, null required pointers (parent_state only when M_in == 0),
+ * a context, a state or an output state shorter than its _bytes query says, a misaligned buffer, a negative M, or an
+ * out_state that overlaps parent_state: NFST_ERR_ARG; M, M_in or M_out above 1024 or more than 160 KiB of LDS:
+ * NFST_ERR_LIMIT.  n_lattices == 0, M_out == 0 and M == 0 are successful no-ops (n_lattices == 0: the _bytes queries
+ * return 0).
+ */
+int64_t nfst_string_prefix_open_ws_bytes(const nfst_batch *lat, int32_t marker_mode);
+int nfst_string_prefix_open(const nfst_batch *lat, const nfst_scores *scores, const uint8_t *keep /* [vocab] or NULL */,
+                            int32_t marker /* -1: none */, void *ws, int64_t ws_bytes, double *logz /* [B] */, int32_t *status,
+                            void *stream);
+int64_t nfst_string_prefix_state_bytes(const nfst_batch *lat, int32_t M, int32_t marker_mode);
+int nfst_string_prefix_extend(const nfst_batch *lat, const nfst_scores *scores, const uint8_t *keep, int32_t marker, const void *ctx_ws,
+                              int64_t ctx_bytes, const double *parent_state, int64_t parent_bytes, int32_t M_in,
+                              const int32_t *parent /* [B,M_out] */, const int32_t *symbol /* [B,M_out] */, double *out_state,
+                              int64_t out_bytes, int32_t M_out, int32_t *status, void *stream);
+int nfst_string_prefix_state_next(const nfst_batch *lat, const nfst_scores *scores, const uint8_t *keep, int32_t marker,
+                                  const void *ctx_ws, int64_t ctx_bytes, const double *state, int64_t state_bytes, int32_t M,
+                                  double *next /* [B,M,vocab] */, double *eos /* [B,M] */, double *log_prefix /* [B,M] */,
+                                  int32_t *status, void *stream);
+
+/*
  * Alignments to given strings (DESIGN.md sections 2 and 4.24).  Tape, scores, paths, candidates (strings [B, M, N],
  * lengths [B, M]), the canonical order of the arcs and the workspace are nfst_string_logprob's.  A walk is in a state
  * (s, j, f): lattice state, tokens of y already spelled, and (marker mode) "the arc into s was an active marker"; it

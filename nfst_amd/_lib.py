@@ -27,6 +27,7 @@ CHK_SUM_WORDS = 8  # summary of a program cut on the device (nfst_pack_chunks_de
  META_BWD_SLOT_OFF) = range(16)
 
 OK = 0
+ERR_INDEX = -2
 ERR_LENGTH = -9
 POS_WS_POSTERIOR, POS_WS_VITERBI, POS_WS_SAMPLE = 1, 2, 8  # flags of nfst_positional_ws_bytes
 
@@ -169,6 +170,11 @@ def _load():
         "nfst_string_prefix": (C.c_int, [BP, SP, vp, vp, i32, i32, vp, i32, vp, i64, vp, vp, vp, vp]),
         "nfst_string_next_ws_bytes": (i64, [BP, i32, i32, i32]),
         "nfst_string_next": (C.c_int, [BP, SP, vp, vp, i32, i32, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp]),
+        "nfst_string_prefix_open_ws_bytes": (i64, [BP, i32]),
+        "nfst_string_prefix_open": (C.c_int, [BP, SP, vp, i32, vp, i64, vp, vp, vp]),
+        "nfst_string_prefix_state_bytes": (i64, [BP, i32, i32]),
+        "nfst_string_prefix_extend": (C.c_int, [BP, SP, vp, i32, vp, i64, vp, i64, i32, vp, vp, vp, i64, i32, vp, vp]),
+        "nfst_string_prefix_state_next": (C.c_int, [BP, SP, vp, i32, vp, i64, vp, i64, i32, vp, vp, vp, vp, vp]),
         "nfst_string_viterbi_ws_bytes": (i64, [BP, i32, i32, i32]),
         "nfst_string_viterbi": (C.c_int, [BP, SP, vp, vp, i32, i32, vp, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
         "nfst_string_sample_ws_bytes": (i64, [BP, i32, i32, i32]),

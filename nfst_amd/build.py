@@ -95,7 +95,7 @@ def check_resources(res: dict) -> list:
       (DESIGN.md section 4.18), and neither do ``k_merge_paths`` and ``k_string_logprob`` (sections 4.20 and 4.21) nor the
       gradient's ``k_string_logprob_index``, ``k_string_logprob_fwd`` and ``k_string_logprob_arcs`` (section 4.22) nor
       ``k_string_prefix``, ``k_string_label_index`` and ``k_string_next`` (section 4.23) nor ``k_string_viterbi_sweep`` and
-      ``k_string_walk`` (section 4.24).
+      ``k_string_walk`` (section 4.24) nor ``k_string_extend`` and ``k_string_state_next`` (section 4.25).
     """
     bad = []
     for name, r in res.items():
@@ -108,7 +108,7 @@ def check_resources(res: dict) -> list:
             bad.append(f"{name}: VGPR spill {r.get('vgpr_spill')} in a sweep kernel")
         if re.search(r"k_lattice_edit_", name) and (r.get("vgpr_spill", 0) != 0 or r.get("scratch", 0) != 0):
             bad.append(f"{name}: VGPR spill {r.get('vgpr_spill')}, scratch {r.get('scratch')} in a kernel that must use no scratch")
-        if re.search(r"k_(merge_paths|string_logprob(_index|_fwd|_arcs)?|string_(prefix|label_index|next|viterbi_sweep|walk))\b", name) and (r.get("vgpr_spill", 0) != 0 or r.get("scratch", 0) != 0):
+        if re.search(r"k_(merge_paths|string_logprob(_index|_fwd|_arcs)?|string_(prefix|label_index|next|viterbi_sweep|walk|extend|state_next))\b", name) and (r.get("vgpr_spill", 0) != 0 or r.get("scratch", 0) != 0):
             bad.append(f"{name}: VGPR spill {r.get('vgpr_spill')}, scratch {r.get('scratch')} in a kernel that must use no scratch")
         if not fused and re.search(r"k_(forward_backward|backward)<", name) and r.get("agprs", 0) != 0:
             bad.append(f"{name}: {r.get('agprs')} AGPRs in a kernel that stages nothing in them")

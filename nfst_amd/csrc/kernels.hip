@@ -48,6 +48,7 @@ using namespace nfst_tile;
 #include "string_align_kernels.h"
 #include "string_logprob_grad_kernels.h"
 #include "string_prefix_kernels.h"
+#include "string_extend_kernels.h"
 #include "slack_kernels.h"
 #include "intersect_kernels.h"
 #include "intersect_wide_kernels.h"
@@ -1420,6 +1421,131 @@ int nfst_string_next(const nfst_batch *lat, const nfst_scores *scores, const int
     return r;
   };
   return marker >= 0 ? run(std::true_type{}) : run(std::false_type{});
+}
+
+// ------------------------------------------------------------------ prefix states (string_extend_kernels.h)
+// The context is nfst_string_next's workspace without a table F (M = 0): zn, z, az, the level arrays, the in-arc lists
+// and the label lists.  A state is 8 bytes per row, plane and hypothesis.
+static int64_t se_ctx_layout(const nfst_batch *lat, int planes, char *base, SlWs *w, SlWs *wz, SlgWs *g, SpWs *p) {
+  return sp_ws_layout(lat, 0, 0, planes, base, w, wz, g, p);
+}
+static int64_t se_state_bytes(const nfst_batch *lat, int64_t M, int planes) {
+  return (8 * planes * M * lat->total_rows + 255) & ~(int64_t)255;
+}
+// what the three entry points behind nfst_string_prefix_open check alike; *noop: nothing to launch
+static int se_check(const nfst_batch *lat, const nfst_scores *scores, const uint8_t *keep, int32_t marker, const void *ctx,
+                    int64_t ctx_bytes, const int32_t *status, bool *noop) {
+  *noop = false;
+  if (!lat || !status) return NFST_ERR_ARG;
+  int rc = tape_check(keep, marker, lat->vocab, true);
+  if (rc) return rc;
+  if (lat->n_lattices == 0) {
+    *noop = true;
+    return NFST_OK;
+  }
+  if ((rc = check_batch(lat))) return rc;
+  if ((rc = check_scores(lat, scores))) return rc;
+  if (!ctx || ((uintptr_t)ctx & 15) || ctx_bytes < se_ctx_layout(lat, marker >= 0 ? 2 : 1, nullptr, nullptr, nullptr, nullptr, nullptr))
+    return NFST_ERR_ARG;
+  return NFST_OK;
+}
+
+int64_t nfst_string_prefix_open_ws_bytes(const nfst_batch *lat, int32_t marker_mode) {
+  if (!lat) return NFST_ERR_ARG;
+  if (lat->n_lattices == 0) return 0;
+  if (int rc = check_batch(lat)) return rc;
+  return se_ctx_layout(lat, marker_mode ? 2 : 1, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+int nfst_string_prefix_open(const nfst_batch *lat, const nfst_scores *scores, const uint8_t *keep, int32_t marker, void *ws,
+                            int64_t ws_bytes, double *logz, int32_t *status, void *stream) {
+  bool noop;
+  int rc = se_check(lat, scores, keep, marker, ws, ws_bytes, status, &noop);
+  if (rc || noop) return rc;
+  if (!logz) return NFST_ERR_ARG;
+  const int64_t lds_lev = (int64_t)lat->max_rows * 12 + 16;
+  const int64_t lds_sweep = ((int64_t)lat->max_rows * 2 + 1) * 4;
+  const int64_t lds_index = ((int64_t)lat->max_rows * 3 + 1 + kSlgIndexThreads) * 4;
+  const int64_t lds_label = ((int64_t)lat->max_rows + lat->vocab + 1 + kSpIndexThreads) * 4;
+  if (lds_lev > kMaxLds || lds_sweep > kMaxLds || lds_index > kMaxLds || lds_label > kMaxLds) return NFST_ERR_LIMIT;
+  SlWs w, wz;
+  SlgWs g;
+  SpWs p;
+  se_ctx_layout(lat, marker >= 0 ? 2 : 1, (char *)ws, &w, &wz, &g, &p);
+  const KbWs lw{nullptr, w.order, w.lev, w.n_lev};  // (k_kbest_levels writes the level arrays only)
+  const SlIn none{nullptr, nullptr, 0, 0, keep, (int)marker};   // no candidate: az alone
+  const SlIn empty{nullptr, nullptr, 1, 0, keep, (int)marker};  // the empty prefix once per lattice: zn, z and logz
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 lattices(lat->n_lattices);
+  if ((rc = launch(k_kbest_levels, lattices, dim3(kKbLevelThreads), lds_lev, st, *lat, lw))) return rc;
+  auto run = [&](auto MK) {
+    constexpr bool mk = decltype(MK)::value;
+    int r = launch(k_string_prefix<mk>, lattices, dim3(kSlThreads), lds_sweep, st, *lat, *scores, empty, wz, p.zn_lp, logz, status);
+    if (!r) r = launch(k_string_logprob_index, lattices, dim3(kSlgIndexThreads), lds_index, st, *lat, w, g);
+    if (!r) r = launch(k_string_logprob_fwd<mk>, lattices, dim3(kSlThreads), lds_sweep, st, *lat, *scores, none, w, g);
+    if (!r) r = launch(k_string_label_index, lattices, dim3(kSpIndexThreads), lds_label, st, *lat, w, p);
+    return r;
+  };
+  return marker >= 0 ? run(std::true_type{}) : run(std::false_type{});
+}
+
+int64_t nfst_string_prefix_state_bytes(const nfst_batch *lat, int32_t M, int32_t marker_mode) {
+  if (!lat || M < 0) return NFST_ERR_ARG;
+  if (M > kSeMaxM) return NFST_ERR_LIMIT;
+  if (lat->n_lattices == 0) return 0;
+  if (int rc = check_batch(lat)) return rc;
+  return se_state_bytes(lat, M, marker_mode ? 2 : 1);
+}
+
+int nfst_string_prefix_extend(const nfst_batch *lat, const nfst_scores *scores, const uint8_t *keep, int32_t marker, const void *ctx_ws,
+                              int64_t ctx_bytes, const double *parent_state, int64_t parent_bytes, int32_t M_in,
+                              const int32_t *parent, const int32_t *symbol, double *out_state, int64_t out_bytes, int32_t M_out,
+                              int32_t *status, void *stream) {
+  if (M_in < 0 || M_out < 0) return NFST_ERR_ARG;
+  bool noop;
+  int rc = se_check(lat, scores, keep, marker, ctx_ws, ctx_bytes, status, &noop);
+  if (rc) return rc;
+  if (M_in > kSeMaxM || M_out > kSeMaxM) return NFST_ERR_LIMIT;
+  if (noop || M_out == 0) return NFST_OK;
+  const int planes = marker >= 0 ? 2 : 1;
+  const int64_t need_in = M_in ? se_state_bytes(lat, M_in, planes) : 0, need_out = se_state_bytes(lat, M_out, planes);
+  if (!parent || !symbol || !out_state || ((uintptr_t)out_state & 15) || out_bytes < need_out) return NFST_ERR_ARG;
+  if (M_in > 0 && (!parent_state || ((uintptr_t)parent_state & 15) || parent_bytes < need_in)) return NFST_ERR_ARG;
+  if (M_in > 0 && (const char *)parent_state < (const char *)out_state + need_out && (const char *)out_state < (const char *)parent_state + need_in)
+    return NFST_ERR_ARG;  // (the children read their parents' cells while they are written)
+  const int64_t lds_sweep = ((int64_t)lat->max_rows * 2 + 1) * 4;
+  if (lds_sweep > kMaxLds) return NFST_ERR_LIMIT;
+  SlWs w;
+  SlgWs g;
+  se_ctx_layout(lat, planes, (char *)ctx_ws, &w, nullptr, &g, nullptr);
+  const SlIn in{nullptr, nullptr, 0, 0, keep, (int)marker};
+  const SeIn x{M_in ? parent_state : nullptr, parent, symbol, out_state, (int)M_in, (int)M_out};
+  // one wave per SIMD while a level is a few items; four when the hypotheses multiply them (the bits are the same)
+  const dim3 grid(lat->n_lattices, (unsigned)((M_out + 63) / 64)), block(M_out >= 8 ? kSlThreads : 256);
+  const hipStream_t st = (hipStream_t)stream;
+  if (marker >= 0) return launch(k_string_extend<true>, grid, block, lds_sweep, st, *lat, *scores, in, w, g, x, status);
+  return launch(k_string_extend<false>, grid, block, lds_sweep, st, *lat, *scores, in, w, g, x, status);
+}
+
+int nfst_string_prefix_state_next(const nfst_batch *lat, const nfst_scores *scores, const uint8_t *keep, int32_t marker,
+                                  const void *ctx_ws, int64_t ctx_bytes, const double *state, int64_t state_bytes, int32_t M,
+                                  double *next, double *eos, double *log_prefix, int32_t *status, void *stream) {
+  if (M < 0) return NFST_ERR_ARG;
+  bool noop;
+  int rc = se_check(lat, scores, keep, marker, ctx_ws, ctx_bytes, status, &noop);
+  if (rc) return rc;
+  if (M > kSeMaxM) return NFST_ERR_LIMIT;
+  if (noop || M == 0) return NFST_OK;
+  const int planes = marker >= 0 ? 2 : 1;
+  if (!state || ((uintptr_t)state & 15) || state_bytes < se_state_bytes(lat, M, planes) || !next || !eos || !log_prefix) return NFST_ERR_ARG;
+  SlgWs g;
+  SpWs p;
+  se_ctx_layout(lat, planes, (char *)ctx_ws, nullptr, nullptr, &g, &p);
+  const SlIn in{nullptr, nullptr, 0, 0, keep, (int)marker};
+  const dim3 grid(lat->n_lattices, (unsigned)M), block(kSpNextThreads);
+  const hipStream_t st = (hipStream_t)stream;
+  if (marker >= 0) return launch(k_string_state_next<true>, grid, block, 0, st, *lat, *scores, in, g, p, state, (int)M, next, eos, log_prefix);
+  return launch(k_string_state_next<false>, grid, block, 0, st, *lat, *scores, in, g, p, state, (int)M, next, eos, log_prefix);
 }
 
 // ------------------------------------------------------------------ arc slack and beam masks (slack_kernels.h)

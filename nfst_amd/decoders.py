@@ -237,7 +237,7 @@ class PrefixSearchResult(NamedTuple):
 
 
 def prefix_search(lat, theta, k: int = 8, max_len: Optional[int] = None, *, keep=None, marker: Optional[int] = None, arc_scores=None,
-                  pad: int = 0, reserve: int = 64, refine_steps: int = 32) -> PrefixSearchResult:
+                  pad: int = 0, reserve: int = 64, refine_steps: int = 32, incremental: bool = False) -> PrefixSearchResult:
     """Prefix beam search for the most probable output strings with exact prefix probabilities
     (``ops.string_next_log_probs``), in two phases.  The first is length-synchronous: step t holds at most ``k`` open
     prefixes of length t per lattice and asks for their ``eos`` and ``next`` in one call (M = k, N = t).  Every ``eos`` is the
@@ -254,7 +254,11 @@ def prefix_search(lat, theta, k: int = 8, max_len: Optional[int] = None, *, keep
     ``exact[b]`` is set when the first entry weighs at least ``bound[b]`` and at least every prefix that was open when the
     first phase stopped: it is then the most probable string of lattice b, which no list of paths can certify.
     ``reserve=0, refine_steps=0`` is the first phase alone, ``bound`` the heaviest mass ever pruned.  ``log_prob`` and
-    ``bound`` are less log Z.  Every step sweeps the prefix table of the whole prefix again.  No gradient."""
+    ``bound`` are less log Z.  Every step sweeps the prefix table of the whole prefix again.  No gradient.
+    ``incremental=True`` opens an ``ops.PrefixContext`` once and holds the open prefixes of the first phase as a
+    ``PrefixState``, which every step extends by the symbols it picked: one column per step in place of the whole table,
+    and the per-lattice indexes once per search.  Every field of the result is the same, bit for bit; k <= 1024.  The
+    second phase is the same either way (its prefixes are scored once and never extended).  No gradient."""
     ops._check_k(k, bounded=False)
     if (keep is None) == (marker is None):
         raise ValueError("give keep (a set of labels) or marker (a label)")
@@ -276,10 +280,14 @@ def prefix_search(lat, theta, k: int = 8, max_len: Optional[int] = None, *, keep
               res_rows=new_rows(R), res_len=torch.zeros((B, R), dtype=i32, device=dev), res_mass=new_mass(R),
               logz=torch.zeros(B, dtype=f64, device=dev))
 
-    def expand(rows, lens, live, N):
-        """One call on the open prefixes: their eos into the complete lists, their extensions' masses [B, k V] (-inf for a
-        dead slot and for a prefix of max_len symbols, whose mass beyond its eos raises the bound)"""
-        ns = ops.string_next_log_probs(lat, theta, rows[:, :, :max(N, 1)], lens, keep=keep, marker=marker, arc_scores=arc_scores)
+    def expand(rows, lens, live, N, state=None):
+        """One call on the open prefixes (on their state where there is one): their eos into the complete lists, their
+        extensions' masses [B, k V] (-inf for a dead slot and for a prefix of max_len symbols, whose mass beyond its eos
+        raises the bound)"""
+        if state is not None:
+            ns = ctx.next(state)
+        else:
+            ns = ops.string_next_log_probs(lat, theta, rows[:, :, :max(N, 1)], lens, keep=keep, marker=marker, arc_scores=arc_scores)
         st["logz"] = ns.logz
         eos = torch.where(live, ns.eos, torch.full_like(ns.eos, ninf))
         nxt = torch.where(live[:, :, None], ns.next, torch.full_like(ns.next, ninf))
@@ -326,8 +334,12 @@ def prefix_search(lat, theta, k: int = 8, max_len: Optional[int] = None, *, keep
     open_at_stop = new_mass(1)[:, 0]
     active = torch.ones(B, dtype=torch.bool, device=dev)
     n_open = min(k, k * V)
+    ctx = ops.string_prefix_open(lat, theta, keep=keep, marker=marker, arc_scores=arc_scores) if incremental else None
+    state, grown = None, None  # the open prefixes' state, and the (parent slot, symbol) [B, k] that make the next one
     for t in range(max_len + 1):
-        flat = expand(open_rows, open_len, active[:, None] & (open_mass > ninf), t)
+        if incremental:
+            state = ctx.root(k) if grown is None else ops.PrefixState(ctx._extend(state.cells, k, *grown)[0], open_len)
+        flat = expand(open_rows, open_len, active[:, None] & (open_mass > ninf), t, state)
         order = torch.sort(-flat, dim=1, stable=True).indices[:, :n_open]
         mass = flat.gather(1, order)
         rows, lens = extended(open_rows, open_len, order)
@@ -337,6 +349,8 @@ def prefix_search(lat, theta, k: int = 8, max_len: Optional[int] = None, *, keep
         open_rows[:, :n_open] = torch.where(alive[:, :, None], rows, open_rows[:, :n_open])
         open_len[:, :n_open] = torch.where(alive, lens, open_len[:, :n_open])
         open_mass[:, :n_open] = mass
+        if incremental:  # (a pick of no mass leaves its slot dead)
+            grown = (torch.where(alive, order // V, torch.full_like(order, -1)).to(i32), (order % V).to(i32))
         go_on = active & (open_mass > st["comp_w"][:, k - 1, None]).any(dim=1)
         open_at_stop = torch.where(active & ~go_on, open_mass.max(dim=1).values, open_at_stop)
         active = go_on

@@ -1681,4 +1681,5 @@ from .edit import EDIT_MAX_LEN, LatticeEditResult, edit_distance, lattice_edit_d
 from .constraints import constraint_log_prob  # noqa: E402,F401
 from .strings import (MERGE_MAX_K, NextSymbols, PrefixScores, StringScores, StringSet, merge_paths, string_arc_posteriors,  # noqa: E402,F401
                       string_log_prob, string_next_log_probs, string_prefix_log_prob)
+from .strings import STATE_MAX_M, PrefixContext, PrefixState, string_prefix_open  # noqa: E402,F401
 from .strings import StringAlignment, StringSampleResult, string_alignment_log_prob, string_sample_paths, string_viterbi  # noqa: E402,F401

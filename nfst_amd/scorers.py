@@ -191,9 +191,16 @@ class LatticeScorer(torch.nn.Module):
         tape = dict(keep=kw.pop("keep")) if kw.get("keep") is not None else dict(marker=marker)
         return ops.string_next_log_probs(self._lat(), self.theta.detach(), prefixes, lengths, **tape, **kw)
 
+    def prefix_context(self, marker: Optional[int] = 4, **kw):
+        """An ``ops.PrefixContext`` on the lattices under the ``theta`` of this moment (``ops.string_prefix_open``): prefix
+        states that grow by one symbol per sweep, for incremental decoding at O(arcs) per symbol.  The tape is ``marker``
+        (default: the output mark 4) or ``keep=`` a set of labels.  Open it again after ``theta`` changes.  No gradient."""
+        tape = dict(keep=kw.pop("keep")) if kw.get("keep") is not None else dict(marker=marker)
+        return ops.string_prefix_open(self._lat(), self.theta.detach(), **tape, **kw)
+
     def prefix_search(self, k: int = 8, marker: Optional[int] = 4, **kw):
         """The most probable output strings of every lattice by exact prefix beam search: ``decoders.PrefixSearchResult``
-        (``decoders.prefix_search``; ``kw``: ``max_len``, ``keep`` in place of ``marker``), whose ``exact`` flags say where
+        (``decoders.prefix_search``; ``kw``: ``max_len``, ``incremental``, ``keep`` in place of ``marker``), whose ``exact`` flags say where
         the first string is provably the most probable one."""
         from .decoders import prefix_search
 

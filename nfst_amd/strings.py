@@ -620,3 +620,165 @@ def string_next_log_probs(lat, theta, prefixes: torch.Tensor, lengths: torch.Ten
     log p(v | y, x) and ``logz`` for probabilities.  The results carry no gradient: gradients of prefix masses are out
     of scope."""
     return NextSymbols(*_prefix_launches("nfst_string_next", lat, theta, prefixes, lengths, keep, marker, arc_scores, max_workspace_bytes, 3))
+
+
+# ----------------------------------------------------------------------------- prefix states
+STATE_MAX_M = 1024  # nfst_string_prefix_extend: the hypotheses of one state
+
+
+class PrefixState(NamedTuple):
+    cells: torch.Tensor    # opaque float64: one column of the prefix table per lattice row, plane and slot
+    lengths: torch.Tensor  # [B, M] int32: the symbols of the slot's prefix, -1 for a dead slot
+
+
+class PrefixContext:
+    """What ``string_next_log_probs`` works out per call from the lattice and the scores alone, worked out once
+    (``nfst_string_prefix_open``), and the prefix states that live on it: ``root`` makes the empty prefix, ``extend``
+    appends one symbol to chosen parents in one sweep of one column -- O(arcs) per symbol whatever the prefix length --
+    and ``next`` gives ``string_next_log_probs``'s results for a state's prefixes, bit for bit.  The caller keeps the
+    tokens; a state only knows its lengths.  A decoder that fuses the lattice with an external scorer is this loop::
+
+        ctx = ops.string_prefix_open(lat, theta, marker=4)
+        state = ctx.root(k)
+        for t in range(max_len):
+            ns = ctx.next(state)                         # next [B, k, V], eos, log_prefix
+            slot, label = choose(ns.next - ns.log_prefix[:, :, None] + external_scores)   # [B, k] each, -1: none
+            state = ctx.extend(state, slot, label)
+
+    The context is a snapshot of the scores: it must be opened again after the parameters change.  No gradient.
+    A state is 8 * planes * M * total_rows bytes (planes = 2 with ``marker``), and a step holds two."""
+
+    def __init__(self, lat, sc, alive, keep_mask, marker: int, ws: torch.Tensor, logz: torch.Tensor):
+        self.lat, self.marker, self.keep_mask, self.ws, self.logz = lat, marker, keep_mask, ws, logz
+        self._sc, self._alive = sc, alive  # (the nfst_scores struct points into the tensors of ``alive``)
+
+    @property
+    def planes(self) -> int:
+        return 2 if self.marker >= 0 else 1
+
+    def _cells(self, M: int) -> torch.Tensor:
+        if isinstance(M, bool) or not isinstance(M, int) or M < 1:
+            raise ValueError("a state holds M >= 1 hypotheses")
+        n = int(_lib.lib.nfst_string_prefix_state_bytes(C.byref(self.lat.c_struct()), M, int(self.marker >= 0)))
+        if n < 0:
+            _lib.check(n, "nfst_string_prefix_state_bytes")  # (M > STATE_MAX_M: NFST_ERR_LIMIT)
+        return torch.empty(max(n, 16) // 8, dtype=torch.float64, device=self.lat.device)
+
+    def _extend(self, cells, M_in: int, parent: torch.Tensor, symbol: torch.Tensor) -> tuple:
+        """One launch of ``nfst_string_prefix_extend``: ``(the children's cells, status word on the device)``"""
+        from .ops import _call
+
+        out = self._cells(parent.shape[1])
+        status = torch.zeros(1, dtype=torch.int32, device=self.lat.device)
+        _call("nfst_string_prefix_extend", self.lat, self._sc, self.keep_mask, self.marker, self.ws, self.ws.numel(), cells,
+              0 if cells is None else cells.numel() * 8, M_in, parent, symbol, out, out.numel() * 8, parent.shape[1], status)
+        return out, status
+
+    def _slots(self, x, name: str, M_out=None) -> torch.Tensor:
+        B = self.lat.n_lattices
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] != B or x.is_floating_point() or (M_out is not None and x.shape[1] != M_out):
+            raise ValueError(f"{name} must be an integer tensor [{B}, M_out]")
+        return x.to(device=self.lat.device, dtype=torch.int32).contiguous()
+
+    def root(self, M: int = 1) -> PrefixState:
+        """A state of ``M`` slots: slot 0 is the empty prefix, the other slots are dead."""
+        B, dev = self.lat.n_lattices, self.lat.device
+        parent = torch.full((B, M), -1, dtype=torch.int32, device=dev)
+        parent[:, 0] = -2
+        cells, _ = self._extend(None, 0, parent, torch.zeros_like(parent))
+        lengths = torch.full((B, M), -1, dtype=torch.int32, device=dev)
+        lengths[:, 0] = 0
+        return PrefixState(cells, lengths)
+
+    def extend(self, state: PrefixState, parent: torch.Tensor, symbol: torch.Tensor) -> PrefixState:
+        """The state of the prefixes ``state[parent[b, m]] + (symbol[b, m],)`` (``parent`` and ``symbol`` [B, M_out]
+        integers, M_out <= 1024; children are independent and may share a parent).  ``parent`` -1 makes a dead slot and
+        -2 the empty prefix; so does a dead parent make a dead child.  A symbol that no path spells there is no error:
+        the child's masses are -inf.  A ``parent`` outside [-2, M) or a ``symbol`` outside the vocabulary raises
+        ``NfstError`` (NFST_ERR_INDEX) after the launch."""
+        from .ops import _raise_status
+
+        parent = self._slots(parent, "parent")
+        symbol = self._slots(symbol, "symbol", parent.shape[1])
+        M_in = state.lengths.shape[1]
+        cells, status = self._extend(state.cells, M_in, parent, symbol)
+        _raise_status(status, "nfst_string_prefix_extend")
+        return PrefixState(cells, self._lengths(state.lengths, parent))
+
+    @staticmethod
+    def _lengths(lengths: torch.Tensor, parent: torch.Tensor) -> torch.Tensor:
+        of = lengths.gather(1, parent.clamp(min=0).to(torch.int64))
+        grown = torch.where((parent >= 0) & (of >= 0), of + 1, torch.full_like(of, -1))
+        return torch.where(parent == -2, torch.zeros_like(of), grown)
+
+    def next(self, state: PrefixState) -> NextSymbols:
+        """``string_next_log_probs`` of the state's prefixes (``nfst_string_prefix_state_next``), bit for bit; a dead
+        slot gets -inf everywhere.  ``logz`` is the context's."""
+        from .ops import _call
+
+        B, M = state.lengths.shape
+        dev, f64 = self.lat.device, torch.float64
+        nxt = torch.empty((B, M, self.lat.vocab), dtype=f64, device=dev)
+        eos, pre = torch.empty((B, M), dtype=f64, device=dev), torch.empty((B, M), dtype=f64, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        _call("nfst_string_prefix_state_next", self.lat, self._sc, self.keep_mask, self.marker, self.ws, self.ws.numel(), state.cells,
+              state.cells.numel() * 8, M, nxt, eos, pre, status)
+        return NextSymbols(nxt, eos, pre, self.logz)
+
+    def state_of(self, prefixes: torch.Tensor, lengths: torch.Tensor) -> PrefixState:
+        """The state of given prefixes (``prefixes`` [B, M, N], ``lengths`` [B, M], as ``string_next_log_probs`` takes
+        them; a negative length makes a dead slot): ``extend`` position by position, slot m from slot m -- the entry for
+        a search that starts from a prompt.  O(arcs * longest prefix); no kernel of its own."""
+        B, dev = self.lat.n_lattices, self.lat.device
+        if not isinstance(prefixes, torch.Tensor) or prefixes.dim() != 3 or prefixes.shape[0] != B or prefixes.is_floating_point():
+            raise ValueError(f"prefixes must be an integer tensor [{B}, M, N]")
+        M, N = prefixes.shape[1], prefixes.shape[2]
+        lens = self._slots(lengths, "lengths", M)
+        rows = prefixes.to(device=dev, dtype=torch.int32)
+        if bool((lens > N).any()):
+            raise ValueError(f"a length exceeds the row stride {N}")
+        own = torch.arange(M, dtype=torch.int32, device=dev).expand(B, M).contiguous()
+        none = torch.full_like(own, -1)
+        cells, _ = self._extend(None, 0, torch.where(lens >= 0, torch.full_like(own, -2), none), torch.zeros_like(own))
+        state = PrefixState(cells, torch.where(lens >= 0, torch.zeros_like(lens), none))
+        for t in range(int(lens.max()) if B * M else 0):
+            grows = lens > t
+            nxt = self.extend(state, torch.where(grows, own, none), rows[:, :, t].contiguous())
+            if not bool(grows.all()):  # a slot whose prefix is complete keeps its column
+                nxt = PrefixState(self._carry(state.cells, nxt.cells, grows), torch.where(grows, nxt.lengths, state.lengths))
+            state = nxt
+        return state
+
+    def _carry(self, old: torch.Tensor, new: torch.Tensor, grows: torch.Tensor) -> torch.Tensor:
+        """``new`` in the slots that grew [B, M] and ``old`` in the others, for two states of M slots"""
+        lat, M = self.lat, grows.shape[1]
+        lat_of_row = np.searchsorted(lat.row_off.astype(np.int64), np.arange(lat.total_rows), side="right") - 1
+        per_row = grows[torch.as_tensor(lat_of_row, device=new.device)]  # [total_rows, M]
+        n = lat.total_rows * self.planes * M
+        out = new.clone()
+        out[:n] = torch.where(per_row[:, None, :], new[:n].view(-1, self.planes, M), old[:n].view(-1, self.planes, M)).reshape(-1)
+        return out
+
+
+def string_prefix_open(lat, theta, *, keep=None, marker: Optional[int] = None, arc_scores=None) -> PrefixContext:
+    """Opens a ``PrefixContext`` on a batch (``nfst_string_prefix_open``): the level pass, the continuation weights of
+    every state, the in-arc and label lists and ``logz`` (``string_log_prob``'s, bit for bit), everything that
+    ``string_next_log_probs`` repeats per call although it depends on no prefix.  Tape and scores are
+    ``string_log_prob``'s; the scores are copied, so later changes of ``theta`` or ``arc_scores`` do not reach the
+    context.  No gradient."""
+    from .ops import _call, _need_gpu, _raise_status, _scores
+
+    _need_gpu(lat)
+    keep_mask, mk, _ = _tape(keep, marker, lat.vocab, lat.device, need_one=True)
+    if not isinstance(theta, torch.Tensor):
+        theta = torch.as_tensor(theta, dtype=torch.float32)
+    sc, alive = _scores(lat, theta.detach().clone(), None if arc_scores is None else arc_scores.detach().clone())
+    n = int(_lib.lib.nfst_string_prefix_open_ws_bytes(C.byref(lat.c_struct()), int(mk >= 0)))
+    if n < 0:
+        _lib.check(n, "nfst_string_prefix_open_ws_bytes")
+    ws = torch.empty(max(n, 16), dtype=torch.uint8, device=lat.device)
+    logz = torch.empty(lat.n_lattices, dtype=torch.float64, device=lat.device)
+    status = torch.zeros(1, dtype=torch.int32, device=lat.device)
+    _call("nfst_string_prefix_open", lat, sc, keep_mask, mk, ws, ws.numel(), logz, status)
+    _raise_status(status, "nfst_string_prefix_open")
+    return PrefixContext(lat, sc, alive, keep_mask, mk, ws, logz)
